@@ -12,6 +12,11 @@ its own batch of 64 requests (weak scaling) and there is no data-path collective
 
 Rank 0 prints ONE JSON line.  `value` = algorithmic bytes (q + k + v + o, the reference's formula,
 flashinfer/testing/utils.py:476-480) of all ranks / the timed wall time (max over ranks).
+
+A plain run measures the headline alone.  `--full` adds the side measurements: the C5 cascade exchange step,
+the torch-CPU baseline and the C3 / C4 secondary workloads.  `--dump-outputs DIR` writes the output of the last
+timed step as DIR/out.npy (float32; DIR/out_rank<r>.npy on rank r > 0); the inputs are seeded, so runs with the
+same arguments see the same data.
 """
 import argparse
 import json
@@ -19,6 +24,8 @@ import math
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for p in (ROOT, os.path.join(ROOT, "flashinfer-ai_amd")):
@@ -396,10 +403,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--no-permute", action="store_true", help="arange page table instead of a random permutation")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C3 / C4 side measurements (N=1 only)")
-    ap.add_argument("--no-c5", action="store_true", help="N=1: skip the cascade exchange step on a one-rank RCCL group")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the C5 cascade step, the CPU baseline and the C3 / C4 workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output as DIR/out.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the torch-CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the C3 / C4 side measurements (N=1 only)")
+    ap.add_argument("--no-c5", action="store_true", help="--full, N=1: skip the cascade exchange step on a one-rank RCCL group")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -461,10 +473,14 @@ def main():
         elapsed = float(t.item())
     per_step = [s.elapsed_time(e) for s, e in zip(starts, ends)]
     kernel_ms = sum(per_step) / args.steps
+    if args.dump_outputs:  # what the caller of wrapper.run receives: o [64, 32, 128], 1 MB as float32
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "out.npy" if rank == 0 else f"out_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), out.float().cpu().numpy())
 
     nbytes, flops = algorithmic_bytes_flops(cfg)
     c5 = None
-    if not distributed and not args.no_c5:
+    if args.full and not distributed and not args.no_c5:
         # N = 1 from the driver: the exchange step still runs through RCCL, on a one-rank group (the collectives
         # degenerate to local copies inside the library, but it is the same code path the N > 1 runs take)
         try:
@@ -479,7 +495,7 @@ def main():
             distributed = True
         except Exception as exc:
             c5 = {"error": "one-rank RCCL group: " + repr(exc)}
-    if distributed and c5 is None:  # the one exchange step of the path (RCCL all-to-all of shared-prefix states)
+    if args.full and distributed and c5 is None:  # the one exchange step of the path (RCCL all-to-all of shared-prefix states)
         try:
             c5 = c5_cascade(device, world, rank, dist)
         except Exception as exc:
@@ -537,9 +553,9 @@ def main():
         }
         if c5 is not None:
             line["c5"] = c5
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             del cache, q, out
             torch.cuda.empty_cache()
             try:
