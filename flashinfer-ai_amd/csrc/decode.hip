@@ -48,71 +48,51 @@ static decode_launch_fn find_launcher(int kv_dt, int head_dim) {
 #undef FI_ROW
 }
 
-// q-head tile: the wave keeps GT query heads of one kv head in registers.
-static int pick_head_tile(int group_size, int kv_dt = FI_DTYPE_BF16) {
-  static const int max_tile = [] {
-    const char* e = getenv("FI_DECODE_MAX_HEAD_TILE");
-    int v = e ? atoi(e) : 0;
-    return (v == 1 || v == 2 || v == 4) ? v : 4;
-  }();
-  // groups larger than 4 are processed as several 4-head tiles by neighbouring waves of one workgroup
-  // (they stream the same K/V rows, so HBM sees them once): measured 1.7-1.9x faster than an 8-head tile,
-  // which is VALU-bound and spills (profiles/r01 notes in DESIGN.md).
-  int t = group_size <= 1 ? 1 : group_size == 2 ? 2 : 4;
-  (void)kv_dt;
-  return t < max_tile ? t : max_tile;
+static int env_int(const char* name, int unset) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : unset;
 }
 
-// Matrix-core decode (decode_mfma_kernel.h): groups too wide for the VALU kernel, K/V stored in the q
-// dtype.  FI_DECODE_MFMA_MIN_GROUP moves the crossover (0 disables the path).
-hipError_t decode_mfma_launch(const DecodeKernelParams& p, int q_dtype, int kv_dtype, int head_dim, int rope, int grid,
-                              hipStream_t stream);
-hipError_t decode_mfma16_launch(const DecodeKernelParams& p, int q_dtype, int kv_dtype, int head_dim, int rope,
-                                int grid, hipStream_t stream);
-// the 16x16x32 form (decode_mfma16_kernel.h) serves every group of <= 16 heads the matrix-core path accepts:
-// measured >= the VALU kernel (G <= 4) and >= the 32x32x16 form (G 5..16) on every shape of
-// tools/bench_decode_kernels.py (C2 6.35 -> 6.52 TB/s, bs 8 x 1024 20.3 -> 16.1 us), and the only one with room
-// for the fused-RoPE rotation.  FI_DECODE_MFMA16=0 restores the r1 choice.
-static bool mfma16_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("FI_DECODE_MFMA16");
-    return e ? atoi(e) != 0 : true;
-  }();
-  return on;
-}
-static bool mfma16_decode(int group_size, bool rope) {
-  (void)rope;
-  return group_size <= 16 && mfma16_enabled();
-}
-static int tokens_per_load(int kv_dt, int head_dim);
-static int ilog2_exact(int x);
-static bool mfma_decode_shape(int group_size, int q_dt, int kv_dt, int head_dim, int page_size, bool rope = false) {
-  static const int min_group = [] {
-    const char* e = getenv("FI_DECODE_MFMA_MIN_GROUP");
-    return e ? atoi(e) : 5;
-  }();
-  static const int min_group_fp8 = [] {
+// The FI_DECODE_* knobs, read once per process (FI_DECODE_WAVES_PER_CU excepted, see decode_waves_per_cu).
+struct DecodeKnobs {
+  int max_head_tile;       // FI_DECODE_MAX_HEAD_TILE: 1, 2 or 4 (anything else: 4)
+  bool mfma16;             // FI_DECODE_MFMA16=0: no 16x16x32 kernel (the r1 choice)
+  int mfma_min_group;      // FI_DECODE_MFMA_MIN_GROUP: matrix-core crossover, 16-bit cache (0 disables the path)
+  int mfma_min_group_fp8;  // FI_DECODE_MFMA_MIN_GROUP_FP8: the same for an fp8 cache
+  bool mfma_rope;          // FI_DECODE_MFMA_ROPE=0: fused RoPE stays on the VALU kernel
+  bool force_generic;      // FI_DECODE_FORCE_GENERIC set: never the VALU kernel's fast path
+};
+
+static const DecodeKnobs& decode_knobs() {
+  static const DecodeKnobs k = [] {
+    DecodeKnobs k;
+    const int t = env_int("FI_DECODE_MAX_HEAD_TILE", 0);
+    k.max_head_tile = (t == 1 || t == 2 || t == 4) ? t : 4;
+    k.mfma16 = env_int("FI_DECODE_MFMA16", 1) != 0;
+    k.mfma_min_group = env_int("FI_DECODE_MFMA_MIN_GROUP", 5);
     // an fp8 cache doubles the VALU work per byte: measured 5.0 (VALU) vs 6.35 TB/s (MFMA) at G = 4,
     // 6.6 vs 6.4 TB/s at G = 1
-    const char* e = getenv("FI_DECODE_MFMA_MIN_GROUP_FP8");
-    return e ? atoi(e) : 3;
+    k.mfma_min_group_fp8 = env_int("FI_DECODE_MFMA_MIN_GROUP_FP8", 3);
+    k.mfma_rope = env_int("FI_DECODE_MFMA_ROPE", 1) != 0;
+    k.force_generic = getenv("FI_DECODE_FORCE_GENERIC") != nullptr;
+    return k;
   }();
-  const bool fp8 = kv_dt == FI_DTYPE_FP8_E4M3 || kv_dt == FI_DTYPE_FP8_E5M2;
-  int mg = fp8 ? min_group_fp8 : min_group;
-  // pages too small (or not a power of two) for the VALU kernel's scalar-page fast path: its per-lane
-  // page-lookup fallback runs at 4.5 TB/s (page_size 1), the matrix-core kernel -- which always gathers per
-  // lane -- at 6.3; token-granular page tables (page_size 1) are common
-  if (mg > 0 && (ilog2_exact(page_size) < 0 || page_size < tokens_per_load(kv_dt, head_dim))) mg = 1;
-  // fused RoPE: the K rotation is vector-ALU work that the VALU kernel has no room for (4.8 TB/s at G = 4);
-  // on the matrix-core kernel it rides an idle pipe.  FI_DECODE_MFMA_ROPE=0 keeps the VALU kernel.
-  static const bool rope_on_mfma = [] {
-    const char* e = getenv("FI_DECODE_MFMA_ROPE");
-    return e ? atoi(e) != 0 : true;
-  }();
-  if (rope && mg > 0) mg = rope_on_mfma ? 1 : 0x7fffffff;
-  if (!rope && mg > 0 && group_size <= 16 && mfma16_enabled()) mg = 1;
-  return mg > 0 && group_size >= mg && (q_dt == kv_dt || fp8) &&
-         (q_dt == FI_DTYPE_F16 || q_dt == FI_DTYPE_BF16) && (head_dim == 64 || head_dim == 128);
+  return k;
+}
+
+// work items per CU the planner cuts the batch into (FI_DECODE_WAVES_PER_CU overrides; read at every plan, as
+// tools/bench_decode_sweep.py sweeps it within one process).  r3 sweep over the reference
+// benchmark's grid (tools/bench_ref_grids.py, tools/r3/dsweep.py; bf16 32 / 4 and 32 / 8 heads, random and identity
+// page order): with a 16-bit cache 4 per CU is level with 8 at C2 (6.72 against 6.65 TB/s) and ahead on everything
+// smaller, where 8 cuts chunks of 256-512 tokens whose fixed cost shows (bs 256 x kv 1024: 6.46 against 5.32 -- no
+// split at all; bs 64 x kv 4096, 32 / 4: 5.84 against 4.98; bs 32 x kv 4096: 5.05 against 4.37); an fp8 cache moves
+// half the bytes per token and keeps 8 (C2 shape 6.08 against 5.59).  Counts that do not divide the chunking evenly
+// (3, 5, 6) lose 5-20 %.  A single request (fi_single_decode) always wants many chunks: 8.
+static int decode_waves_per_cu(int kv_dtype, bool batch) {
+  const int v = env_int("FI_DECODE_WAVES_PER_CU", 0);
+  if (v > 0) return v;
+  const bool fp8 = kv_dtype == FI_DTYPE_FP8_E4M3 || kv_dtype == FI_DTYPE_FP8_E5M2;
+  return (batch && !fp8) ? 4 : 8;
 }
 
 static int tokens_per_load(int kv_dt, int head_dim) {
@@ -127,20 +107,77 @@ static int ilog2_exact(int x) {
   return l;
 }
 
-// work items per CU the planner cuts the batch into (FI_DECODE_WAVES_PER_CU overrides).  r3 sweep over the reference
-// benchmark's grid (tools/bench_ref_grids.py, tools/r3/dsweep.py; bf16 32 / 4 and 32 / 8 heads, random and identity
-// page order): with a 16-bit cache 4 per CU is level with 8 at C2 (6.72 against 6.65 TB/s) and ahead on everything
-// smaller, where 8 cuts chunks of 256-512 tokens whose fixed cost shows (bs 256 x kv 1024: 6.46 against 5.32 -- no
-// split at all; bs 64 x kv 4096, 32 / 4: 5.84 against 4.98; bs 32 x kv 4096: 5.05 against 4.37); an fp8 cache moves
-// half the bytes per token and keeps 8 (C2 shape 6.08 against 5.59).  Counts that do not divide the chunking evenly
-// (3, 5, 6) lose 5-20 %.  A single request (fi_single_decode) always wants many chunks: 8.
-static int decode_waves_per_cu(int kv_dtype, bool batch) {
-  if (const char* e = getenv("FI_DECODE_WAVES_PER_CU")) {
-    int v = atoi(e);
-    if (v > 0) return v;
+// Matrix-core decode (decode_mfma_kernel.h): groups too wide for the VALU kernel, K/V stored in the q
+// dtype.  FI_DECODE_MFMA_MIN_GROUP moves the crossover (0 disables the path).
+hipError_t decode_mfma_launch(const DecodeKernelParams& p, int q_dtype, int kv_dtype, int head_dim, int rope, int grid,
+                              hipStream_t stream);
+hipError_t decode_mfma16_launch(const DecodeKernelParams& p, int q_dtype, int kv_dtype, int head_dim, int rope,
+                                int grid, hipStream_t stream);
+static bool mfma_decode_shape(int group_size, int q_dt, int kv_dt, int head_dim, int page_size, bool rope) {
+  const DecodeKnobs& k = decode_knobs();
+  const bool fp8 = kv_dt == FI_DTYPE_FP8_E4M3 || kv_dt == FI_DTYPE_FP8_E5M2;
+  int mg = fp8 ? k.mfma_min_group_fp8 : k.mfma_min_group;
+  // pages too small (or not a power of two) for the VALU kernel's scalar-page fast path: its per-lane
+  // page-lookup fallback runs at 4.5 TB/s (page_size 1), the matrix-core kernel -- which always gathers per
+  // lane -- at 6.3; token-granular page tables (page_size 1) are common
+  if (mg > 0 && (ilog2_exact(page_size) < 0 || page_size < tokens_per_load(kv_dt, head_dim))) mg = 1;
+  // fused RoPE: the K rotation is vector-ALU work that the VALU kernel has no room for (4.8 TB/s at G = 4);
+  // on the matrix-core kernel it rides an idle pipe.  FI_DECODE_MFMA_ROPE=0 keeps the VALU kernel.
+  if (rope && mg > 0) mg = k.mfma_rope ? 1 : 0x7fffffff;
+  if (!rope && mg > 0 && group_size <= 16 && k.mfma16) mg = 1;
+  return mg > 0 && group_size >= mg && (q_dt == kv_dt || fp8) &&
+         (q_dt == FI_DTYPE_F16 || q_dt == FI_DTYPE_BF16) && (head_dim == 64 || head_dim == 128);
+}
+
+enum class DecodeKernel { VALU, MFMA32, MFMA16 };
+
+struct DecodeChoice {
+  DecodeKernel kind;
+  int head_tiles;  // work items per (chunk, kv head): waves that split the group's query heads
+  int gt;          // VALU kernel: query heads one wave keeps in registers
+};
+
+// The one decode kernel rule, for plan (which knows neither the logits transform nor the strides) and run.
+static DecodeChoice choose_decode(int group, int q_dt, int kv_dt, int head_dim, int page_size, bool rope,
+                                  bool plain_logits, bool strides_fit_31_bits) {
+  DecodeChoice c;
+  // groups larger than 4 are processed as several 4-head tiles by neighbouring waves of one workgroup
+  // (they stream the same K/V rows, so HBM sees them once): measured 1.7-1.9x faster than an 8-head tile,
+  // which is VALU-bound and spills (profiles/r01 notes in DESIGN.md).
+  c.gt = std::min(group <= 1 ? 1 : group == 2 ? 2 : 4, decode_knobs().max_head_tile);
+  // the 16x16x32 form (decode_mfma16_kernel.h) serves every group of <= 16 heads the matrix-core path accepts:
+  // measured >= the VALU kernel (G <= 4) and >= the 32x32x16 form (G 5..16) on every shape of
+  // tools/bench_decode_kernels.py (C2 6.35 -> 6.52 TB/s, bs 8 x 1024 20.3 -> 16.1 us), and the only one with room
+  // for the fused-RoPE rotation.  ALiBi and the logits soft cap exist in the VALU and 16x16x32 kernels only.
+  const bool mfma16 = group <= 16 && decode_knobs().mfma16;
+  const bool mfma = mfma_decode_shape(group, q_dt, kv_dt, head_dim, page_size, rope) &&
+                    (plain_logits || mfma16) && strides_fit_31_bits;
+  c.kind = !mfma ? DecodeKernel::VALU : mfma16 ? DecodeKernel::MFMA16 : DecodeKernel::MFMA32;
+  // a matrix-core wave covers the whole group
+  c.head_tiles = mfma ? ceil_div(group, 32) : ceil_div(group, c.gt);
+  return c;
+}
+
+// The chosen kernel, then for a split kv axis the n-way merge of the partial states of merge_rows output rows:
+// ragged over kp.o_indptr (batch), or merge_n per row (single).
+static int launch_decode(const DecodeKernelParams& kp, const DecodeChoice& c, int q_dt, int kv_dt, int head_dim,
+                         bool rope, int merge_n, int merge_rows, hipStream_t stream) {
+  if (kp.num_items > 0) {
+    const int grid = ceil_div(kp.num_items, kDecodeWaves);
+    if (c.kind == DecodeKernel::MFMA16)
+      FI_HIP_CALL(decode_mfma16_launch(kp, q_dt, kv_dt, head_dim, rope, grid, stream));
+    else if (c.kind == DecodeKernel::MFMA32)
+      FI_HIP_CALL(decode_mfma_launch(kp, q_dt, kv_dt, head_dim, rope, grid, stream));
+    else
+      FI_HIP_CALL(find_launcher(kv_dt, head_dim)(kp, c.gt, rope, grid, stream));
   }
-  const bool fp8 = kv_dtype == FI_DTYPE_FP8_E4M3 || kv_dtype == FI_DTYPE_FP8_E5M2;
-  return (batch && !fp8) ? 4 : 8;
+  if (kp.split_kv) {
+    // ref: VariableLengthMergeStates after the partition-kv kernel, decode.cuh:798-821
+    MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.o_indptr, kp.o, kp.lse, merge_n, merge_rows,
+                    kp.num_qo_heads, head_dim, FI_DTYPE_F32, q_dt};
+    FI_HIP_CALL(launch_merge_n(mp, stream));
+  }
+  return 0;
 }
 
 // ref: PartitionPagedKVCacheBinarySearchMinNumPagePerBatch, scheduler.cuh:73-99
@@ -187,11 +224,12 @@ extern "C" FI_API int fi_batch_decode_plan(void* float_ws, size_t float_ws_bytes
   for (int i = 0; i < batch_size; ++i)
     FI_REQUIRE(indptr_h[i + 1] >= indptr_h[i], "batch_decode_plan: indptr must be non-decreasing");
 
-  const int group = num_qo_heads / num_kv_heads;
-  const int gt = pick_head_tile(group, kv_dtype);
-  // the matrix-core kernel covers the whole group with one wave; a run() that cannot use it (rope, alibi,
-  // soft cap, window) still works on this plan, with head_tiles x the work items
-  const int head_tiles = mfma_decode_shape(group, q_dtype, kv_dtype, head_dim, page_size) ? ceil_div(group, 32) : ceil_div(group, gt);
+  // The plan sizes the grid for the kernel a plain run() gets (no RoPE, plain logits, strides that fit).  A run()
+  // that ends up on another kernel (RoPE, ALiBi, soft cap, wide strides) still works on this plan: the work list
+  // holds (request, chunk) pairs only, and run() derives num_items = padded x kv heads x its own head_tiles.
+  const int head_tiles = choose_decode(num_qo_heads / num_kv_heads, q_dtype, kv_dtype, head_dim, page_size,
+                                       /*rope=*/false, /*plain_logits=*/true, /*strides_fit_31_bits=*/true)
+                             .head_tiles;
   const uint32_t gdy = (uint32_t)(num_kv_heads * head_tiles);
   // head tiles of one kv head stream the same rows (the partner wave's loads hit in L2), so a multi-tile
   // launch is sized for twice the waves: measured 4.42 vs 3.73 TB/s at Hq/Hkv = 64/8 (r1)
@@ -298,19 +336,45 @@ extern "C" FI_API int fi_batch_decode_plan(void* float_ws, size_t float_ws_bytes
 
 namespace fi {
 
-static int fill_common(DecodeKernelParams& kp, int kv_dt, int head_dim, int num_qo_heads,
-                       int num_kv_heads, int page_size) {
-  const int group = num_qo_heads / num_kv_heads;
-  const int gt = pick_head_tile(group, kv_dt);
-  kp.num_qo_heads = num_qo_heads;
+// The checks and DecodeKernelParams fields batch and single decode share (A is fi_batch_decode_params_t or
+// fi_single_decode_params_t: the fields read here have the same names in both), and the kernel choice.
+template <class A>
+static int check_and_fill_decode(const char* who, const A& a, int kv_dt, int head_dim, int num_kv_heads,
+                                 int page_size, int64_t kv_stride_page, int64_t kv_stride_n, int64_t kv_stride_h,
+                                 DecodeKernelParams& kp, DecodeChoice& choice) {
+  FI_REQUIRE(a.q_dtype == FI_DTYPE_F16 || a.q_dtype == FI_DTYPE_BF16, "%s: q dtype must be f16/bf16", who);
+  FI_REQUIRE(num_kv_heads > 0 && a.num_qo_heads % num_kv_heads == 0,
+             "%s: num_qo_heads must be a multiple of num_kv_heads", who);
+  FI_REQUIRE(find_launcher(kv_dt, head_dim), "%s: unsupported kv dtype %d / head_dim %d", who, kv_dt, head_dim);
+  FI_REQUIRE(a.pos_encoding_mode != FI_POS_ALIBI || a.alibi_slopes, "%s: ALIBI needs alibi_slopes", who);
+  memset(&kp, 0, sizeof(kp));
+  kp.q = a.q;
+  kp.o = a.o;
+  kp.lse = a.lse;
+  kp.alibi_slopes = a.alibi_slopes;
+  kp.kv_stride_page = kv_stride_page;
+  kp.kv_stride_n = kv_stride_n;
+  kp.kv_stride_h = kv_stride_h;
+  kp.num_qo_heads = a.num_qo_heads;
   kp.num_kv_heads = num_kv_heads;
-  kp.group_size = group;
-  kp.head_tiles = ceil_div(group, gt);
+  kp.group_size = a.num_qo_heads / num_kv_heads;
   kp.page_size = page_size;
   kp.log2_page_size = ilog2_exact(page_size);
   kp.uniform_page = kp.log2_page_size >= 0 && page_size >= tokens_per_load(kv_dt, head_dim);
   kp.page_div = FastDiv((uint32_t)page_size);
-  return gt;
+  kp.window_left = a.window_left;
+  kp.q_dtype = a.q_dtype;
+  kp.use_alibi = a.pos_encoding_mode == FI_POS_ALIBI;
+  kp.logits_soft_cap = a.logits_soft_cap > 0.f ? a.logits_soft_cap : 0.f;
+  kp.sm_scale = a.sm_scale;
+  kp.rope_rcp_scale = a.rope_rcp_scale;
+  kp.rope_rcp_theta = a.rope_rcp_theta;
+  const bool plain_logits = a.pos_encoding_mode != FI_POS_ALIBI && !(a.logits_soft_cap > 0.f);
+  choice = choose_decode(kp.group_size, a.q_dtype, kv_dt, head_dim, page_size,
+                         a.pos_encoding_mode == FI_POS_ROPE_LLAMA, plain_logits,
+                         kv_stride_page < (1ll << 31) && kv_stride_n < (1ll << 31));
+  kp.head_tiles = choice.head_tiles;
+  return 0;
 }
 
 }  // namespace fi
@@ -328,19 +392,16 @@ extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes,
              "batch_decode_run: null tensor");
   FI_REQUIRE(int_ws, "batch_decode_run: null int workspace");
   const fi_paged_kv_t& kv = a->kv;
-  FI_REQUIRE(a->q_dtype == FI_DTYPE_F16 || a->q_dtype == FI_DTYPE_BF16,
-             "batch_decode_run: q dtype must be f16/bf16");
   FI_REQUIRE(kv.batch_size == plan_info[FI_DP_BATCH_SIZE],
              "batch_decode_run: batch size %d differs from the planned %lld", kv.batch_size,
              (long long)plan_info[FI_DP_BATCH_SIZE]);
-  FI_REQUIRE(kv.num_kv_heads > 0 && a->num_qo_heads % kv.num_kv_heads == 0,
-             "batch_decode_run: num_qo_heads must be a multiple of num_kv_heads");
-  decode_launch_fn fn = find_launcher(kv.dtype, kv.head_dim);
-  FI_REQUIRE(fn, "batch_decode_run: unsupported kv dtype %d / head_dim %d", kv.dtype, kv.head_dim);
   FI_REQUIRE(a->pos_encoding_mode >= 0 && a->pos_encoding_mode <= 2,
              "batch_decode_run: bad pos_encoding_mode %d", a->pos_encoding_mode);
-  FI_REQUIRE(a->pos_encoding_mode != FI_POS_ALIBI || a->alibi_slopes,
-             "batch_decode_run: ALIBI needs alibi_slopes");
+  DecodeKernelParams kp;
+  DecodeChoice choice;
+  if (check_and_fill_decode("batch_decode_run", *a, kv.dtype, kv.head_dim, kv.num_kv_heads, kv.page_size,
+                            kv.stride_page, kv.stride_n, kv.stride_h, kp, choice))
+    return 1;
   const size_t esz = dtype_size(kv.dtype);
   FI_REQUIRE(((uintptr_t)a->q % 16) == 0 && (a->q_stride_n * 2) % 16 == 0 && (a->q_stride_h * 2) % 16 == 0,
              "batch_decode_run: q rows must be 16-byte aligned");
@@ -352,13 +413,6 @@ extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes,
 
   const bool split = plan_info[FI_DP_SPLIT_KV] != 0;
   const int64_t padded = plan_info[FI_DP_PADDED_BATCH_SIZE];
-  DecodeKernelParams kp;
-  memset(&kp, 0, sizeof(kp));
-  const int gt = fill_common(kp, kv.dtype, kv.head_dim, a->num_qo_heads, kv.num_kv_heads,
-                             kv.page_size);
-  kp.q = a->q;
-  kp.o = a->o;
-  kp.lse = a->lse;
   kp.k = kv.k_data;
   kp.v = kv.v_data;
   kp.indptr = kv.indptr;
@@ -375,35 +429,17 @@ extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes,
   (void)int_ws_bytes;
   kp.q_rope_offset = a->q_rope_offset;
   kp.kv_rope_pos_offset = kv.rope_pos_offset;
-  kp.alibi_slopes = a->alibi_slopes;
   kp.q_stride_n = a->q_stride_n;
   kp.q_stride_h = a->q_stride_h;
-  kp.kv_stride_page = kv.stride_page;
-  kp.kv_stride_n = kv.stride_n;
-  kp.kv_stride_h = kv.stride_h;
-  const bool rope = a->pos_encoding_mode == FI_POS_ROPE_LLAMA;
-  // ALiBi and the logits soft cap exist in the 16x16x32 kernel only
-  const bool plain_logits = a->pos_encoding_mode != FI_POS_ALIBI && !(a->logits_soft_cap > 0.f);
-  const bool use_mfma = mfma_decode_shape(kp.group_size, a->q_dtype, kv.dtype, kv.head_dim, kv.page_size, rope) &&
-                        (plain_logits || mfma16_decode(kp.group_size, rope)) &&
-                        kv.stride_page < (1ll << 31) && kv.stride_n < (1ll << 31);
-  if (use_mfma) kp.head_tiles = ceil_div(kp.group_size, 32);
   kp.num_items = (int32_t)(padded * kv.num_kv_heads * kp.head_tiles);
   kp.kv_chunk_size = (int32_t)plan_info[FI_DP_KV_CHUNK_SIZE];
   // the kernels read the chunk size from the slot plan() refreshes (graph replay after a re-plan)
   kp.kv_chunk_size_ptr = (const int32_t*)(ib + plan_info[FI_DP_KV_CHUNK_SIZE_PTR_OFFSET]);
   kp.split_kv = split;
-  kp.window_left = a->window_left;
   // chunks were cut from the window's pages at plan(): the kernel offsets them by the same first page
   kp.plan_window_left = (int32_t)plan_info[FI_DP_WINDOW_LEFT];
   FI_REQUIRE(kp.plan_window_left < 0 || kp.plan_window_left == a->window_left,
              "batch_decode_run: window_left %d differs from the planned %d", a->window_left, kp.plan_window_left);
-  kp.q_dtype = a->q_dtype;
-  kp.use_alibi = a->pos_encoding_mode == FI_POS_ALIBI;
-  kp.logits_soft_cap = a->logits_soft_cap > 0.f ? a->logits_soft_cap : 0.f;
-  kp.sm_scale = a->sm_scale;
-  kp.rope_rcp_scale = a->rope_rcp_scale;
-  kp.rope_rcp_theta = a->rope_rcp_theta;
   if (split) {
     FI_REQUIRE(float_ws, "batch_decode_run: split-kv plan needs the float workspace");
     const size_t need = (size_t)plan_info[FI_DP_S_OFFSET] +
@@ -414,39 +450,23 @@ extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes,
   }
   // fast path: scalar page ids, no logits transform (see decode_kernel.h)
   kp.fast_path = kp.uniform_page && kp.indices && !kp.use_alibi && kp.logits_soft_cap == 0.f &&
-                 !getenv("FI_DECODE_FORCE_GENERIC");
-  if (kp.num_items > 0) {
-    const int grid = ceil_div(kp.num_items, kDecodeWaves);
-    if (use_mfma && mfma16_decode(kp.group_size, rope))
-      FI_HIP_CALL(decode_mfma16_launch(kp, a->q_dtype, kv.dtype, kv.head_dim, rope, grid, stream));
-    else if (use_mfma)
-      FI_HIP_CALL(decode_mfma_launch(kp, a->q_dtype, kv.dtype, kv.head_dim, rope, grid, stream));
-    else
-      FI_HIP_CALL(fn(kp, gt, a->pos_encoding_mode == FI_POS_ROPE_LLAMA, grid, stream));
-  }
-  if (split) {
-    // ref: VariableLengthMergeStates after the partition-kv kernel, decode.cuh:798-821
-    MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.o_indptr, a->o, a->lse, 0, kv.batch_size,
-                    a->num_qo_heads, kv.head_dim, FI_DTYPE_F32, a->q_dtype};
-    FI_HIP_CALL(launch_merge_n(mp, stream));
-  }
-  return 0;
+                 !decode_knobs().force_generic;
+  return launch_decode(kp, choice, a->q_dtype, kv.dtype, kv.head_dim, a->pos_encoding_mode == FI_POS_ROPE_LLAMA,
+                       /*merge_n=*/0, kv.batch_size, stream);
 }
 
 extern "C" FI_API int fi_single_decode_run(const fi_single_decode_params_t* a, void* tmp, size_t tmp_bytes,
                                     fi_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   FI_REQUIRE(a && a->q && a->k && a->v && a->o, "single_decode_run: null tensor");
-  FI_REQUIRE(a->q_dtype == FI_DTYPE_F16 || a->q_dtype == FI_DTYPE_BF16,
-             "single_decode_run: q dtype must be f16/bf16");
-  FI_REQUIRE(a->num_kv_heads > 0 && a->num_qo_heads % a->num_kv_heads == 0,
-             "single_decode_run: num_qo_heads must be a multiple of num_kv_heads");
   FI_REQUIRE(a->kv_len >= 0, "single_decode_run: negative kv_len");
-  decode_launch_fn fn = find_launcher(a->kv_dtype, a->head_dim);
-  FI_REQUIRE(fn, "single_decode_run: unsupported kv dtype %d / head_dim %d", a->kv_dtype,
-             a->head_dim);
-  FI_REQUIRE(a->pos_encoding_mode != FI_POS_ALIBI || a->alibi_slopes,
-             "single_decode_run: ALIBI needs alibi_slopes");
+  // The dense tensor is addressed as an identity page table of 16-token pages.
+  const int vpage = 16;
+  DecodeKernelParams kp;
+  DecodeChoice choice;
+  if (check_and_fill_decode("single_decode_run", *a, a->kv_dtype, a->head_dim, a->num_kv_heads, vpage,
+                            (int64_t)vpage * a->kv_stride_n, a->kv_stride_n, a->kv_stride_h, kp, choice))
+    return 1;
   const size_t esz = dtype_size(a->kv_dtype);
   FI_REQUIRE(((uintptr_t)a->q % 16) == 0 && (a->q_stride_h * 2) % 16 == 0,
              "single_decode_run: q rows must be 16-byte aligned");
@@ -454,38 +474,12 @@ extern "C" FI_API int fi_single_decode_run(const fi_single_decode_params_t* a, v
                  ((uintptr_t)a->k % 16) == 0 && ((uintptr_t)a->v % 16) == 0,
              "single_decode_run: k/v rows must be 16-byte aligned");
 
-  // The dense tensor is addressed as an identity page table of 16-token pages.
-  const int vpage = 16;
-  DecodeKernelParams kp;
-  memset(&kp, 0, sizeof(kp));
-  const int gt = fill_common(kp, a->kv_dtype, a->head_dim, a->num_qo_heads, a->num_kv_heads, vpage);
-  kp.q = a->q;
-  kp.o = a->o;
-  kp.lse = a->lse;
   kp.k = a->k;
   kp.v = a->v;
-  kp.alibi_slopes = a->alibi_slopes;
   kp.q_stride_n = 0;
   kp.q_stride_h = a->q_stride_h;
-  kp.kv_stride_page = (int64_t)vpage * a->kv_stride_n;
-  kp.kv_stride_n = a->kv_stride_n;
-  kp.kv_stride_h = a->kv_stride_h;
   kp.single_kv_len = a->kv_len;
-  kp.window_left = a->window_left;
   kp.plan_window_left = -1;
-  kp.q_dtype = a->q_dtype;
-  kp.use_alibi = a->pos_encoding_mode == FI_POS_ALIBI;
-  kp.logits_soft_cap = a->logits_soft_cap > 0.f ? a->logits_soft_cap : 0.f;
-  kp.sm_scale = a->sm_scale;
-  kp.rope_rcp_scale = a->rope_rcp_scale;
-  kp.rope_rcp_theta = a->rope_rcp_theta;
-
-  const bool rope = a->pos_encoding_mode == FI_POS_ROPE_LLAMA;
-  const bool plain_logits = a->pos_encoding_mode != FI_POS_ALIBI && !(a->logits_soft_cap > 0.f);
-  const bool use_mfma = mfma_decode_shape(kp.group_size, a->q_dtype, a->kv_dtype, a->head_dim, vpage, rope) &&
-                        (plain_logits || mfma16_decode(kp.group_size, rope)) &&
-                        kp.kv_stride_page < (1ll << 31);
-  if (use_mfma) kp.head_tiles = ceil_div(kp.group_size, 32);
   // split-KV so that the chip is filled (ref: decode.cuh:689-733, kv_len > 256 -> chunks >= 256)
   const int gdy = a->num_kv_heads * kp.head_tiles;
   const int max_grid = fi_num_compute_units() * decode_waves_per_cu(a->kv_dtype, false);
@@ -510,18 +504,7 @@ extern "C" FI_API int fi_single_decode_run(const fi_single_decode_params_t* a, v
     vbytes = (vbytes + 15) / 16 * 16;
     kp.tmp_lse = (float*)((char*)tmp + vbytes);
   }
-  const int grid = ceil_div(kp.num_items, kDecodeWaves);
-  if (use_mfma && mfma16_decode(kp.group_size, rope))
-    FI_HIP_CALL(decode_mfma16_launch(kp, a->q_dtype, a->kv_dtype, a->head_dim, rope, grid, stream));
-  else if (use_mfma)
-    FI_HIP_CALL(decode_mfma_launch(kp, a->q_dtype, a->kv_dtype, a->head_dim, rope, grid, stream));
-  else
-    FI_HIP_CALL(fn(kp, gt, a->pos_encoding_mode == FI_POS_ROPE_LLAMA, grid, stream));
-  if (kp.split_kv) {
-    // partial states are [nchunks, Hq, D] == dense [row=1, n=nchunks, Hq, D]
-    MergeNParams mp{kp.tmp_o, kp.tmp_lse, nullptr, a->o, a->lse, nchunks, 1,
-                    a->num_qo_heads, a->head_dim, FI_DTYPE_F32, a->q_dtype};
-    FI_HIP_CALL(launch_merge_n(mp, stream));
-  }
-  return 0;
+  // partial states are [nchunks, Hq, D] == dense [row=1, n=nchunks, Hq, D]
+  return launch_decode(kp, choice, a->q_dtype, a->kv_dtype, a->head_dim, a->pos_encoding_mode == FI_POS_ROPE_LLAMA,
+                       nchunks, /*merge_rows=*/1, stream);
 }

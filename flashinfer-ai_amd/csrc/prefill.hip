@@ -363,7 +363,23 @@ extern "C" FI_API int fi_batch_prefill_plan(
 }
 
 namespace fi {
-static int check_prefill_dtypes(const char* who, int q_dt, int kv_dt, int o_dt) {
+
+// What one prefill launch runs: the kernel instantiated for the dtypes and head_dim, or the fp8-native one.
+struct PrefillLaunch {
+  prefill_launch_fn fn;
+  bool fp8_native, rope;
+  int q_dtype, head_dim;
+};
+
+// The checks and PrefillKernelParams fields batch and single prefill share (A is fi_batch_prefill_params_t or
+// fi_single_prefill_params_t: the fields read here have the same names in both), then the kernel choice.
+template <class A>
+static int check_and_fill_prefill(const char* who, const A& a, const void* k, const void* v, int kv_dt, int head_dim,
+                                  int num_kv_heads, int page_size, int64_t stride_page, int64_t stride_n,
+                                  int64_t stride_h, int tile_q, PrefillKernelParams& kp, PrefillLaunch& launch) {
+  FI_REQUIRE(num_kv_heads > 0 && a.num_qo_heads % num_kv_heads == 0,
+             "%s: num_qo_heads must be a multiple of num_kv_heads", who);
+  const int q_dt = a.q_dtype, o_dt = a.o_dtype;
   FI_REQUIRE(o_dt == FI_DTYPE_F16 || o_dt == FI_DTYPE_BF16, "%s: output dtype must be f16/bf16", who);
   if (q_dt == FI_DTYPE_F16 || q_dt == FI_DTYPE_BF16) {
     FI_REQUIRE(o_dt == q_dt, "%s: output dtype must equal the 16-bit q dtype", who);
@@ -373,8 +389,81 @@ static int check_prefill_dtypes(const char* who, int q_dt, int kv_dt, int o_dt) 
     FI_REQUIRE((q_dt == FI_DTYPE_FP8_E4M3 || q_dt == FI_DTYPE_FP8_E5M2) && kv_dt == q_dt,
                "%s: fp8 attention needs q, k and v of one fp8 type (e4m3 or e5m2)", who);
   }
+  launch.fn = find_prefill(compute_type(q_dt, o_dt), kv_dt, q_dt, head_dim);
+  FI_REQUIRE(launch.fn, "%s: unsupported q/kv dtype %d/%d or head_dim %d", who, q_dt, kv_dt, head_dim);
+  FI_REQUIRE(a.pos_encoding_mode != FI_POS_ALIBI || a.alibi_slopes, "%s: ALIBI needs alibi_slopes", who);
+  // q, k and v are 1- or 2-byte types here, so 8 elements are 16 bytes (8 for fp8)
+  FI_REQUIRE(((uintptr_t)a.q % 16) == 0 && a.q_stride_n % 8 == 0 && a.q_stride_h % 8 == 0,
+             "%s: q rows must be aligned to 8 elements", who);
+  FI_REQUIRE(stride_n % 8 == 0 && stride_h % 8 == 0 && stride_page % 8 == 0 && ((uintptr_t)k % 16) == 0 &&
+                 ((uintptr_t)v % 16) == 0,
+             "%s: k/v rows must be aligned to 8 elements", who);
+  FI_REQUIRE(stride_page < (1ll << 31) && stride_n < (1ll << 31) && stride_page >= 0 && stride_n >= 0,
+             "%s: kv page / token strides must be below 2^31 elements", who);
+  memset(&kp, 0, sizeof(kp));
+  kp.q = a.q;
+  kp.o = a.o;
+  kp.lse = a.lse;
+  kp.k = k;
+  kp.v = v;
+  kp.alibi_slopes = a.alibi_slopes;
+  kp.scale_q = a.scale_q;
+  kp.scale_k = a.scale_k;
+  kp.scale_v = a.scale_v;
+  kp.q_stride_n = a.q_stride_n;
+  kp.q_stride_h = a.q_stride_h;
+  kp.kv_stride_page = stride_page;
+  kp.kv_stride_n = stride_n;
+  kp.kv_stride_h = stride_h;
+  kp.num_qo_heads = a.num_qo_heads;
+  kp.num_kv_heads = num_kv_heads;
+  kp.group_size = a.num_qo_heads / num_kv_heads;
+  kp.page_size = page_size;
+  kp.page_div = FastDiv((uint32_t)page_size);
+  kp.group_div = FastDiv((uint32_t)kp.group_size);
+  // multi-item scoring is causal plus the per-item predicate (ref: prefill.cuh:845-856); plan() must have
+  // been called with causal = true so that the kv range of a q tile ends at its last row
+  kp.causal = a.mask_mode == FI_MASK_CAUSAL || a.mask_mode == FI_MASK_MULTIITEMSCORING;
+  if (a.mask_mode == FI_MASK_CUSTOM) kp.custom_mask = a.custom_mask;
+  kp.window_left = a.window_left;
+  kp.use_alibi = a.pos_encoding_mode == FI_POS_ALIBI;
+  kp.o_dtype = o_dt;
+  kp.fp8_p_quant = q_dt == FI_DTYPE_FP8_E4M3 || q_dt == FI_DTYPE_FP8_E5M2;
+  kp.logits_soft_cap = a.logits_soft_cap > 0.f ? a.logits_soft_cap : 0.f;
+  kp.sm_scale = a.sm_scale;
+  kp.rope_rcp_scale = a.rope_rcp_scale;
+  kp.rope_rcp_theta = a.rope_rcp_theta;
+  kp.bf16_pv_mode = a.bf16_pv_mode;
+  kp.tile_q = tile_q;
+  launch.rope = a.pos_encoding_mode == FI_POS_ROPE_LLAMA;
+  launch.fp8_native = use_fp8_native(kp, q_dt, kv_dt, head_dim, launch.rope);
+  launch.q_dtype = q_dt;
+  launch.head_dim = head_dim;
+  FI_REQUIRE(kp.tile_q == kTileQ || launch.fp8_native,
+             "%s: the plan was cut for %d-row q tiles (fi_batch_prefill_plan_tile), which only the fp8-native kernel "
+             "runs: fp8 q/k/v of one type, head_dim 128, no RoPE / ALiBi / soft cap / window / mask",
+             who, kp.tile_q);
   return 0;
 }
+
+// The kernel, then for a split kv axis (kp.tmp_o set) the n-way merge of the partial states of merge_rows query
+// rows: ragged over kp.merge_indptr (batch), or kp.num_kv_chunks per row (single).
+static int launch_prefill(const PrefillKernelParams& kp, const PrefillLaunch& launch, int32_t merge_rows,
+                          hipStream_t stream) {
+  if (launch.fp8_native)
+    FI_HIP_CALL(prefill_fp8_launch(kp, kp.o_dtype, launch.q_dtype == FI_DTYPE_FP8_E5M2, launch.head_dim, stream));
+  else
+    FI_HIP_CALL(launch.fn(kp, launch.rope, stream));
+  if (kp.tmp_o) {
+    // ref: VariableLengthMergeStates after the partition-kv kernel, prefill.cuh:2590-2671; the padding rows of a
+    // graph plan have no entries and are left alone
+    MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.merge_indptr, kp.o, kp.lse, kp.num_kv_chunks, merge_rows,
+                    kp.num_qo_heads, launch.head_dim, FI_DTYPE_F32, kp.o_dtype, /*skip_empty=*/kp.merge_indptr != nullptr};
+    FI_HIP_CALL(launch_merge_n(mp, stream));
+  }
+  return 0;
+}
+
 }  // namespace fi
 
 extern "C" FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws_bytes, void* int_ws,
@@ -383,7 +472,6 @@ extern "C" FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws
                                                  const fi_batch_prefill_params_t* a,
                                                  fi_stream_t stream_) {
   (void)int_ws_bytes;
-  hipStream_t stream = (hipStream_t)stream_;
   FI_REQUIRE(plan_info && plan_info_len == FI_PREFILL_PLAN_INFO_LEN &&
                  plan_info[FI_PP_MAGIC] == FI_PREFILL_PLAN_MAGIC,
              "batch_prefill_paged_run: plan_info is not a prefill plan (call plan() first)");
@@ -396,8 +484,6 @@ extern "C" FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws
              "batch_prefill_paged_run: null tensor");
   FI_REQUIRE(kv.last_page_len || !kv.indices, "batch_prefill_paged_run: a page table needs last_page_len");
   FI_REQUIRE(kv.batch_size == plan_info[FI_PP_BATCH_SIZE], "batch_prefill_paged_run: batch size differs from the plan");
-  FI_REQUIRE(kv.num_kv_heads > 0 && a->num_qo_heads % kv.num_kv_heads == 0,
-             "batch_prefill_paged_run: num_qo_heads must be a multiple of num_kv_heads");
   FI_REQUIRE(a->mask_mode >= FI_MASK_NON_CAUSAL && a->mask_mode <= FI_MASK_MULTIITEMSCORING,
              "batch_prefill_paged_run: bad mask_mode %d", a->mask_mode);
   FI_REQUIRE(a->mask_mode != FI_MASK_CUSTOM || (a->custom_mask && a->mask_indptr),
@@ -409,39 +495,19 @@ extern "C" FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws
   FI_REQUIRE(a->mask_mode != FI_MASK_MULTIITEMSCORING ||
                  (a->q_dtype == FI_DTYPE_F16 || a->q_dtype == FI_DTYPE_BF16),
              "batch_prefill_paged_run: multi-item scoring needs 16-bit queries");
-  if (check_prefill_dtypes("batch_prefill_paged_run", a->q_dtype, kv.dtype, a->o_dtype)) return 1;
-  const int t16 = compute_type(a->q_dtype, a->o_dtype);
-  prefill_launch_fn fn = find_prefill(t16, kv.dtype, a->q_dtype, kv.head_dim);
-  FI_REQUIRE(fn, "batch_prefill_paged_run: unsupported q/kv dtype %d/%d or head_dim %d", a->q_dtype,
-             kv.dtype, kv.head_dim);
-  FI_REQUIRE(a->pos_encoding_mode != FI_POS_ALIBI || a->alibi_slopes,
-             "batch_prefill_paged_run: ALIBI needs alibi_slopes");
-  const size_t qsz = dtype_size(a->q_dtype), ksz = dtype_size(kv.dtype);
-  FI_REQUIRE(((uintptr_t)a->q % 16) == 0 && (a->q_stride_n * qsz) % 8 == 0 &&
-                 (a->q_stride_h * qsz) % 8 == 0 && (qsz == 1 || ((a->q_stride_n * qsz) % 16 == 0 && (a->q_stride_h * qsz) % 16 == 0)),
-             "batch_prefill_paged_run: q rows must be 16-byte (8-byte for fp8) aligned");
-  FI_REQUIRE((kv.stride_n * ksz) % (8 * ksz) == 0 && (kv.stride_h * ksz) % (8 * ksz) == 0 &&
-                 (kv.stride_page * ksz) % (8 * ksz) == 0 && ((uintptr_t)kv.k_data % 16) == 0 &&
-                 ((uintptr_t)kv.v_data % 16) == 0,
-             "batch_prefill_paged_run: kv cache rows must be aligned to 8 elements");
-
-  FI_REQUIRE(kv.stride_page < (1ll << 31) && kv.stride_n < (1ll << 31) && kv.stride_page >= 0 && kv.stride_n >= 0,
-             "batch_prefill_paged_run: kv page / token strides must be below 2^31 elements");
   PrefillKernelParams kp;
-  memset(&kp, 0, sizeof(kp));
-  kp.q = a->q;
-  kp.o = a->o;
-  kp.lse = a->lse;
-  kp.k = kv.k_data;
-  kp.v = kv.v_data;
+  PrefillLaunch launch;
+  if (check_and_fill_prefill("batch_prefill_paged_run", *a, kv.k_data, kv.v_data, kv.dtype, kv.head_dim,
+                             kv.num_kv_heads, kv.page_size, kv.stride_page, kv.stride_n, kv.stride_h,
+                             (int)plan_info[FI_PP_CTA_TILE_Q], kp, launch))
+    return 1;
   kp.qo_indptr = a->qo_indptr;
   kp.kv_indptr = kv.indptr;
   kp.kv_indices = kv.indices;
   kp.kv_last_page_len = kv.last_page_len;
   kp.request_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_REQUEST_INDICES_OFFSET]);
   kp.qo_tile_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_QO_TILE_INDICES_OFFSET]);
-  const bool split = plan_info[FI_PP_SPLIT_KV] != 0;
-  if (split) {
+  if (plan_info[FI_PP_SPLIT_KV]) {
     FI_REQUIRE(float_ws, "batch_prefill_paged_run: a split-kv plan needs the float workspace");
     FI_REQUIRE((size_t)plan_info[FI_PP_V_OFFSET] <= float_ws_bytes,
                "batch_prefill_paged_run: float workspace smaller than at plan()");
@@ -452,130 +518,35 @@ extern "C" FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws
     kp.kv_chunk_size = (int32_t)plan_info[FI_PP_KV_CHUNK_SIZE];
     kp.kv_chunk_size_ptr = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_KV_CHUNK_SIZE_PTR_OFFSET]);
   }
-  kp.alibi_slopes = a->alibi_slopes;
-  kp.scale_q = a->scale_q;
-  kp.scale_k = a->scale_k;
-  kp.scale_v = a->scale_v;
-  kp.q_stride_n = a->q_stride_n;
-  kp.q_stride_h = a->q_stride_h;
-  kp.kv_stride_page = kv.stride_page;
-  kp.kv_stride_n = kv.stride_n;
-  kp.kv_stride_h = kv.stride_h;
   kp.num_work = (int32_t)num_work;
-  kp.num_qo_heads = a->num_qo_heads;
-  kp.num_kv_heads = kv.num_kv_heads;
-  kp.group_size = a->num_qo_heads / kv.num_kv_heads;
-  kp.page_size = kv.page_size;
-  kp.page_div = FastDiv((uint32_t)kv.page_size);
-  kp.group_div = FastDiv((uint32_t)kp.group_size);
-  // multi-item scoring is causal plus the per-item predicate (ref: prefill.cuh:845-856); plan() must have
-  // been called with causal = true so that the kv range of a q tile ends at its last row
-  kp.causal = a->mask_mode == FI_MASK_CAUSAL || a->mask_mode == FI_MASK_MULTIITEMSCORING;
-  if (a->mask_mode == FI_MASK_CUSTOM) {
-    kp.custom_mask = a->custom_mask;
-    kp.mask_indptr = a->mask_indptr;
-  }
+  if (a->mask_mode == FI_MASK_CUSTOM) kp.mask_indptr = a->mask_indptr;
   if (a->mask_mode == FI_MASK_MULTIITEMSCORING) {
     kp.prefix_len_ptr = a->prefix_len_ptr;
     kp.token_pos_in_items_ptr = a->token_pos_in_items_ptr;
     kp.token_pos_in_items_len = a->token_pos_in_items_len;
   }
-  kp.window_left = a->window_left;
-  kp.use_alibi = a->pos_encoding_mode == FI_POS_ALIBI;
-  kp.o_dtype = a->o_dtype;
-  kp.fp8_p_quant = a->q_dtype == FI_DTYPE_FP8_E4M3 || a->q_dtype == FI_DTYPE_FP8_E5M2;
-  kp.logits_soft_cap = a->logits_soft_cap > 0.f ? a->logits_soft_cap : 0.f;
-  kp.sm_scale = a->sm_scale;
-  kp.rope_rcp_scale = a->rope_rcp_scale;
-  kp.rope_rcp_theta = a->rope_rcp_theta;
-  kp.bf16_pv_mode = a->bf16_pv_mode;
-  kp.tile_q = (int32_t)plan_info[FI_PP_CTA_TILE_Q];
-  const bool fp8_native = use_fp8_native(kp, a->q_dtype, kv.dtype, kv.head_dim, a->pos_encoding_mode == FI_POS_ROPE_LLAMA);
-  FI_REQUIRE(kp.tile_q == kTileQ || fp8_native,
-             "batch_prefill_paged_run: the plan was cut for %d-row q tiles (fi_batch_prefill_plan_tile), which only "
-             "the fp8-native kernel runs: fp8 q/k/v of one type, head_dim 128, no RoPE / ALiBi / soft cap / window / mask",
-             kp.tile_q);
-  if (fp8_native) {
-    FI_HIP_CALL(prefill_fp8_launch(kp, a->o_dtype, a->q_dtype == FI_DTYPE_FP8_E5M2, kv.head_dim, stream));
-  } else {
-    FI_HIP_CALL(fn(kp, a->pos_encoding_mode == FI_POS_ROPE_LLAMA, stream));
-  }
-  if (split) {
-    // ref: VariableLengthMergeStates after the partition-kv kernel, prefill.cuh:2590-2671
-    MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.merge_indptr, a->o, a->lse, 0,
-                    (int32_t)plan_info[FI_PP_TOTAL_NUM_ROWS], a->num_qo_heads, kv.head_dim, FI_DTYPE_F32,
-                    a->o_dtype, /*skip_empty=*/1};
-    FI_HIP_CALL(launch_merge_n(mp, stream));
-  }
-  return 0;
+  return launch_prefill(kp, launch, (int32_t)plan_info[FI_PP_TOTAL_NUM_ROWS], (hipStream_t)stream_);
 }
 
 extern "C" FI_API int fi_single_prefill_run(const fi_single_prefill_params_t* a, void* tmp,
                                             size_t tmp_bytes, fi_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   FI_REQUIRE(a, "single_prefill_run: null params");
   if (a->qo_len == 0) return 0;
   FI_REQUIRE(a->q && a->k && a->v && a->o, "single_prefill_run: null tensor");
-  FI_REQUIRE(a->num_kv_heads > 0 && a->num_qo_heads % a->num_kv_heads == 0,
-             "single_prefill_run: num_qo_heads must be a multiple of num_kv_heads");
   FI_REQUIRE(a->mask_mode >= FI_MASK_NON_CAUSAL && a->mask_mode <= FI_MASK_CUSTOM,
              "single_prefill_run: bad mask_mode %d", a->mask_mode);
   FI_REQUIRE(a->mask_mode != FI_MASK_CUSTOM || a->custom_mask,
              "single_prefill_run: mask_mode CUSTOM needs custom_mask");
-  if (check_prefill_dtypes("single_prefill_run", a->q_dtype, a->kv_dtype, a->o_dtype)) return 1;
-  const int t16 = compute_type(a->q_dtype, a->o_dtype);
-  prefill_launch_fn fn = find_prefill(t16, a->kv_dtype, a->q_dtype, a->head_dim);
-  FI_REQUIRE(fn, "single_prefill_run: unsupported q/kv dtype %d/%d or head_dim %d", a->q_dtype,
-             a->kv_dtype, a->head_dim);
-  FI_REQUIRE(a->pos_encoding_mode != FI_POS_ALIBI || a->alibi_slopes,
-             "single_prefill_run: ALIBI needs alibi_slopes");
-  const size_t qsz = dtype_size(a->q_dtype), ksz = dtype_size(a->kv_dtype);
-  FI_REQUIRE(((uintptr_t)a->q % 16) == 0 && (a->q_stride_n * qsz) % (8 * qsz) == 0 &&
-                 (a->q_stride_h * qsz) % (8 * qsz) == 0,
-             "single_prefill_run: q rows must be aligned to 8 elements");
-  FI_REQUIRE((a->kv_stride_n * ksz) % (8 * ksz) == 0 && (a->kv_stride_h * ksz) % (8 * ksz) == 0 &&
-                 ((uintptr_t)a->k % 16) == 0 && ((uintptr_t)a->v % 16) == 0,
-             "single_prefill_run: k/v rows must be aligned to 8 elements");
-  const int vpage = 16;  // dense tensor == identity page table of 16-token pages
-  FI_REQUIRE(a->kv_stride_n >= 0 && (int64_t)vpage * a->kv_stride_n < (1ll << 31),
-             "single_prefill_run: kv token stride must be below 2^27 elements");
+  // the dense k / v are an identity page table of 16-token pages
+  const int vpage = 16;
   PrefillKernelParams kp;
-  memset(&kp, 0, sizeof(kp));
-  kp.q = a->q;
-  kp.o = a->o;
-  kp.lse = a->lse;
-  kp.k = a->k;
-  kp.v = a->v;
-  kp.alibi_slopes = a->alibi_slopes;
-  kp.scale_q = a->scale_q;
-  kp.scale_k = a->scale_k;
-  kp.scale_v = a->scale_v;
-  kp.q_stride_n = a->q_stride_n;
-  kp.q_stride_h = a->q_stride_h;
-  kp.kv_stride_page = (int64_t)vpage * a->kv_stride_n;
-  kp.kv_stride_n = a->kv_stride_n;
-  kp.kv_stride_h = a->kv_stride_h;
-  kp.num_qo_heads = a->num_qo_heads;
-  kp.num_kv_heads = a->num_kv_heads;
-  kp.group_size = a->num_qo_heads / a->num_kv_heads;
-  kp.tile_q = kTileQ;
+  PrefillLaunch launch;
+  if (check_and_fill_prefill("single_prefill_run", *a, a->k, a->v, a->kv_dtype, a->head_dim, a->num_kv_heads, vpage,
+                             (int64_t)vpage * a->kv_stride_n, a->kv_stride_n, a->kv_stride_h, kTileQ, kp, launch))
+    return 1;
   kp.num_work = (int32_t)ceil_div<int64_t>((int64_t)a->qo_len * kp.group_size, kTileQ);
-  kp.page_size = vpage;
-  kp.page_div = FastDiv((uint32_t)vpage);
-  kp.group_div = FastDiv((uint32_t)kp.group_size);
   kp.single_qo_len = a->qo_len;
   kp.single_kv_len = a->kv_len;
-  kp.causal = a->mask_mode == FI_MASK_CAUSAL;
-  if (a->mask_mode == FI_MASK_CUSTOM) kp.custom_mask = a->custom_mask;
-  kp.window_left = a->window_left;
-  kp.use_alibi = a->pos_encoding_mode == FI_POS_ALIBI;
-  kp.o_dtype = a->o_dtype;
-  kp.fp8_p_quant = a->q_dtype == FI_DTYPE_FP8_E4M3 || a->q_dtype == FI_DTYPE_FP8_E5M2;
-  kp.logits_soft_cap = a->logits_soft_cap > 0.f ? a->logits_soft_cap : 0.f;
-  kp.sm_scale = a->sm_scale;
-  kp.rope_rcp_scale = a->rope_rcp_scale;
-  kp.rope_rcp_theta = a->rope_rcp_theta;
-  kp.bf16_pv_mode = a->bf16_pv_mode;
   // split the kv axis when the q tiles alone cannot fill the chip and the caller lent a scratch buffer
   // (same search as the batch planner; ref: PrefillBinarySearchKVChunkSize, scheduler.cuh:101-130)
   if (tmp && tmp_bytes > 0 && a->mask_mode != FI_MASK_CUSTOM) {
@@ -611,16 +582,6 @@ extern "C" FI_API int fi_single_prefill_run(const fi_single_prefill_params_t* a,
       kp.tmp_lse = (float*)((char*)tmp + vbytes);
     }
   }
-  if (use_fp8_native(kp, a->q_dtype, a->kv_dtype, a->head_dim, a->pos_encoding_mode == FI_POS_ROPE_LLAMA)) {
-    FI_HIP_CALL(prefill_fp8_launch(kp, a->o_dtype, a->q_dtype == FI_DTYPE_FP8_E5M2, a->head_dim, stream));
-  } else {
-    FI_HIP_CALL(fn(kp, a->pos_encoding_mode == FI_POS_ROPE_LLAMA, stream));
-  }
-  if (kp.num_kv_chunks > 1) {
-    // partial states are [qo_len, chunks, Hq, D]: the dense n-way merge
-    MergeNParams mp{kp.tmp_o, kp.tmp_lse, nullptr, a->o, a->lse, kp.num_kv_chunks, a->qo_len, a->num_qo_heads,
-                    a->head_dim, FI_DTYPE_F32, a->o_dtype, 0};
-    FI_HIP_CALL(launch_merge_n(mp, stream));
-  }
-  return 0;
+  // partial states are [qo_len, chunks, Hq, D]: the dense n-way merge
+  return launch_prefill(kp, launch, a->qo_len, (hipStream_t)stream_);
 }

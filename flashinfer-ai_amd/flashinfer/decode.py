@@ -9,7 +9,6 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-import math
 from typing import Any, List, Optional, Tuple, Union
 
 import torch
@@ -25,6 +24,7 @@ from .utils import (
     _get_cache_alibi_slopes_buf,
     _get_cache_buf,
     _get_range_buf,
+    _resolve_logits_params,
     _unpack_paged_kv_cache,
     canonicalize_torch_dtype,
     check_shape_dtype_device,
@@ -127,18 +127,6 @@ def single_decode_with_kv_cache(
         raise ValueError("q must be [num_qo_heads, head_dim]; k and v must be 3-D with equal shapes")
     head_dim = q.shape[-1]
     num_qo_heads = q.shape[0]
-    if logits_soft_cap is None:
-        logits_soft_cap = 0.0
-    if sm_scale is None:
-        sm_scale = 1.0 / math.sqrt(head_dim)
-    if q_scale is not None:
-        sm_scale *= q_scale
-    if k_scale is not None:
-        sm_scale *= k_scale
-    if rope_scale is None:
-        rope_scale = 1.0
-    if rope_theta is None:
-        rope_theta = 1e4
     if kv_layout == "NHD":
         kv_len, num_kv_heads = k.shape[0], k.shape[1]
         stride_n, stride_h = k.stride(0), k.stride(1)
@@ -165,8 +153,8 @@ def single_decode_with_kv_cache(
         alibi_slopes=_lib.ptr(alibi), kv_len=kv_len, num_qo_heads=num_qo_heads,
         num_kv_heads=num_kv_heads, head_dim=head_dim, q_dtype=_lib.fi_dtype(q.dtype),
         kv_dtype=_lib.fi_dtype(k.dtype), pos_encoding_mode=PosEncodingMode[pos_encoding_mode].value,
-        window_left=window_left, logits_soft_cap=logits_soft_cap, sm_scale=sm_scale,
-        rope_rcp_scale=1.0 / rope_scale, rope_rcp_theta=1.0 / rope_theta,
+        window_left=window_left,
+        **_resolve_logits_params(head_dim, sm_scale, q_scale, k_scale, logits_soft_cap, rope_scale, rope_theta),
     )
     with torch.cuda.device(q.device):
         _lib.check(
@@ -521,22 +509,6 @@ class BatchDecodeWithPagedKVCacheWrapper:
         )
         pos_encoding_mode = self._pos_encoding_mode
         _check_pos_encoding_mode(pos_encoding_mode)
-        logits_soft_cap = self._logits_soft_cap
-        sm_scale = self._sm_scale
-        rope_scale = self._rope_scale
-        rope_theta = self._rope_theta
-        if logits_soft_cap is None:
-            logits_soft_cap = 0.0
-        if sm_scale is None:
-            sm_scale = 1.0 / math.sqrt(q.shape[-1])
-        if q_scale is not None:
-            sm_scale *= q_scale
-        if k_scale is not None:
-            sm_scale *= k_scale
-        if rope_scale is None:
-            rope_scale = 1.0
-        if rope_theta is None:
-            rope_theta = 1e4
         if q.dim() != 3 or q.shape[0] != self._batch_size or q.shape[1] != self._num_qo_heads:
             raise ValueError(
                 f"q must have shape [{self._batch_size}, {self._num_qo_heads}, head_dim], got {tuple(q.shape)}"
@@ -569,8 +541,9 @@ class BatchDecodeWithPagedKVCacheWrapper:
             o=out.data_ptr(), lse=_lib.ptr(lse),
             alibi_slopes=_lib.ptr(alibi), q_rope_offset=None, num_qo_heads=self._num_qo_heads,
             q_dtype=_lib.fi_dtype(q.dtype), pos_encoding_mode=PosEncodingMode[pos_encoding_mode].value,
-            window_left=self._window_left, logits_soft_cap=logits_soft_cap, sm_scale=sm_scale,
-            rope_rcp_scale=1.0 / rope_scale, rope_rcp_theta=1.0 / rope_theta,
+            window_left=self._window_left,
+            **_resolve_logits_params(q.shape[-1], self._sm_scale, q_scale, k_scale, self._logits_soft_cap,
+                                     self._rope_scale, self._rope_theta),
         )
         self._fws_ptr = self._float_workspace_buffer.data_ptr()
         self._fws_bytes = self._float_workspace_buffer.numel() * self._float_workspace_buffer.element_size()

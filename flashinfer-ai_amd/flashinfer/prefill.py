@@ -9,7 +9,6 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-import math
 import os
 from typing import Any, List, Optional, Tuple, Union
 
@@ -26,6 +25,7 @@ from .utils import (
     _check_pos_encoding_mode,
     _get_cache_alibi_slopes_buf,
     _get_cache_buf,
+    _resolve_logits_params,
     _unpack_paged_kv_cache,
     canonicalize_torch_dtype,
     check_shape_dtype_device,
@@ -151,6 +151,55 @@ def _plan_custom_mask(wrapper, custom_mask, packed_custom_mask, qo_indptr_host, 
     return packed_custom_mask.contiguous(), mask_indptr.contiguous()
 
 
+def _run_batch_prefill(wrapper, name, q, kv, o_dtype, out, lse, return_lse, window_left, q_scale, k_scale, v_scale,
+                       scale_q=None, scale_k=None, scale_v=None):
+    """run() of the paged and ragged wrappers once the kv view ``kv`` (a ``_lib.PagedKV``; ragged: an identity table
+    of one-token pages) is resolved and checked against the plan: out / lse, fi_batch_prefill_paged_run, v_scale."""
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    if return_lse:
+        if lse is None:
+            lse = torch.empty((q.size(0), q.size(1)), dtype=torch.float32, device=q.device)
+        else:
+            check_shape_dtype_device(lse, (q.size(0), q.size(1)), torch.float32, q.device, "lse")
+    out_shape = q.shape[:-1] + (kv.head_dim,)
+    if out is None:
+        out = torch.empty(out_shape, dtype=o_dtype, device=q.device)
+    else:
+        check_shape_dtype_device(out, out_shape, o_dtype, q.device, "out")
+    alibi = _get_cache_alibi_slopes_buf(q.shape[1], q.device) if wrapper._pos_encoding_mode == "ALIBI" else None
+    params = _lib.BatchPrefillParams(
+        q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), qo_indptr=wrapper._qo_indptr_buf.data_ptr(),
+        kv=kv, o=out.data_ptr(), lse=_lib.ptr(lse) if return_lse else None, alibi_slopes=_lib.ptr(alibi),
+        scale_q=_lib.ptr(scale_q), scale_k=_lib.ptr(scale_k), scale_v=_lib.ptr(scale_v),
+        num_qo_heads=wrapper._num_qo_heads, q_dtype=_lib.fi_dtype(q.dtype), o_dtype=_lib.fi_dtype(o_dtype),
+        custom_mask=_lib.ptr(wrapper._custom_mask_buf), mask_indptr=_lib.ptr(wrapper._mask_indptr_buf),
+        prefix_len_ptr=_lib.ptr(wrapper._prefix_len_ptr),
+        token_pos_in_items_ptr=_lib.ptr(wrapper._token_pos_in_items_ptr),
+        max_item_len_ptr=_lib.ptr(wrapper._max_item_len_ptr), token_pos_in_items_len=wrapper._token_pos_in_items_len,
+        mask_mode=_mask_mode(wrapper), pos_encoding_mode=PosEncodingMode[wrapper._pos_encoding_mode].value,
+        window_left=window_left, bf16_pv_mode=getattr(wrapper, "_bf16_pv_mode", 0),
+        **_resolve_logits_params(q.size(-1), wrapper._sm_scale, q_scale, k_scale, wrapper._logits_soft_cap,
+                                 wrapper._rope_scale, wrapper._rope_theta),
+    )
+    fws = wrapper._float_workspace_buffer
+    with torch.cuda.device(q.device):
+        _lib.check(
+            _lib.lib().fi_batch_prefill_paged_run(
+                fws.data_ptr(), fws.numel() * fws.element_size(), wrapper._int_workspace_buffer.data_ptr(),
+                wrapper._int_workspace_buffer.numel(), wrapper._plan_info_c, _lib.FI_PREFILL_PLAN_INFO_LEN,
+                C.byref(params), _lib.current_stream(q.device),
+            ),
+            name,
+        )
+    if v_scale is not None:
+        if is_float8(out):
+            out = (out.to(torch.float32) * v_scale).to(out.dtype)
+        else:
+            out *= v_scale
+    return (out, lse) if return_lse else out
+
+
 def single_prefill_with_kv_cache(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -203,14 +252,6 @@ def single_prefill_with_kv_cache(
         _lib.require_gpu_tensor(t, name)
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape:
         raise ValueError("q must be [qo_len, num_qo_heads, head_dim]; k, v 3-D with equal shapes")
-    if logits_soft_cap is None:
-        logits_soft_cap = 0.0
-    if sm_scale is None:
-        sm_scale = 1.0 / math.sqrt(q.size(-1))
-    if rope_scale is None:
-        rope_scale = 1.0
-    if rope_theta is None:
-        rope_theta = 1e4
     qo_len, num_qo_heads, head_dim = q.shape
     if kv_layout == "NHD":
         kv_len, num_kv_heads = k.shape[0], k.shape[1]
@@ -254,8 +295,8 @@ def single_prefill_with_kv_cache(
         mask_mode=(MaskMode.CUSTOM.value if packed_custom_mask is not None
                    else MaskMode.CAUSAL.value if causal else MaskMode.NON_CAUSAL.value),
         pos_encoding_mode=PosEncodingMode[pos_encoding_mode].value, window_left=window_left,
-        logits_soft_cap=logits_soft_cap, sm_scale=sm_scale, rope_rcp_scale=1.0 / rope_scale,
-        rope_rcp_theta=1.0 / rope_theta, bf16_pv_mode=1 if bf16_pv_exact_range else 0,
+        bf16_pv_mode=1 if bf16_pv_exact_range else 0,
+        **_resolve_logits_params(head_dim, sm_scale, None, None, logits_soft_cap, rope_scale, rope_theta),
     )
     # scratch for split-KV partial states (ref: the 32 MB cached buffer of single_prefill, prefill.py:1125)
     tmp = _get_cache_buf("single_prefill_with_kv_cache_tmp", 32 * 1024 * 1024, q.device)
@@ -569,22 +610,6 @@ class BatchPrefillWithPagedKVCacheWrapper:
         )
         window_left = self._window_left if window_left is None else window_left
         assert window_left == self._window_left
-        logits_soft_cap = self._logits_soft_cap
-        sm_scale = self._sm_scale
-        rope_scale = self._rope_scale
-        rope_theta = self._rope_theta
-        if logits_soft_cap is None:
-            logits_soft_cap = 0.0
-        if sm_scale is None:
-            sm_scale = 1.0 / math.sqrt(q.size(-1))
-        if q_scale is not None:
-            sm_scale *= q_scale
-        if k_scale is not None:
-            sm_scale *= k_scale
-        if rope_scale is None:
-            rope_scale = 1.0
-        if rope_theta is None:
-            rope_theta = 1e4
         if q.dim() != 3 or q.shape[0] != self._total_num_rows or q.shape[1] != self._num_qo_heads:
             raise ValueError(
                 f"q must have shape [{self._total_num_rows}, {self._num_qo_heads}, head_dim], got {tuple(q.shape)}"
@@ -593,67 +618,21 @@ class BatchPrefillWithPagedKVCacheWrapper:
             raise ValueError("head_dim of q / kv cache does not match the planned head_dim")
         if num_kv_heads != self._num_kv_heads or page_size != self._page_size:
             raise ValueError("kv cache shape does not match the planned num_kv_heads / page_size")
-        if q.stride(-1) != 1:
-            q = q.contiguous()
-        o_dtype = self._cached_o_data_type
-        if return_lse:
-            if lse is None:
-                lse = torch.empty((q.size(0), q.size(1)), dtype=torch.float32, device=q.device)
-            else:
-                check_shape_dtype_device(lse, (q.size(0), q.size(1)), torch.float32, q.device, "lse")
-        out_shape = q.shape[:-1] + v_cache.shape[-1:]
-        if out is None:
-            out = torch.empty(out_shape, dtype=o_dtype, device=q.device)
-        else:
-            check_shape_dtype_device(out, out_shape, o_dtype, q.device, "out")
-            if not out.is_contiguous():
-                raise ValueError("out must be contiguous")
-        # missing scales are NULL pointers (= 1 in the kernels): run() creates no tensor and stays capturable
-        scale_q = _scale_tensor(scale_q, self._num_qo_heads, q.device)
-        scale_k = _scale_tensor(scale_k, num_kv_heads, q.device)
-        scale_v = _scale_tensor(scale_v, num_kv_heads, q.device)
-        alibi = None
-        if self._pos_encoding_mode == "ALIBI":
-            alibi = _get_cache_alibi_slopes_buf(q.shape[1], q.device)
-        params = _lib.BatchPrefillParams(
-            q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1),
-            qo_indptr=self._qo_indptr_buf.data_ptr(),
-            kv=_lib.PagedKV(
-                k_data=k_cache.data_ptr(), v_data=v_cache.data_ptr(),
-                indptr=self._paged_kv_indptr_buf.data_ptr(), indices=self._paged_kv_indices_buf.data_ptr(),
-                last_page_len=self._paged_kv_last_page_len_buf.data_ptr(), rope_pos_offset=None,
-                stride_page=stride_page, stride_n=stride_n, stride_h=stride_h, page_size=page_size,
-                num_kv_heads=num_kv_heads, head_dim=head_dim, batch_size=self._batch_size,
-                dtype=_lib.fi_dtype(k_cache.dtype),
-            ),
-            o=out.data_ptr(), lse=_lib.ptr(lse) if return_lse else None, alibi_slopes=_lib.ptr(alibi),
-            scale_q=_lib.ptr(scale_q), scale_k=_lib.ptr(scale_k), scale_v=_lib.ptr(scale_v),
-            num_qo_heads=self._num_qo_heads, q_dtype=_lib.fi_dtype(q.dtype), o_dtype=_lib.fi_dtype(o_dtype),
-            custom_mask=_lib.ptr(self._custom_mask_buf), mask_indptr=_lib.ptr(self._mask_indptr_buf),
-            prefix_len_ptr=_lib.ptr(self._prefix_len_ptr), token_pos_in_items_ptr=_lib.ptr(self._token_pos_in_items_ptr),
-            max_item_len_ptr=_lib.ptr(self._max_item_len_ptr), token_pos_in_items_len=self._token_pos_in_items_len,
-            mask_mode=_mask_mode(self),
-            pos_encoding_mode=PosEncodingMode[self._pos_encoding_mode].value, window_left=window_left,
-            logits_soft_cap=logits_soft_cap, sm_scale=sm_scale, rope_rcp_scale=1.0 / rope_scale,
-            rope_rcp_theta=1.0 / rope_theta, bf16_pv_mode=getattr(self, "_bf16_pv_mode", 0),
+        if out is not None and not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+        kv = _lib.PagedKV(
+            k_data=k_cache.data_ptr(), v_data=v_cache.data_ptr(),
+            indptr=self._paged_kv_indptr_buf.data_ptr(), indices=self._paged_kv_indices_buf.data_ptr(),
+            last_page_len=self._paged_kv_last_page_len_buf.data_ptr(), rope_pos_offset=None,
+            stride_page=stride_page, stride_n=stride_n, stride_h=stride_h, page_size=page_size,
+            num_kv_heads=num_kv_heads, head_dim=head_dim, batch_size=self._batch_size,
+            dtype=_lib.fi_dtype(k_cache.dtype),
         )
-        with torch.cuda.device(q.device):
-            _lib.check(
-                _lib.lib().fi_batch_prefill_paged_run(
-                    self._float_workspace_buffer.data_ptr(),
-                    self._float_workspace_buffer.numel() * self._float_workspace_buffer.element_size(),
-                    self._int_workspace_buffer.data_ptr(), self._int_workspace_buffer.numel(),
-                    self._plan_info_c, _lib.FI_PREFILL_PLAN_INFO_LEN, C.byref(params),
-                    _lib.current_stream(q.device),
-                ),
-                "BatchPrefillWithPagedKVCacheWrapper.run",
-            )
-        if v_scale is not None:
-            if is_float8(out):
-                out = (out.to(torch.float32) * v_scale).to(out.dtype)
-            else:
-                out *= v_scale
-        return (out, lse) if return_lse else out
+        # missing scales are NULL pointers (= 1 in the kernels): run() creates no tensor and stays capturable
+        return _run_batch_prefill(
+            self, "BatchPrefillWithPagedKVCacheWrapper.run", q, kv, self._cached_o_data_type, out, lse, return_lse,
+            window_left, q_scale, k_scale, v_scale, _scale_tensor(scale_q, self._num_qo_heads, q.device),
+            _scale_tensor(scale_k, num_kv_heads, q.device), _scale_tensor(scale_v, num_kv_heads, q.device))
 
     run_return_lse = functools.partialmethod(run, return_lse=True)
 
@@ -874,58 +853,14 @@ class BatchPrefillWithRaggedKVCacheWrapper:
             raise ValueError("k/v shape does not match the plan")
         if q.dim() != 3 or q.shape[0] != self._total_num_rows or q.shape[1] != self._num_qo_heads:
             raise ValueError("q shape does not match the plan")
-        if q.stride(-1) != 1:
-            q = q.contiguous()
-        logits_soft_cap = self._logits_soft_cap or 0.0
-        sm_scale = self._sm_scale if self._sm_scale is not None else 1.0 / math.sqrt(q.size(-1))
-        if q_scale is not None:
-            sm_scale *= q_scale
-        if k_scale is not None:
-            sm_scale *= k_scale
-        rope_scale = self._rope_scale or 1.0
-        rope_theta = self._rope_theta or 1e4
-        if return_lse:
-            if lse is None:
-                lse = torch.empty((q.size(0), q.size(1)), dtype=torch.float32, device=q.device)
-            else:
-                check_shape_dtype_device(lse, (q.size(0), q.size(1)), torch.float32, q.device, "lse")
-        if out is None:
-            out = torch.empty(q.shape[:-1] + v.shape[-1:], dtype=q.dtype, device=q.device)
-        else:
-            check_shape_dtype_device(out, q.shape[:-1] + v.shape[-1:], q.dtype, q.device, "out")
-        alibi = _get_cache_alibi_slopes_buf(q.shape[1], q.device) if self._pos_encoding_mode == "ALIBI" else None
-        params = _lib.BatchPrefillParams(
-            q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), qo_indptr=self._qo_indptr_buf.data_ptr(),
-            kv=_lib.PagedKV(
-                k_data=k.data_ptr(), v_data=v.data_ptr(), indptr=self._kv_indptr_buf.data_ptr(), indices=None,
-                last_page_len=None, rope_pos_offset=None, stride_page=stride_n, stride_n=stride_n, stride_h=stride_h,
-                page_size=1, num_kv_heads=num_kv_heads, head_dim=head_dim, batch_size=self._batch_size,
-                dtype=_lib.fi_dtype(k.dtype),
-            ),
-            o=out.data_ptr(), lse=_lib.ptr(lse) if return_lse else None, alibi_slopes=_lib.ptr(alibi),
-            scale_q=None, scale_k=None, scale_v=None, num_qo_heads=self._num_qo_heads,
-            custom_mask=_lib.ptr(self._custom_mask_buf), mask_indptr=_lib.ptr(self._mask_indptr_buf),
-            prefix_len_ptr=_lib.ptr(self._prefix_len_ptr), token_pos_in_items_ptr=_lib.ptr(self._token_pos_in_items_ptr),
-            max_item_len_ptr=_lib.ptr(self._max_item_len_ptr), token_pos_in_items_len=self._token_pos_in_items_len,
-            q_dtype=_lib.fi_dtype(q.dtype), o_dtype=_lib.fi_dtype(q.dtype),
-            mask_mode=_mask_mode(self),
-            pos_encoding_mode=PosEncodingMode[self._pos_encoding_mode].value, window_left=self._window_left,
-            logits_soft_cap=logits_soft_cap, sm_scale=sm_scale, rope_rcp_scale=1.0 / rope_scale,
-            rope_rcp_theta=1.0 / rope_theta, bf16_pv_mode=getattr(self, "_bf16_pv_mode", 0),
+        kv = _lib.PagedKV(
+            k_data=k.data_ptr(), v_data=v.data_ptr(), indptr=self._kv_indptr_buf.data_ptr(), indices=None,
+            last_page_len=None, rope_pos_offset=None, stride_page=stride_n, stride_n=stride_n, stride_h=stride_h,
+            page_size=1, num_kv_heads=num_kv_heads, head_dim=head_dim, batch_size=self._batch_size,
+            dtype=_lib.fi_dtype(k.dtype),
         )
-        with torch.cuda.device(q.device):
-            _lib.check(
-                _lib.lib().fi_batch_prefill_paged_run(
-                    self._float_workspace_buffer.data_ptr(),
-                    self._float_workspace_buffer.numel() * self._float_workspace_buffer.element_size(),
-                    self._int_workspace_buffer.data_ptr(), self._int_workspace_buffer.numel(), self._plan_info_c,
-                    _lib.FI_PREFILL_PLAN_INFO_LEN, C.byref(params), _lib.current_stream(q.device),
-                ),
-                "BatchPrefillWithRaggedKVCacheWrapper.run",
-            )
-        if v_scale is not None:
-            out *= v_scale
-        return (out, lse) if return_lse else out
+        return _run_batch_prefill(self, "BatchPrefillWithRaggedKVCacheWrapper.run", q, kv, q.dtype, out, lse,
+                                  return_lse, self._window_left, q_scale, k_scale, v_scale)
 
     run_return_lse = functools.partialmethod(run, return_lse=True)
 

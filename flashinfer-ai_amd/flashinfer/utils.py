@@ -155,6 +155,32 @@ def _get_cache_alibi_slopes_buf(num_qo_heads: int, device: torch.device) -> torc
     return buf
 
 
+def _resolve_logits_params(
+    head_dim: int,
+    sm_scale: Optional[float],
+    q_scale: Optional[float],
+    k_scale: Optional[float],
+    logits_soft_cap: Optional[float],
+    rope_scale: Optional[float],
+    rope_theta: Optional[float],
+) -> Dict[str, float]:
+    """The logits fields of the C parameter blocks (``logits_soft_cap``, ``sm_scale``, ``rope_rcp_scale``,
+    ``rope_rcp_theta``) with the reference's defaults: no soft cap, ``1 / sqrt(head_dim)``, scale 1, theta 1e4.
+    ``q_scale`` / ``k_scale`` (fp8 calibration) are folded into ``sm_scale``."""
+    if sm_scale is None:
+        sm_scale = 1.0 / math.sqrt(head_dim)
+    if q_scale is not None:
+        sm_scale *= q_scale
+    if k_scale is not None:
+        sm_scale *= k_scale
+    return dict(
+        logits_soft_cap=0.0 if logits_soft_cap is None else logits_soft_cap,
+        sm_scale=sm_scale,
+        rope_rcp_scale=1.0 / (1.0 if rope_scale is None else rope_scale),
+        rope_rcp_theta=1.0 / (1e4 if rope_theta is None else rope_theta),
+    )
+
+
 def _check_cached_qkv_data_type(
     q: torch.Tensor, k: torch.Tensor, dtype_q: torch.dtype, dtype_kv: torch.dtype
 ) -> None:
