@@ -82,7 +82,7 @@ static const DecodeKnobs& decode_knobs() {
 
 // work items per CU the planner cuts the batch into (FI_DECODE_WAVES_PER_CU overrides; read at every plan, as
 // tools/bench_decode_sweep.py sweeps it within one process).  r3 sweep over the reference
-// benchmark's grid (tools/bench_ref_grids.py, tools/r3/dsweep.py; bf16 32 / 4 and 32 / 8 heads, random and identity
+// benchmark's grid (tools/bench_ref_grids.py and a one-off r3 sweep; bf16 32 / 4 and 32 / 8 heads, random and identity
 // page order): with a 16-bit cache 4 per CU is level with 8 at C2 (6.72 against 6.65 TB/s) and ahead on everything
 // smaller, where 8 cuts chunks of 256-512 tokens whose fixed cost shows (bs 256 x kv 1024: 6.46 against 5.32 -- no
 // split at all; bs 64 x kv 4096, 32 / 4: 5.84 against 4.98; bs 32 x kv 4096: 5.05 against 4.37); an fp8 cache moves

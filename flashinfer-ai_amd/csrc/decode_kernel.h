@@ -18,9 +18,6 @@
 
 namespace fi {
 
-#ifndef FI_DECODE_XCD_REMAP
-#define FI_DECODE_XCD_REMAP 1
-#endif
 constexpr int kDecodeThreads = 256;  // 4 waves; waves are independent
 constexpr int kDecodeWaves = kDecodeThreads / 64;
 constexpr float kMInit = -1.0e30f;  // finite "minus infinity" for the running max
@@ -520,7 +517,6 @@ __global__ void __launch_bounds__(kDecodeThreads, 2)
     const int qn = total >> 3, rn = total & 7;
     lb = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
   }
-  if (FI_DECODE_XCD_REMAP == 0) lb = blockIdx.x;
   const int item = lb * kDecodeWaves + wave;
   if (item >= p.num_items) return;
   DecodeWave<KV_DT, HEAD_DIM, GT, ROPE, FAST, NLOAD, NT> w(p);

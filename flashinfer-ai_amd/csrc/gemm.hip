@@ -9,7 +9,7 @@
 // Structure: one workgroup (4 waves) owns a 128 (m) x 128 (n) output tile of one group and walks K in
 // 128-wide blocks = the scale granularity.  A and B tiles are staged through LDS ([128 rows][128 B] fp8
 // images, 16-byte chunks XOR-swizzled so that ds_read_b128 is conflict-free) with register prefetch of the
-// next block.  The product is computed TRANSPOSED (D^T = B A^T, mfma_f32_32x32x16_fp8_fp8): the m index
+// next block.  The product is computed TRANSPOSED (D^T = B A^T, v_mfma_scale_f32_32x32x64_f8f6f4): the m index
 // then sits on the lane, so the per-row A scale is one value per lane and the per-block B scale is wave
 // uniform; each K block's partial product is folded into the running f32 accumulator with one fma per
 // element (two-level accumulation, exactly the block-scaled definition).
@@ -22,19 +22,10 @@
 
 namespace fi {
 
-template <bool A_E5M2, bool B_E5M2>
-__device__ __forceinline__ f32x16g mfma_fp8(long a, long b, f32x16g c) {
-  if constexpr (!A_E5M2 && !B_E5M2) return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a, b, c, 0, 0, 0);
-  else if constexpr (!A_E5M2 && B_E5M2) return __builtin_amdgcn_mfma_f32_32x32x16_fp8_bf8(a, b, c, 0, 0, 0);
-  else if constexpr (A_E5M2 && !B_E5M2) return __builtin_amdgcn_mfma_f32_32x32x16_bf8_fp8(a, b, c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf8_bf8(a, b, c, 0, 0, 0);
-}
-
-// MA_E5M2 / MB_E5M2 refer to the MFMA A operand (= matrix B of the GEMM) and MFMA B operand (= matrix A)
-
-// MX: use the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 with unit (E8M0 = 127) scales -- the plain fp8
+// MA_E5M2 / MB_E5M2 refer to the MFMA A operand (= matrix B of the GEMM) and MFMA B operand (= matrix A).
+// The MFMA is the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 with unit (E8M0 = 127) scales -- the plain fp8
 // product at twice the rate of the non-scaled fp8 MFMA (MI355X_MICROARCH.md, matrix cores).
-template <bool MA_E5M2, bool MB_E5M2, bool MX>
+template <bool MA_E5M2, bool MB_E5M2>
 __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const GemmParams p) {
   // the 256 x 256 kernel's hardware-scale variant already did this call (launch_gemm: mid-size problems)
   if (fi_scales_are_pow2(p.pow2_flag)) return;
@@ -157,80 +148,40 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
     load_scales(kb + 1);
     issue(kb + 1, rs);
 
-    if constexpr (MX) {
-      // A fragments of the whole k block stay in registers; the two 32-column halves of the wave's tile
-      // are then processed one after the other, each with its own 32-register partial product, so that
-      // folding half 0 into the accumulator (vector pipe) runs beside the MFMAs of half 1 (matrix pipe)
-      i32x8g fa[2][2];  // [kk][mb]: this lane holds bytes [64 kk + 32 lh, +32) of its row
+    // A fragments of the whole k block stay in registers; the two 32-column halves of the wave's tile
+    // are then processed one after the other, each with its own 32-register partial product, so that
+    // folding half 0 into the accumulator (vector pipe) runs beside the MFMAs of half 1 (matrix pipe)
+    i32x8g fa[2][2];  // [kk][mb]: this lane holds bytes [64 kk + 32 lh, +32) of its row
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
+    for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-          const u32x4 lo = *(const u32x4*)(&smem[buf][0][lds_off(64 * wm + 32 * mb + lq, 4 * kk + 2 * lh)]);
-          const u32x4 hi = *(const u32x4*)(&smem[buf][0][lds_off(64 * wm + 32 * mb + lq, 4 * kk + 2 * lh + 1)]);
-          fa[kk][mb] = i32x8g{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-        }
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-        f32x16g part[2];
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) part[mb][r] = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const u32x4 lo = *(const u32x4*)(&smem[buf][1][lds_off(64 * wn + 32 * nb + lq, 4 * kk + 2 * lh)]);
-          const u32x4 hi = *(const u32x4*)(&smem[buf][1][lds_off(64 * wn + 32 * nb + lq, 4 * kk + 2 * lh + 1)]);
-          const i32x8g fb = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-#pragma unroll
-          for (int mb = 0; mb < 2; ++mb)
-            part[mb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-                fb, fa[kk][mb], part[mb], MA_E5M2 ? 1 : 0, MB_E5M2 ? 1 : 0, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
-        }
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-          const float s = sa[mb] * sb;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[nb][mb][r] += s * part[mb][r];
-        }
+      for (int mb = 0; mb < 2; ++mb) {
+        const u32x4 lo = *(const u32x4*)(&smem[buf][0][lds_off(64 * wm + 32 * mb + lq, 4 * kk + 2 * lh)]);
+        const u32x4 hi = *(const u32x4*)(&smem[buf][0][lds_off(64 * wm + 32 * mb + lq, 4 * kk + 2 * lh + 1)]);
+        fa[kk][mb] = i32x8g{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
       }
-    } else {
-    f32x16g part[2][2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) part[i][j][r] = 0.f;
-#pragma unroll
-    for (int kp = 0; kp < 4; ++kp) {  // 32 bytes of k per step pair: bytes [32 kp + 16 lh, +16)
-      u32x4 fa[2], fb[2];
+    for (int nb = 0; nb < 2; ++nb) {
+      f32x16g part[2];
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb)
-        fa[mb] = *(const u32x4*)(&smem[buf][0][lds_off(64 * wm + 32 * mb + lq, 2 * kp + lh)]);
 #pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-        fb[nb] = *(const u32x4*)(&smem[buf][1][lds_off(64 * wn + 32 * nb + lq, 2 * kp + lh)]);
+        for (int r = 0; r < 16; ++r) part[mb][r] = 0.f;
 #pragma unroll
-      for (int half = 0; half < 2; ++half) {
+      for (int kk = 0; kk < 2; ++kk) {
+        const u32x4 lo = *(const u32x4*)(&smem[buf][1][lds_off(64 * wn + 32 * nb + lq, 4 * kk + 2 * lh)]);
+        const u32x4 hi = *(const u32x4*)(&smem[buf][1][lds_off(64 * wn + 32 * nb + lq, 4 * kk + 2 * lh + 1)]);
+        const i32x8g fb = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-          const long bfrag = (long)fb[nb][2 * half] | ((long)fb[nb][2 * half + 1] << 32);
-#pragma unroll
-          for (int mb = 0; mb < 2; ++mb) {
-            const long afrag = (long)fa[mb][2 * half] | ((long)fa[mb][2 * half + 1] << 32);
-            part[nb][mb] = mfma_fp8<MA_E5M2, MB_E5M2>(bfrag, afrag, part[nb][mb]);
-          }
-        }
+        for (int mb = 0; mb < 2; ++mb)
+          part[mb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+              fb, fa[kk][mb], part[mb], MA_E5M2 ? 1 : 0, MB_E5M2 ? 1 : 0, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
       }
-    }
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb) {
         const float s = sa[mb] * sb;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nb][mb][r] += s * part[nb][mb][r];
+        for (int r = 0; r < 16; ++r) acc[nb][mb][r] += s * part[mb][r];
       }
     }
     commit(buf ^ 1, rs);
@@ -289,17 +240,15 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
 
 // ---- 256 x 128 tile persistent kernel for large problems (LDS-DMA staging) --------------------------------------
 // One 512-thread workgroup per CU owns a 256 (m) x 128 (n) tile (or 128 x 256, TM): 8 waves of 64 x 64, two per SIMD;
-// the tile needs 25 % fewer operand bytes per flop from L2 than 128 x 128 (170 flop/B).  (r1's register-staged form
-// of this kernel was removed in r3: the DMA form below replaced it as the default in r1 and nothing selected it.)
+// the tile needs 25 % fewer operand bytes per flop from L2 than 128 x 128 (170 flop/B).  Operands go global -> LDS
+// directly (`global_load_lds_dwordx4`, 1 KiB per wave instruction), two k blocks ahead through a ring of three 52 KB
+// LDS stages (156 of the 160 KB): no staging registers, no VGPR -> LDS store transfer.  Synchronisation is by hand:
+// every wave waits `vmcnt(8)` (its own pieces of the NEXT block landed, the 8 DMA instructions of the block after it
+// still in flight) and then a raw `s_barrier` -- `__syncthreads()` would drain vmcnt.  (r1's register-staged form of
+// this kernel was removed in r3: the DMA form replaced it as the default in r1 and nothing selected it.)
 constexpr int kWsThreads = 512;
 constexpr int kWsBM = 256;
 
-// ---- the same 256 x 128 persistent kernel with LDS-DMA staging (default for large problems) --------------
-// Operands go global -> LDS directly (`global_load_lds_dwordx4`, 1 KiB per wave instruction), two k blocks
-// ahead through a ring of three 52 KB LDS stages (156 of the 160 KB): no staging registers, no
-// VGPR -> LDS store transfer.  Synchronisation is by hand: every wave waits `vmcnt(8)` (its own pieces of the
-// NEXT block landed, the 8 DMA instructions of the block after it still in flight) and then a raw `s_barrier`
-// -- `__syncthreads()` would drain vmcnt.
 template <bool MA_E5M2, bool MB_E5M2, int TM>
 __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const GemmParams p) {
   if (fi_scales_are_pow2(p.pow2_flag)) return;  // see group_gemm_fp8_kernel
@@ -603,104 +552,110 @@ __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const
   if (have_out) store_tile();
 }
 
-static hipError_t launch_gemm(const GemmParams& p_in, hipStream_t stream) {
-  GemmParams p = p_in;
-  const int grid = p.num_m_tiles_bound * p.n_tiles;
-  if (grid <= 0) return hipSuccess;
-  // MFMA A operand = GEMM matrix B, MFMA B operand = GEMM matrix A
-  const int sel = (p.b_is_e5m2 ? 2 : 0) | (p.a_is_e5m2 ? 1 : 0);
-  static const bool use_mx = [] {
-    const char* e = getenv("FI_GEMM_MX");
-    return e ? atoi(e) != 0 : true;
+static int env_int(const char* name, int unset) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : unset;
+}
+
+// The FI_GEMM_* knobs, read once per process; the tests force kernels through them.
+struct GemmKnobs {
+  int ws_min_tiles;        // FI_GEMM_WS_MIN_TILES: fewest tiles for the persistent kernels (-1: never; default 2 x CUs)
+  int forced_tm;           // FI_GEMM_DMA_TM = 128 / 256: force the LDS-DMA kernel's tile shape (0: by the group sizes)
+  int big_hws_min_tiles;   // FI_GEMM_BIG_MIN_TILES, 256 x 256 hardware-scale variant (-1: never, FI_GEMM_BIG=0)
+  int big_fold_min_tiles;  // FI_GEMM_BIG_FOLD_MIN_TILES, 256 x 256 fold variant
+  bool hw_scales;          // FI_GEMM_HW_SCALES=0: never the hardware-scale variant (A/B runs)
+};
+
+static const GemmKnobs& gemm_knobs() {
+  static const GemmKnobs k = [] {
+    GemmKnobs k;
+    const int cus = fi_num_compute_units();
+    k.ws_min_tiles = env_int("FI_GEMM_WS_MIN_TILES", 2 * cus);
+    k.forced_tm = env_int("FI_GEMM_DMA_TM", 0);
+    k.big_hws_min_tiles = env_int("FI_GEMM_BIG", 1) == 0 ? -1 : env_int("FI_GEMM_BIG_MIN_TILES", cus / 2);
+    // a forced FI_GEMM_BIG_MIN_TILES (tests, A/B runs) applies to both variants
+    k.big_fold_min_tiles = env_int("FI_GEMM_BIG_FOLD_MIN_TILES", env_int("FI_GEMM_BIG_MIN_TILES", 4 * cus));
+    k.hw_scales = env_int("FI_GEMM_HW_SCALES", 1) != 0;
+    return k;
   }();
-  // producer/consumer kernel: MX path, enough 256 x 128 tiles to give every CU a few
-  static const int ws_min_tiles = [] {
-    const char* e = getenv("FI_GEMM_WS_MIN_TILES");
-    return e ? atoi(e) : 2 * fi_num_compute_units();
-  }();
-  const int ws_tiles = p.num_m_tiles_bound_ws * p.n_tiles;
-  const int ws_grid = (fi_num_compute_units() / 8) * 8;  // persistent: one workgroup per CU, XCD-aligned
-  const bool use_ws = use_mx && ws_min_tiles >= 0 && ws_tiles >= ws_min_tiles && ws_grid >= 8;
-  constexpr bool use_dma = true;
+  return k;
+}
+
+// Which 256 x 256 launch (gemm_big.hip) a call makes, and which kernel follows it.  HWS_ONLY: the hardware-scale
+// variant does the call when the scales qualify; otherwise it returns at once and the following kernel, given the
+// flag words, does the call.
+enum class GemmBig { NONE, HWS_ONLY, BOTH };
+enum class GemmNext { NONE, DMA_128x256, DMA_256x128, TILE_128x128 };
+struct GemmChoice {
+  GemmBig big;
+  GemmNext next;
+  int persistent_grid;  // the persistent kernels' grid: one workgroup per CU, XCD-aligned
+};
+
+static GemmChoice choose_gemm(const GemmParams& p) {
+  const GemmKnobs& k = gemm_knobs();
+  GemmChoice c{GemmBig::NONE, GemmNext::TILE_128x128, (fi_num_compute_units() / 8) * 8};
+  const bool persistent = k.ws_min_tiles >= 0 && c.persistent_grid >= 8;
   // 128 x 256 tiles for grouped problems whose groups have few rows (a <= 128-row group fills half of a
   // 256-row tile); FI_GEMM_DMA_TM = 128 / 256 forces the shape
-  static const int forced_tm = [] {
-    const char* e = getenv("FI_GEMM_DMA_TM");
-    return e ? atoi(e) : 0;
-  }();
   const bool few_rows = p.m_indptr != nullptr && p.m_total <= 160 * (int64_t)p.num_groups;
-  const bool tall = forced_tm == 128 || (forced_tm != 256 && few_rows);
-  const int tall_tiles = p.num_m_tiles_bound * ceil_div(p.n, 2 * kBN);
-  // 256 x 256 tiles (gemm_big.hip); FI_GEMM_BIG=0 keeps 256 x 128 / 128 x 128.  r3 (tools/bench_gemm_threshold.py):
+  const bool tall = k.forced_tm == 128 || (k.forced_tm != 256 && few_rows);
+  // groups of few rows: from ~96 rows per group on the 256 x 256 kernel with its half-empty row tiles is ahead of the
+  // 128 x 256 kernel (256 groups x 128 x 4096 x 7168: 1.03 against 0.81 PFLOP/s with power-of-two scales, 0.92 against
+  // 0.82 folded; 160 rows: 1.23 against 0.76; 64 rows: equal; 96 rows 0.69 against 0.54 / 0.53 against 0.55)
+  const bool big_rows = k.forced_tm == 256 || (k.forced_tm == 0 && (!few_rows || p.m_total > 96 * (int64_t)p.num_groups));
+  const int big_tiles = p.num_m_tiles_bound_ws * ceil_div(p.n, 2 * kBN);
+  // 256 x 256 tiles; FI_GEMM_BIG=0 keeps 256 x 128 / 128 x 128.  r3 (tools/bench_gemm_threshold.py):
   //  * power-of-two scales (the reference quantiser's; decided on the device): the hardware-scale variant beats the
   //    256 x 128 LDS-DMA kernel on every shape that reaches either (8 x 1024 x 4096 x 7168: 2.32 against 1.37 PFLOP/s;
   //    256 tiles = one per CU: 1.27 against 1.10) and the 128 x 128 kernel from 128 tiles on (2048 x 4096 x 4096: 1.12
   //    against 0.83, 3072 x 4096 x 4096: 1.65 against 1.13; 64 tiles: the 128 x 128 kernel's 256 workgroups win) -> from
   //    half a tile per CU on (for scales that do NOT qualify the check kernel and the variant that returns at once
   //    cost 5-7 us, ~7 % of the smallest such calls);
-  //  * arbitrary scales (the fold variant): mixed below four tiles per CU (8 x 1024 x 4096 x 7168 1.57 against 1.32,
-  //    4 x 1024 x 7168 x 2048 0.88 against 1.18) -> from 4 x CUs tiles on, as in r2.
-  // In between only the hardware-scale variant is launched (it returns at once when the scales do not qualify) and
-  // the kernel chosen below gets the flag word and returns at once when they do.
-  static const int big_hws_min_tiles = [] {
-    const char* e = getenv("FI_GEMM_BIG");
-    if (e && atoi(e) == 0) return -1;
-    const char* t = getenv("FI_GEMM_BIG_MIN_TILES");
-    return t ? atoi(t) : fi_num_compute_units() / 2;
-  }();
-  static const int big_fold_min_tiles = [] {
-    const char* t = getenv("FI_GEMM_BIG_FOLD_MIN_TILES");
-    if (t) return atoi(t);
-    const char* h = getenv("FI_GEMM_BIG_MIN_TILES");  // a forced threshold (tests, A/B runs) applies to both variants
-    return h ? atoi(h) : 4 * fi_num_compute_units();
-  }();
-  const int big_tiles = p.num_m_tiles_bound_ws * ceil_div(p.n, 2 * kBN);
-  // groups of few rows: from ~96 rows per group on the 256 x 256 kernel with its half-empty row tiles is ahead of the
-  // 128 x 256 kernel (256 groups x 128 x 4096 x 7168: 1.03 against 0.81 PFLOP/s with power-of-two scales, 0.92 against
-  // 0.82 folded; 160 rows: 1.23 against 0.76; 64 rows: equal; 96 rows 0.69 against 0.54 / 0.53 against 0.55)
-  const bool rows_ok = forced_tm == 256 || (forced_tm == 0 && (!few_rows || p.m_total > 96 * (int64_t)p.num_groups));
-  const bool big_ok = use_mx && ws_min_tiles >= 0 && ws_grid >= 8 && use_dma && big_hws_min_tiles >= 0 && rows_ok;
-  if (big_ok && big_tiles >= big_hws_min_tiles) {
-    GemmParams q = p;
-    q.num_m_tiles_bound = p.num_m_tiles_bound_ws;
-    if (big_tiles >= big_fold_min_tiles) return launch_gemm_big(q, ws_grid, stream, nullptr);
-    uint32_t* flag = nullptr;
-    hipError_t e = launch_gemm_big(q, ws_grid, stream, &flag);
-    if (e != hipSuccess) return e;
-    p.pow2_flag = flag;  // null (no flag ring yet under a stream capture, FI_GEMM_HW_SCALES=0): nothing was launched
+  if (persistent && big_rows && k.big_hws_min_tiles >= 0 && big_tiles >= k.big_hws_min_tiles) {
+    //  * arbitrary scales (the fold variant): mixed below four tiles per CU (8 x 1024 x 4096 x 7168 1.57 against 1.32,
+    //    4 x 1024 x 7168 x 2048 0.88 against 1.18) -> from 4 x CUs tiles on, as in r2.
+    if (big_tiles >= k.big_fold_min_tiles) return {GemmBig::BOTH, GemmNext::NONE, c.persistent_grid};
+    c.big = GemmBig::HWS_ONLY;
   }
-  if (use_dma && use_mx && ws_min_tiles >= 0 && ws_grid >= 8 && tall && tall_tiles >= ws_min_tiles) {
-    switch (sel) {  // num_m_tiles_bound already counts 128-row tiles
-      case 0: group_gemm_fp8_dma_kernel<false, false, 128><<<dim3(ws_grid), dim3(kWsThreads), 0, stream>>>(p); break;
-      case 1: group_gemm_fp8_dma_kernel<false, true, 128><<<dim3(ws_grid), dim3(kWsThreads), 0, stream>>>(p); break;
-      case 2: group_gemm_fp8_dma_kernel<true, false, 128><<<dim3(ws_grid), dim3(kWsThreads), 0, stream>>>(p); break;
-      default: group_gemm_fp8_dma_kernel<true, true, 128><<<dim3(ws_grid), dim3(kWsThreads), 0, stream>>>(p); break;
+  // producer/consumer kernel: enough 256 x 128 tiles to give every CU a few
+  if (persistent && tall && p.num_m_tiles_bound * ceil_div(p.n, 2 * kBN) >= k.ws_min_tiles)
+    c.next = GemmNext::DMA_128x256;
+  else if (persistent && p.num_m_tiles_bound_ws * p.n_tiles >= k.ws_min_tiles)
+    c.next = GemmNext::DMA_256x128;
+  return c;
+}
+
+static hipError_t launch_gemm(const GemmParams& p_in, hipStream_t stream) {
+  if (p_in.num_m_tiles_bound * p_in.n_tiles <= 0) return hipSuccess;
+  const GemmChoice c = choose_gemm(p_in);
+  GemmParams p = p_in;
+  GemmParams ws = p_in;  // the 256-row-tile kernels count 256-row tiles
+  ws.num_m_tiles_bound = p_in.num_m_tiles_bound_ws;
+  if (c.big != GemmBig::NONE) {
+    // the pow2 check and the hardware-scale variant need a flag slot: none under a stream capture before the first
+    // eager call, or with FI_GEMM_HW_SCALES=0.  HWS_ONLY then launches nothing and the following kernel does the call.
+    ws.pow2_flag = gemm_knobs().hw_scales ? pow2_flag_slot(stream) : nullptr;
+    if (ws.pow2_flag != nullptr) {
+      launch_pow2_check(ws, stream);
+      launch_gemm_big(ws, /*hws=*/true, c.persistent_grid, stream);
     }
-    return hipGetLastError();
+    if (c.big == GemmBig::BOTH) launch_gemm_big(ws, /*hws=*/false, c.persistent_grid, stream);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess || c.big == GemmBig::BOTH) return e;
+    p.pow2_flag = ws.pow2_flag;  // the following kernel returns at once when the hardware-scale variant did the call
   }
-  if (use_ws && use_dma) {
-    GemmParams q = p;
-    q.num_m_tiles_bound = p.num_m_tiles_bound_ws;
-    switch (sel) {
-      case 0: group_gemm_fp8_dma_kernel<false, false, 256><<<dim3(ws_grid), dim3(kWsThreads), 0, stream>>>(q); break;
-      case 1: group_gemm_fp8_dma_kernel<false, true, 256><<<dim3(ws_grid), dim3(kWsThreads), 0, stream>>>(q); break;
-      case 2: group_gemm_fp8_dma_kernel<true, false, 256><<<dim3(ws_grid), dim3(kWsThreads), 0, stream>>>(q); break;
-      default: group_gemm_fp8_dma_kernel<true, true, 256><<<dim3(ws_grid), dim3(kWsThreads), 0, stream>>>(q); break;
+  with_fp8_formats(p, [&](auto ma, auto mb) {
+    constexpr bool A = decltype(ma)::value, B = decltype(mb)::value;
+    const dim3 grid(c.persistent_grid), block(kWsThreads);
+    switch (c.next) {
+      case GemmNext::DMA_128x256: group_gemm_fp8_dma_kernel<A, B, 128><<<grid, block, 0, stream>>>(p); break;
+      case GemmNext::DMA_256x128: group_gemm_fp8_dma_kernel<A, B, 256><<<grid, block, 0, stream>>>(ws); break;
+      case GemmNext::TILE_128x128:
+        group_gemm_fp8_kernel<A, B><<<dim3(p.num_m_tiles_bound * p.n_tiles), dim3(kGemmThreads), 0, stream>>>(p);
+        break;
+      case GemmNext::NONE: break;
     }
-    return hipGetLastError();
-  }
-#define FI_GEMM_LAUNCH(A, B)                                                                   \
-  if (use_mx)                                                                                  \
-    group_gemm_fp8_kernel<A, B, true><<<dim3(grid), dim3(kGemmThreads), 0, stream>>>(p);       \
-  else                                                                                         \
-    group_gemm_fp8_kernel<A, B, false><<<dim3(grid), dim3(kGemmThreads), 0, stream>>>(p);
-  switch (sel) {
-    case 0: FI_GEMM_LAUNCH(false, false) break;
-    case 1: FI_GEMM_LAUNCH(false, true) break;
-    case 2: FI_GEMM_LAUNCH(true, false) break;
-    default: FI_GEMM_LAUNCH(true, true) break;
-  }
-#undef FI_GEMM_LAUNCH
+  });
   return hipGetLastError();
 }
 

@@ -16,8 +16,6 @@
 //     the block's scales, a ring of TWO stages (136 KB): block kb + 1 is issued at the top of step kb and
 //     awaited (`vmcnt(0)` + barrier, one asm statement) at its end;
 //   * output through LDS (stage 1, free at a tile border) as whole 128-byte row pieces.
-#include <stdlib.h>
-
 #include <atomic>
 #include <mutex>
 #include <type_traits>
@@ -30,25 +28,8 @@ constexpr int kBigThreads = 512;
 constexpr int kBigTM = 256, kBigTN = 256;
 constexpr int kBigScOff = (kBigTM + kBigTN) * kBK;              // 64 KB of operands, then the scales
 constexpr int kBigStage = kBigScOff + (kBigThreads / 64) * 512;  // per wave: 64 A scales, 64 x the B scale
+constexpr int kBigBandRows = 1024;  // rows of a band of tiles (see the kernel's tile order)
 
-#ifndef FI_GEMM_BIG_NT_STORE
-#define FI_GEMM_BIG_NT_STORE 1  // output stores non-temporal: 128 KB per tile that nobody reads again stay out of the L2's way
-#endif
-#ifndef FI_GEMM_BIG_CARRY
-#define FI_GEMM_BIG_CARRY 2  // 0 none, 1 the held-back pair behind the DMA issue, 2 in front of it
-#endif
-#ifndef FI_GEMM_BIG_BRANCHFREE
-#define FI_GEMM_BIG_BRANCHFREE 3  // bit 0: hardware-scale path, bit 1: fold path (see k_step)
-#endif
-#ifndef FI_GEMM_BIG_BAND
-#define FI_GEMM_BIG_BAND 1024
-#endif
-#ifndef FI_GEMM_BIG_INTERLEAVE
-#define FI_GEMM_BIG_INTERLEAVE 1
-#endif
-#ifndef FI_GEMM_BIG_KO
-#define FI_GEMM_BIG_KO 0  // experiments only, bit mask: 1 no output stores, 2 no fold, 4 no DMA in the k loop, 8 / 32 (timing only, wrong results): the step awaits none / all but the newest block of its DMA
-#endif
 
 // flag[block] = 1 when the block saw a scale that is not a positive normal power of two, else 0 (kPow2Words blocks:
 // every word of the call's slot is rewritten, nothing to reset).  HBM-bound, a few microseconds: C4's a_scale is 4 MB.
@@ -106,11 +87,11 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
   // XCD x a contiguous tile range, which at C4 is group x for the whole launch).
   const int n_tiles = (N + kBigTN - 1) / kBigTN;
   const int total = p.num_m_tiles_bound * n_tiles;
-  constexpr int kBandM = FI_GEMM_BIG_BAND / kBigTM;  // 1024 rows x all n per band
+  constexpr int kBandM = kBigBandRows / kBigTM;  // 1024 rows x all n per band
   const int band_tiles = kBandM * n_tiles;
   // whole rounds of 8 bands are dealt one band per XCD; what is left (fewer than 8 bands, the last one possibly
   // short) is split into contiguous ranges so that every XCD gets the same number of tiles (+- 1)
-  const int n_inter = FI_GEMM_BIG_INTERLEAVE ? (p.num_m_tiles_bound / (8 * kBandM)) * band_tiles : 0;  // per XCD
+  const int n_inter = (p.num_m_tiles_bound / (8 * kBandM)) * band_tiles;  // per XCD
   const int logical_step = gridDim.x >> 3;
   const int xcd_id = blockIdx.x & 7;
   int logical = blockIdx.x >> 3, logical_end, rem_base;
@@ -179,8 +160,7 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
         if (m >= out_m_end || n >= N) continue;  // n is a multiple of 8 and so is N
         uint16_t* dst = (uint16_t*)p.d + (int64_t)m * N + n;
         if (d_aligned16) {
-          if (FI_GEMM_BIG_NT_STORE) __builtin_nontemporal_store(v, (u32x4*)dst);
-          else *(u32x4*)dst = v;
+          __builtin_nontemporal_store(v, (u32x4*)dst);  // 128 KB per tile that nobody reads again stay out of the L2's way
         } else {
           *(u32x2*)dst = u32x2{v[0], v[1]};
           *(u32x2*)(dst + 4) = u32x2{v[2], v[3]};
@@ -285,7 +265,7 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
     // block 0 of the next tile goes out BEFORE the finished tile is converted and stored (stage 0; the store's
     // scratch is stage 1, which block 1 enters only in step 0, behind the barrier below)
     dma(0, 0);
-    if (have_out && !(FI_GEMM_BIG_KO & 1)) store_tile();
+    if (have_out) store_tile();
     out_m0 = m0;
     out_n0 = n0;
     out_m_end = m_end;
@@ -299,15 +279,16 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
     // block 0 landed (the output stores are younger and vmcnt retires in order: 0 is the only safe count);
     // every wave is done with its stage 1 scratch
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    // Hardware-scale path (FI_GEMM_BIG_CARRY): the last two MFMAs of a step (n block 3, second k half) are held
-    // back and issued BEHIND the barrier, in front of the next step's first MFMA -- the matrix pipe has work while
-    // the new step's DMA instructions issue and its first fragment reads are in flight.  Their operands (the A
-    // fragments' second k halves, one B fragment, the step's scale exponents) stay in the registers they are in;
-    // the new step's reads go to the first-k-half registers first.  Zero operands in front of step 0.
+    // Hardware-scale path: the last two MFMAs of a step (n block 3, second k half) are held back and issued BEHIND
+    // the barrier, in front of the next step's first MFMA -- the matrix pipe has work while the new step's DMA
+    // instructions issue and its first fragment reads are in flight.  Their operands (the A fragments' second k
+    // halves, one B fragment, the step's scale exponents as E8M0 = the f32 exponent field of a power of two) stay in
+    // the registers they are in; the new step's reads go to the first-k-half registers first.  Zero operands in
+    // front of step 0.
     i32x8g hfa[2][2];  // [m block][k half]
     i32x8g hfb[2][2];  // [n block parity][k half]
     int he_b = 127, he_a0 = 127, he_a1 = 127;
-    if constexpr (HWS && FI_GEMM_BIG_CARRY) {
+    if constexpr (HWS) {
 #pragma unroll
       for (int r = 0; r < 8; ++r) hfa[0][1][r] = hfa[1][1][r] = hfb[1][1][r] = 0;
     }
@@ -322,16 +303,12 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
       // here splits the step's scheduling region (the allocator then spills around it, and the last step's copy
       // of the loop body cost 7 % of C4).  The LAST step issues the same instructions with every lane's offset
       // pushed out of the descriptor's range: zeros, written without a memory access into the stage nobody reads.
+      // The hardware-scale path issues it behind the held-back pair of MFMAs.
       auto dma_next = [&]() {
         const uint32_t oob = kb + 1 < kblocks ? 0u : 0x80000000u;
-        if (!(FI_GEMM_BIG_KO & 4) || kb == 0) dma(min(kb + 1, kblocks - 1), buf ^ 1, oob);
+        dma(min(kb + 1, kblocks - 1), buf ^ 1, oob);
       };
-      constexpr bool kDmaBehindCarry = HWS && FI_GEMM_BIG_CARRY == 2;
-      if (FI_GEMM_BIG_BRANCHFREE & (HWS ? 1 : 2)) {
-        if (!kDmaBehindCarry) dma_next();
-      } else if (kb + 1 < kblocks && (!(FI_GEMM_BIG_KO & 4) || kb == 0)) {
-        dma(kb + 1, buf ^ 1);
-      }
+      if constexpr (!HWS) dma_next();
       asm volatile("" : "+v"(a_rd_base), "+v"(b_rd_base));
       const uint8_t* const stage = &smem[buf * kBigStage];
       auto frag = [&](uint32_t base, int kk, int blk) {
@@ -351,12 +328,8 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
                                                                0x7F7F7F7F, 0, 0x7F7F7F7F);
       };
       auto fold = [&](int nb, int mb, const f32x16g& part, float s) {
-        if (FI_GEMM_BIG_KO & 2) {
-          acc[nb][mb][0] += s * part[0];
-        } else {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc[nb][mb][r] += s * part[r];
-        }
+        for (int r = 0; r < 16; ++r) acc[nb][mb][r] += s * part[r];
         asm volatile("" : "+v"(acc[nb][mb]));  // IR-level sinking ignores sched_barrier: pin the fold here
       };
       i32x8g fa[2][2];  // [m block][k half], held for the step
@@ -373,9 +346,7 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
       const float* const sc = (const float*)(&smem[buf * kBigStage + kBigScOff + wave * 512]);
       const float sa[2] = {sc[lq], sc[32 + lq]};
       const float sb = sc[64 + lane];
-      if constexpr (HWS && FI_GEMM_BIG_CARRY) {
-        const float* const sc = (const float*)(&smem[buf * kBigStage + kBigScOff + wave * 512]);
-        const float sa0 = sc[lq], sa1 = sc[32 + lq], sb = sc[64 + lane];
+      if constexpr (HWS) {
         hfa[0][0] = frag(a_rd_base, 0, 0);
         hfb[0][0] = frag(b_rd_base, 0, 0);
         hfa[1][0] = frag(a_rd_base, 0, 1);
@@ -387,16 +358,14 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
         acc[3][0] = mfma_c(hfb[1][1], hfa[0][1], acc[3][0], he_b, he_a0);
         acc[3][1] = mfma_c(hfb[1][1], hfa[1][1], acc[3][1], he_b, he_a1);
         __builtin_amdgcn_sched_barrier(0);
-        if (kDmaBehindCarry) {
-          dma_next();
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        dma_next();
+        __builtin_amdgcn_sched_barrier(0);
         hfa[0][1] = frag(a_rd_base, 1, 0);
         hfb[0][1] = frag(b_rd_base, 1, 0);
         hfa[1][1] = frag(a_rd_base, 1, 1);
         he_b = (int)(__builtin_bit_cast(uint32_t, sb) >> 23);
-        he_a0 = (int)(__builtin_bit_cast(uint32_t, sa0) >> 23);
-        he_a1 = (int)(__builtin_bit_cast(uint32_t, sa1) >> 23);
+        he_a0 = (int)(__builtin_bit_cast(uint32_t, sa[0]) >> 23);
+        he_a1 = (int)(__builtin_bit_cast(uint32_t, sa[1]) >> 23);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
@@ -414,34 +383,6 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
           __builtin_amdgcn_sched_barrier(0);
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        return;
-      }
-      if constexpr (HWS) {
-        // E8M0 = the f32 exponent field of a power of two.  MFMA A operand = B matrix rows (one scale per wave: sb),
-        // MFMA B operand = A matrix rows, the lane's row (sa)
-        const int e_b = (int)(__builtin_bit_cast(uint32_t, sb) >> 23);
-        const int e_a0 = (int)(__builtin_bit_cast(uint32_t, sa[0]) >> 23), e_a1 = (int)(__builtin_bit_cast(uint32_t, sa[1]) >> 23);
-        auto mfma_s = [&](const i32x8g& b, const i32x8g& a, const f32x16g& c, int ea) {
-          return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b, a, c, MA_E5M2 ? 1 : 0, MB_E5M2 ? 1 : 0, 0, e_b, 0, ea);
-        };
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-          const int cur = nb & 1;
-          acc[nb][0] = mfma_s(fb[cur][0], fa[0][0], acc[nb][0], e_a0);
-          if (nb < 3) {
-            fb[cur ^ 1][0] = frag(b_rd_base, 0, nb + 1);
-            fb[cur ^ 1][1] = frag(b_rd_base, 1, nb + 1);
-          }
-          acc[nb][1] = mfma_s(fb[cur][0], fa[1][0], acc[nb][1], e_a1);
-          acc[nb][0] = mfma_s(fb[cur][1], fa[0][1], acc[nb][0], e_a0);
-          acc[nb][1] = mfma_s(fb[cur][1], fa[1][1], acc[nb][1], e_a1);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (FI_GEMM_BIG_KO & 8) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        else if (FI_GEMM_BIG_KO & 32) asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         return;
       }
@@ -486,71 +427,55 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
     if constexpr (!HWS) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[3][1][r] += s_carry * p_carry[r];
-    } else if constexpr (FI_GEMM_BIG_CARRY) {
+    } else {
       acc[3][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hfb[1][1], hfa[0][1], acc[3][0], MA_E5M2 ? 1 : 0,
                                                                   MB_E5M2 ? 1 : 0, 0, he_b, 0, he_a0);
       acc[3][1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hfb[1][1], hfa[1][1], acc[3][1], MA_E5M2 ? 1 : 0,
                                                                   MB_E5M2 ? 1 : 0, 0, he_b, 0, he_a1);
     }
   }
-  if (have_out && (!(FI_GEMM_BIG_KO & 1) || p.k == 12345)) store_tile();
+  if (have_out) store_tile();
 }
 
 // flag words for the power-of-two check: a ring of slots per device (a call's three kernels read / write ITS slot;
 // calls in flight on other streams use other slots), allocated at the first call outside a stream capture
-static uint32_t* pow2_flag_slot(hipStream_t stream) {
+uint32_t* pow2_flag_slot(hipStream_t stream) {
   constexpr int kSlots = 1024;  // x kPow2Words words
-  static uint32_t* ring[64] = {nullptr};
+  static std::atomic<uint32_t*> ring[64] = {};
   static std::atomic<unsigned> next{0};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  if (ring[dev] == nullptr) {
+  uint32_t* base = ring[dev].load(std::memory_order_acquire);
+  if (base == nullptr) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return nullptr;
     static std::mutex mu;
     std::lock_guard<std::mutex> lock(mu);
-    if (ring[dev] == nullptr) {
-      uint32_t* ptr = nullptr;
-      if (hipMalloc(&ptr, (size_t)kSlots * kPow2Words * sizeof(uint32_t)) != hipSuccess) return nullptr;
-      ring[dev] = ptr;
+    base = ring[dev].load(std::memory_order_relaxed);  // the mutex orders it against the store below
+    if (base == nullptr) {
+      if (hipMalloc(&base, (size_t)kSlots * kPow2Words * sizeof(uint32_t)) != hipSuccess) return nullptr;
+      ring[dev].store(base, std::memory_order_release);
     }
   }
-  return ring[dev] + (size_t)(next.fetch_add(1) % kSlots) * kPow2Words;
+  return base + (size_t)(next.fetch_add(1) % kSlots) * kPow2Words;
 }
 
-template <bool HWS>
-static void launch_big_variant(const GemmParams& p, int sel, int grid, hipStream_t stream) {
-  switch (sel) {
-    case 0: group_gemm_fp8_big_kernel<false, false, HWS><<<dim3(grid), dim3(kBigThreads), 0, stream>>>(p); break;
-    case 1: group_gemm_fp8_big_kernel<false, true, HWS><<<dim3(grid), dim3(kBigThreads), 0, stream>>>(p); break;
-    case 2: group_gemm_fp8_big_kernel<true, false, HWS><<<dim3(grid), dim3(kBigThreads), 0, stream>>>(p); break;
-    default: group_gemm_fp8_big_kernel<true, true, HWS><<<dim3(grid), dim3(kBigThreads), 0, stream>>>(p); break;
-  }
+void launch_pow2_check(const GemmParams& p, hipStream_t stream) {
+  const int kblocks = p.k / kBK;
+  const int64_t m_cnt = p.a_gran_m == 1 ? p.m_total : (p.m_total + p.a_gran_m - 1) / p.a_gran_m;
+  const int64_t na = m_cnt * kblocks;
+  const int64_t nb = (int64_t)(p.m_indptr ? p.num_groups : 1) * kblocks * ((p.n + 127) / 128);
+  scales_pow2_check_kernel<<<dim3(kPow2Words), dim3(256), 0, stream>>>((const uint32_t*)p.a_scale, na,
+                                                                       (const uint32_t*)p.b_scale, nb,
+                                                                       (uint32_t*)p.pow2_flag);
 }
 
-hipError_t launch_gemm_big(const GemmParams& p_in, int grid, hipStream_t stream, uint32_t** hws_only_flag) {
-  // MFMA A operand = GEMM matrix B, MFMA B operand = GEMM matrix A
-  GemmParams p = p_in;
-  const int sel = (p.b_is_e5m2 ? 2 : 0) | (p.a_is_e5m2 ? 1 : 0);
-  // FI_GEMM_HW_SCALES=0: never take the hardware-scale path (A/B runs)
-  static const bool hw_scales = [] {
-    const char* e = getenv("FI_GEMM_HW_SCALES");
-    return !(e && atoi(e) == 0);
-  }();
-  uint32_t* flag = hw_scales ? pow2_flag_slot(stream) : nullptr;
-  p.pow2_flag = flag;
-  if (flag != nullptr) {
-    const int kblocks = p.k / kBK;
-    const int64_t m_cnt = p.a_gran_m == 1 ? p.m_total : (p.m_total + p.a_gran_m - 1) / p.a_gran_m;
-    const int64_t na = m_cnt * kblocks;
-    const int64_t nb = (int64_t)(p.m_indptr ? p.num_groups : 1) * kblocks * ((p.n + 127) / 128);
-    scales_pow2_check_kernel<<<dim3(kPow2Words), dim3(256), 0, stream>>>((const uint32_t*)p.a_scale, na, (const uint32_t*)p.b_scale,
-                                                                  nb, flag);
-    launch_big_variant<true>(p, sel, grid, stream);
-  }
-  if (hws_only_flag != nullptr) *hws_only_flag = flag;
-  else launch_big_variant<false>(p, sel, grid, stream);
-  return hipGetLastError();
+void launch_gemm_big(const GemmParams& p, bool hws, int grid, hipStream_t stream) {
+  with_fp8_formats(p, [&](auto ma, auto mb) {
+    constexpr bool A = decltype(ma)::value, B = decltype(mb)::value;
+    if (hws) group_gemm_fp8_big_kernel<A, B, true><<<dim3(grid), dim3(kBigThreads), 0, stream>>>(p);
+    else group_gemm_fp8_big_kernel<A, B, false><<<dim3(grid), dim3(kBigThreads), 0, stream>>>(p);
+  });
 }
 
 }  // namespace fi

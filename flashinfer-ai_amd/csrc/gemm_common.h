@@ -1,6 +1,8 @@
 // Shared by the fp8 groupwise GEMM translation units (gemm.hip, gemm_big.hip): launch parameters and the
 // device-side (group, m tile) search.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace fi {
@@ -68,7 +70,6 @@ __device__ __forceinline__ bool find_group_tile(const int32_t* m_indptr, int num
 
 using i32x8g = __attribute__((ext_vector_type(8))) int;
 
-// 256 x 256 tile persistent kernel (gemm_big.hip); p.num_m_tiles_bound counts 256-row tiles
 // The power-of-two verdict of a call: kPow2Words words, one per workgroup of the check kernel (non-zero = that
 // workgroup saw a scale that is not a positive normal power of two).  No word is ever reset: every call's check
 // kernel rewrites all of its slot's words, so there is no memset node in front of it.
@@ -77,10 +78,25 @@ __device__ __forceinline__ bool fi_scales_are_pow2(const uint32_t* flag) {
   return flag != nullptr && !__any(flag[threadIdx.x & (kPow2Words - 1)] != 0);
 }
 
-// hws_only_flag == nullptr: both variants (power-of-two scales on the hardware path, anything else folded).
-// Otherwise only the hardware-scale variant, and *hws_only_flag receives the call's device flag words (fi_scales_are_pow2 after the check
-// kernel = that variant does the call; the caller's own kernel must return at once then), or nullptr when nothing
-// was launched.
-hipError_t launch_gemm_big(const GemmParams& p, int grid, hipStream_t stream, uint32_t** hws_only_flag);
+// f(std::bool_constant<MA_E5M2>{}, std::bool_constant<MB_E5M2>{}) for the call's fp8 formats: the MFMA A operand is
+// GEMM matrix B, the MFMA B operand GEMM matrix A
+template <class F>
+void with_fp8_formats(const GemmParams& p, F&& f) {
+  auto with_ma = [&](auto ma) {
+    if (p.a_is_e5m2) f(ma, std::true_type{});
+    else f(ma, std::false_type{});
+  };
+  if (p.b_is_e5m2) with_ma(std::true_type{});
+  else with_ma(std::false_type{});
+}
+
+// 256 x 256 tile persistent kernel (gemm_big.hip); p.num_m_tiles_bound counts 256-row tiles.
+// A call's flag words (kPow2Words), or nullptr under a stream capture before the first eager call.
+uint32_t* pow2_flag_slot(hipStream_t stream);
+// The check kernel: writes p.pow2_flag (non-null) from p's scales.
+void launch_pow2_check(const GemmParams& p, hipStream_t stream);
+// hws: the hardware-scale variant (does the call when fi_scales_are_pow2(p.pow2_flag), else returns at once);
+// otherwise the fold variant (the reverse).
+void launch_gemm_big(const GemmParams& p, bool hws, int grid, hipStream_t stream);
 
 }  // namespace fi

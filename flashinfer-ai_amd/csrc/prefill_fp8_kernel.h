@@ -34,16 +34,6 @@
 
 #include "prefill_kernel.h"
 
-#ifndef FI_PF8_KO
-#define FI_PF8_KO 0  // timing experiments only (results are wrong), bit mask: 1 no exp2, 2 no DMA in the steps,
-                     // 4 no barrier / vmcnt wait, 8 no P.V MFMAs, 16 no QK^T MFMAs, 32 no rescale check,
-                     // 64 one workgroup per CU (LDS padded)
-#endif
-
-#ifndef FI_PF8_ASM_MFMA
-#define FI_PF8_ASM_MFMA 1  // the steps' MFMAs as asm volatile statements: they stay where the source puts them
-#endif
-
 namespace fi {
 
 using i32x8 = __attribute__((ext_vector_type(8))) int;
@@ -141,7 +131,7 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
   // ONE static array for every LDS object: the compiler separates an LDS-DMA target from an LDS read by
   // constant offsets (and index ranges) inside one object; with a second object, or unbounded indices, it
   // puts s_waitcnt vmcnt(0) in front of the reads and the prefetch is gone
-  __shared__ __attribute__((aligned(1024))) char smem[kF8Smem + ((FI_PF8_KO & 64) ? 40960 : 0)];
+  __shared__ __attribute__((aligned(1024))) char smem[kF8Smem];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -440,7 +430,7 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
     auto exp_arg = [&](float sv) { return __builtin_fmaf(sv, UNI ? c_sreg : c_lane, -m_adj); };
     // exp2 of registers r0 .. r0 + 7 of a score block: their sum and their e4m3 image (two words of the B operand)
     auto exp_chunk = [&](const f32x16& s, int r0, int& w0, int& w1, float& cs) {
-#define FI_F8_EXP(i) ((FI_PF8_KO & 1) ? exp_arg(s[r0 + i]) : fast_exp2(exp_arg(s[r0 + i])))
+#define FI_F8_EXP(i) fast_exp2(exp_arg(s[r0 + i]))
       const float x[8] = {FI_F8_EXP(0), FI_F8_EXP(1), FI_F8_EXP(2), FI_F8_EXP(3), FI_F8_EXP(4), FI_F8_EXP(5), FI_F8_EXP(6), FI_F8_EXP(7)};
 #undef FI_F8_EXP
       // two chains of single adds (packed f32 adds beside MFMAs cost more than the pairs they replace; the
@@ -571,7 +561,6 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
       // row offsets of tile t+3 (its DMA is issued inside region A, after the table read has returned)
       DmaOffs f;
       dma_offsets((ST + 3) & 3, f);
-      const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       const char* const kb = smem + ((ST + 1) & 3) * kF8KTile;  // tile t+1 (past the end: the last tile again)
       int p8w[8];
       float cs0, cs1, cs2, cs3;
@@ -602,38 +591,28 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
   __builtin_amdgcn_sched_barrier(0);
       int unit = 0x7F7F7F7F;
       asm volatile("" : "+v"(unit));
-#if FI_PF8_ASM_MFMA
-#define FI_F8_QK0(dst, a, b) if (!(FI_PF8_KO & 16)) mfma_fp8_k64_asm_zero<BF8>(dst, a, b, unit)
-#define FI_F8_QK1(dst, a, b) if (!(FI_PF8_KO & 16)) mfma_fp8_k64_asm<BF8>(dst, a, b, unit)
-#define FI_F8_PV(dst, a, b) if (!(FI_PF8_KO & 8)) mfma_fp8_k64_asm<BF8>(dst, a, b, unit)
-#else
-#define FI_F8_QK0(dst, a, b) if (!(FI_PF8_KO & 16)) dst = mfma_fp8_k64_fmt<BF8>(a, b, zero)
-#define FI_F8_QK1(dst, a, b) if (!(FI_PF8_KO & 16)) dst = mfma_fp8_k64_fmt<BF8>(a, b, dst)
-#define FI_F8_PV(dst, a, b) if (!(FI_PF8_KO & 8)) dst = mfma_fp8_k64_fmt<BF8>(a, b, dst)
-#endif
       i32x8 kf0 = k_frag(kb, 0);
       i32x8 kf1 = k_frag(kb, 1);
       __builtin_amdgcn_sched_barrier(0);  // every LDS read of the step's head is in flight before the first chunk
       exp_chunk(sc[0], 0, p8w[0], p8w[1], cs0);
       // new rows for the ring: tile t+3 into the stage tile t-1 left (every wave passed the barrier of t-1)
-      if (!(FI_PF8_KO & 2)) dma_issue((ST + 3) & 3, f);
+      dma_issue((ST + 3) & 3, f);
       __builtin_amdgcn_sched_barrier(0);
-      FI_F8_QK0(sn[0], kf0, q0);
+      mfma_fp8_k64_asm_zero<BF8>(sn[0], kf0, q0, unit);
       kf0 = k_frag(kb, 2);
       exp_chunk(sc[0], 8, p8w[2], p8w[3], cs1);
       FI_F8_GROUP(2)
-      FI_F8_QK1(sn[0], kf1, q1);
+      mfma_fp8_k64_asm<BF8>(sn[0], kf1, q1, unit);
       kf1 = k_frag(kb, 3);
       exp_chunk(sc[1], 0, p8w[4], p8w[5], cs2);
       FI_F8_GROUP(2)
-      FI_F8_QK0(sn[1], kf0, q0);
+      mfma_fp8_k64_asm_zero<BF8>(sn[1], kf0, q0, unit);
       exp_chunk(sc[1], 8, p8w[6], p8w[7], cs3);
       FI_F8_GROUP(0)
 #undef FI_F8_GROUP
-      FI_F8_QK1(sn[1], kf1, q1);
-      if (FI_PF8_KO & 16) asm volatile("" : "+v"(kf0), "+v"(kf1));
+      mfma_fp8_k64_asm<BF8>(sn[1], kf1, q1, unit);
       __builtin_amdgcn_sched_barrier(0);
-      if (__builtin_expect(!(FI_PF8_KO & 32) && __any(!(fmaxf(fmaxf(cs0, cs1), fmaxf(cs2, cs3)) <= kPMax)), 0)) {
+      if (__builtin_expect(__any(!(fmaxf(fmaxf(cs0, cs1), fmaxf(cs2, cs3)) <= kPMax)), 0)) {
         // rare: some probability may have left the e4m3 range -- exact maximum of tile t, move the exponent, again
         rescale_to(fmaxf(m_run, row_max(sc) * c_exp));
         exp_chunk(sc[0], 0, p8w[0], p8w[1], cs0);
@@ -645,34 +624,28 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
       const i32x8 p8 = {p8w[0], p8w[1], p8w[2], p8w[3], p8w[4], p8w[5], p8w[6], p8w[7]};
       // ---- region B ----  (the fourth QK^T MFMA runs under the wait for the first V^T fragment)
       FI_F8_VWAIT(4, va);
-      { const i32x8 vf = FI_F8_VFRAG(va); FI_F8_PV(o_acc[0], vf, p8); }
+      mfma_fp8_k64_asm<BF8>(o_acc[0], FI_F8_VFRAG(va), p8, unit);
       FI_F8_VREAD(va, 2)
       __builtin_amdgcn_sched_barrier(0);
       FI_F8_VWAIT(4, vb);
-      { const i32x8 vf = FI_F8_VFRAG(vb); FI_F8_PV(o_acc[1], vf, p8); }
+      mfma_fp8_k64_asm<BF8>(o_acc[1], FI_F8_VFRAG(vb), p8, unit);
       FI_F8_VREAD(vb, 3)
       __builtin_amdgcn_sched_barrier(0);
       FI_F8_VWAIT(4, va);
-      { const i32x8 vf = FI_F8_VFRAG(va); FI_F8_PV(o_acc[2], vf, p8); }
+      mfma_fp8_k64_asm<BF8>(o_acc[2], FI_F8_VFRAG(va), p8, unit);
       __builtin_amdgcn_sched_barrier(0);
       FI_F8_VWAIT(0, vb);
-      { const i32x8 vf = FI_F8_VFRAG(vb); FI_F8_PV(o_acc[3], vf, p8); }
-      if (FI_PF8_KO & 8) asm volatile("" :: "v"(p8), "v"(va[0]), "v"(vb[0]));
+      mfma_fp8_k64_asm<BF8>(o_acc[3], FI_F8_VFRAG(vb), p8, unit);
       if constexpr (MASK) apply_mask(t + 1, sn);
 #undef FI_F8_VREAD
 #undef FI_F8_VWAIT
 #undef FI_F8_VFRAG
-#undef FI_F8_QK0
-#undef FI_F8_QK1
-#undef FI_F8_PV
       // K of tile t+2 (and everything older, V of tile t+1 included) of this wave's pieces landed; then the
       // workgroup barrier.  ONE asm statement: the s_barrier builtin alone is no memory fence for the compiler,
       // which would hoist the next step's LDS reads between the wait and the barrier.
       // (in flight afterwards: V of tile t+2 and both operands of tile t+3 -- 6 pieces, 3 with NW = 8)
-      if (!(FI_PF8_KO & 4)) {
-        if constexpr (PASSES == 2) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      }
+      if constexpr (PASSES == 2) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");
       }  // D == 128
     };
     auto refill_if_needed = [&](int t_first, int t_last) {

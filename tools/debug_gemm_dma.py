@@ -1,4 +1,4 @@
-"""Compare a forced GEMM kernel (FI_GEMM_WS_MIN_TILES=0 with FI_GEMM_DMA / FI_GEMM_DMA_TM) with the exact
+"""Compare a forced GEMM kernel (FI_GEMM_WS_MIN_TILES=0, optionally FI_GEMM_DMA_TM=256 / 128) with the exact
 small-integer result rounded to fp16; prints where they differ."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
