@@ -127,3 +127,89 @@ extern "C" FI_API int fi_append_paged_kv_cache(const void* append_key, const voi
   FI_HIP_CALL(hipGetLastError());
   return 0;
 }
+
+namespace fi {
+
+struct AppendMlaParams {
+  const char* ckv;
+  const char* kpe;
+  char* ckv_cache;
+  char* kpe_cache;
+  const int32_t* batch_indices;
+  const int32_t* positions;
+  const int32_t* kv_indptr;
+  const int32_t* kv_indices;
+  int64_t ckv_stride_n, kpe_stride_n;                       // append tensors (elements)
+  int64_t ckv_stride_page, ckv_cache_stride_n, kpe_stride_page, kpe_cache_stride_n;  // caches (elements)
+  FastDiv page_div;
+  int32_t page_size, nnz;
+};
+
+// MLA append (ref: AppendPagedKVMlaCacheKernel semantics, flashinfer/page.py:250-298): one 16-byte chunk per
+// thread, 72 chunks per token (64 of the 512-wide ckv row, 8 of the 64-wide kpe row), 16-bit elements.
+constexpr int kMlaAppendChunks = (512 + 64) * 2 / 16;
+__global__ void __launch_bounds__(kPageThreads) append_paged_mla_kv_cache_kernel(const AppendMlaParams p) {
+  const int64_t total = (int64_t)p.nnz * kMlaAppendChunks;
+  for (int64_t it = (int64_t)blockIdx.x * kPageThreads + threadIdx.x; it < total;
+       it += (int64_t)gridDim.x * kPageThreads) {
+    const int c = (int)(it % kMlaAppendChunks);
+    const int i = (int)(it / kMlaAppendChunks);
+    const int b = p.batch_indices[i];
+    const int pos = p.positions[i];
+    const int pi = (int)fast_div((uint32_t)pos, p.page_div);
+    const int entry = pos - pi * p.page_size;
+    const int64_t page = p.kv_indices[p.kv_indptr[b] + pi];
+    if (c < 64) {
+      *(u32x4*)(p.ckv_cache + (page * p.ckv_stride_page + entry * p.ckv_cache_stride_n) * 2 + c * 16) =
+          *(const u32x4*)(p.ckv + (int64_t)i * p.ckv_stride_n * 2 + c * 16);
+    } else {
+      *(u32x4*)(p.kpe_cache + (page * p.kpe_stride_page + entry * p.kpe_cache_stride_n) * 2 + (c - 64) * 16) =
+          *(const u32x4*)(p.kpe + (int64_t)i * p.kpe_stride_n * 2 + (c - 64) * 16);
+    }
+  }
+}
+
+}  // namespace fi
+
+extern "C" FI_API int fi_append_paged_mla_kv_cache(const fi_append_paged_mla_kv_params_t* a, fi_stream_t stream) {
+  FI_REQUIRE(a, "append_paged_mla_kv_cache: null params");
+  if (a->nnz == 0) return 0;
+  FI_REQUIRE(a->head_dim_ckv == 512 && a->head_dim_kpe == 64,
+             "append_paged_mla_kv_cache: unsupported head dims %d / %d (only 512 / 64)", a->head_dim_ckv,
+             a->head_dim_kpe);
+  FI_REQUIRE(a->dtype == FI_DTYPE_F16 || a->dtype == FI_DTYPE_BF16,
+             "append_paged_mla_kv_cache: unsupported dtype %d (f16 / bf16)", a->dtype);
+  FI_REQUIRE(a->append_ckv && a->append_kpe && a->batch_indices && a->positions && a->ckv_cache && a->kpe_cache &&
+                 a->kv_indices && a->kv_indptr,
+             "append_paged_mla_kv_cache: null tensor");
+  FI_REQUIRE(a->nnz > 0 && a->page_size > 0, "append_paged_mla_kv_cache: bad nnz / page size");
+  const int64_t strides[] = {a->append_ckv_stride_n, a->append_kpe_stride_n, a->ckv_stride_page, a->ckv_stride_n,
+                             a->kpe_stride_page, a->kpe_stride_n};
+  for (int64_t s : strides) FI_REQUIRE(s % 8 == 0, "append_paged_mla_kv_cache: rows must be 16-byte aligned");
+  FI_REQUIRE(((uintptr_t)a->append_ckv | (uintptr_t)a->append_kpe | (uintptr_t)a->ckv_cache |
+              (uintptr_t)a->kpe_cache) % 16 == 0,
+             "append_paged_mla_kv_cache: rows must be 16-byte aligned");
+  AppendMlaParams p;
+  p.ckv = (const char*)a->append_ckv;
+  p.kpe = (const char*)a->append_kpe;
+  p.ckv_cache = (char*)a->ckv_cache;
+  p.kpe_cache = (char*)a->kpe_cache;
+  p.batch_indices = a->batch_indices;
+  p.positions = a->positions;
+  p.kv_indptr = a->kv_indptr;
+  p.kv_indices = a->kv_indices;
+  p.ckv_stride_n = a->append_ckv_stride_n;
+  p.kpe_stride_n = a->append_kpe_stride_n;
+  p.ckv_stride_page = a->ckv_stride_page;
+  p.ckv_cache_stride_n = a->ckv_stride_n;
+  p.kpe_stride_page = a->kpe_stride_page;
+  p.kpe_cache_stride_n = a->kpe_stride_n;
+  p.page_div = FastDiv((uint32_t)a->page_size);
+  p.page_size = a->page_size;
+  p.nnz = a->nnz;
+  const int64_t total = (int64_t)a->nnz * kMlaAppendChunks;
+  const int grid = (int)std::min<int64_t>((total + kPageThreads - 1) / kPageThreads, 256 * 8);
+  append_paged_mla_kv_cache_kernel<<<dim3(grid), dim3(kPageThreads), 0, (hipStream_t)stream>>>(p);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}

@@ -5,6 +5,7 @@ v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-written HIP kernels 
 ``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided.
 """
 from . import _lib as _lib
+from . import mla as mla
 from .cascade import (
     BatchDecodeWithSharedPrefixPagedKVCacheWrapper as BatchDecodeWithSharedPrefixPagedKVCacheWrapper,
 )
@@ -27,7 +28,9 @@ from .decode import fast_decode_plan as fast_decode_plan
 from .decode import single_decode_with_kv_cache as single_decode_with_kv_cache
 from .gemm import gemm_fp8_nt_groupwise as gemm_fp8_nt_groupwise
 from .gemm import group_gemm_fp8_nt_groupwise as group_gemm_fp8_nt_groupwise
+from .mla import BatchMLAPagedAttentionWrapper as BatchMLAPagedAttentionWrapper
 from .page import append_paged_kv_cache as append_paged_kv_cache
+from .page import append_paged_mla_kv_cache as append_paged_mla_kv_cache
 from .page import apply_rope_append_paged_kv_cache as apply_rope_append_paged_kv_cache
 from .page import get_batch_indices_positions as get_batch_indices_positions
 from .page import get_seq_lens as get_seq_lens

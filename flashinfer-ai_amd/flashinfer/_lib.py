@@ -181,7 +181,49 @@ class RopeParams(C.Structure):
     ]
 
 
+class MlaPlanParams(C.Structure):
+    _fields_ = [
+        ("int_ws", C.c_void_p), ("pinned_int_ws", C.c_void_p), ("int_ws_bytes", C.c_size_t),
+        ("float_ws_bytes", C.c_size_t), ("qo_indptr_h", C.c_void_p), ("kv_indptr_h", C.c_void_p),
+        ("kv_len_arr_h", C.c_void_p), ("batch_size", C.c_int32), ("num_heads", C.c_int32),
+        ("head_dim_ckv", C.c_int32), ("head_dim_kpe", C.c_int32), ("page_size", C.c_int32), ("causal", C.c_int32),
+        ("q_dtype", C.c_int32), ("kv_dtype", C.c_int32), ("enable_cuda_graph", C.c_int32),
+        ("fixed_split_size", C.c_int32),
+    ]
+
+
+class MlaParams(C.Structure):
+    _fields_ = [
+        ("q_nope", C.c_void_p), ("q_nope_stride_n", C.c_int64), ("q_nope_stride_h", C.c_int64),
+        ("q_pe", C.c_void_p), ("q_pe_stride_n", C.c_int64), ("q_pe_stride_h", C.c_int64),
+        ("ckv", C.c_void_p), ("ckv_stride_page", C.c_int64), ("ckv_stride_n", C.c_int64),
+        ("kpe", C.c_void_p), ("kpe_stride_page", C.c_int64), ("kpe_stride_n", C.c_int64),
+        ("kv_indices", C.c_void_p), ("o", C.c_void_p), ("lse", C.c_void_p),
+        ("float_ws", C.c_void_p), ("float_ws_bytes", C.c_size_t), ("int_ws", C.c_void_p), ("int_ws_bytes", C.c_size_t),
+        ("num_rows", C.c_int32), ("num_heads", C.c_int32), ("page_size", C.c_int32), ("dtype", C.c_int32),
+        ("causal", C.c_int32), ("sm_scale", C.c_float),
+    ]
+
+
+class AppendMlaParams(C.Structure):
+    _fields_ = [
+        ("append_ckv", C.c_void_p), ("append_ckv_stride_n", C.c_int64),
+        ("append_kpe", C.c_void_p), ("append_kpe_stride_n", C.c_int64),
+        ("batch_indices", C.c_void_p), ("positions", C.c_void_p),
+        ("ckv_cache", C.c_void_p), ("ckv_stride_page", C.c_int64), ("ckv_stride_n", C.c_int64),
+        ("kpe_cache", C.c_void_p), ("kpe_stride_page", C.c_int64), ("kpe_stride_n", C.c_int64),
+        ("kv_indices", C.c_void_p), ("kv_indptr", C.c_void_p),
+        ("nnz", C.c_int32), ("page_size", C.c_int32), ("head_dim_ckv", C.c_int32), ("head_dim_kpe", C.c_int32),
+        ("dtype", C.c_int32),
+    ]
+
+
 FI_PREFILL_PLAN_INFO_LEN = 16
+FI_MLA_PLAN_INFO_LEN = 16
+# plan_info slots of fi_batch_mla_plan (include/fi_mi355.h, enum fi_mla_plan_slot)
+(FI_MLA_NUM_WORK, FI_MLA_GRID, FI_MLA_TOTAL_ROWS, FI_MLA_KV_CHUNK_SIZE, FI_MLA_SPLIT_KV, FI_MLA_ENABLE_CUDA_GRAPH,
+ FI_MLA_NUM_HEADS, FI_MLA_BATCH_SIZE, FI_MLA_INT_BYTES_USED, FI_MLA_MERGE_INDPTR_OFFSET, FI_MLA_ITEMS_OFFSET,
+ FI_MLA_NUM_ENTRIES, FI_MLA_V_OFFSET, FI_MLA_PAGE_SIZE, FI_MLA_DTYPE, FI_MLA_MAGIC) = range(16)
 
 _lib: Optional[C.CDLL] = None
 
@@ -210,6 +252,9 @@ EXPORTED_SYMBOLS = [
     "fi_rope_positions_from_indptr",
     "fi_packbits",
     "fi_segment_packbits",
+    "fi_batch_mla_plan",
+    "fi_batch_mla_run",
+    "fi_append_paged_mla_kv_cache",
 ]
 
 
@@ -248,6 +293,9 @@ def lib() -> C.CDLL:
     l.fi_apply_rope_pos_ids.argtypes = [C.POINTER(RopeParams), vp]
     l.fi_apply_rope_append_paged_kv_cache.argtypes = [C.POINTER(RopeParams), vp, C.c_int64, C.c_int64, vp, vp, C.POINTER(PagedKV), vp]
     l.fi_rope_positions_from_indptr.argtypes = [vp, vp, i32, i32, vp, vp]
+    l.fi_batch_mla_plan.argtypes = [C.POINTER(MlaPlanParams), i64p, vp]
+    l.fi_batch_mla_run.argtypes = [i64p, i32, C.POINTER(MlaParams), vp]
+    l.fi_append_paged_mla_kv_cache.argtypes = [C.POINTER(AppendMlaParams), vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(l, name)
         if name not in ("fi_last_error",):

@@ -1,0 +1,231 @@
+"""Multi-head Latent Attention (MLA, DeepSeek-V2/V3/R1) over a paged cache (ref: flashinfer/mla.py:85-420).
+
+The absorbed form: one shared KV "head" whose keys are ``[ckv | kpe]`` (512 + 64 dims) and whose values are the
+``ckv`` part alone.  Every backend name the reference accepts for this path (``auto`` / ``fa2`` / ``fa3``) runs the
+one HIP kernel of ``csrc/mla.hip``; the planner splits long requests into kv chunks and merges their partial states.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple, Union
+
+import torch
+
+from . import _lib
+
+_MLA_INT_WORKSPACE_BYTES = 8 * 1024 * 1024
+
+
+def _last_dim_contiguous(t: torch.Tensor, name: str) -> None:
+    if t.stride(-1) != 1:
+        raise ValueError(f"{name} must have a contiguous last dimension")
+
+
+class BatchMLAPagedAttentionWrapper:
+    r"""Wrapper class for MLA PagedAttention on DeepSeek models, for decode, speculative verify and incremental
+    prefill with the matrix-absorbed weights (ref: flashinfer/mla.py:85-420).
+
+    ``head_dim_ckv = 512`` and ``head_dim_kpe = 64`` only; q and the caches both float16 or both bfloat16.
+    ``ckv_cache``: ``[num_pages, page_size, 512]``, ``kpe_cache``: ``[num_pages, page_size, 64]`` (3-D, or 4-D
+    with a middle head axis of 1).  Only the last dimension of each input must be contiguous, so views of one
+    576-wide tensor (``q[..., :512]`` / ``q[..., 512:]``) are taken as they are.  ``lse`` is base 2.
+
+    With ``use_cuda_graph=True`` plan() copies the page table into the buffers given here, and run() launches a
+    fixed grid whose work list is read from the workspace, so a captured run() stays valid across plans for the
+    same batch size, query count and head count; plan() refuses a change of any of them.
+    """
+
+    def __init__(
+        self,
+        float_workspace_buffer: torch.Tensor,
+        use_cuda_graph: bool = False,
+        qo_indptr: Optional[torch.Tensor] = None,
+        kv_indptr: Optional[torch.Tensor] = None,
+        kv_indices: Optional[torch.Tensor] = None,
+        kv_len_arr: Optional[torch.Tensor] = None,
+        backend: str = "auto",
+    ) -> None:
+        if backend == "cutlass":
+            raise ValueError(
+                "BatchMLAPagedAttentionWrapper: backend='cutlass' is not available on MI355X "
+                "(use 'auto', 'fa2' or 'fa3', which all run the HIP kernel)"
+            )
+        if backend not in ("auto", "fa2", "fa3"):
+            raise ValueError(f"BatchMLAPagedAttentionWrapper: unknown backend {backend!r}")
+        _lib.require_gpu_tensor(float_workspace_buffer, "float_workspace_buffer")
+        self._float_workspace_buffer = float_workspace_buffer
+        self.device = float_workspace_buffer.device
+        self._backend = backend
+        self._int_workspace_buffer = torch.empty((_MLA_INT_WORKSPACE_BYTES,), dtype=torch.uint8, device=self.device)
+        self._pin_memory_int_workspace_buffer = torch.empty(
+            (_MLA_INT_WORKSPACE_BYTES,), dtype=torch.uint8, pin_memory=True, device="cpu"
+        )
+        self._use_cuda_graph = use_cuda_graph
+        if use_cuda_graph:
+            for t, name in ((qo_indptr, "qo_indptr"), (kv_indptr, "kv_indptr"), (kv_indices, "kv_indices"),
+                            (kv_len_arr, "kv_len_arr")):
+                if t is None:
+                    raise ValueError(f"use_cuda_graph=True needs the {name} buffer")
+        self._qo_indptr_buf = qo_indptr
+        self._kv_indptr_buf = kv_indptr
+        self._kv_indices_buf = kv_indices
+        self._kv_len_arr_buf = kv_len_arr
+        self._plan_info = None
+        self._graph_rows = None  # (qo_indptr[-1], num_heads) of the first graph plan
+
+    def plan(
+        self,
+        qo_indptr: torch.Tensor,
+        kv_indptr: torch.Tensor,
+        kv_indices: torch.Tensor,
+        kv_len_arr: torch.Tensor,
+        num_heads: int,
+        head_dim_ckv: int,
+        head_dim_kpe: int,
+        page_size: int,
+        causal: bool,
+        sm_scale: float,
+        q_data_type: torch.dtype,
+        kv_data_type: torch.dtype,
+        use_profiler: bool = False,
+    ) -> None:
+        r"""Plan the MLA attention of a batch (ref: flashinfer/mla.py:219-317).
+
+        qo_indptr ``[batch + 1]``, kv_indptr ``[batch + 1]`` (pages), kv_indices ``[kv_indptr[-1]]``,
+        kv_len_arr ``[batch]`` (tokens), all int32.  ``causal`` aligns query rows to the end of the sequence.
+        """
+        if use_profiler:
+            raise ValueError("BatchMLAPagedAttentionWrapper: the profiler is not available on MI355X")
+        for t, name in ((kv_len_arr, "kv_len_arr"), (kv_indptr, "kv_indptr"), (qo_indptr, "qo_indptr"),
+                        (kv_indices, "kv_indices")):
+            if t.dtype != torch.int32:
+                raise ValueError(f"Expected {name}.dtype == torch.int32, got {t.dtype}")
+        qo_indptr_host = qo_indptr.to("cpu").contiguous()
+        kv_indptr_host = kv_indptr.to("cpu").contiguous()
+        kv_len_arr_host = kv_len_arr.to("cpu").contiguous()
+        batch_size = qo_indptr_host.numel() - 1
+        if kv_indptr_host.numel() != batch_size + 1 or kv_len_arr_host.numel() != batch_size:
+            raise ValueError("qo_indptr, kv_indptr and kv_len_arr disagree on the batch size")
+        if self._use_cuda_graph:
+            if batch_size + 1 != self._qo_indptr_buf.numel():
+                raise ValueError("use_cuda_graph: the batch size cannot change after construction")
+            # a captured run() holds the q / out tensors and the merge launch of the first plan's packed row count
+            # (qo_indptr[-1] x num_heads), and the workspace layout moves with it: every later plan must keep both
+            graph_rows = (int(qo_indptr_host[-1]), int(num_heads))
+            if self._graph_rows is not None and graph_rows != self._graph_rows:
+                raise ValueError(
+                    "use_cuda_graph: the query count and num_heads cannot change between plans "
+                    f"(qo_indptr[-1], num_heads = {graph_rows}; first plan {self._graph_rows})"
+                )
+            if kv_indices.numel() > self._kv_indices_buf.numel():
+                raise ValueError("use_cuda_graph: kv_indices does not fit the kv_indices buffer")
+            self._qo_indptr_buf.copy_(qo_indptr, non_blocking=True)
+            self._kv_indptr_buf.copy_(kv_indptr, non_blocking=True)
+            self._kv_indices_buf[: len(kv_indices)].copy_(kv_indices, non_blocking=True)
+            self._kv_len_arr_buf.copy_(kv_len_arr, non_blocking=True)
+        else:
+            self._qo_indptr_buf = qo_indptr.to(self.device, non_blocking=True)
+            self._kv_indptr_buf = kv_indptr.to(self.device, non_blocking=True)
+            self._kv_indices_buf = kv_indices.to(self.device, non_blocking=True)
+            self._kv_len_arr_buf = kv_len_arr.to(self.device, non_blocking=True)
+        params = _lib.MlaPlanParams(
+            int_ws=self._int_workspace_buffer.data_ptr(),
+            pinned_int_ws=self._pin_memory_int_workspace_buffer.data_ptr(),
+            int_ws_bytes=self._int_workspace_buffer.numel(),
+            float_ws_bytes=self._float_workspace_buffer.numel() * self._float_workspace_buffer.element_size(),
+            qo_indptr_h=qo_indptr_host.data_ptr(), kv_indptr_h=kv_indptr_host.data_ptr(),
+            kv_len_arr_h=kv_len_arr_host.data_ptr(), batch_size=batch_size, num_heads=num_heads,
+            head_dim_ckv=head_dim_ckv, head_dim_kpe=head_dim_kpe, page_size=page_size, causal=int(bool(causal)),
+            q_dtype=_lib.fi_dtype(q_data_type), kv_dtype=_lib.fi_dtype(kv_data_type),
+            enable_cuda_graph=int(bool(self._use_cuda_graph)), fixed_split_size=0,
+        )
+        info = (C.c_int64 * _lib.FI_MLA_PLAN_INFO_LEN)()
+        with torch.cuda.device(self.device):
+            _lib.check(
+                _lib.lib().fi_batch_mla_plan(C.byref(params), info, _lib.current_stream(self.device)),
+                "BatchMLAPagedAttentionWrapper.plan",
+            )
+        self._plan_info = info
+        if self._use_cuda_graph and self._graph_rows is None:
+            self._graph_rows = graph_rows
+        self._num_heads = num_heads
+        self._page_size = page_size
+        self._causal = bool(causal)
+        self._sm_scale = float(sm_scale)
+        self._q_data_type = q_data_type
+        self._kv_data_type = kv_data_type
+
+    def run(
+        self,
+        q_nope: torch.Tensor,
+        q_pe: torch.Tensor,
+        ckv_cache: torch.Tensor,
+        kpe_cache: torch.Tensor,
+        out: Optional[torch.Tensor] = None,
+        lse: Optional[torch.Tensor] = None,
+        return_lse: bool = False,
+        profiler_buffer: Optional[torch.Tensor] = None,
+        kv_len: Optional[torch.Tensor] = None,
+        page_table: Optional[torch.Tensor] = None,
+    ) -> Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+        r"""Run the planned MLA attention (ref: flashinfer/mla.py:345-420).
+
+        q_nope ``[nnz_qo, num_heads, 512]``, q_pe ``[nnz_qo, num_heads, 64]``; returns ``o`` of q_nope's shape
+        and dtype, and with ``return_lse`` also ``lse`` ``[nnz_qo, num_heads]`` float32 (base 2).
+        """
+        if profiler_buffer is not None:
+            raise ValueError("BatchMLAPagedAttentionWrapper: profiler_buffer is not supported on MI355X")
+        if kv_len is not None or page_table is not None:
+            raise ValueError("BatchMLAPagedAttentionWrapper: the kv_len / page_table call form is the cutlass "
+                             "backend's and is not supported on MI355X")
+        if self._plan_info is None:
+            raise RuntimeError("BatchMLAPagedAttentionWrapper: call plan() before run()")
+        for t, name in ((q_nope, "q_nope"), (q_pe, "q_pe"), (ckv_cache, "ckv_cache"), (kpe_cache, "kpe_cache")):
+            _lib.require_gpu_tensor(t, name)
+            _last_dim_contiguous(t, name)
+        if q_nope.dtype != self._q_data_type or q_pe.dtype != self._q_data_type:
+            raise ValueError(f"q_nope / q_pe must be {self._q_data_type}, as planned")
+        if ckv_cache.dtype != self._kv_data_type or kpe_cache.dtype != self._kv_data_type:
+            raise ValueError(f"ckv_cache / kpe_cache must be {self._kv_data_type}, as planned")
+        H = self._num_heads
+        if q_nope.dim() != 3 or q_nope.shape[1:] != (H, 512) or q_pe.shape != (q_nope.shape[0], H, 64):
+            raise ValueError("q_nope must be [nnz, num_heads, 512] and q_pe [nnz, num_heads, 64]")
+        ckv3, kpe3 = ckv_cache, kpe_cache
+        if ckv3.dim() == 4:
+            ckv3 = ckv3.squeeze(2)
+        if kpe3.dim() == 4:
+            kpe3 = kpe3.squeeze(2)
+        if ckv3.dim() != 3 or ckv3.shape[1] != self._page_size or ckv3.shape[2] != 512:
+            raise ValueError("ckv_cache must be [num_pages, page_size, 512]")
+        if kpe3.dim() != 3 or kpe3.shape[:2] != ckv3.shape[:2] or kpe3.shape[2] != 64:
+            raise ValueError("kpe_cache must be [num_pages, page_size, 64]")
+        nnz = q_nope.shape[0]
+        if out is None:
+            out = torch.empty((nnz, H, 512), dtype=q_nope.dtype, device=q_nope.device)
+        elif out.shape != (nnz, H, 512) or out.dtype != q_nope.dtype or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [nnz, num_heads, 512] tensor of q's dtype")
+        if return_lse:
+            if lse is None:
+                lse = torch.empty((nnz, H), dtype=torch.float32, device=q_nope.device)
+            elif lse.shape != (nnz, H) or lse.dtype != torch.float32 or not lse.is_contiguous():
+                raise ValueError("lse must be a contiguous float32 [nnz, num_heads] tensor")
+        fw = self._float_workspace_buffer
+        params = _lib.MlaParams(
+            q_nope=q_nope.data_ptr(), q_nope_stride_n=q_nope.stride(0), q_nope_stride_h=q_nope.stride(1),
+            q_pe=q_pe.data_ptr(), q_pe_stride_n=q_pe.stride(0), q_pe_stride_h=q_pe.stride(1),
+            ckv=ckv3.data_ptr(), ckv_stride_page=ckv3.stride(0), ckv_stride_n=ckv3.stride(1),
+            kpe=kpe3.data_ptr(), kpe_stride_page=kpe3.stride(0), kpe_stride_n=kpe3.stride(1),
+            kv_indices=self._kv_indices_buf.data_ptr(), o=out.data_ptr(),
+            lse=None if not return_lse else lse.data_ptr(),
+            float_ws=fw.data_ptr(), float_ws_bytes=fw.numel() * fw.element_size(),
+            int_ws=self._int_workspace_buffer.data_ptr(), int_ws_bytes=self._int_workspace_buffer.numel(),
+            num_rows=nnz * H, num_heads=H, page_size=self._page_size, dtype=_lib.fi_dtype(q_nope.dtype),
+            causal=int(self._causal), sm_scale=self._sm_scale,
+        )
+        with torch.cuda.device(q_nope.device):
+            _lib.check(
+                _lib.lib().fi_batch_mla_run(self._plan_info, _lib.FI_MLA_PLAN_INFO_LEN, C.byref(params),
+                                            _lib.current_stream(q_nope.device)),
+                "BatchMLAPagedAttentionWrapper.run",
+            )
+        return (out, lse) if return_lse else out

@@ -205,3 +205,64 @@ def apply_rope_append_paged_kv_cache(
             "apply_rope_append_paged_kv_cache",
         )
     return q_out
+
+
+def append_paged_mla_kv_cache(
+    append_ckv: torch.Tensor,
+    append_kpe: torch.Tensor,
+    batch_indices: torch.Tensor,
+    positions: torch.Tensor,
+    ckv_cache: Optional[torch.Tensor],
+    kpe_cache: Optional[torch.Tensor],
+    kv_indices: torch.Tensor,
+    kv_indptr: torch.Tensor,
+    kv_last_page_len: torch.Tensor,
+) -> None:
+    r"""Append MLA rows to the paged ``ckv`` / ``kpe`` caches (in place; ref: flashinfer/page.py:250-298).
+
+    append_ckv ``[nnz, 512]``, append_kpe ``[nnz, 64]`` (last dim contiguous); ckv_cache
+    ``[num_pages, page_size, 512]``, kpe_cache ``[num_pages, page_size, 64]``; batch_indices / positions
+    ``[nnz]`` int32 (see :func:`get_batch_indices_positions`); the page table is the one AFTER the append.
+    Only ``ckv_dim = 512`` and ``kpe_dim = 64``, float16 or bfloat16.
+    """
+    if ckv_cache is None or kpe_cache is None:
+        raise ValueError("append_paged_mla_kv_cache: ckv_cache and kpe_cache are required")
+    for t, name in ((append_ckv, "append_ckv"), (append_kpe, "append_kpe"), (ckv_cache, "ckv_cache"),
+                    (kpe_cache, "kpe_cache")):
+        _lib.require_gpu_tensor(t, name)
+        if t.stride(-1) != 1:
+            raise ValueError(f"append_paged_mla_kv_cache: {name} must have a contiguous last dimension")
+    if ckv_cache.dim() == 4:
+        ckv_cache = ckv_cache.squeeze(2)
+    if kpe_cache.dim() == 4:
+        kpe_cache = kpe_cache.squeeze(2)
+    if append_ckv.dim() != 2 or append_kpe.dim() != 2 or append_ckv.shape[0] != append_kpe.shape[0]:
+        raise ValueError("append_paged_mla_kv_cache: append_ckv / append_kpe must be [nnz, 512] / [nnz, 64]")
+    if ckv_cache.dim() != 3 or kpe_cache.dim() != 3 or ckv_cache.shape[:2] != kpe_cache.shape[:2]:
+        raise ValueError("append_paged_mla_kv_cache: caches must be [num_pages, page_size, dim]")
+    if not (append_ckv.dtype == append_kpe.dtype == ckv_cache.dtype == kpe_cache.dtype):
+        raise ValueError("append_paged_mla_kv_cache: all tensors must have one dtype")
+    if append_ckv.shape[1] != ckv_cache.shape[2] or append_kpe.shape[1] != kpe_cache.shape[2]:
+        raise ValueError("append_paged_mla_kv_cache: append rows do not match the cache width")
+    dev = ckv_cache.device
+    nnz = append_ckv.shape[0]
+    batch_indices = batch_indices.to(device=dev, dtype=torch.int32).contiguous()
+    positions = positions.to(device=dev, dtype=torch.int32).contiguous()
+    kv_indices = kv_indices.to(device=dev, dtype=torch.int32).contiguous()
+    kv_indptr = kv_indptr.to(device=dev, dtype=torch.int32).contiguous()
+    if batch_indices.numel() != nnz or positions.numel() != nnz:
+        raise ValueError("batch_indices and positions must have nnz entries")
+    p = _lib.AppendMlaParams(
+        append_ckv=append_ckv.data_ptr(), append_ckv_stride_n=append_ckv.stride(0),
+        append_kpe=append_kpe.data_ptr(), append_kpe_stride_n=append_kpe.stride(0),
+        batch_indices=batch_indices.data_ptr(), positions=positions.data_ptr(),
+        ckv_cache=ckv_cache.data_ptr(), ckv_stride_page=ckv_cache.stride(0), ckv_stride_n=ckv_cache.stride(1),
+        kpe_cache=kpe_cache.data_ptr(), kpe_stride_page=kpe_cache.stride(0), kpe_stride_n=kpe_cache.stride(1),
+        kv_indices=kv_indices.data_ptr(), kv_indptr=kv_indptr.data_ptr(), nnz=nnz, page_size=ckv_cache.shape[1],
+        head_dim_ckv=ckv_cache.shape[2], head_dim_kpe=kpe_cache.shape[2], dtype=_lib.fi_dtype(ckv_cache.dtype),
+    )
+    with torch.cuda.device(dev):
+        _lib.check(
+            _lib.lib().fi_append_paged_mla_kv_cache(C.byref(p), _lib.current_stream(dev)),
+            "append_paged_mla_kv_cache",
+        )

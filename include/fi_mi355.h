@@ -370,6 +370,97 @@ FI_API int fi_append_paged_kv_cache(const void* append_key, const void* append_v
                              const fi_paged_kv_t* kv, fi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Multi-head Latent Attention (absorbed form) over a paged cache.  ref: BatchMLAPagedAttentionWrapper,
+ * flashinfer/mla.py:85-420; append_paged_mla_kv_cache flashinfer/page.py:250-298.
+ *   one shared KV head; K = [ckv | kpe] (512 + 64 dims), V = ckv (512 dims)
+ *   ckv cache: [pages, page_size, 512], kpe cache: [pages, page_size, 64] (element strides below)
+ *   q_nope: [nnz_qo, num_heads, 512], q_pe: [nnz_qo, num_heads, 64]; o: [nnz_qo, num_heads, 512] contiguous
+ *   causal: query qo_idx of a request sees keys kv_idx <= kv_len - qo_len + qo_idx
+ * Packed row r of a request is (qo_idx = r / num_heads, head = r % num_heads); a work item is (request, tile of
+ * 16 packed rows, kv chunk).  Only head_dim_ckv = 512, head_dim_kpe = 64 and q dtype == kv dtype (f16 / bf16).
+ * ---------------------------------------------------------------------------------------------- */
+#define FI_MLA_PLAN_INFO_LEN 16
+enum fi_mla_plan_slot {
+  FI_MLA_NUM_WORK = 0,           /* work items */
+  FI_MLA_GRID = 1,               /* workgroups launched (fixed for graph plans; the kernel strides over items) */
+  FI_MLA_TOTAL_ROWS = 2,         /* qo_indptr[batch] * num_heads */
+  FI_MLA_KV_CHUNK_SIZE = 3,      /* tokens */
+  FI_MLA_SPLIT_KV = 4,           /* some request is cut into several chunks (then run() merges) */
+  FI_MLA_ENABLE_CUDA_GRAPH = 5,  /* run() always launches kernel + merge */
+  FI_MLA_NUM_HEADS = 6,
+  FI_MLA_BATCH_SIZE = 7,
+  FI_MLA_INT_BYTES_USED = 8,
+  FI_MLA_MERGE_INDPTR_OFFSET = 9, /* int workspace: int32 [total_rows + 1], partial entries per packed row */
+  FI_MLA_ITEMS_OFFSET = 10,       /* int workspace: int32 [num_work][8] work items (see csrc/mla.hip) */
+  FI_MLA_NUM_ENTRIES = 11,        /* partial states written (f32 [entries, 512] + [entries]) */
+  FI_MLA_V_OFFSET = 12,           /* float workspace: byte offset of the partial rows (lse entries start at 0) */
+  FI_MLA_PAGE_SIZE = 13,
+  FI_MLA_DTYPE = 14,
+  FI_MLA_MAGIC = 15
+};
+#define FI_MLA_PLAN_MAGIC 0x46494d4c41ll /* "FIMLA" */
+
+typedef struct fi_batch_mla_plan_params {
+  void* int_ws;          /* device; NULL plans on the host only (CPU tests) */
+  void* pinned_int_ws;   /* host; the plan is written here, then copied to int_ws on `stream` */
+  size_t int_ws_bytes;
+  size_t float_ws_bytes; /* size of the float workspace run() will get (partial states) */
+  const int32_t* qo_indptr_h;  /* HOST [batch + 1] */
+  const int32_t* kv_indptr_h;  /* HOST [batch + 1], pages */
+  const int32_t* kv_len_arr_h; /* HOST [batch], tokens */
+  int32_t batch_size, num_heads, head_dim_ckv, head_dim_kpe, page_size, causal;
+  int32_t q_dtype, kv_dtype;
+  int32_t enable_cuda_graph;
+  int32_t fixed_split_size; /* > 0: kv chunk of this many tokens (rounded up to 64); 0: the planner's choice */
+} fi_batch_mla_plan_params_t;
+
+FI_API int fi_batch_mla_plan(const fi_batch_mla_plan_params_t* params, int64_t* plan_info_out, fi_stream_t stream);
+
+typedef struct fi_batch_mla_params {
+  const void* q_nope;
+  int64_t q_nope_stride_n, q_nope_stride_h;
+  const void* q_pe;
+  int64_t q_pe_stride_n, q_pe_stride_h;
+  const void* ckv;
+  int64_t ckv_stride_page, ckv_stride_n;
+  const void* kpe;
+  int64_t kpe_stride_page, kpe_stride_n;
+  const int32_t* kv_indices; /* device, the page table the plan's kv_indptr indexes */
+  void* o;                   /* [nnz_qo, num_heads, 512] contiguous, q dtype */
+  float* lse;                /* optional [nnz_qo, num_heads], base 2 */
+  void* float_ws;
+  size_t float_ws_bytes;
+  void* int_ws;
+  size_t int_ws_bytes;
+  int32_t num_rows; /* nnz_qo * num_heads of the q tensors */
+  int32_t num_heads, page_size, dtype, causal;
+  float sm_scale;
+} fi_batch_mla_params_t;
+
+FI_API int fi_batch_mla_run(const int64_t* plan_info, int32_t plan_info_len, const fi_batch_mla_params_t* params,
+                            fi_stream_t stream);
+
+/* Append: row i of append_ckv [nnz, 512] / append_kpe [nnz, 64] goes to page
+ * kv_indices[kv_indptr[batch_indices[i]] + positions[i] / page_size], entry positions[i] % page_size. */
+typedef struct fi_append_paged_mla_kv_params {
+  const void* append_ckv;
+  int64_t append_ckv_stride_n;
+  const void* append_kpe;
+  int64_t append_kpe_stride_n;
+  const int32_t* batch_indices; /* [nnz] device */
+  const int32_t* positions;     /* [nnz] device */
+  void* ckv_cache;
+  int64_t ckv_stride_page, ckv_stride_n;
+  void* kpe_cache;
+  int64_t kpe_stride_page, kpe_stride_n;
+  const int32_t* kv_indices;
+  const int32_t* kv_indptr;
+  int32_t nnz, page_size, head_dim_ckv, head_dim_kpe, dtype;
+} fi_append_paged_mla_kv_params_t;
+
+FI_API int fi_append_paged_mla_kv_cache(const fi_append_paged_mla_kv_params_t* params, fi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Standalone rotary embedding (SURVEY.md 8f "next" row).  ref: apply_rope / apply_rope_pos_ids /
  * apply_llama31_rope* / apply_rope_pos_ids_cos_sin_cache in csrc/rope.cu, include/flashinfer/pos_enc.cuh:465-1070,
  * flashinfer/rope.py:321-1150.  One entry point: positions are explicit (fi_rope_positions_from_indptr
