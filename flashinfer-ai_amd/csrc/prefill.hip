@@ -8,6 +8,7 @@
 
 #include "merge_kernel.h"
 #include "prefill_kernel.h"
+#include "prefill_qkvo_kernel.h"
 
 namespace fi {
 
@@ -123,9 +124,15 @@ extern "C" FI_API int fi_batch_prefill_plan_tile(
   FI_REQUIRE(num_kv_heads > 0 && num_qo_heads % num_kv_heads == 0,
              "batch_prefill_plan: num_qo_heads (%d) must be a multiple of num_kv_heads (%d)",
              num_qo_heads, num_kv_heads);
-  FI_REQUIRE(head_dim_qk == head_dim_vo, "batch_prefill_plan: head_dim_qk != head_dim_vo unsupported");
-  FI_REQUIRE(head_dim_qk == 64 || head_dim_qk == 128 || head_dim_qk == 256,
+  // (192, 128): the ragged / single prefill_qkvo kernel (fi_batch_prefill_qkvo_run), 128-row tiles only
+  const bool qkvo = head_dim_qk == 192 && head_dim_vo == 128;
+  FI_REQUIRE(head_dim_qk == head_dim_vo || qkvo,
+             "batch_prefill_plan: head_dim_qk %d / head_dim_vo %d unsupported (equal, or 192 / 128)", head_dim_qk,
+             head_dim_vo);
+  FI_REQUIRE(qkvo || head_dim_qk == 64 || head_dim_qk == 128 || head_dim_qk == 256,
              "batch_prefill_plan: unsupported head_dim %d (64/128/256)", head_dim_qk);
+  FI_REQUIRE(!qkvo || cta_tile_q == kTileQ, "batch_prefill_plan: head_dim_qk 192 / head_dim_vo 128 needs cta_tile_q %d",
+             kTileQ);
   FI_REQUIRE(qo_indptr_h[0] == 0, "batch_prefill_plan: qo_indptr[0] must be 0");
   const int group = num_qo_heads / num_kv_heads;
 
@@ -341,7 +348,9 @@ extern "C" FI_API int fi_batch_prefill_plan_tile(
   plan_info_out[FI_PP_NUM_WORK] = (int64_t)req.size();
   plan_info_out[FI_PP_ENABLE_CUDA_GRAPH] = enable_cuda_graph ? 1 : 0;
   plan_info_out[FI_PP_SPLIT_KV] = split_kv ? 1 : 0;
-  plan_info_out[FI_PP_MAGIC] = FI_PREFILL_PLAN_MAGIC;
+  // a (192, 128) plan carries its own tag: its partial states are sized for head_dim_vo 128, and only
+  // fi_batch_prefill_qkvo_run runs it
+  plan_info_out[FI_PP_MAGIC] = qkvo ? FI_PREFILL_QKVO_PLAN_MAGIC : FI_PREFILL_PLAN_MAGIC;
   if (int_ws && ia.used)
     FI_HIP_CALL(hipMemcpyAsync(int_ws, pinned_int_ws, ia.used, hipMemcpyHostToDevice,
                                (hipStream_t)stream));
@@ -472,6 +481,10 @@ extern "C" FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws
                                                  const fi_batch_prefill_params_t* a,
                                                  fi_stream_t stream_) {
   (void)int_ws_bytes;
+  FI_REQUIRE(!plan_info || plan_info_len != FI_PREFILL_PLAN_INFO_LEN ||
+                 plan_info[FI_PP_MAGIC] != FI_PREFILL_QKVO_PLAN_MAGIC,
+             "batch_prefill_paged_run: the plan is for head_dim_qk 192 / head_dim_vo 128, which runs through "
+             "fi_batch_prefill_qkvo_run (ragged kv) only");
   FI_REQUIRE(plan_info && plan_info_len == FI_PREFILL_PLAN_INFO_LEN &&
                  plan_info[FI_PP_MAGIC] == FI_PREFILL_PLAN_MAGIC,
              "batch_prefill_paged_run: plan_info is not a prefill plan (call plan() first)");
@@ -584,4 +597,153 @@ extern "C" FI_API int fi_single_prefill_run(const fi_single_prefill_params_t* a,
   }
   // partial states are [qo_len, chunks, Hq, D]: the dense n-way merge
   return launch_prefill(kp, launch, a->qo_len, (hipStream_t)stream_);
+}
+
+// ---- head_dim_qk 192 / head_dim_vo 128 (prefill_qkvo_kernel.h) ----
+
+namespace fi {
+
+hipError_t prefill_qkvo_launch(const PrefillQkvoParams& p, int dtype, int pmode, hipStream_t stream);
+
+// The checks and PrefillQkvoParams fields batch and single runs share.
+static int check_and_fill_qkvo(const char* who, const fi_prefill_qkvo_params_t& a, PrefillQkvoParams& kp) {
+  FI_REQUIRE(a.q && a.k && a.v && a.o, "%s: null tensor", who);
+  FI_REQUIRE(a.head_dim_qk == kQkvoDimQK && a.head_dim_vo == kQkvoDimVO,
+             "%s: head_dim_qk %d / head_dim_vo %d unsupported (192 / 128)", who, a.head_dim_qk, a.head_dim_vo);
+  FI_REQUIRE((a.q_dtype == FI_DTYPE_F16 || a.q_dtype == FI_DTYPE_BF16) && a.kv_dtype == a.q_dtype &&
+                 a.o_dtype == a.q_dtype,
+             "%s: q, k, v and o must share one 16-bit dtype (f16 / bf16; no fp8 at head_dim_qk 192 / head_dim_vo 128)",
+             who);
+  FI_REQUIRE(a.num_kv_heads > 0 && a.num_qo_heads > 0 && a.num_qo_heads % a.num_kv_heads == 0,
+             "%s: num_qo_heads must be a multiple of num_kv_heads", who);
+  FI_REQUIRE(a.mask_mode == FI_MASK_NON_CAUSAL || a.mask_mode == FI_MASK_CAUSAL,
+             "%s: mask_mode %d unsupported (non-causal / causal; no custom mask or multi-item scoring)", who,
+             a.mask_mode);
+  FI_REQUIRE(a.pos_encoding_mode == FI_POS_NONE, "%s: pos_encoding_mode must be NONE (no fused RoPE / ALiBi)", who);
+  FI_REQUIRE(!(a.logits_soft_cap > 0.f), "%s: logits_soft_cap is not supported", who);
+  FI_REQUIRE(((uintptr_t)a.q % 16) == 0 && a.q_stride_n % 8 == 0 && a.q_stride_h % 8 == 0,
+             "%s: q rows must be aligned to 8 elements", who);
+  FI_REQUIRE(((uintptr_t)a.k % 16) == 0 && ((uintptr_t)a.v % 16) == 0 && a.k_stride_n % 8 == 0 &&
+                 a.k_stride_h % 8 == 0 && a.v_stride_n % 8 == 0 && a.v_stride_h % 8 == 0,
+             "%s: k / v rows must be aligned to 8 elements", who);
+  FI_REQUIRE(a.k_stride_n >= 0 && a.k_stride_n < (1ll << 31) && a.v_stride_n >= 0 && a.v_stride_n < (1ll << 31),
+             "%s: k / v token strides must be below 2^31 elements", who);
+  memset(&kp, 0, sizeof(kp));
+  kp.q = a.q;
+  kp.k = a.k;
+  kp.v = a.v;
+  kp.o = a.o;
+  kp.lse = a.lse;
+  kp.q_stride_n = a.q_stride_n;
+  kp.q_stride_h = a.q_stride_h;
+  kp.k_stride_n = a.k_stride_n;
+  kp.k_stride_h = a.k_stride_h;
+  kp.v_stride_n = a.v_stride_n;
+  kp.v_stride_h = a.v_stride_h;
+  kp.num_qo_heads = a.num_qo_heads;
+  kp.num_kv_heads = a.num_kv_heads;
+  kp.group_size = a.num_qo_heads / a.num_kv_heads;
+  kp.group_div = FastDiv((uint32_t)kp.group_size);
+  kp.causal = a.mask_mode == FI_MASK_CAUSAL;
+  kp.window_left = a.window_left;
+  kp.sm_scale = a.sm_scale;
+  return 0;
+}
+
+// the kernel, then for a split kv axis the n-way merge of merge_rows query rows (head_dim_vo wide)
+static int launch_qkvo(const PrefillQkvoParams& kp, const fi_prefill_qkvo_params_t& a, int32_t merge_rows,
+                       hipStream_t stream) {
+  // bf16: P.V on the f16 MFMA by default; bf16_pv_mode 1 = hi + lo bf16 P, 3 = one bf16 rounding of P
+  const int pmode = a.bf16_pv_mode == 1 ? 1 : a.bf16_pv_mode == 3 ? 0 : 2;
+  FI_HIP_CALL(prefill_qkvo_launch(kp, a.q_dtype, pmode, stream));
+  if (kp.tmp_o) {
+    MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.merge_indptr, kp.o, kp.lse, kp.num_kv_chunks, merge_rows,
+                    kp.num_qo_heads, kQkvoDimVO, FI_DTYPE_F32, a.o_dtype, /*skip_empty=*/kp.merge_indptr != nullptr};
+    FI_HIP_CALL(launch_merge_n(mp, stream));
+  }
+  return 0;
+}
+
+}  // namespace fi
+
+extern "C" FI_API int fi_batch_prefill_qkvo_run(void* float_ws, size_t float_ws_bytes, void* int_ws,
+                                                size_t int_ws_bytes, const int64_t* plan_info, int32_t plan_info_len,
+                                                const fi_prefill_qkvo_params_t* a, fi_stream_t stream_) {
+  (void)int_ws_bytes;
+  FI_REQUIRE(plan_info && plan_info_len == FI_PREFILL_PLAN_INFO_LEN,
+             "batch_prefill_qkvo_run: plan_info is not a prefill plan (call plan() first)");
+  // the tag also guarantees partial states sized for head_dim_vo 128 (a plan for equal head dims sized them for its
+  // own head_dim)
+  FI_REQUIRE(plan_info[FI_PP_MAGIC] == FI_PREFILL_QKVO_PLAN_MAGIC,
+             "batch_prefill_qkvo_run: the plan was not made for head_dim_qk 192 / head_dim_vo 128");
+  FI_REQUIRE(a && int_ws, "batch_prefill_qkvo_run: null argument");
+  const int64_t num_work = plan_info[FI_PP_PADDED_BATCH_SIZE];
+  FI_REQUIRE(a->batch_size == plan_info[FI_PP_BATCH_SIZE], "batch_prefill_qkvo_run: batch size differs from the plan");
+  if (num_work == 0 || a->batch_size == 0) return 0;
+  FI_REQUIRE(a->qo_indptr && a->kv_indptr, "batch_prefill_qkvo_run: null indptr");
+  PrefillQkvoParams kp;
+  if (check_and_fill_qkvo("batch_prefill_qkvo_run", *a, kp)) return 1;
+  kp.qo_indptr = a->qo_indptr;
+  kp.kv_indptr = a->kv_indptr;
+  kp.request_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_REQUEST_INDICES_OFFSET]);
+  kp.qo_tile_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_QO_TILE_INDICES_OFFSET]);
+  if (plan_info[FI_PP_SPLIT_KV]) {
+    FI_REQUIRE(float_ws, "batch_prefill_qkvo_run: a split-kv plan needs the float workspace");
+    FI_REQUIRE((size_t)plan_info[FI_PP_V_OFFSET] <= float_ws_bytes,
+               "batch_prefill_qkvo_run: float workspace smaller than at plan()");
+    kp.kv_tile_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_KV_TILE_INDICES_OFFSET]);
+    kp.merge_indptr = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_MERGE_INDPTR_OFFSET]);
+    kp.tmp_o = (float*)((char*)float_ws + plan_info[FI_PP_V_OFFSET]);
+    kp.tmp_lse = (float*)((char*)float_ws + plan_info[FI_PP_S_OFFSET]);
+    kp.kv_chunk_size = (int32_t)plan_info[FI_PP_KV_CHUNK_SIZE];
+    kp.kv_chunk_size_ptr = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_KV_CHUNK_SIZE_PTR_OFFSET]);
+  }
+  kp.num_work = (int32_t)num_work;
+  return launch_qkvo(kp, *a, (int32_t)plan_info[FI_PP_TOTAL_NUM_ROWS], (hipStream_t)stream_);
+}
+
+extern "C" FI_API int fi_single_prefill_qkvo_run(const fi_prefill_qkvo_params_t* a, void* tmp, size_t tmp_bytes,
+                                                 fi_stream_t stream_) {
+  FI_REQUIRE(a, "single_prefill_qkvo_run: null params");
+  FI_REQUIRE(a->qo_len >= 0 && a->kv_len >= 0, "single_prefill_qkvo_run: negative length");
+  if (a->qo_len == 0) return 0;
+  PrefillQkvoParams kp;
+  if (check_and_fill_qkvo("single_prefill_qkvo_run", *a, kp)) return 1;
+  kp.num_work = (int32_t)ceil_div<int64_t>((int64_t)a->qo_len * kp.group_size, kTileQ);
+  kp.single_qo_len = a->qo_len;
+  kp.single_kv_len = a->kv_len;
+  // split the kv axis as fi_single_prefill_run does, partial states head_dim_vo wide
+  if (tmp && tmp_bytes > 0) {
+    const int64_t q_tiles = kp.num_work;
+    const int64_t max_items = std::max<int64_t>((int64_t)fi_num_compute_units() * 2 / a->num_kv_heads, 1);
+    int64_t span = std::max<int64_t>(a->kv_len, 1);
+    if (a->window_left >= 0)
+      span = std::min<int64_t>(span, (int64_t)a->window_left + (kp.causal ? kTileQ : a->qo_len) + kTileKV);
+    int64_t low = 128 / kTileKV, high = ceil_div<int64_t>(span, kTileKV);
+    while (low < high) {
+      const int64_t mid = (low + high) / 2;
+      if (q_tiles * ceil_div<int64_t>(span, mid * kTileKV) > max_items) low = mid + 1; else high = mid;
+    }
+    int64_t chunk = std::max<int64_t>(low, 128 / kTileKV) * kTileKV;
+    const int64_t rows = a->qo_len;
+    chunk = price_kv_chunk(chunk, span, 1, &q_tiles, &span, &rows, a->num_kv_heads, a->num_qo_heads, kQkvoDimQK,
+                           kQkvoDimVO);
+    auto need = [&](int64_t c) {
+      return ((int64_t)a->qo_len * ceil_div<int64_t>(span, c) * a->num_qo_heads * (kQkvoDimVO + 1) + 64) *
+             (int64_t)sizeof(float);
+    };
+    while (chunk < span && need(chunk) > (int64_t)tmp_bytes) chunk *= 2;
+    const int64_t nchunks = ceil_div<int64_t>(span, chunk);
+    if (nchunks > 1 && q_tiles * nchunks < (1ll << 30)) {
+      kp.num_kv_chunks = (int32_t)nchunks;
+      kp.kv_chunk_size = (int32_t)chunk;
+      kp.num_work = (int32_t)(q_tiles * nchunks);
+      kp.tmp_o = (float*)tmp;
+      size_t vbytes = (size_t)a->qo_len * nchunks * a->num_qo_heads * kQkvoDimVO * sizeof(float);
+      vbytes = (vbytes + 15) / 16 * 16;
+      kp.tmp_lse = (float*)((char*)tmp + vbytes);
+    }
+  }
+  // partial states are [qo_len, chunks, Hq, 128]: the dense n-way merge
+  return launch_qkvo(kp, *a, a->qo_len, (hipStream_t)stream_);
 }

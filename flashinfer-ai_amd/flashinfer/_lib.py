@@ -169,6 +169,41 @@ class SinglePrefillParams(C.Structure):
     ]
 
 
+class PrefillQkvoParams(C.Structure):
+    """fi_prefill_qkvo_params_t: prefill with head_dim_qk 192 / head_dim_vo 128 (batch ragged or single)."""
+    _fields_ = [
+        ("q", C.c_void_p),
+        ("q_stride_n", C.c_int64),
+        ("q_stride_h", C.c_int64),
+        ("k", C.c_void_p),
+        ("k_stride_n", C.c_int64),
+        ("k_stride_h", C.c_int64),
+        ("v", C.c_void_p),
+        ("v_stride_n", C.c_int64),
+        ("v_stride_h", C.c_int64),
+        ("o", C.c_void_p),
+        ("lse", C.c_void_p),
+        ("qo_indptr", C.c_void_p),
+        ("kv_indptr", C.c_void_p),
+        ("batch_size", C.c_int32),
+        ("qo_len", C.c_int32),
+        ("kv_len", C.c_int32),
+        ("num_qo_heads", C.c_int32),
+        ("num_kv_heads", C.c_int32),
+        ("head_dim_qk", C.c_int32),
+        ("head_dim_vo", C.c_int32),
+        ("q_dtype", C.c_int32),
+        ("kv_dtype", C.c_int32),
+        ("o_dtype", C.c_int32),
+        ("mask_mode", C.c_int32),
+        ("pos_encoding_mode", C.c_int32),
+        ("window_left", C.c_int32),
+        ("logits_soft_cap", C.c_float),
+        ("sm_scale", C.c_float),
+        ("bf16_pv_mode", C.c_int32),
+    ]
+
+
 class RopeParams(C.Structure):
     _fields_ = [
         ("q", C.c_void_p), ("k", C.c_void_p), ("q_out", C.c_void_p), ("k_out", C.c_void_p),
@@ -219,6 +254,8 @@ class AppendMlaParams(C.Structure):
 
 
 FI_PREFILL_PLAN_INFO_LEN = 16
+FI_PREFILL_PLAN_MAGIC = 0x4649505245
+FI_PREFILL_QKVO_PLAN_MAGIC = 0x4649514B564F  # plan_info[15] of a head_dim_qk 192 / head_dim_vo 128 plan
 FI_MLA_PLAN_INFO_LEN = 16
 # plan_info slots of fi_batch_mla_plan (include/fi_mi355.h, enum fi_mla_plan_slot)
 (FI_MLA_NUM_WORK, FI_MLA_GRID, FI_MLA_TOTAL_ROWS, FI_MLA_KV_CHUNK_SIZE, FI_MLA_SPLIT_KV, FI_MLA_ENABLE_CUDA_GRAPH,
@@ -243,6 +280,8 @@ EXPORTED_SYMBOLS = [
     "fi_batch_prefill_plan_tile",
     "fi_batch_prefill_paged_run",
     "fi_single_prefill_run",
+    "fi_batch_prefill_qkvo_run",
+    "fi_single_prefill_qkvo_run",
     "fi_gemm_fp8_nt_groupwise",
     "fi_group_gemm_fp8_nt_groupwise",
     "fi_get_batch_indices_positions",
@@ -284,6 +323,8 @@ def lib() -> C.CDLL:
     l.fi_batch_prefill_plan_tile.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp] + [i32] * 13 + [i64p, vp]
     l.fi_batch_prefill_paged_run.argtypes = [vp, sz, vp, sz, i64p, i32, C.POINTER(BatchPrefillParams), vp]
     l.fi_single_prefill_run.argtypes = [C.POINTER(SinglePrefillParams), vp, sz, vp]
+    l.fi_batch_prefill_qkvo_run.argtypes = [vp, sz, vp, sz, i64p, i32, C.POINTER(PrefillQkvoParams), vp]
+    l.fi_single_prefill_qkvo_run.argtypes = [C.POINTER(PrefillQkvoParams), vp, sz, vp]
     l.fi_gemm_fp8_nt_groupwise.argtypes = [vp] * 5 + [i32] * 10 + [vp]
     l.fi_group_gemm_fp8_nt_groupwise.argtypes = [vp] * 6 + [i32] * 11 + [vp]
     l.fi_packbits.argtypes = [vp, C.c_int64, i32, vp, vp]

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import math
 import os
 from typing import Any, List, Optional, Tuple, Union
 
@@ -200,6 +201,82 @@ def _run_batch_prefill(wrapper, name, q, kv, o_dtype, out, lse, return_lse, wind
     return (out, lse) if return_lse else out
 
 
+# Unequal (head_dim_qk, head_dim_vo) pairs with a kernel of their own (csrc/prefill_qkvo_kernel.h): DeepSeek-style MLA
+# prefill in its non-absorbed form, 128 nope + 64 rope dims for q / k and 128-dim v (ref: aot.py:568).
+_QKVO_HEAD_DIMS = ((192, 128),)
+
+
+def _check_qkvo_config(head_dim_qk, head_dim_vo, q_dtype, kv_dtype, pos_encoding_mode, logits_soft_cap, masked):
+    """ValueError for whatever the head_dim_qk 192 / head_dim_vo 128 kernel does not run."""
+    if (head_dim_qk, head_dim_vo) not in _QKVO_HEAD_DIMS:
+        raise ValueError(f"head_dim_qk {head_dim_qk} / head_dim_vo {head_dim_vo} is unsupported: the head dims must be "
+                         "equal, or 192 / 128")
+    if q_dtype not in (torch.float16, torch.bfloat16) or kv_dtype != q_dtype:
+        raise ValueError(f"head_dim_qk {head_dim_qk} / head_dim_vo {head_dim_vo} needs float16 or bfloat16 q and kv "
+                         f"of one dtype (got {q_dtype} / {kv_dtype}; there is no fp8 kernel for this pair)")
+    if pos_encoding_mode != "NONE":
+        raise ValueError(f"head_dim_qk {head_dim_qk} / head_dim_vo {head_dim_vo} supports pos_encoding_mode='NONE' "
+                         f"only (got {pos_encoding_mode!r}): apply RoPE to the rope dims before the call")
+    if logits_soft_cap:
+        raise ValueError(f"head_dim_qk {head_dim_qk} / head_dim_vo {head_dim_vo} does not support logits_soft_cap")
+    if masked:
+        raise ValueError(f"head_dim_qk {head_dim_qk} / head_dim_vo {head_dim_vo} does not support custom masks or "
+                         "multi-item scoring (causal / non-causal and window_left only)")
+
+
+def _qkvo_params(q, k, v, kv_layout, out, lse, causal, window_left, sm_scale, bf16_pv_mode, **extra):
+    """fi_prefill_qkvo_params_t for q [rows, Hq, 192] and k / v [kv rows, Hkv, 192 / 128] (NHD; HND: heads first),
+    k and v each by their own strides."""
+    if kv_layout == "NHD":
+        k_sn, k_sh, v_sn, v_sh = k.stride(0), k.stride(1), v.stride(0), v.stride(1)
+    else:
+        k_sh, k_sn, v_sh, v_sn = k.stride(0), k.stride(1), v.stride(0), v.stride(1)
+    dt = _lib.fi_dtype(q.dtype)
+    return _lib.PrefillQkvoParams(
+        q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), k=k.data_ptr(), k_stride_n=k_sn,
+        k_stride_h=k_sh, v=v.data_ptr(), v_stride_n=v_sn, v_stride_h=v_sh, o=out.data_ptr(), lse=_lib.ptr(lse),
+        num_qo_heads=q.shape[1], num_kv_heads=k.shape[1] if kv_layout == "NHD" else k.shape[0],
+        head_dim_qk=q.shape[2], head_dim_vo=v.shape[2], q_dtype=dt, kv_dtype=_lib.fi_dtype(k.dtype), o_dtype=dt,
+        mask_mode=MaskMode.CAUSAL.value if causal else MaskMode.NON_CAUSAL.value,
+        pos_encoding_mode=PosEncodingMode.NONE.value, window_left=window_left, logits_soft_cap=0.0,
+        sm_scale=sm_scale, bf16_pv_mode=bf16_pv_mode, **extra,
+    )
+
+
+def _check_qkvo_kv(k, v):
+    if k.dim() != 3 or v.dim() != 3 or k.stride(-1) != 1 or v.stride(-1) != 1:
+        raise ValueError("k and v must be 3-D and contiguous in their last dim")
+
+
+def _single_prefill_qkvo(q, k, v, causal, kv_layout, pos_encoding_mode, sm_scale, window_left, logits_soft_cap,
+                         return_lse, bf16_pv_exact_range, masked, o_dtype):
+    """single_prefill_with_kv_cache for v.shape[-1] != q.shape[-1] (head_dim_qk 192 / head_dim_vo 128)."""
+    _check_qkvo_kv(k, v)
+    head_dim_qk, head_dim_vo = q.shape[-1], v.shape[-1]
+    _check_qkvo_config(head_dim_qk, head_dim_vo, q.dtype, k.dtype, pos_encoding_mode, logits_soft_cap, masked)
+    if k.shape[:-1] != v.shape[:-1] or k.shape[-1] != head_dim_qk or v.dtype != k.dtype:
+        raise ValueError("k must be [.., head_dim_qk] and v [.., head_dim_vo] over the same tokens and heads, one dtype")
+    if o_dtype is not None and o_dtype != q.dtype:
+        raise ValueError("the output dtype must equal the q dtype at head_dim_qk 192 / head_dim_vo 128")
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    qo_len, num_qo_heads = q.shape[0], q.shape[1]
+    kv_len = k.shape[0] if kv_layout == "NHD" else k.shape[1]
+    out = torch.empty((qo_len, num_qo_heads, head_dim_vo), dtype=q.dtype, device=q.device)
+    lse = torch.empty((qo_len, num_qo_heads), dtype=torch.float32, device=q.device) if return_lse else None
+    params = _qkvo_params(q, k, v, kv_layout, out, lse, causal, window_left,
+                          1.0 / math.sqrt(head_dim_qk) if sm_scale is None else sm_scale,
+                          1 if bf16_pv_exact_range else 0, qo_len=qo_len, kv_len=kv_len)
+    tmp = _get_cache_buf("single_prefill_with_kv_cache_tmp", 32 * 1024 * 1024, q.device)
+    with torch.cuda.device(q.device):
+        _lib.check(
+            _lib.lib().fi_single_prefill_qkvo_run(C.byref(params), tmp.data_ptr(), tmp.numel() * tmp.element_size(),
+                                                  _lib.current_stream(q.device)),
+            "single_prefill_with_kv_cache",
+        )
+    return (out, lse) if return_lse else out
+
+
 def single_prefill_with_kv_cache(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -250,6 +327,11 @@ def single_prefill_with_kv_cache(
         packed_custom_mask = packbits(custom_mask.contiguous().view(-1), bitorder="little")
     for t, name in ((q, "q"), (k, "k"), (v, "v")):
         _lib.require_gpu_tensor(t, name)
+    if q.dim() == 3 and v.dim() == 3 and v.shape[-1] != q.shape[-1]:
+        # head_dim_qk = q.shape[-1], head_dim_vo = v.shape[-1] (ref: prefill.py:1166-1167)
+        return _single_prefill_qkvo(q, k, v, causal, kv_layout, pos_encoding_mode, sm_scale, window_left,
+                                    logits_soft_cap, return_lse, bf16_pv_exact_range, packed_custom_mask is not None,
+                                    o_dtype)
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape:
         raise ValueError("q must be [qo_len, num_qo_heads, head_dim]; k, v 3-D with equal shapes")
     qo_len, num_qo_heads, head_dim = q.shape
@@ -468,6 +550,10 @@ class BatchPrefillWithPagedKVCacheWrapper:
             logits_soft_cap = 0.0
         if head_dim_vo is None:
             head_dim_vo = head_dim_qk
+        if head_dim_vo != head_dim_qk:
+            # K and V share one page layout (ref: the paged wrappers take one head_dim)
+            raise ValueError(f"the paged KV cache needs head_dim_qk == head_dim_vo (got {head_dim_qk} / {head_dim_vo}); "
+                             "use BatchPrefillWithRaggedKVCacheWrapper for head_dim_qk 192 / head_dim_vo 128")
         batch_size = len(qo_indptr) - 1
         if len(paged_kv_indptr) != batch_size + 1 or len(paged_kv_last_page_len) != batch_size:
             raise ValueError("qo_indptr, paged_kv_indptr and paged_kv_last_page_len disagree on the batch size")
@@ -762,6 +848,12 @@ class BatchPrefillWithRaggedKVCacheWrapper:
             logits_soft_cap = 0.0
         if head_dim_vo is None:
             head_dim_vo = head_dim_qk
+        self._qkvo = head_dim_vo != head_dim_qk
+        if self._qkvo:
+            _check_qkvo_config(head_dim_qk, head_dim_vo, q_data_type, kv_data_type, pos_encoding_mode,
+                               logits_soft_cap, custom_mask is not None or packed_custom_mask is not None
+                               or prefix_len_ptr is not None)
+        self._head_dim_vo = head_dim_vo
         batch_size = len(qo_indptr) - 1
         if len(kv_indptr) != batch_size + 1:
             raise ValueError("The kv_indptr length should be equal to qo_indptr length.")
@@ -841,6 +933,8 @@ class BatchPrefillWithRaggedKVCacheWrapper:
         _check_cached_qkv_data_type(q, k, self._cached_q_data_type, self._cached_kv_data_type)
         if is_float8(q):
             raise ValueError("fp8 queries are supported by the paged wrapper only")
+        if self._qkvo:
+            return self._run_qkvo(q, k, v, q_scale, k_scale, v_scale, out, lse, return_lse)
         if k.shape != v.shape or k.stride() != v.stride() or k.dim() != 3 or k.stride(-1) != 1:
             raise ValueError("k and v must be 3-D with equal shapes/strides, contiguous in head_dim")
         if self._kv_layout == "NHD":
@@ -861,6 +955,51 @@ class BatchPrefillWithRaggedKVCacheWrapper:
         )
         return _run_batch_prefill(self, "BatchPrefillWithRaggedKVCacheWrapper.run", q, kv, q.dtype, out, lse,
                                   return_lse, self._window_left, q_scale, k_scale, v_scale)
+
+    def _run_qkvo(self, q, k, v, q_scale, k_scale, v_scale, out, lse, return_lse):
+        """run() of a head_dim_qk 192 / head_dim_vo 128 plan: k and v by their own strides, no copy."""
+        _check_qkvo_kv(k, v)
+        nhd = self._kv_layout == "NHD"
+        nnz_k, hk, dk = (k.shape if nhd else (k.shape[1], k.shape[0], k.shape[2]))
+        nnz_v, hv, dv = (v.shape if nhd else (v.shape[1], v.shape[0], v.shape[2]))
+        if (hk, dk) != (self._num_kv_heads, self._head_dim) or (hv, dv) != (self._num_kv_heads, self._head_dim_vo):
+            raise ValueError(f"k must be [.., {self._num_kv_heads}, {self._head_dim}] and v [.., {self._num_kv_heads}, "
+                             f"{self._head_dim_vo}] as planned, got {tuple(k.shape)} / {tuple(v.shape)}")
+        if min(nnz_k, nnz_v) < self._total_kv_rows or v.dtype != k.dtype:
+            raise ValueError("k / v hold fewer rows than kv_indptr[-1], or differ in dtype")
+        if q.dim() != 3 or q.shape != (self._total_num_rows, self._num_qo_heads, self._head_dim):
+            raise ValueError("q shape does not match the plan")
+        if q.stride(-1) != 1:
+            q = q.contiguous()
+        out_shape = (q.shape[0], q.shape[1], self._head_dim_vo)
+        if out is None:
+            out = torch.empty(out_shape, dtype=q.dtype, device=q.device)
+        else:
+            check_shape_dtype_device(out, out_shape, q.dtype, q.device, "out")
+        if return_lse:
+            if lse is None:
+                lse = torch.empty((q.size(0), q.size(1)), dtype=torch.float32, device=q.device)
+            else:
+                check_shape_dtype_device(lse, (q.size(0), q.size(1)), torch.float32, q.device, "lse")
+        sm_scale = _resolve_logits_params(self._head_dim, self._sm_scale, q_scale, k_scale, None, None,
+                                          None)["sm_scale"]
+        params = _qkvo_params(q, k, v, self._kv_layout, out, lse if return_lse else None, self._causal,
+                              self._window_left, sm_scale, self._bf16_pv_mode,
+                              qo_indptr=self._qo_indptr_buf.data_ptr(), kv_indptr=self._kv_indptr_buf.data_ptr(),
+                              batch_size=self._batch_size)
+        fws = self._float_workspace_buffer
+        with torch.cuda.device(q.device):
+            _lib.check(
+                _lib.lib().fi_batch_prefill_qkvo_run(
+                    fws.data_ptr(), fws.numel() * fws.element_size(), self._int_workspace_buffer.data_ptr(),
+                    self._int_workspace_buffer.numel(), self._plan_info_c, _lib.FI_PREFILL_PLAN_INFO_LEN,
+                    C.byref(params), _lib.current_stream(q.device),
+                ),
+                "BatchPrefillWithRaggedKVCacheWrapper.run",
+            )
+        if v_scale is not None:
+            out *= v_scale
+        return (out, lse) if return_lse else out
 
     run_return_lse = functools.partialmethod(run, return_lse=True)
 

@@ -321,6 +321,51 @@ typedef struct fi_single_prefill_params {
 FI_API int fi_single_prefill_run(const fi_single_prefill_params_t* params, void* tmp, size_t tmp_bytes,
                           fi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Prefill with head_dim_qk 192 / head_dim_vo 128 (DeepSeek-style MLA in its non-absorbed form: prefill and
+ * chunked prefill), ragged or single-request K / V, f16 or bf16.  ref: the FA2 prefill kernels at
+ * (HEAD_DIM_QK, HEAD_DIM_VO) = (192, 128), flashinfer/aot.py:568.
+ * K and V have separate head dims and separate strides (v may be a view into a fused projection output).
+ * Plain logits only: mask_mode NON_CAUSAL / CAUSAL, window_left, sm_scale; q / k / v / o of one 16-bit
+ * dtype.  fp8, pos_encoding_mode != NONE, logits_soft_cap > 0, custom masks and multi-item scoring are
+ * refused.  Partial states of a split kv axis are head_dim_vo wide and merged by run().
+ * ---------------------------------------------------------------------------------------------- */
+/* plan_info[FI_PP_MAGIC] of a fi_batch_prefill_plan made with head_dim_qk 192 / head_dim_vo 128: only
+ * fi_batch_prefill_qkvo_run takes such a plan, and it takes no other */
+#define FI_PREFILL_QKVO_PLAN_MAGIC 0x4649514b564fll /* "FIQKVO" */
+
+typedef struct fi_prefill_qkvo_params {
+  const void* q; /* [rows, num_qo_heads, head_dim_qk] */
+  int64_t q_stride_n, q_stride_h;
+  const void* k; /* [kv rows, num_kv_heads, head_dim_qk] (NHD) or [num_kv_heads, kv rows, ...] (HND) by strides */
+  int64_t k_stride_n, k_stride_h;
+  const void* v; /* [kv rows, num_kv_heads, head_dim_vo] by its own strides */
+  int64_t v_stride_n, v_stride_h;
+  void* o;    /* [rows, num_qo_heads, head_dim_vo] contiguous */
+  float* lse; /* optional [rows, num_qo_heads], base 2 */
+  const int32_t* qo_indptr; /* batch run: [batch_size + 1] device; single run: unused */
+  const int32_t* kv_indptr; /* batch run: [batch_size + 1] device, ragged K / V rows */
+  int32_t batch_size;       /* batch run: as planned */
+  int32_t qo_len, kv_len;   /* single run */
+  int32_t num_qo_heads, num_kv_heads;
+  int32_t head_dim_qk, head_dim_vo; /* 192, 128 */
+  int32_t q_dtype, kv_dtype, o_dtype; /* all FI_DTYPE_F16 or all FI_DTYPE_BF16 */
+  int32_t mask_mode;         /* FI_MASK_NON_CAUSAL / FI_MASK_CAUSAL */
+  int32_t pos_encoding_mode; /* FI_POS_NONE */
+  int32_t window_left;
+  float logits_soft_cap; /* must be 0 */
+  float sm_scale;
+  int32_t bf16_pv_mode; /* as fi_batch_prefill_params_t.bf16_pv_mode */
+} fi_prefill_qkvo_params_t;
+
+/* Ragged batch run of a plan made by fi_batch_prefill_plan with head_dim_qk 192 / head_dim_vo 128. */
+FI_API int fi_batch_prefill_qkvo_run(void* float_ws, size_t float_ws_bytes, void* int_ws, size_t int_ws_bytes,
+                              const int64_t* plan_info, int32_t plan_info_len,
+                              const fi_prefill_qkvo_params_t* params, fi_stream_t stream);
+/* Single request over dense K / V (qo_len, kv_len); tmp as fi_single_prefill_run (split-kv scratch, may be NULL). */
+FI_API int fi_single_prefill_qkvo_run(const fi_prefill_qkvo_params_t* params, void* tmp, size_t tmp_bytes,
+                               fi_stream_t stream);
+
 /* Bit packing of boolean masks (numpy.packbits semantics).  ref: csrc/quantization.cu,
  * include/flashinfer/quantization.cuh:29-126, Python flashinfer/quantization.py:57-153.
  *   x: n bytes, each 0 / non-zero;  y: ceil(n / 8) bytes;  bitorder_little: 0 = "big", 1 = "little".
