@@ -455,22 +455,86 @@ static int check_and_fill_prefill(const char* who, const A& a, const void* k, co
   return 0;
 }
 
-// The kernel, then for a split kv axis (kp.tmp_o set) the n-way merge of the partial states of merge_rows query
-// rows: ragged over kp.merge_indptr (batch), or kp.num_kv_chunks per row (single).
+// Binds a batch plan's workspace offsets to kernel params (KP: PrefillKernelParams or PrefillQkvoParams): work list
+// and, for a split plan, kv tiles, merge indptr, partial states and chunk size.
+template <class KP>
+static int bind_batch_plan(const char* who, const int64_t* plan_info, void* float_ws, size_t float_ws_bytes,
+                           void* int_ws, KP& kp) {
+  auto iws = [&](int field) { return (const int32_t*)((const char*)int_ws + plan_info[field]); };
+  kp.request_indices = iws(FI_PP_REQUEST_INDICES_OFFSET);
+  kp.qo_tile_indices = iws(FI_PP_QO_TILE_INDICES_OFFSET);
+  if (plan_info[FI_PP_SPLIT_KV]) {
+    FI_REQUIRE(float_ws, "%s: a split-kv plan needs the float workspace", who);
+    FI_REQUIRE((size_t)plan_info[FI_PP_V_OFFSET] <= float_ws_bytes, "%s: float workspace smaller than at plan()", who);
+    kp.kv_tile_indices = iws(FI_PP_KV_TILE_INDICES_OFFSET);
+    kp.merge_indptr = iws(FI_PP_MERGE_INDPTR_OFFSET);
+    kp.tmp_o = (float*)((char*)float_ws + plan_info[FI_PP_V_OFFSET]);
+    kp.tmp_lse = (float*)((char*)float_ws + plan_info[FI_PP_S_OFFSET]);
+    kp.kv_chunk_size = (int32_t)plan_info[FI_PP_KV_CHUNK_SIZE];
+    kp.kv_chunk_size_ptr = iws(FI_PP_KV_CHUNK_SIZE_PTR_OFFSET);
+  }
+  return 0;
+}
+
+// Splits a single request's kv axis when the q tiles alone (kp.num_work) cannot fill the chip, and the partial
+// states ([qo_len, chunks, Hq, head_dim_vo] f32 + lse) fit the caller's scratch buffer: same search as the batch
+// planner (ref: PrefillBinarySearchKVChunkSize, scheduler.cuh:101-130), then the priced chunk, doubled until the
+// partial states fit.  Leaves kp unsplit otherwise.
+template <class KP>
+static void split_single_kv(KP& kp, void* tmp, size_t tmp_bytes, int qo_len, int kv_len, int window_left,
+                            int head_dim_qk, int head_dim_vo) {
+  const int64_t q_tiles = kp.num_work;
+  const int64_t max_items = std::max<int64_t>((int64_t)fi_num_compute_units() * 2 / kp.num_kv_heads, 1);
+  int64_t span = std::max<int64_t>(kv_len, 1);
+  if (window_left >= 0)
+    span = std::min<int64_t>(span, (int64_t)window_left + (kp.causal ? kTileQ : qo_len) + kTileKV);
+  int64_t low = 128 / kTileKV, high = ceil_div<int64_t>(span, kTileKV);
+  while (low < high) {
+    const int64_t mid = (low + high) / 2;
+    if (q_tiles * ceil_div<int64_t>(span, mid * kTileKV) > max_items) low = mid + 1; else high = mid;
+  }
+  int64_t chunk = std::max<int64_t>(low, 128 / kTileKV) * kTileKV;
+  const int64_t rows = qo_len;
+  chunk = price_kv_chunk(chunk, span, 1, &q_tiles, &span, &rows, kp.num_kv_heads, kp.num_qo_heads, head_dim_qk,
+                         head_dim_vo);
+  auto need = [&](int64_t c) {
+    return ((int64_t)qo_len * ceil_div<int64_t>(span, c) * kp.num_qo_heads * (head_dim_vo + 1) + 64) *
+           (int64_t)sizeof(float);
+  };
+  while (chunk < span && need(chunk) > (int64_t)tmp_bytes) chunk *= 2;
+  const int64_t nchunks = ceil_div<int64_t>(span, chunk);
+  if (nchunks > 1 && q_tiles * nchunks < (1ll << 30)) {
+    kp.num_kv_chunks = (int32_t)nchunks;
+    kp.kv_chunk_size = (int32_t)chunk;
+    kp.num_work = (int32_t)(q_tiles * nchunks);
+    kp.tmp_o = (float*)tmp;
+    size_t vbytes = (size_t)qo_len * nchunks * kp.num_qo_heads * head_dim_vo * sizeof(float);
+    vbytes = (vbytes + 15) / 16 * 16;
+    kp.tmp_lse = (float*)((char*)tmp + vbytes);
+  }
+}
+
+// For a split kv axis (kp.tmp_o set), the n-way merge of the partial states of merge_rows query rows: ragged over
+// kp.merge_indptr (batch), or kp.num_kv_chunks per row (single).  ref: VariableLengthMergeStates after the
+// partition-kv kernel, prefill.cuh:2590-2671; the padding rows of a graph plan have no entries and are left alone.
+template <class KP>
+static int merge_split_kv(const KP& kp, int head_dim_vo, int o_dtype, int32_t merge_rows, hipStream_t stream) {
+  if (kp.tmp_o) {
+    MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.merge_indptr, kp.o, kp.lse, kp.num_kv_chunks, merge_rows,
+                    kp.num_qo_heads, head_dim_vo, FI_DTYPE_F32, o_dtype, /*skip_empty=*/kp.merge_indptr != nullptr};
+    FI_HIP_CALL(launch_merge_n(mp, stream));
+  }
+  return 0;
+}
+
+// The kernel, then the merge of a split kv axis.
 static int launch_prefill(const PrefillKernelParams& kp, const PrefillLaunch& launch, int32_t merge_rows,
                           hipStream_t stream) {
   if (launch.fp8_native)
     FI_HIP_CALL(prefill_fp8_launch(kp, kp.o_dtype, launch.q_dtype == FI_DTYPE_FP8_E5M2, launch.head_dim, stream));
   else
     FI_HIP_CALL(launch.fn(kp, launch.rope, stream));
-  if (kp.tmp_o) {
-    // ref: VariableLengthMergeStates after the partition-kv kernel, prefill.cuh:2590-2671; the padding rows of a
-    // graph plan have no entries and are left alone
-    MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.merge_indptr, kp.o, kp.lse, kp.num_kv_chunks, merge_rows,
-                    kp.num_qo_heads, launch.head_dim, FI_DTYPE_F32, kp.o_dtype, /*skip_empty=*/kp.merge_indptr != nullptr};
-    FI_HIP_CALL(launch_merge_n(mp, stream));
-  }
-  return 0;
+  return merge_split_kv(kp, launch.head_dim, kp.o_dtype, merge_rows, stream);
 }
 
 }  // namespace fi
@@ -518,19 +582,7 @@ extern "C" FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws
   kp.kv_indptr = kv.indptr;
   kp.kv_indices = kv.indices;
   kp.kv_last_page_len = kv.last_page_len;
-  kp.request_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_REQUEST_INDICES_OFFSET]);
-  kp.qo_tile_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_QO_TILE_INDICES_OFFSET]);
-  if (plan_info[FI_PP_SPLIT_KV]) {
-    FI_REQUIRE(float_ws, "batch_prefill_paged_run: a split-kv plan needs the float workspace");
-    FI_REQUIRE((size_t)plan_info[FI_PP_V_OFFSET] <= float_ws_bytes,
-               "batch_prefill_paged_run: float workspace smaller than at plan()");
-    kp.kv_tile_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_KV_TILE_INDICES_OFFSET]);
-    kp.merge_indptr = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_MERGE_INDPTR_OFFSET]);
-    kp.tmp_o = (float*)((char*)float_ws + plan_info[FI_PP_V_OFFSET]);
-    kp.tmp_lse = (float*)((char*)float_ws + plan_info[FI_PP_S_OFFSET]);
-    kp.kv_chunk_size = (int32_t)plan_info[FI_PP_KV_CHUNK_SIZE];
-    kp.kv_chunk_size_ptr = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_KV_CHUNK_SIZE_PTR_OFFSET]);
-  }
+  if (bind_batch_plan("batch_prefill_paged_run", plan_info, float_ws, float_ws_bytes, int_ws, kp)) return 1;
   kp.num_work = (int32_t)num_work;
   if (a->mask_mode == FI_MASK_CUSTOM) kp.mask_indptr = a->mask_indptr;
   if (a->mask_mode == FI_MASK_MULTIITEMSCORING) {
@@ -560,41 +612,9 @@ extern "C" FI_API int fi_single_prefill_run(const fi_single_prefill_params_t* a,
   kp.num_work = (int32_t)ceil_div<int64_t>((int64_t)a->qo_len * kp.group_size, kTileQ);
   kp.single_qo_len = a->qo_len;
   kp.single_kv_len = a->kv_len;
-  // split the kv axis when the q tiles alone cannot fill the chip and the caller lent a scratch buffer
-  // (same search as the batch planner; ref: PrefillBinarySearchKVChunkSize, scheduler.cuh:101-130)
-  if (tmp && tmp_bytes > 0 && a->mask_mode != FI_MASK_CUSTOM) {
-    const int64_t q_tiles = kp.num_work;
-    const int64_t max_items = std::max<int64_t>((int64_t)fi_num_compute_units() * 2 / a->num_kv_heads, 1);
-    int64_t span = std::max<int64_t>(a->kv_len, 1);
-    if (a->window_left >= 0)
-      span = std::min<int64_t>(span, (int64_t)a->window_left + (kp.causal ? kTileQ : a->qo_len) + kTileKV);
-    int64_t low = 128 / kTileKV, high = ceil_div<int64_t>(span, kTileKV);
-    while (low < high) {
-      const int64_t mid = (low + high) / 2;
-      if (q_tiles * ceil_div<int64_t>(span, mid * kTileKV) > max_items) low = mid + 1; else high = mid;
-    }
-    int64_t chunk = std::max<int64_t>(low, 128 / kTileKV) * kTileKV;
-    {
-      const int64_t rows = a->qo_len;
-      chunk = price_kv_chunk(chunk, span, 1, &q_tiles, &span, &rows, a->num_kv_heads, a->num_qo_heads, a->head_dim,
-                             a->head_dim);
-    }
-    auto need = [&](int64_t c) {
-      return ((int64_t)a->qo_len * ceil_div<int64_t>(span, c) * a->num_qo_heads * (a->head_dim + 1) + 64) *
-             (int64_t)sizeof(float);
-    };
-    while (chunk < span && need(chunk) > (int64_t)tmp_bytes) chunk *= 2;
-    const int64_t nchunks = ceil_div<int64_t>(span, chunk);
-    if (nchunks > 1 && q_tiles * nchunks < (1ll << 30)) {
-      kp.num_kv_chunks = (int32_t)nchunks;
-      kp.kv_chunk_size = (int32_t)chunk;
-      kp.num_work = (int32_t)(q_tiles * nchunks);
-      kp.tmp_o = (float*)tmp;
-      size_t vbytes = (size_t)a->qo_len * nchunks * a->num_qo_heads * a->head_dim * sizeof(float);
-      vbytes = (vbytes + 15) / 16 * 16;
-      kp.tmp_lse = (float*)((char*)tmp + vbytes);
-    }
-  }
+  // split the kv axis when the caller lent a scratch buffer and there is no custom mask
+  if (tmp && tmp_bytes > 0 && a->mask_mode != FI_MASK_CUSTOM)
+    split_single_kv(kp, tmp, tmp_bytes, a->qo_len, a->kv_len, a->window_left, a->head_dim, a->head_dim);
   // partial states are [qo_len, chunks, Hq, D]: the dense n-way merge
   return launch_prefill(kp, launch, a->qo_len, (hipStream_t)stream_);
 }
@@ -656,12 +676,7 @@ static int launch_qkvo(const PrefillQkvoParams& kp, const fi_prefill_qkvo_params
   // bf16: P.V on the f16 MFMA by default; bf16_pv_mode 1 = hi + lo bf16 P, 3 = one bf16 rounding of P
   const int pmode = a.bf16_pv_mode == 1 ? 1 : a.bf16_pv_mode == 3 ? 0 : 2;
   FI_HIP_CALL(prefill_qkvo_launch(kp, a.q_dtype, pmode, stream));
-  if (kp.tmp_o) {
-    MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.merge_indptr, kp.o, kp.lse, kp.num_kv_chunks, merge_rows,
-                    kp.num_qo_heads, kQkvoDimVO, FI_DTYPE_F32, a.o_dtype, /*skip_empty=*/kp.merge_indptr != nullptr};
-    FI_HIP_CALL(launch_merge_n(mp, stream));
-  }
-  return 0;
+  return merge_split_kv(kp, kQkvoDimVO, a.o_dtype, merge_rows, stream);
 }
 
 }  // namespace fi
@@ -685,19 +700,7 @@ extern "C" FI_API int fi_batch_prefill_qkvo_run(void* float_ws, size_t float_ws_
   if (check_and_fill_qkvo("batch_prefill_qkvo_run", *a, kp)) return 1;
   kp.qo_indptr = a->qo_indptr;
   kp.kv_indptr = a->kv_indptr;
-  kp.request_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_REQUEST_INDICES_OFFSET]);
-  kp.qo_tile_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_QO_TILE_INDICES_OFFSET]);
-  if (plan_info[FI_PP_SPLIT_KV]) {
-    FI_REQUIRE(float_ws, "batch_prefill_qkvo_run: a split-kv plan needs the float workspace");
-    FI_REQUIRE((size_t)plan_info[FI_PP_V_OFFSET] <= float_ws_bytes,
-               "batch_prefill_qkvo_run: float workspace smaller than at plan()");
-    kp.kv_tile_indices = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_KV_TILE_INDICES_OFFSET]);
-    kp.merge_indptr = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_MERGE_INDPTR_OFFSET]);
-    kp.tmp_o = (float*)((char*)float_ws + plan_info[FI_PP_V_OFFSET]);
-    kp.tmp_lse = (float*)((char*)float_ws + plan_info[FI_PP_S_OFFSET]);
-    kp.kv_chunk_size = (int32_t)plan_info[FI_PP_KV_CHUNK_SIZE];
-    kp.kv_chunk_size_ptr = (const int32_t*)((const char*)int_ws + plan_info[FI_PP_KV_CHUNK_SIZE_PTR_OFFSET]);
-  }
+  if (bind_batch_plan("batch_prefill_qkvo_run", plan_info, float_ws, float_ws_bytes, int_ws, kp)) return 1;
   kp.num_work = (int32_t)num_work;
   return launch_qkvo(kp, *a, (int32_t)plan_info[FI_PP_TOTAL_NUM_ROWS], (hipStream_t)stream_);
 }
@@ -712,38 +715,9 @@ extern "C" FI_API int fi_single_prefill_qkvo_run(const fi_prefill_qkvo_params_t*
   kp.num_work = (int32_t)ceil_div<int64_t>((int64_t)a->qo_len * kp.group_size, kTileQ);
   kp.single_qo_len = a->qo_len;
   kp.single_kv_len = a->kv_len;
-  // split the kv axis as fi_single_prefill_run does, partial states head_dim_vo wide
-  if (tmp && tmp_bytes > 0) {
-    const int64_t q_tiles = kp.num_work;
-    const int64_t max_items = std::max<int64_t>((int64_t)fi_num_compute_units() * 2 / a->num_kv_heads, 1);
-    int64_t span = std::max<int64_t>(a->kv_len, 1);
-    if (a->window_left >= 0)
-      span = std::min<int64_t>(span, (int64_t)a->window_left + (kp.causal ? kTileQ : a->qo_len) + kTileKV);
-    int64_t low = 128 / kTileKV, high = ceil_div<int64_t>(span, kTileKV);
-    while (low < high) {
-      const int64_t mid = (low + high) / 2;
-      if (q_tiles * ceil_div<int64_t>(span, mid * kTileKV) > max_items) low = mid + 1; else high = mid;
-    }
-    int64_t chunk = std::max<int64_t>(low, 128 / kTileKV) * kTileKV;
-    const int64_t rows = a->qo_len;
-    chunk = price_kv_chunk(chunk, span, 1, &q_tiles, &span, &rows, a->num_kv_heads, a->num_qo_heads, kQkvoDimQK,
-                           kQkvoDimVO);
-    auto need = [&](int64_t c) {
-      return ((int64_t)a->qo_len * ceil_div<int64_t>(span, c) * a->num_qo_heads * (kQkvoDimVO + 1) + 64) *
-             (int64_t)sizeof(float);
-    };
-    while (chunk < span && need(chunk) > (int64_t)tmp_bytes) chunk *= 2;
-    const int64_t nchunks = ceil_div<int64_t>(span, chunk);
-    if (nchunks > 1 && q_tiles * nchunks < (1ll << 30)) {
-      kp.num_kv_chunks = (int32_t)nchunks;
-      kp.kv_chunk_size = (int32_t)chunk;
-      kp.num_work = (int32_t)(q_tiles * nchunks);
-      kp.tmp_o = (float*)tmp;
-      size_t vbytes = (size_t)a->qo_len * nchunks * a->num_qo_heads * kQkvoDimVO * sizeof(float);
-      vbytes = (vbytes + 15) / 16 * 16;
-      kp.tmp_lse = (float*)((char*)tmp + vbytes);
-    }
-  }
+  // split the kv axis when the caller lent a scratch buffer
+  if (tmp && tmp_bytes > 0)
+    split_single_kv(kp, tmp, tmp_bytes, a->qo_len, a->kv_len, a->window_left, kQkvoDimQK, kQkvoDimVO);
   // partial states are [qo_len, chunks, Hq, 128]: the dense n-way merge
   return launch_qkvo(kp, *a, a->qo_len, (hipStream_t)stream_);
 }

@@ -303,12 +303,9 @@ __global__ void __launch_bounds__(kPrefillThreads, D == 256 ? 1 : 2)
   const bool row_valid = pr < packed_len;
   // A wave none of whose 32 rows exist (a decode-like request fills 1-8 of the tile's 128 rows) only helps staging
   // the K / V tiles: no MFMA, no softmax.  In a mixed batch its SIMD's matrix pipe is then free for the co-resident
-  // workgroup's full tiles (wave-uniform, constant for the kernel's lifetime).
-#ifndef FI_PF_WAVE_SKIP
-#define FI_PF_WAVE_SKIP 1
-#endif
-  // (not at head_dim 256: the second path made that 512-register instantiation spill inside its loop)
-  const bool wave_active = !FI_PF_WAVE_SKIP || D == 256 || row0 < packed_len;
+  // workgroup's full tiles (wave-uniform, constant for the kernel's lifetime).  Not at head_dim 256: the second path
+  // made that 512-register instantiation spill inside its loop.
+  const bool wave_active = D == 256 || row0 < packed_len;
   const int prc = row_valid ? pr : (packed_len > 0 ? packed_len - 1 : 0);
   const int qo_idx = (int)fast_div((uint32_t)prc, p.group_div);
   const int hg = prc - qo_idx * G;

@@ -152,26 +152,45 @@ def _plan_custom_mask(wrapper, custom_mask, packed_custom_mask, qo_indptr_host, 
     return packed_custom_mask.contiguous(), mask_indptr.contiguous()
 
 
+def _out_and_lse(q, out, lse, return_lse, out_shape, o_dtype):
+    """``out`` (allocated, or checked to be ``out_shape`` / ``o_dtype`` on q's device) and, with ``return_lse``, the
+    ``[rows, num_qo_heads]`` float32 ``lse`` (likewise); ``lse`` is None without ``return_lse``."""
+    if return_lse:
+        if lse is None:
+            lse = torch.empty((q.size(0), q.size(1)), dtype=torch.float32, device=q.device)
+        else:
+            check_shape_dtype_device(lse, (q.size(0), q.size(1)), torch.float32, q.device, "lse")
+    else:
+        lse = None
+    if out is None:
+        out = torch.empty(out_shape, dtype=o_dtype, device=q.device)
+    else:
+        check_shape_dtype_device(out, out_shape, o_dtype, q.device, "out")
+    return out, lse
+
+
+def _run_single_prefill(run_fn, params, device):
+    """``run_fn`` (fi_single_prefill_run or fi_single_prefill_qkvo_run) with the cached scratch buffer for split-KV
+    partial states (ref: the 32 MB cached buffer of single_prefill, prefill.py:1125)."""
+    tmp = _get_cache_buf("single_prefill_with_kv_cache_tmp", 32 * 1024 * 1024, device)
+    with torch.cuda.device(device):
+        _lib.check(
+            run_fn(C.byref(params), tmp.data_ptr(), tmp.numel() * tmp.element_size(), _lib.current_stream(device)),
+            "single_prefill_with_kv_cache",
+        )
+
+
 def _run_batch_prefill(wrapper, name, q, kv, o_dtype, out, lse, return_lse, window_left, q_scale, k_scale, v_scale,
                        scale_q=None, scale_k=None, scale_v=None):
     """run() of the paged and ragged wrappers once the kv view ``kv`` (a ``_lib.PagedKV``; ragged: an identity table
     of one-token pages) is resolved and checked against the plan: out / lse, fi_batch_prefill_paged_run, v_scale."""
     if q.stride(-1) != 1:
         q = q.contiguous()
-    if return_lse:
-        if lse is None:
-            lse = torch.empty((q.size(0), q.size(1)), dtype=torch.float32, device=q.device)
-        else:
-            check_shape_dtype_device(lse, (q.size(0), q.size(1)), torch.float32, q.device, "lse")
-    out_shape = q.shape[:-1] + (kv.head_dim,)
-    if out is None:
-        out = torch.empty(out_shape, dtype=o_dtype, device=q.device)
-    else:
-        check_shape_dtype_device(out, out_shape, o_dtype, q.device, "out")
+    out, lse = _out_and_lse(q, out, lse, return_lse, q.shape[:-1] + (kv.head_dim,), o_dtype)
     alibi = _get_cache_alibi_slopes_buf(q.shape[1], q.device) if wrapper._pos_encoding_mode == "ALIBI" else None
     params = _lib.BatchPrefillParams(
         q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), qo_indptr=wrapper._qo_indptr_buf.data_ptr(),
-        kv=kv, o=out.data_ptr(), lse=_lib.ptr(lse) if return_lse else None, alibi_slopes=_lib.ptr(alibi),
+        kv=kv, o=out.data_ptr(), lse=_lib.ptr(lse), alibi_slopes=_lib.ptr(alibi),
         scale_q=_lib.ptr(scale_q), scale_k=_lib.ptr(scale_k), scale_v=_lib.ptr(scale_v),
         num_qo_heads=wrapper._num_qo_heads, q_dtype=_lib.fi_dtype(q.dtype), o_dtype=_lib.fi_dtype(o_dtype),
         custom_mask=_lib.ptr(wrapper._custom_mask_buf), mask_indptr=_lib.ptr(wrapper._mask_indptr_buf),
@@ -262,18 +281,11 @@ def _single_prefill_qkvo(q, k, v, causal, kv_layout, pos_encoding_mode, sm_scale
         q = q.contiguous()
     qo_len, num_qo_heads = q.shape[0], q.shape[1]
     kv_len = k.shape[0] if kv_layout == "NHD" else k.shape[1]
-    out = torch.empty((qo_len, num_qo_heads, head_dim_vo), dtype=q.dtype, device=q.device)
-    lse = torch.empty((qo_len, num_qo_heads), dtype=torch.float32, device=q.device) if return_lse else None
+    out, lse = _out_and_lse(q, None, None, return_lse, (qo_len, num_qo_heads, head_dim_vo), q.dtype)
     params = _qkvo_params(q, k, v, kv_layout, out, lse, causal, window_left,
                           1.0 / math.sqrt(head_dim_qk) if sm_scale is None else sm_scale,
                           1 if bf16_pv_exact_range else 0, qo_len=qo_len, kv_len=kv_len)
-    tmp = _get_cache_buf("single_prefill_with_kv_cache_tmp", 32 * 1024 * 1024, q.device)
-    with torch.cuda.device(q.device):
-        _lib.check(
-            _lib.lib().fi_single_prefill_qkvo_run(C.byref(params), tmp.data_ptr(), tmp.numel() * tmp.element_size(),
-                                                  _lib.current_stream(q.device)),
-            "single_prefill_with_kv_cache",
-        )
+    _run_single_prefill(_lib.lib().fi_single_prefill_qkvo_run, params, q.device)
     return (out, lse) if return_lse else out
 
 
@@ -356,10 +368,7 @@ def single_prefill_with_kv_cache(
         scale_q = scale_k = scale_v = None
     if o_dtype is None:
         o_dtype = q.dtype
-    out = torch.empty(q.shape[:-1] + v.shape[-1:], dtype=o_dtype, device=q.device)
-    lse = None
-    if return_lse:
-        lse = torch.empty((qo_len, num_qo_heads), dtype=torch.float32, device=q.device)
+    out, lse = _out_and_lse(q, None, None, return_lse, q.shape[:-1] + v.shape[-1:], o_dtype)
     if packed_custom_mask is not None:
         _lib.require_gpu_tensor(packed_custom_mask, "packed_custom_mask")
         if packed_custom_mask.dtype != torch.uint8 or packed_custom_mask.numel() * 8 < qo_len * kv_len:
@@ -380,14 +389,7 @@ def single_prefill_with_kv_cache(
         bf16_pv_mode=1 if bf16_pv_exact_range else 0,
         **_resolve_logits_params(head_dim, sm_scale, None, None, logits_soft_cap, rope_scale, rope_theta),
     )
-    # scratch for split-KV partial states (ref: the 32 MB cached buffer of single_prefill, prefill.py:1125)
-    tmp = _get_cache_buf("single_prefill_with_kv_cache_tmp", 32 * 1024 * 1024, q.device)
-    with torch.cuda.device(q.device):
-        _lib.check(
-            _lib.lib().fi_single_prefill_run(C.byref(params), tmp.data_ptr(), tmp.numel() * tmp.element_size(),
-                                             _lib.current_stream(q.device)),
-            "single_prefill_with_kv_cache",
-        )
+    _run_single_prefill(_lib.lib().fi_single_prefill_run, params, q.device)
     return (out, lse) if return_lse else out
 
 
@@ -971,19 +973,10 @@ class BatchPrefillWithRaggedKVCacheWrapper:
             raise ValueError("q shape does not match the plan")
         if q.stride(-1) != 1:
             q = q.contiguous()
-        out_shape = (q.shape[0], q.shape[1], self._head_dim_vo)
-        if out is None:
-            out = torch.empty(out_shape, dtype=q.dtype, device=q.device)
-        else:
-            check_shape_dtype_device(out, out_shape, q.dtype, q.device, "out")
-        if return_lse:
-            if lse is None:
-                lse = torch.empty((q.size(0), q.size(1)), dtype=torch.float32, device=q.device)
-            else:
-                check_shape_dtype_device(lse, (q.size(0), q.size(1)), torch.float32, q.device, "lse")
+        out, lse = _out_and_lse(q, out, lse, return_lse, (q.shape[0], q.shape[1], self._head_dim_vo), q.dtype)
         sm_scale = _resolve_logits_params(self._head_dim, self._sm_scale, q_scale, k_scale, None, None,
                                           None)["sm_scale"]
-        params = _qkvo_params(q, k, v, self._kv_layout, out, lse if return_lse else None, self._causal,
+        params = _qkvo_params(q, k, v, self._kv_layout, out, lse, self._causal,
                               self._window_left, sm_scale, self._bf16_pv_mode,
                               qo_indptr=self._qo_indptr_buf.data_ptr(), kv_indptr=self._kv_indptr_buf.data_ptr(),
                               batch_size=self._batch_size)
