@@ -48,40 +48,18 @@ static decode_launch_fn find_launcher(int kv_dt, int head_dim) {
 #undef FI_ROW
 }
 
-static int env_int(const char* name, int unset) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : unset;
-}
-
-// The FI_DECODE_* knobs, read once per process (FI_DECODE_WAVES_PER_CU excepted, see decode_waves_per_cu).
-struct DecodeKnobs {
-  int max_head_tile;       // FI_DECODE_MAX_HEAD_TILE: 1, 2 or 4 (anything else: 4)
-  bool mfma16;             // FI_DECODE_MFMA16=0: no 16x16x32 kernel (the r1 choice)
-  int mfma_min_group;      // FI_DECODE_MFMA_MIN_GROUP: matrix-core crossover, 16-bit cache (0 disables the path)
-  int mfma_min_group_fp8;  // FI_DECODE_MFMA_MIN_GROUP_FP8: the same for an fp8 cache
-  bool mfma_rope;          // FI_DECODE_MFMA_ROPE=0: fused RoPE stays on the VALU kernel
-  bool force_generic;      // FI_DECODE_FORCE_GENERIC set: never the VALU kernel's fast path
-};
-
-static const DecodeKnobs& decode_knobs() {
-  static const DecodeKnobs k = [] {
-    DecodeKnobs k;
-    const int t = env_int("FI_DECODE_MAX_HEAD_TILE", 0);
-    k.max_head_tile = (t == 1 || t == 2 || t == 4) ? t : 4;
-    k.mfma16 = env_int("FI_DECODE_MFMA16", 1) != 0;
-    k.mfma_min_group = env_int("FI_DECODE_MFMA_MIN_GROUP", 5);
-    // an fp8 cache doubles the VALU work per byte: measured 5.0 (VALU) vs 6.35 TB/s (MFMA) at G = 4,
-    // 6.6 vs 6.4 TB/s at G = 1
-    k.mfma_min_group_fp8 = env_int("FI_DECODE_MFMA_MIN_GROUP_FP8", 3);
-    k.mfma_rope = env_int("FI_DECODE_MFMA_ROPE", 1) != 0;
-    k.force_generic = getenv("FI_DECODE_FORCE_GENERIC") != nullptr;
-    return k;
+// FI_DECODE_MFMA16=0: the r1 kernel choice (see choose_decode), read once per process.  The decode suite runs
+// through both choices: by default the 16x16x32 kernel takes the shapes the VALU kernel and the 32x32x16 kernel
+// serve under r1.
+static bool decode_mfma16() {
+  static const bool on = [] {
+    const char* e = getenv("FI_DECODE_MFMA16");
+    return !e || atoi(e) != 0;
   }();
-  return k;
+  return on;
 }
 
-// work items per CU the planner cuts the batch into (FI_DECODE_WAVES_PER_CU overrides; read at every plan, as
-// tools/bench_decode_sweep.py sweeps it within one process).  r3 sweep over the reference
+// work items per CU the planner cuts the batch into.  r3 sweep over the reference
 // benchmark's grid (tools/bench_ref_grids.py and a one-off r3 sweep; bf16 32 / 4 and 32 / 8 heads, random and identity
 // page order): with a 16-bit cache 4 per CU is level with 8 at C2 (6.72 against 6.65 TB/s) and ahead on everything
 // smaller, where 8 cuts chunks of 256-512 tokens whose fixed cost shows (bs 256 x kv 1024: 6.46 against 5.32 -- no
@@ -89,8 +67,6 @@ static const DecodeKnobs& decode_knobs() {
 // half the bytes per token and keeps 8 (C2 shape 6.08 against 5.59).  Counts that do not divide the chunking evenly
 // (3, 5, 6) lose 5-20 %.  A single request (fi_single_decode) always wants many chunks: 8.
 static int decode_waves_per_cu(int kv_dtype, bool batch) {
-  const int v = env_int("FI_DECODE_WAVES_PER_CU", 0);
-  if (v > 0) return v;
   const bool fp8 = kv_dtype == FI_DTYPE_FP8_E4M3 || kv_dtype == FI_DTYPE_FP8_E5M2;
   return (batch && !fp8) ? 4 : 8;
 }
@@ -107,27 +83,16 @@ static int ilog2_exact(int x) {
   return l;
 }
 
-// Matrix-core decode (decode_mfma_kernel.h): groups too wide for the VALU kernel, K/V stored in the q
-// dtype.  FI_DECODE_MFMA_MIN_GROUP moves the crossover (0 disables the path).
+// Matrix-core decode: decode_mfma16_kernel.h (16x16x32) and decode_mfma_kernel.h (32x32x16).
 hipError_t decode_mfma_launch(const DecodeKernelParams& p, int q_dtype, int kv_dtype, int head_dim, int rope, int grid,
                               hipStream_t stream);
 hipError_t decode_mfma16_launch(const DecodeKernelParams& p, int q_dtype, int kv_dtype, int head_dim, int rope,
                                 int grid, hipStream_t stream);
-static bool mfma_decode_shape(int group_size, int q_dt, int kv_dt, int head_dim, int page_size, bool rope) {
-  const DecodeKnobs& k = decode_knobs();
-  const bool fp8 = kv_dt == FI_DTYPE_FP8_E4M3 || kv_dt == FI_DTYPE_FP8_E5M2;
-  int mg = fp8 ? k.mfma_min_group_fp8 : k.mfma_min_group;
-  // pages too small (or not a power of two) for the VALU kernel's scalar-page fast path: its per-lane
-  // page-lookup fallback runs at 4.5 TB/s (page_size 1), the matrix-core kernel -- which always gathers per
-  // lane -- at 6.3; token-granular page tables (page_size 1) are common
-  if (mg > 0 && (ilog2_exact(page_size) < 0 || page_size < tokens_per_load(kv_dt, head_dim))) mg = 1;
-  // fused RoPE: the K rotation is vector-ALU work that the VALU kernel has no room for (4.8 TB/s at G = 4);
-  // on the matrix-core kernel it rides an idle pipe.  FI_DECODE_MFMA_ROPE=0 keeps the VALU kernel.
-  if (rope && mg > 0) mg = k.mfma_rope ? 1 : 0x7fffffff;
-  if (!rope && mg > 0 && group_size <= 16 && k.mfma16) mg = 1;
-  return mg > 0 && group_size >= mg && (q_dt == kv_dt || fp8) &&
-         (q_dt == FI_DTYPE_F16 || q_dt == FI_DTYPE_BF16) && (head_dim == 64 || head_dim == 128);
-}
+
+// r1 choice: the smallest group the 32x32x16 kernel takes from the VALU kernel.  An fp8 cache doubles the VALU
+// work per byte: measured 5.0 (VALU) vs 6.35 TB/s (MFMA) at G = 4, 6.6 vs 6.4 TB/s at G = 1.
+constexpr int kMfmaMinGroup = 5;
+constexpr int kMfmaMinGroupFp8 = 3;
 
 enum class DecodeKernel { VALU, MFMA32, MFMA16 };
 
@@ -144,17 +109,31 @@ static DecodeChoice choose_decode(int group, int q_dt, int kv_dt, int head_dim, 
   // groups larger than 4 are processed as several 4-head tiles by neighbouring waves of one workgroup
   // (they stream the same K/V rows, so HBM sees them once): measured 1.7-1.9x faster than an 8-head tile,
   // which is VALU-bound and spills (profiles/r01 notes in DESIGN.md).
-  c.gt = std::min(group <= 1 ? 1 : group == 2 ? 2 : 4, decode_knobs().max_head_tile);
-  // the 16x16x32 form (decode_mfma16_kernel.h) serves every group of <= 16 heads the matrix-core path accepts:
-  // measured >= the VALU kernel (G <= 4) and >= the 32x32x16 form (G 5..16) on every shape of
-  // tools/bench_decode_kernels.py (C2 6.35 -> 6.52 TB/s, bs 8 x 1024 20.3 -> 16.1 us), and the only one with room
-  // for the fused-RoPE rotation.  ALiBi and the logits soft cap exist in the VALU and 16x16x32 kernels only.
-  const bool mfma16 = group <= 16 && decode_knobs().mfma16;
-  const bool mfma = mfma_decode_shape(group, q_dt, kv_dt, head_dim, page_size, rope) &&
-                    (plain_logits || mfma16) && strides_fit_31_bits;
-  c.kind = !mfma ? DecodeKernel::VALU : mfma16 ? DecodeKernel::MFMA16 : DecodeKernel::MFMA32;
+  c.gt = group <= 1 ? 1 : group == 2 ? 2 : 4;
+  const bool fp8 = kv_dt == FI_DTYPE_FP8_E4M3 || kv_dt == FI_DTYPE_FP8_E5M2;
+  // the matrix-core kernels: 16-bit q, K/V in the q dtype or fp8, head_dim 64 / 128, 32-bit element offsets
+  const bool mfma = (q_dt == FI_DTYPE_F16 || q_dt == FI_DTYPE_BF16) && (kv_dt == q_dt || fp8) &&
+                    (head_dim == 64 || head_dim == 128) && strides_fit_31_bits;
+  if (decode_mfma16()) {
+    // the 16x16x32 form (decode_mfma16_kernel.h) serves every group of <= 16 heads: measured >= the VALU kernel
+    // (G <= 4) and >= the 32x32x16 form (G 5..16) on every shape of tools/bench_decode_kernels.py (C2 6.35 -> 6.52
+    // TB/s, bs 8 x 1024 20.3 -> 16.1 us), and the only one with room for the fused-RoPE rotation.  ALiBi and the
+    // logits soft cap exist in the VALU and 16x16x32 kernels only.
+    c.kind = !(mfma && (plain_logits || group <= 16)) ? DecodeKernel::VALU
+             : group <= 16                            ? DecodeKernel::MFMA16
+                                                      : DecodeKernel::MFMA32;
+  } else {
+    // r1: the 32x32x16 kernel from the crossover group up.  It is 1 for fused RoPE (the K rotation is vector-ALU
+    // work that the VALU kernel has no room for: 4.8 TB/s at G = 4; on the matrix-core kernel it rides an idle
+    // pipe) and for pages too small (or not a power of two) for the VALU kernel's scalar-page fast path (its
+    // per-lane page lookup runs at 4.5 TB/s at page_size 1, the matrix-core kernel, which always gathers per lane,
+    // at 6.3; token-granular page tables are common).
+    const bool small_pages = ilog2_exact(page_size) < 0 || page_size < tokens_per_load(kv_dt, head_dim);
+    const int min_group = (rope || small_pages) ? 1 : fp8 ? kMfmaMinGroupFp8 : kMfmaMinGroup;
+    c.kind = mfma && plain_logits && group >= min_group ? DecodeKernel::MFMA32 : DecodeKernel::VALU;
+  }
   // a matrix-core wave covers the whole group
-  c.head_tiles = mfma ? ceil_div(group, 32) : ceil_div(group, c.gt);
+  c.head_tiles = c.kind == DecodeKernel::VALU ? ceil_div(group, c.gt) : ceil_div(group, 32);
   return c;
 }
 
@@ -449,8 +428,7 @@ extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes,
     kp.tmp_lse = (float*)((char*)float_ws + plan_info[FI_DP_S_OFFSET]);
   }
   // fast path: scalar page ids, no logits transform (see decode_kernel.h)
-  kp.fast_path = kp.uniform_page && kp.indices && !kp.use_alibi && kp.logits_soft_cap == 0.f &&
-                 !decode_knobs().force_generic;
+  kp.fast_path = kp.uniform_page && kp.indices && !kp.use_alibi && kp.logits_soft_cap == 0.f;
   return launch_decode(kp, choice, a->q_dtype, kv.dtype, kv.head_dim, a->pos_encoding_mode == FI_POS_ROPE_LLAMA,
                        /*merge_n=*/0, kv.batch_size, stream);
 }

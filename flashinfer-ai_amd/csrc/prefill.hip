@@ -27,27 +27,11 @@ FI_PF_DECL_D(0, 2, 2) FI_PF_DECL_D(1, 2, 2) FI_PF_DECL_D(0, 3, 3) FI_PF_DECL_D(1
 
 hipError_t prefill_fp8_launch(const PrefillKernelParams& p, int out_dtype, int e5m2, int head_dim, hipStream_t stream);
 
-// fp8-native kernel (MX-scaled MFMA for both contractions): e4m3 or e5m2 q/k/v, head_dim 128, plain logits, no fused
-// RoPE, no sliding window.  FI_PREFILL_FP8_NATIVE=0 forces the
-// upcast-to-16-bit kernel (same arithmetic, kept as the cross-check).
-static bool use_fp8_native(const PrefillKernelParams& kp, int q_dt, int kv_dt, int head_dim, int rope) {
-  static const bool enabled = [] {
-    const char* e = getenv("FI_PREFILL_FP8_NATIVE");
-    return e ? atoi(e) != 0 : true;
-  }();
-  static const bool d256 = [] {  // FI_PREFILL_FP8_NATIVE_D256=0: head_dim 256 through the upcast kernel (cross-check)
-    const char* e = getenv("FI_PREFILL_FP8_NATIVE_D256");
-    return e ? atoi(e) != 0 : true;
-  }();
-  static const bool d64 = [] {
-    const char* e = getenv("FI_PREFILL_FP8_NATIVE_D64");
-    return e ? atoi(e) != 0 : true;
-  }();
-  return enabled && (q_dt == FI_DTYPE_FP8_E4M3 || q_dt == FI_DTYPE_FP8_E5M2) && kv_dt == q_dt &&
-         (head_dim == 128 || (head_dim == 64 && d64 && kp.tile_q == kTileQ) ||
-          (head_dim == 256 && d256 && kp.tile_q == kTileQ)) &&
-         !rope && !kp.use_alibi && kp.logits_soft_cap == 0.f &&
-         kp.window_left < 0 && !kp.custom_mask;
+// fp8-native kernel (MX-scaled MFMA for both contractions): e4m3 or e5m2 q/k/v, plain logits, no fused RoPE, no
+// sliding window, no custom mask.  fp8 runs with any of those go through the upcast-to-16-bit kernel.
+static bool use_fp8_native(const PrefillKernelParams& kp, int q_dt, int kv_dt, int rope) {
+  return (q_dt == FI_DTYPE_FP8_E4M3 || q_dt == FI_DTYPE_FP8_E5M2) && kv_dt == q_dt && !rope && !kp.use_alibi &&
+         kp.logits_soft_cap == 0.f && kp.window_left < 0 && !kp.custom_mask;
 }
 
 static prefill_launch_fn find_prefill(int t16, int kvs, int qs, int d) {
@@ -106,33 +90,27 @@ static int64_t price_kv_chunk(int64_t ref_chunk, int64_t max_kv_len, int n, cons
   return best;
 }
 
-extern "C" FI_API int fi_batch_prefill_plan_tile(
+extern "C" FI_API int fi_batch_prefill_plan(
     void* float_ws, size_t float_ws_bytes, void* int_ws, void* pinned_int_ws, size_t int_ws_bytes,
     const int32_t* qo_indptr_h, const int32_t* kv_indptr_h, const int32_t* kv_len_arr_h,
     int32_t total_num_rows, int32_t batch_size, int32_t num_qo_heads, int32_t num_kv_heads,
     int32_t page_size, int32_t enable_cuda_graph, int32_t head_dim_qk, int32_t head_dim_vo,
     int32_t causal, int32_t window_left, int32_t fixed_split_size, int32_t disable_split_kv,
-    int32_t cta_tile_q, int64_t* plan_info_out, fi_stream_t stream) {
+    int64_t* plan_info_out, fi_stream_t stream) {
   (void)float_ws; (void)kv_indptr_h;
-  FI_REQUIRE(cta_tile_q == kTileQ || cta_tile_q == 2 * kTileQ,
-             "batch_prefill_plan: cta_tile_q must be %d or %d (the fp8-native kernel's 8-wave form)", kTileQ,
-             2 * kTileQ);
-  const int64_t tile_q = cta_tile_q;
   FI_REQUIRE(pinned_int_ws && qo_indptr_h && kv_len_arr_h && plan_info_out,
              "batch_prefill_plan: null argument");
   FI_REQUIRE(batch_size >= 0 && page_size > 0, "batch_prefill_plan: bad batch size / page size");
   FI_REQUIRE(num_kv_heads > 0 && num_qo_heads % num_kv_heads == 0,
              "batch_prefill_plan: num_qo_heads (%d) must be a multiple of num_kv_heads (%d)",
              num_qo_heads, num_kv_heads);
-  // (192, 128): the ragged / single prefill_qkvo kernel (fi_batch_prefill_qkvo_run), 128-row tiles only
+  // (192, 128): the ragged / single prefill_qkvo kernel (fi_batch_prefill_qkvo_run)
   const bool qkvo = head_dim_qk == 192 && head_dim_vo == 128;
   FI_REQUIRE(head_dim_qk == head_dim_vo || qkvo,
              "batch_prefill_plan: head_dim_qk %d / head_dim_vo %d unsupported (equal, or 192 / 128)", head_dim_qk,
              head_dim_vo);
   FI_REQUIRE(qkvo || head_dim_qk == 64 || head_dim_qk == 128 || head_dim_qk == 256,
              "batch_prefill_plan: unsupported head_dim %d (64/128/256)", head_dim_qk);
-  FI_REQUIRE(!qkvo || cta_tile_q == kTileQ, "batch_prefill_plan: head_dim_qk 192 / head_dim_vo 128 needs cta_tile_q %d",
-             kTileQ);
   FI_REQUIRE(qo_indptr_h[0] == 0, "batch_prefill_plan: qo_indptr[0] must be 0");
   const int group = num_qo_heads / num_kv_heads;
 
@@ -144,20 +122,20 @@ extern "C" FI_API int fi_batch_prefill_plan_tile(
     const int64_t qo_len = qo_indptr_h[b + 1] - qo_indptr_h[b];
     FI_REQUIRE(qo_len >= 0, "batch_prefill_plan: qo_indptr must be non-decreasing");
     FI_REQUIRE(kv_len_arr_h[b] >= 0, "batch_prefill_plan: negative kv length");
-    q_tiles[b] = ceil_div<int64_t>(qo_len * group, tile_q);
+    q_tiles[b] = ceil_div<int64_t>(qo_len * group, kTileQ);
     kv_len[b] = std::max<int64_t>(kv_len_arr_h[b], 1);
     // sliding window: a q tile only walks the keys from its first row's window start on (the kernel
     // skips the rest), so chunks are cut from that span (ref: effective_kv_len_arr, scheduler.cuh:561-567)
     if (window_left >= 0)
-      kv_len[b] = std::min<int64_t>(kv_len[b], (int64_t)window_left + (causal ? tile_q : qo_len) + kTileKV);
+      kv_len[b] = std::min<int64_t>(kv_len[b], (int64_t)window_left + (causal ? kTileQ : qo_len) + kTileKV);
     total_q_tiles += q_tiles[b];
     max_kv_len = std::max(max_kv_len, kv_len[b]);
   }
   // resident workgroups (2 per CU) over the kv heads each item is launched for
   // (ref: max_batch_size_if_split = max_grid_size / num_kv_heads, scheduler.cuh:718)
-  const int64_t max_items = std::max<int64_t>((int64_t)fi_num_compute_units() * (tile_q == kTileQ ? 2 : 1) / num_kv_heads, 1);
+  const int64_t max_items = std::max<int64_t>((int64_t)fi_num_compute_units() * 2 / num_kv_heads, 1);
   const int64_t graph_bound =
-      ceil_div<int64_t>((int64_t)total_num_rows * group, tile_q) + std::max(batch_size, 1) - 1;
+      ceil_div<int64_t>((int64_t)total_num_rows * group, kTileQ) + std::max(batch_size, 1) - 1;
   // chunk sizes are multiples of one 64-row kv tile and at least 128 tokens (ref: min_kv_chunk_size)
   auto items_at = [&](int64_t chunk) {
     int64_t n = 0;
@@ -219,7 +197,7 @@ extern "C" FI_API int fi_batch_prefill_plan_tile(
         int64_t lse_entries = entries;
         if (enable_cuda_graph)  // the fixed lse region of a graph plan (below)
           lse_entries = std::max(entries, std::max(items_at(chunk), std::max(max_items, graph_bound)) *
-                                              (ceil_div<int64_t>(tile_q, group) + 1));
+                                              (ceil_div<int64_t>(kTileQ, group) + 1));
         return (entries * num_qo_heads * head_dim_vo + lse_entries * num_qo_heads + 64) * (int64_t)sizeof(float);
       };
       while (kv_chunk < max_kv_len && ws_need(kv_chunk) > (int64_t)float_ws_bytes) kv_chunk *= 2;
@@ -239,7 +217,7 @@ extern "C" FI_API int fi_batch_prefill_plan_tile(
   // prefill request go out before the memory-bound one-row items of equally long decode requests and run beside
   // them, instead of forming the tail -- bench_batch_attention.py's 254 x (8192, 1) + (8192, 4096))
   auto item_cost = [&](int b) {
-    const int64_t rows = std::min<int64_t>((int64_t)(qo_indptr_h[b + 1] - qo_indptr_h[b]) * group, tile_q);
+    const int64_t rows = std::min<int64_t>((int64_t)(qo_indptr_h[b + 1] - qo_indptr_h[b]) * group, kTileQ);
     return (int64_t)kv_len_arr_h[b] * std::max<int64_t>(rows, 1);
   };
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return item_cost(a) > item_cost(b); });
@@ -261,8 +239,8 @@ extern "C" FI_API int fi_batch_prefill_plan_tile(
     std::vector<size_t> wide, narrow;
     for (size_t i = 0; i < req.size(); ++i) {
       const int b = req[i];
-      const int64_t rows_left = (int64_t)(qo_indptr_h[b + 1] - qo_indptr_h[b]) * group - (int64_t)tile[i] * tile_q;
-      (std::min<int64_t>(rows_left, tile_q) * 2 >= tile_q ? wide : narrow).push_back(i);
+      const int64_t rows_left = (int64_t)(qo_indptr_h[b + 1] - qo_indptr_h[b]) * group - (int64_t)tile[i] * kTileQ;
+      (std::min<int64_t>(rows_left, kTileQ) * 2 >= kTileQ ? wide : narrow).push_back(i);
     }
     if (!wide.empty() && !narrow.empty()) {
       std::vector<int32_t> r2, t2, k2;
@@ -319,11 +297,11 @@ extern "C" FI_API int fi_batch_prefill_plan_tile(
   int64_t v_off = 0, s_off = 0;
   if (split_kv) {
     // lse region first, sized for the most partial states a launch of `padded` items can write (each
-    // (row, chunk) pair belongs to one item of <= tile_q / G + 1 rows): with a fixed-shape (graph) plan
+    // (row, chunk) pair belongs to one item of <= kTileQ / G + 1 rows): with a fixed-shape (graph) plan
     // both offsets are then the same for every plan, so a captured run() stays valid after a re-plan.
     // The outputs follow and may use the rest of the workspace.
     OffsetAllocator fa(float_ws_bytes);
-    const int64_t rows_per_item = ceil_div<int64_t>(tile_q, group) + 1;
+    const int64_t rows_per_item = ceil_div<int64_t>(kTileQ, group) + 1;
     const int64_t lse_entries =
         enable_cuda_graph ? std::max<int64_t>(entries, (int64_t)padded * rows_per_item) : std::max<int64_t>(entries, 1);
     s_off = fa.alloc((size_t)lse_entries * num_qo_heads * sizeof(float));
@@ -336,7 +314,7 @@ extern "C" FI_API int fi_batch_prefill_plan_tile(
   plan_info_out[FI_PP_PADDED_BATCH_SIZE] = (int64_t)padded;
   plan_info_out[FI_PP_TOTAL_NUM_ROWS] = split_kv ? nrows_tab : total_num_rows;
   plan_info_out[FI_PP_KV_CHUNK_SIZE_PTR_OFFSET] = chunk_off;
-  plan_info_out[FI_PP_CTA_TILE_Q] = tile_q;
+  plan_info_out[FI_PP_CTA_TILE_Q] = kTileQ;
   plan_info_out[FI_PP_REQUEST_INDICES_OFFSET] = req_off;
   plan_info_out[FI_PP_QO_TILE_INDICES_OFFSET] = tile_off;
   plan_info_out[FI_PP_KV_TILE_INDICES_OFFSET] = kvt_off;
@@ -357,20 +335,6 @@ extern "C" FI_API int fi_batch_prefill_plan_tile(
   return 0;
 }
 
-
-extern "C" FI_API int fi_batch_prefill_plan(
-    void* float_ws, size_t float_ws_bytes, void* int_ws, void* pinned_int_ws, size_t int_ws_bytes,
-    const int32_t* qo_indptr_h, const int32_t* kv_indptr_h, const int32_t* kv_len_arr_h,
-    int32_t total_num_rows, int32_t batch_size, int32_t num_qo_heads, int32_t num_kv_heads,
-    int32_t page_size, int32_t enable_cuda_graph, int32_t head_dim_qk, int32_t head_dim_vo,
-    int32_t causal, int32_t window_left, int32_t fixed_split_size, int32_t disable_split_kv,
-    int64_t* plan_info_out, fi_stream_t stream) {
-  return fi_batch_prefill_plan_tile(float_ws, float_ws_bytes, int_ws, pinned_int_ws, int_ws_bytes, qo_indptr_h,
-                                    kv_indptr_h, kv_len_arr_h, total_num_rows, batch_size, num_qo_heads,
-                                    num_kv_heads, page_size, enable_cuda_graph, head_dim_qk, head_dim_vo, causal,
-                                    window_left, fixed_split_size, disable_split_kv, kTileQ, plan_info_out, stream);
-}
-
 namespace fi {
 
 // What one prefill launch runs: the kernel instantiated for the dtypes and head_dim, or the fp8-native one.
@@ -385,7 +349,7 @@ struct PrefillLaunch {
 template <class A>
 static int check_and_fill_prefill(const char* who, const A& a, const void* k, const void* v, int kv_dt, int head_dim,
                                   int num_kv_heads, int page_size, int64_t stride_page, int64_t stride_n,
-                                  int64_t stride_h, int tile_q, PrefillKernelParams& kp, PrefillLaunch& launch) {
+                                  int64_t stride_h, PrefillKernelParams& kp, PrefillLaunch& launch) {
   FI_REQUIRE(num_kv_heads > 0 && a.num_qo_heads % num_kv_heads == 0,
              "%s: num_qo_heads must be a multiple of num_kv_heads", who);
   const int q_dt = a.q_dtype, o_dt = a.o_dtype;
@@ -443,15 +407,10 @@ static int check_and_fill_prefill(const char* who, const A& a, const void* k, co
   kp.rope_rcp_scale = a.rope_rcp_scale;
   kp.rope_rcp_theta = a.rope_rcp_theta;
   kp.bf16_pv_mode = a.bf16_pv_mode;
-  kp.tile_q = tile_q;
   launch.rope = a.pos_encoding_mode == FI_POS_ROPE_LLAMA;
-  launch.fp8_native = use_fp8_native(kp, q_dt, kv_dt, head_dim, launch.rope);
+  launch.fp8_native = use_fp8_native(kp, q_dt, kv_dt, launch.rope);
   launch.q_dtype = q_dt;
   launch.head_dim = head_dim;
-  FI_REQUIRE(kp.tile_q == kTileQ || launch.fp8_native,
-             "%s: the plan was cut for %d-row q tiles (fi_batch_prefill_plan_tile), which only the fp8-native kernel "
-             "runs: fp8 q/k/v of one type, head_dim 128, no RoPE / ALiBi / soft cap / window / mask",
-             who, kp.tile_q);
   return 0;
 }
 
@@ -575,8 +534,7 @@ extern "C" FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws
   PrefillKernelParams kp;
   PrefillLaunch launch;
   if (check_and_fill_prefill("batch_prefill_paged_run", *a, kv.k_data, kv.v_data, kv.dtype, kv.head_dim,
-                             kv.num_kv_heads, kv.page_size, kv.stride_page, kv.stride_n, kv.stride_h,
-                             (int)plan_info[FI_PP_CTA_TILE_Q], kp, launch))
+                             kv.num_kv_heads, kv.page_size, kv.stride_page, kv.stride_n, kv.stride_h, kp, launch))
     return 1;
   kp.qo_indptr = a->qo_indptr;
   kp.kv_indptr = kv.indptr;
@@ -607,7 +565,7 @@ extern "C" FI_API int fi_single_prefill_run(const fi_single_prefill_params_t* a,
   PrefillKernelParams kp;
   PrefillLaunch launch;
   if (check_and_fill_prefill("single_prefill_run", *a, a->k, a->v, a->kv_dtype, a->head_dim, a->num_kv_heads, vpage,
-                             (int64_t)vpage * a->kv_stride_n, a->kv_stride_n, a->kv_stride_h, kTileQ, kp, launch))
+                             (int64_t)vpage * a->kv_stride_n, a->kv_stride_n, a->kv_stride_h, kp, launch))
     return 1;
   kp.num_work = (int32_t)ceil_div<int64_t>((int64_t)a->qo_len * kp.group_size, kTileQ);
   kp.single_qo_len = a->qo_len;

@@ -10,17 +10,14 @@ static hipError_t launch_v2(const PrefillKernelParams& p, int head_dim, int grid
   // group sizes 1 / 2 / 4: one query head per wave, logit scale in a scalar register (see the kernel)
   const bool uni = p.group_size == 1 || p.group_size == 2 || p.group_size == 4;
   if (head_dim == 256) {  // one workgroup per CU, plain step (prefill_fp8_kernel.h)
-    if (uni) batch_prefill_fp8_kernel<OUT16, true, 4, BF8, 256><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
-    else batch_prefill_fp8_kernel<OUT16, false, 4, BF8, 256><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
+    if (uni) batch_prefill_fp8_kernel<OUT16, true, BF8, 256><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
+    else batch_prefill_fp8_kernel<OUT16, false, BF8, 256><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
   } else if (head_dim == 64) {
-    if (uni) batch_prefill_fp8_kernel<OUT16, true, 4, BF8, 64><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
-    else batch_prefill_fp8_kernel<OUT16, false, 4, BF8, 64><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
-  } else if (p.tile_q == 2 * kTileQ) {  // plan cut for 256-row q tiles: the 8-wave form
-    if (uni) batch_prefill_fp8_kernel<OUT16, true, 8, BF8><<<dim3(grid), dim3(512), 0, stream>>>(p);
-    else batch_prefill_fp8_kernel<OUT16, false, 8, BF8><<<dim3(grid), dim3(512), 0, stream>>>(p);
+    if (uni) batch_prefill_fp8_kernel<OUT16, true, BF8, 64><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
+    else batch_prefill_fp8_kernel<OUT16, false, BF8, 64><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
   } else {
-    if (uni) batch_prefill_fp8_kernel<OUT16, true, 4, BF8><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
-    else batch_prefill_fp8_kernel<OUT16, false, 4, BF8><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
+    if (uni) batch_prefill_fp8_kernel<OUT16, true, BF8><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
+    else batch_prefill_fp8_kernel<OUT16, false, BF8><<<dim3(grid), dim3(kPrefillThreads), 0, stream>>>(p);
   }
   return hipGetLastError();
 }

@@ -102,31 +102,25 @@ typedef const __attribute__((address_space(1))) void f8_gbl_void;
 // tokens), so the logit scale c = sm_scale * scale_q[head] * scale_k[kv head] * log2 e is wave-uniform and sits in a
 // scalar register: exp2's argument fma(s, c, -m) then reads two vector registers instead of three (a vector
 // instruction with three distinct vector sources issues at half rate: tools/ubench_issue2 measurements).
-// NW: waves per workgroup.  4: 128 packed query rows, two workgroups per CU.  8 (plans cut with cta_tile_q = 256):
-// 256 rows share every K/V tile, so a wave issues two LDS-DMA pieces per 64-key step instead of four and the
-// page-id / row-offset tables are built once per 256 rows; one workgroup per CU, the same 8 waves.
 // BF8: q, k, v e5m2 -- P is scaled by 57344 / 2^kF8Thr and rounded to e5m2 (ref: hopper/variants.cuh:71-73)
-// D: head_dim 128, or 64 (NW = 4 only): rows of 64 bytes in the same ring (a stage keeps its 8 KB stride), one k step
-// per QK^T block and two P.V blocks -- two MFMAs each per 64-key step against the same softmax work, so that form is
-// vector-bound by construction and its step is written plainly (builtin MFMAs, no hand interleave).
-// D = 256 (NW = 4; ref instantiation: hopper/quantization/prefill_sm90.cuh:459-470): 256-byte rows, 16 KB K / V tiles,
+// D: head_dim 128 (two workgroups per CU), or 64: rows of 64 bytes in the same ring (a stage keeps its 8 KB stride),
+// one k step per QK^T block and two P.V blocks -- two MFMAs each per 64-key step against the same softmax work, so
+// that form is vector-bound by construction and its step is written plainly (builtin MFMAs, no hand interleave).
+// D = 256 (ref instantiation: hopper/quantization/prefill_sm90.cuh:459-470): 256-byte rows, 16 KB K / V tiles,
 // one workgroup per CU (128 accumulator + 32 query registers per lane: the 512-register budget of one wave per SIMD),
 // four k steps per QK^T block and eight P.V blocks per 64-key step -- 16 MFMAs against the same softmax, written plainly
 // like the head_dim 64 form.
-template <int OUT16, bool UNI, int NW, bool BF8, int D = 128>
-__global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_prefill_fp8_kernel(const PrefillKernelParams p) {
-  static_assert(D == 128 || ((D == 64 || D == 256) && NW == 4), "head_dim 128, or 64 / 256 with four waves");
+template <int OUT16, bool UNI, bool BF8, int D = 128>
+__global__ void __launch_bounds__(kPrefillThreads, D == 256 ? 1 : 2) batch_prefill_fp8_kernel(const PrefillKernelParams p) {
+  static_assert(D == 64 || D == 128 || D == 256, "head_dim 64, 128 or 256");
   constexpr int kF8KTile = F8Lds<D>::kTile, kF8VOff = F8Lds<D>::kVOff, kF8TabOff = F8Lds<D>::kTabOff;
   constexpr int kF8IdsOff = F8Lds<D>::kIdsOff, kF8Smem = F8Lds<D>::kSmem;
   constexpr int ROWB = D;             // bytes per K / V row in LDS
   constexpr int SLOTS = ROWB / 16;    // 16-byte slots per row
   constexpr int KBLK = 32 * ROWB;     // byte offset of the second 32-row block of a tile
   constexpr int TRR = 16 * ROWB;      // row step of the four transposed V reads
-  constexpr int kThreads = NW * 64;
-  constexpr int kTQ = NW * 32;  // packed query rows per workgroup
   constexpr float kLog2Scale = BF8 ? kBF8Log2Scale : kF8Log2Scale;
   constexpr float kPMax = BF8 ? 57344.f : 448.f;  // largest value of the type P is rounded to
-  static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   constexpr int DBLK = D / 32;
   // ONE static array for every LDS object: the compiler separates an LDS-DMA target from an LDS read by
   // constant offsets (and index ranges) inside one object; with a second object, or unbounded indices, it
@@ -181,8 +175,8 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
   const int packed_len = qo_len * G;
   // packed row (qo_idx * G + head) of this lane inside the workgroup's 128-row tile
   const int row_in_tile = UNI ? ((wave / G) * 32 + lq) * G + (wave % G) : wave * 32 + lq;
-  const int row0 = q_tile * kTQ + (UNI ? (wave / G) * 32 * G : wave * 32);  // the wave's first packed row
-  const int pr = q_tile * kTQ + row_in_tile;
+  const int row0 = q_tile * kTileQ + (UNI ? (wave / G) * 32 * G : wave * 32);  // the wave's first packed row
+  const int pr = q_tile * kTileQ + row_in_tile;
   const bool row_valid = pr < packed_len;
   const int prc = row_valid ? pr : (packed_len > 0 ? packed_len - 1 : 0);
   const int qo_idx = (int)fast_div((uint32_t)prc, p.group_div);
@@ -214,7 +208,7 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
 
   int kv_end = kv_len;
   if (p.causal) {
-    const int last_pr = min(q_tile * kTQ + kTQ, packed_len) - 1;
+    const int last_pr = min(q_tile * kTileQ + kTileQ, packed_len) - 1;
     const int last_qo = last_pr >= 0 ? (int)fast_div((uint32_t)last_pr, p.group_div) : 0;
     kv_end = min(kv_len, max(0, kv_len - qo_len + last_qo + 1));
   }
@@ -298,7 +292,7 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
     int ids_base = (int)fast_div((uint32_t)min(tile_base * kTileKV, max(kv_len - 1, 0)), p.page_div);
     auto fill_ids = [&]() {
       if (p.kv_indices) {
-        for (int i = tid; i < kF8Ids; i += kThreads) {
+        for (int i = tid; i < kF8Ids; i += kPrefillThreads) {
           const int pg = ids_base + i;
           ids[i] = pg < num_pages ? p.kv_indices[page_begin + pg] : 0;
         }
@@ -323,9 +317,9 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
     // DMA of a tile's K and V rows into ring stage `stage`: the row offsets are read from table slot `slot` first
     // (dma_offsets, early in a step) and the four pieces are issued later (dma_issue), so that the LDS latency of
     // the table read does not sit at the top of the step
-    // a pass = the rows the workgroup's threads cover with one 16-byte chunk each (NW * 64 / SLOTS rows); the tile's
-    // 64 rows take PASSES of them (head_dim 256: four), one K and one V piece per wave and pass
-    constexpr int kRowsPerPass = kThreads / SLOTS;
+    // a pass = the rows the workgroup's threads cover with one 16-byte chunk each (kPrefillThreads / SLOTS rows); the
+    // tile's 64 rows take PASSES of them (head_dim 256: four), one K and one V piece per wave and pass
+    constexpr int kRowsPerPass = kPrefillThreads / SLOTS;
     constexpr int PASSES = kTileKV / kRowsPerPass;
     static_assert(PASSES == 1 || PASSES == 2 || PASSES == 4, "passes per tile");
     struct DmaOffs { uint64_t o[PASSES]; };
@@ -338,10 +332,10 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
       char* const vdst = kdst + kF8VOff;
 #pragma unroll
       for (int j = 0; j < PASSES; ++j)
-        __builtin_amdgcn_global_load_lds((f8_gbl_void*)(k_thr + f.o[j]), (f8_lds_void*)(kdst + j * NW * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((f8_gbl_void*)(k_thr + f.o[j]), (f8_lds_void*)(kdst + j * 4096), 16, 0, 0);
 #pragma unroll
       for (int j = 0; j < PASSES; ++j)
-        __builtin_amdgcn_global_load_lds((f8_gbl_void*)(v_thr + f.o[j]), (f8_lds_void*)(vdst + j * NW * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((f8_gbl_void*)(v_thr + f.o[j]), (f8_lds_void*)(vdst + j * 4096), 16, 0, 0);
     };
     auto dma_tile = [&](int slot, int stage) {
       DmaOffs f;
@@ -356,7 +350,7 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
     dma_tile(0, 0);
     dma_tile(1, 1);
     dma_tile(2, 2);
-    // tiles 0 and 1 have landed (tile 2: this wave's 4 (NW = 8: 2) pieces in flight); wait + barrier as one
+    // tiles 0 and 1 have landed (tile 2: this wave's 2 * PASSES pieces in flight); wait + barrier as one
     // statement (see the step)
     // (LDS-DMA pieces per wave and tile: 2 * PASSES)
     if constexpr (PASSES == 4) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
@@ -643,9 +637,8 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || D == 256) ? 1 : 2) batch_
       // K of tile t+2 (and everything older, V of tile t+1 included) of this wave's pieces landed; then the
       // workgroup barrier.  ONE asm statement: the s_barrier builtin alone is no memory fence for the compiler,
       // which would hoist the next step's LDS reads between the wait and the barrier.
-      // (in flight afterwards: V of tile t+2 and both operands of tile t+3 -- 6 pieces, 3 with NW = 8)
-      if constexpr (PASSES == 2) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      // (in flight afterwards: V of tile t+2 and both operands of tile t+3 -- 6 pieces)
+      asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
       }  // D == 128
     };
     auto refill_if_needed = [&](int t_first, int t_last) {

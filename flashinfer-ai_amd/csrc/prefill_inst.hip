@@ -1,7 +1,5 @@
 // One translation unit per (compute type, kv storage, q storage, head_dim); compiled by the Makefile with
 // -DFI_PF_T16=.. -DFI_PF_KVS=.. -DFI_PF_QS=.. -DFI_PF_D=..
-#include <cstdlib>
-
 #include "prefill_kernel.h"
 
 #define FI_CAT5_(a, b, c, d, e) a##b##_##c##_##d##_##e
@@ -46,19 +44,11 @@ static hipError_t launch_features(const PrefillKernelParams& p, int rope, hipStr
 hipError_t FI_LAUNCHER(const PrefillKernelParams& p, int rope, hipStream_t stream) {
 #if FI_PF_T16 == 1 && FI_PF_QS == 1  // FI_DTYPE_BF16 (an enumerator: not visible to the preprocessor)
   static_assert(FI_DTYPE_BF16 == 1, "bf16 tag");
-  // bf16: P.V on the f16 MFMA (prefill_kernel.h, PMODE 2) unless FI_PREFILL_BF16_P selects 0 = the reference's single
-  // bf16 rounding of P (prefill.cuh:962-985; absolute error up to ~4e-3 on unit-variance V) or 1 = hi + lo bf16 halves
-  // (no f16 range limit on V; 25 % slower).  FI_PREFILL_BF16_SINGLE_P=1 is the older spelling of 0.
-  static const int pmode = [] {
-    if (const char* e = getenv("FI_PREFILL_BF16_P")) return atoi(e);
-    const char* s1 = getenv("FI_PREFILL_BF16_SINGLE_P");
-    return (s1 && atoi(s1) != 0) ? 0 : 2;
-  }();
-  // the caller's choice (fi_batch_prefill_params_t.bf16_pv_mode: 1 hi + lo, 2 f16 P.V, 3 single rounding) wins over
-  // the process-wide default
-  const int mode = p.bf16_pv_mode == 1 ? 1 : p.bf16_pv_mode == 2 ? 2 : p.bf16_pv_mode == 3 ? 0 : pmode;
-  if (mode == 2) return launch_features<2>(p, rope, stream);
-  if (mode == 1) return launch_features<1>(p, rope, stream);
+  // bf16: bf16_pv_mode picks the P.V arithmetic (fi_batch_prefill_params_t): 0 / 2 P.V on the f16 MFMA (PMODE 2),
+  // 1 hi + lo bf16 halves of P (no f16 range limit on V; 25 % slower), 3 the reference's single bf16 rounding of P
+  // (prefill.cuh:962-985; absolute error up to ~4e-3 on unit-variance V)
+  if (p.bf16_pv_mode == 1) return launch_features<1>(p, rope, stream);
+  if (p.bf16_pv_mode != 3) return launch_features<2>(p, rope, stream);
 #endif
   return launch_features<0>(p, rope, stream);
 }

@@ -145,7 +145,7 @@ FP8_SEEDS = range(int(os.environ.get("FI_FUZZ_FP8_SEEDS", "24")))
 @pytest.mark.parametrize("seed", FP8_SEEDS)
 def test_fuzz_fp8_attention_prefill(seed):
     """Random fp8 attention (q, k, v of one fp8 type, per-head scales) through the paged wrapper: head_dim 64 / 128
-    (fp8-native kernel: 4- or 8-wave form, e4m3 / e5m2, one head per wave or mixed) and 256 (upcast kernel), GQA
+    / 256 (fp8-native kernel, e4m3 / e5m2, one head per wave or mixed), GQA
     groups that do and do not divide a wave, any page size, both layouts, causal or not, automatic / disabled /
     fixed kv split, rows without visible keys -- against the oracle's restatement of the reference's FA3 arithmetic
     (hopper/variants.cuh:71-90) at the fp8 bars of tests/test_prefill_gpu.py."""

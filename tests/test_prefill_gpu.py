@@ -14,8 +14,8 @@ DEV = "cuda:0"
 def ptol(dtype):
     """fp16: rtol = atol = 1e-3 (the reference's bar).  bf16: the same bar plus the rounding of the bf16 output
     itself (half an ulp = 2^-9 relative; 2^-8 granted).  The bf16 kernel runs P.V on the f16 MFMA (P rounded to
-    f16, 11 mantissa bits, V converted while staged; FI_PREFILL_BF16_P=1 selects hi + lo bf16 halves instead); with
-    the reference's single bf16 rounding of P (prefill.cuh:962-985; FI_PREFILL_BF16_P=0) 83 of the 383 bf16 cases of
+    f16, 11 mantissa bits, V converted while staged; bf16_pv_mode = 1 selects hi + lo bf16 halves instead); with
+    the reference's single bf16 rounding of P (prefill.cuh:962-985; bf16_pv_mode = 3) 83 of the 383 bf16 cases of
     the 900-seed fuzz sweep exceed even rtol 2^-7 / atol 2e-3, all on cancelling rows (|o| << |v|: the error is
     ~2^-9 sum |p v|; worst 4.6e-3 at seed 637, request 1, row 544, head 16 -- tools/bf16_error_scan.py prints the
     census)."""
@@ -502,24 +502,6 @@ def test_single_prefill_splits_long_kv(causal, qo_len, kv_len):
     o = flashinfer.single_prefill_with_kv_cache(q.to(DEV), k.to(DEV), v.to(DEV), custom_mask=mask.to(DEV))
     o_ref, _ = R.attention_ref(q.float(), k.float(), v.float(), custom_mask=mask)
     torch.testing.assert_close(o.float().cpu(), o_ref.float(), rtol=1e-3, atol=1e-3)
-
-
-def test_fp8_prefill_through_the_256_row_tile_form():
-    """FI_PREFILL_FP8_TILE=256: plans cut with fi_batch_prefill_plan_tile(cta_tile_q = 256) and the 8-wave form of the
-    fp8-native kernel (not the default: 4 % slower at C3).  The switch is read at plan(), the fp8 tests run in a child."""
-    import os
-    import subprocess
-    import sys
-
-    if os.environ.get("FI_PREFILL_FP8_TILE") == "256":
-        pytest.skip("already the child")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, FI_PREFILL_FP8_TILE="256")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_prefill_gpu.py"),
-                        os.path.join(root, "tests", "test_graph_replan_gpu.py"), "-x", "-q", "-k", "fp8", "-p",
-                        "no:cacheprovider"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout
 
 
 def _peaked_fp8_case(f8, d, kv_len, qo_len, tail_lo, tail_hi, peak, seed):

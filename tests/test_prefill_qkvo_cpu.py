@@ -93,18 +93,6 @@ def test_unsupported_pairs_are_refused(fi_lib, pair):
     assert b"unsupported" in fi_lib.fi_last_error()
 
 
-def test_plan_tile_256_refused_at_192_128(fi_lib):
-    from flashinfer import _lib
-
-    pinned = (C.c_char * (1 << 20))()
-    qo = (C.c_int32 * 2)(0, 10)
-    kl = (C.c_int32 * 1)(20)
-    info = (C.c_int64 * _lib.FI_PREFILL_PLAN_INFO_LEN)()
-    rc = fi_lib.fi_batch_prefill_plan_tile(None, 0, None, pinned, len(pinned), qo, qo, kl, 10, 1, 4, 4, 1, 0, 192, 128,
-                                           1, -1, -1, 0, 256, info, None)
-    assert rc != 0 and b"cta_tile_q" in fi_lib.fi_last_error()
-
-
 def _params(**kw):
     from flashinfer import _lib
 

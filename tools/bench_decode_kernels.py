@@ -1,5 +1,5 @@
-"""Plain batch decode on the VALU kernel vs the 16x16x32 matrix-core kernel over shapes (run twice: default, and
-with FI_DECODE_MFMA16=1 FI_DECODE_MFMA_MIN_GROUP=1)."""
+"""Plain batch decode over shapes (run twice: default, on the 16x16x32 matrix-core kernel, and with FI_DECODE_MFMA16=0,
+on the VALU kernel for groups of <= 4 heads)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch

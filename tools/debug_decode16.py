@@ -1,4 +1,4 @@
-"""Error structure of the 16x16x32 decode kernel on small cases (run with FI_DECODE_MFMA16=1 FI_DECODE_MFMA_MIN_GROUP=1)."""
+"""Error structure of the 16x16x32 decode kernel on small cases."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "flashinfer-ai_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
