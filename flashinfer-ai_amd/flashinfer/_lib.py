@@ -355,9 +355,52 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def nbytes(t: torch.Tensor) -> int:
+    """Size of a tensor's elements in bytes: what the C ABI takes wherever it takes a buffer size."""
+    return t.numel() * t.element_size()
+
+
 def current_stream(device: torch.device) -> int:
     """hipStream_t of torch's current stream on `device` (ref: csrc/tvm_ffi_utils.h:256-264)."""
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def batch_decode_plan(float_ws, int_ws, pinned_int_ws, indptr_host, batch_size, num_qo_heads, num_kv_heads, page_size,
+                      enable_cuda_graph, head_dim, q_dtype, kv_dtype, max_grid_hint, window_left, what: str):
+    """fi_batch_decode_plan on the float workspace's device; returns the plan_info array.  ``indptr_host`` is the
+    host copy of the page-table prefix sums, ``q_dtype`` / ``kv_dtype`` are torch dtypes."""
+    info = (C.c_int64 * FI_DECODE_PLAN_INFO_LEN)()
+    with torch.cuda.device(float_ws.device):
+        check(
+            lib().fi_batch_decode_plan(
+                float_ws.data_ptr(), nbytes(float_ws), int_ws.data_ptr(), pinned_int_ws.data_ptr(), nbytes(int_ws),
+                indptr_host.data_ptr(), batch_size, num_qo_heads, num_kv_heads, page_size, int(enable_cuda_graph),
+                head_dim, fi_dtype(q_dtype), fi_dtype(kv_dtype), max_grid_hint, window_left, info,
+                current_stream(float_ws.device),
+            ),
+            what,
+        )
+    return info
+
+
+def batch_prefill_plan(float_ws, int_ws, pinned_int_ws, qo_indptr_host, kv_indptr_host, kv_len_arr_host,
+                       total_num_rows, batch_size, num_qo_heads, num_kv_heads, page_size, enable_cuda_graph,
+                       head_dim_qk, head_dim_vo, causal, window_left, fixed_split_size, disable_split_kv, what: str):
+    """fi_batch_prefill_plan on the float workspace's device; returns the plan_info array.  The three index tensors
+    are host int32 tensors; ``fixed_split_size`` is -1 for the planner's own choice."""
+    info = (C.c_int64 * FI_PREFILL_PLAN_INFO_LEN)()
+    with torch.cuda.device(float_ws.device):
+        check(
+            lib().fi_batch_prefill_plan(
+                float_ws.data_ptr(), nbytes(float_ws), int_ws.data_ptr(), pinned_int_ws.data_ptr(), nbytes(int_ws),
+                qo_indptr_host.data_ptr(), kv_indptr_host.data_ptr(), kv_len_arr_host.data_ptr(), total_num_rows,
+                batch_size, num_qo_heads, num_kv_heads, page_size, int(enable_cuda_graph), head_dim_qk, head_dim_vo,
+                int(causal), window_left, fixed_split_size, int(disable_split_kv), info,
+                current_stream(float_ws.device),
+            ),
+            what,
+        )
+    return info
 
 
 def require_gpu_tensor(t: torch.Tensor, name: str) -> None:

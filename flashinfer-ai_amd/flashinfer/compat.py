@@ -21,28 +21,17 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-
-
-def _nbytes(t: torch.Tensor) -> int:
-    return t.numel() * t.element_size()
+from .utils import paged_kv, ragged_kv
 
 
 def _stream(t: torch.Tensor) -> int:
     return _lib.current_stream(t.device)
 
 
-def _paged_kv(k_cache, v_cache, kv_indptr, kv_indices, kv_last_page_len, layout_code: int, batch_size: int):
-    """paged_kv_t from the 4-D K / V views the reference passes (csrc/batch_decode.cu:94-142):
-    layout 0 = NHD [pages, page_size, H, D], 1 = HND [pages, H, page_size, D]; strides from the tensors."""
-    nhd = layout_code == 0
-    if k_cache.stride() != v_cache.stride():
-        raise ValueError("k/v strides must be identical")  # ref: csrc/batch_decode.cu:118-129
-    return _lib.PagedKV(
-        k_data=k_cache.data_ptr(), v_data=v_cache.data_ptr(), indptr=kv_indptr.data_ptr(),
-        indices=_lib.ptr(kv_indices), last_page_len=_lib.ptr(kv_last_page_len), rope_pos_offset=None,
-        stride_page=k_cache.stride(0), stride_n=k_cache.stride(1 if nhd else 2), stride_h=k_cache.stride(2 if nhd else 1),
-        page_size=k_cache.shape[1 if nhd else 2], num_kv_heads=k_cache.shape[2 if nhd else 1],
-        head_dim=k_cache.shape[3], batch_size=batch_size, dtype=_lib.fi_dtype(k_cache.dtype))
+def _kv_layout(layout_code: int) -> str:
+    """The reference's layout code (csrc/batch_decode.cu:94-142): 0 = NHD [pages, page_size, H, D], else HND
+    [pages, H, page_size, D]."""
+    return "NHD" if layout_code == 0 else "HND"
 
 
 @functools.cache
@@ -58,15 +47,10 @@ def get_batch_decode_module(dtype_q, dtype_kv, dtype_o, idtype, head_dim_qk, hea
              head_dim_vo_, empty_q_data, empty_kv_data) -> List[int]:
         """ref: BatchDecodeWithPagedKVCachePlan, csrc/batch_decode.cu:39-44 (15 positional arguments; `indptr` is
         the HOST copy, flashinfer/decode.py:1079-1095)."""
-        info = (C.c_int64 * _lib.FI_DECODE_PLAN_INFO_LEN)()
-        with torch.cuda.device(float_workspace_buffer.device):
-            _lib.check(lib.fi_batch_decode_plan(
-                float_workspace_buffer.data_ptr(), _nbytes(float_workspace_buffer), int_workspace_buffer.data_ptr(),
-                page_locked_int_workspace_buffer.data_ptr(), _nbytes(int_workspace_buffer), indptr.data_ptr(),
-                batch_size, num_qo_heads, num_kv_heads, page_size, int(enable_cuda_graph), head_dim_qk_,
-                _lib.fi_dtype(empty_q_data.dtype), _lib.fi_dtype(empty_kv_data.dtype), 0,
-                window_left if use_sliding_window else -1, info, _stream(float_workspace_buffer)), "batch_decode.plan")
-        return list(info)
+        return list(_lib.batch_decode_plan(
+            float_workspace_buffer, int_workspace_buffer, page_locked_int_workspace_buffer, indptr, batch_size,
+            num_qo_heads, num_kv_heads, page_size, enable_cuda_graph, head_dim_qk_, empty_q_data.dtype,
+            empty_kv_data.dtype, 0, window_left if use_sliding_window else -1, "batch_decode.plan"))
 
     def run(float_workspace_buffer, int_workspace_buffer, plan_info_vec, q, paged_k_cache, paged_v_cache,
             paged_kv_indptr, paged_kv_indices, paged_kv_last_page_len, o, maybe_lse, kv_layout_code, window_left,
@@ -74,8 +58,8 @@ def get_batch_decode_module(dtype_q, dtype_kv, dtype_o, idtype, head_dim_qk, hea
         """ref: BatchDecodeWithPagedKVCacheRun, csrc/batch_decode.cu:81-86 + the default additional parameters
         (flashinfer/jit/attention/modules.py:764-772); the reference's Python shim passes 1/rope_scale and
         1/rope_theta here (flashinfer/decode.py:264-268)."""
-        kv = _paged_kv(paged_k_cache, paged_v_cache, paged_kv_indptr, paged_kv_indices, paged_kv_last_page_len,
-                       kv_layout_code, q.shape[0])
+        kv = paged_kv(paged_k_cache, paged_v_cache, _kv_layout(kv_layout_code), paged_kv_indptr, paged_kv_indices,
+                      paged_kv_last_page_len, q.shape[0])[0]
         p = _lib.BatchDecodeParams(
             q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), kv=kv, o=o.data_ptr(),
             lse=_lib.ptr(maybe_lse), alibi_slopes=_lib.ptr(maybe_alibi_slopes), q_rope_offset=None,
@@ -86,8 +70,8 @@ def get_batch_decode_module(dtype_q, dtype_kv, dtype_o, idtype, head_dim_qk, hea
         info = (C.c_int64 * _lib.FI_DECODE_PLAN_INFO_LEN)(*plan_info_vec)
         with torch.cuda.device(q.device):
             _lib.check(lib.fi_batch_decode_run(
-                float_workspace_buffer.data_ptr(), _nbytes(float_workspace_buffer), int_workspace_buffer.data_ptr(),
-                _nbytes(int_workspace_buffer), info, _lib.FI_DECODE_PLAN_INFO_LEN, C.byref(p), _stream(q)),
+                float_workspace_buffer.data_ptr(), _lib.nbytes(float_workspace_buffer), int_workspace_buffer.data_ptr(),
+                _lib.nbytes(int_workspace_buffer), info, _lib.FI_DECODE_PLAN_INFO_LEN, C.byref(p), _stream(q)),
                 "batch_decode.run")
 
     return SimpleNamespace(plan=plan, run=run)
@@ -107,16 +91,11 @@ def get_batch_prefill_module(backend, dtype_q, dtype_kv, dtype_o, idtype, head_d
         """ref: BatchPrefillWithKVCachePlan, csrc/batch_prefill.cu:47-52 (18 positional arguments; the three index
         tensors are HOST tensors, flashinfer/prefill.py:1884-1908; the fa3 plan stops at window_left,
         csrc/batch_prefill_fp8_sm90.cu:39-44)."""
-        info = (C.c_int64 * _lib.FI_PREFILL_PLAN_INFO_LEN)()
-        with torch.cuda.device(float_workspace_buffer.device):
-            _lib.check(lib.fi_batch_prefill_plan(
-                float_workspace_buffer.data_ptr(), _nbytes(float_workspace_buffer), int_workspace_buffer.data_ptr(),
-                page_locked_int_workspace_buffer.data_ptr(), _nbytes(int_workspace_buffer), qo_indptr.data_ptr(),
-                kv_indptr.data_ptr(), kv_len_arr.data_ptr(), total_num_rows, batch_size, num_qo_heads, num_kv_heads,
-                page_size, int(enable_cuda_graph), head_dim_qk_, head_dim_vo_, int(causal),
-                window_left if use_sliding_window else -1, fixed_split_size, int(disable_split_kv), info,
-                _stream(float_workspace_buffer)), "batch_prefill.plan")
-        return list(info)
+        return list(_lib.batch_prefill_plan(
+            float_workspace_buffer, int_workspace_buffer, page_locked_int_workspace_buffer, qo_indptr, kv_indptr,
+            kv_len_arr, total_num_rows, batch_size, num_qo_heads, num_kv_heads, page_size, enable_cuda_graph,
+            head_dim_qk_, head_dim_vo_, causal, window_left if use_sliding_window else -1, fixed_split_size,
+            disable_split_kv, "batch_prefill.plan"))
 
     def _run(float_ws, int_ws, plan_info_vec, q, k_cache, v_cache, qo_indptr, kv, o, maybe_lse, mask_mode_code,
              window_left, custom_mask, mask_indptr, alibi_slopes, prefix_len_ptr, token_pos_in_items_ptr,
@@ -137,7 +116,7 @@ def get_batch_prefill_module(backend, dtype_q, dtype_kv, dtype_o, idtype, head_d
         info = (C.c_int64 * _lib.FI_PREFILL_PLAN_INFO_LEN)(*plan_info_vec)
         with torch.cuda.device(q.device):
             _lib.check(lib.fi_batch_prefill_paged_run(
-                float_ws.data_ptr(), _nbytes(float_ws), int_ws.data_ptr(), _nbytes(int_ws), info,
+                float_ws.data_ptr(), _lib.nbytes(float_ws), int_ws.data_ptr(), _lib.nbytes(int_ws), info,
                 _lib.FI_PREFILL_PLAN_INFO_LEN, C.byref(p), _stream(q)), what)
 
     def _tail16(additional):
@@ -163,8 +142,8 @@ def get_batch_prefill_module(backend, dtype_q, dtype_kv, dtype_o, idtype, head_d
                      maybe_token_pos_in_items_ptr, maybe_max_item_len_ptr, logits_soft_cap, sm_scale,
                      rope_rcp_scale, rope_rcp_theta, token_pos_in_items_len          (flashinfer/prefill.py:620-650)
           fp8 q    : scale_q, scale_k, scale_v, sm_scale  (csrc/batch_prefill_fp8_sm90.cu:81-90, prefill.py:676-697)"""
-        kv = _paged_kv(paged_k_cache, paged_v_cache, paged_kv_indptr, paged_kv_indices, paged_kv_last_page_len,
-                       layout, paged_kv_indptr.shape[0] - 1)
+        kv = paged_kv(paged_k_cache, paged_v_cache, _kv_layout(layout), paged_kv_indptr, paged_kv_indices,
+                      paged_kv_last_page_len, paged_kv_indptr.shape[0] - 1)[0]
         if q.dtype in (torch.float8_e4m3fn, torch.float8_e5m2):
             scale_q, scale_k, scale_v, sm_scale = additional
             _run(float_workspace_buffer, int_workspace_buffer, plan_info_vec, q, paged_k_cache, paged_v_cache, qo_indptr,
@@ -182,13 +161,7 @@ def get_batch_prefill_module(backend, dtype_q, dtype_kv, dtype_o, idtype, head_d
                    maybe_lse, mask_mode_code, layout, window_left, enable_pdl, *additional) -> None:
         """ref: BatchPrefillWithRaggedKVCacheRun, csrc/batch_prefill.cu:76-82 (k, v ragged [nnz, H, D] (layout 0) or
         [H, nnz, D] (layout 1)); same additional parameters as paged_run."""
-        nhd = layout == 0
-        stride_n, stride_h = (k.stride(0), k.stride(1)) if nhd else (k.stride(1), k.stride(0))
-        kv = _lib.PagedKV(
-            k_data=k.data_ptr(), v_data=v.data_ptr(), indptr=kv_indptr.data_ptr(), indices=None, last_page_len=None,
-            rope_pos_offset=None, stride_page=stride_n, stride_n=stride_n, stride_h=stride_h, page_size=1,
-            num_kv_heads=k.shape[1 if nhd else 0], head_dim=k.shape[2], batch_size=kv_indptr.shape[0] - 1,
-            dtype=_lib.fi_dtype(k.dtype))
+        kv = ragged_kv(k, v, _kv_layout(layout), kv_indptr, kv_indptr.shape[0] - 1)
         (custom_mask, mask_indptr, alibi_slopes, prefix_len_ptr, token_pos_in_items_ptr, max_item_len_ptr,
          logits_soft_cap, sm_scale, rope_rcp_scale, rope_rcp_theta, token_pos_in_items_len) = _tail16(additional)
         _run(float_workspace_buffer, int_workspace_buffer, plan_info_vec, q, k, v, qo_indptr, kv, o, maybe_lse,
@@ -239,8 +212,8 @@ def get_page_module():
     def append_paged_kv_cache(append_key, append_value, batch_indices, positions, paged_k_cache, paged_v_cache,
                               kv_indices, kv_indptr, kv_last_page_len, layout) -> None:
         """ref: append_paged_kv_cache, csrc/page.cu:28-33 (10 positional arguments, flashinfer/page.py:411-424)."""
-        kv = _paged_kv(paged_k_cache, paged_v_cache, kv_indptr, kv_indices, kv_last_page_len, layout,
-                       kv_indptr.shape[0] - 1)
+        kv = paged_kv(paged_k_cache, paged_v_cache, _kv_layout(layout), kv_indptr, kv_indices, kv_last_page_len,
+                      kv_indptr.shape[0] - 1)[0]
         with torch.cuda.device(append_key.device):
             _lib.check(lib.fi_append_paged_kv_cache(
                 append_key.data_ptr(), append_value.data_ptr(), append_key.stride(0), append_key.stride(1),

@@ -14,22 +14,22 @@ from typing import Any, List, Optional, Tuple, Union
 import torch
 
 from . import _lib
+from ._wrapper import BatchAttentionWrapper
 from .page import get_seq_lens
 from .utils import (
     PosEncodingMode,
-    TensorLayout,
+    _apply_v_scale,
     _check_cached_qkv_data_type,
     _check_kv_layout,
     _check_pos_encoding_mode,
     _get_cache_alibi_slopes_buf,
     _get_cache_buf,
-    _get_range_buf,
     _resolve_logits_params,
     _unpack_paged_kv_cache,
-    canonicalize_torch_dtype,
+    canonicalize_qkv_dtypes,
     check_shape_dtype_device,
-    is_float8,
-    paged_kv_strides,
+    dense_kv_dims,
+    paged_kv,
 )
 
 
@@ -127,12 +127,7 @@ def single_decode_with_kv_cache(
         raise ValueError("q must be [num_qo_heads, head_dim]; k and v must be 3-D with equal shapes")
     head_dim = q.shape[-1]
     num_qo_heads = q.shape[0]
-    if kv_layout == "NHD":
-        kv_len, num_kv_heads = k.shape[0], k.shape[1]
-        stride_n, stride_h = k.stride(0), k.stride(1)
-    else:
-        num_kv_heads, kv_len = k.shape[0], k.shape[1]
-        stride_h, stride_n = k.stride(0), k.stride(1)
+    kv_len, num_kv_heads, stride_n, stride_h = dense_kv_dims(k, kv_layout)
     if k.stride() != v.stride() or k.stride(-1) != 1 or q.stride(-1) != 1:
         raise ValueError("k and v must share strides and q/k/v must be contiguous in head_dim")
     if num_qo_heads % num_kv_heads != 0:
@@ -159,19 +154,16 @@ def single_decode_with_kv_cache(
     with torch.cuda.device(q.device):
         _lib.check(
             _lib.lib().fi_single_decode_run(
-                C.byref(params), tmp.data_ptr(), tmp.numel(), _lib.current_stream(q.device)
+                C.byref(params), tmp.data_ptr(), _lib.nbytes(tmp), _lib.current_stream(q.device)
             ),
             "single_decode_with_kv_cache",
         )
     if v_scale is not None:
-        if is_float8(out):
-            out = (out.to(torch.float32) * v_scale).to(out.dtype)
-        else:
-            out *= v_scale
+        out = _apply_v_scale(out, v_scale)
     return (out, lse) if return_lse else out
 
 
-class BatchDecodeWithPagedKVCacheWrapper:
+class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
     r"""Decode attention over a paged KV cache for a batch of requests.
 
     ``plan()`` is host work done once per batch shape and reused by every layer; ``run()`` launches the
@@ -208,20 +200,8 @@ class BatchDecodeWithPagedKVCacheWrapper:
         jit_args : must be None -- there is no JIT in this build.
         """
         _check_kv_layout(kv_layout)
-        if jit_args is not None:
-            raise ValueError("jit_args is not supported: kernels are built ahead of time")
-        if backend not in ("auto", "fa2"):
-            raise ValueError(f"backend {backend!r} is not available on MI355X (use 'auto')")
-        _lib.require_gpu_tensor(float_workspace_buffer, "float_workspace_buffer")
+        super().__init__(float_workspace_buffer, use_cuda_graph, backend, ("auto", "fa2"), jit_args)
         self._kv_layout = kv_layout
-        self._float_workspace_buffer = float_workspace_buffer
-        self.device = float_workspace_buffer.device
-        self._int_workspace_buffer = torch.empty(
-            (8 * 1024 * 1024,), dtype=torch.uint8, device=self.device
-        )
-        self._pin_memory_int_workspace_buffer = torch.empty(
-            (8 * 1024 * 1024,), dtype=torch.uint8, pin_memory=True, device="cpu"
-        )
         if use_cuda_graph:
             if not torch.is_tensor(paged_kv_indptr_buffer):
                 raise ValueError("paged_kv_indptr_buffer should be a torch.Tensor in cudagraph mode")
@@ -234,15 +214,10 @@ class BatchDecodeWithPagedKVCacheWrapper:
             self._fixed_batch_size = len(paged_kv_last_page_len_buffer)
             if len(paged_kv_indptr_buffer) != self._fixed_batch_size + 1:
                 raise ValueError("The size of paged_kv_indptr_buffer should be batch_size + 1")
-        else:
-            self._fixed_batch_size = 0
         self._paged_kv_indptr_buf = paged_kv_indptr_buffer
         self._paged_kv_indices_buf = paged_kv_indices_buffer
         self._paged_kv_last_page_len_buf = paged_kv_last_page_len_buffer
         self._use_tensor_cores = use_tensor_cores
-        self._use_cuda_graph = use_cuda_graph
-        self._backend = backend
-        self._plan_info: Optional[List[int]] = None
         self._run_cache = None
         self._plan_serial = 0
 
@@ -250,23 +225,12 @@ class BatchDecodeWithPagedKVCacheWrapper:
     def use_tensor_cores(self) -> bool:
         return self._use_tensor_cores
 
-    @property
-    def is_cuda_graph_enabled(self) -> bool:
-        return self._use_cuda_graph
-
     def reset_workspace_buffer(
         self, float_workspace_buffer: torch.Tensor, int_workspace_buffer: torch.Tensor
     ) -> None:
         r"""Swap the workspaces; a new pinned mirror of the int workspace is allocated."""
-        self._run_cache = None
-        self._float_workspace_buffer = float_workspace_buffer
-        self._int_workspace_buffer = int_workspace_buffer
-        self._pin_memory_int_workspace_buffer = torch.empty(
-            self._int_workspace_buffer.shape,
-            dtype=self._int_workspace_buffer.dtype,
-            device="cpu",
-            pin_memory=True,
-        )
+        self._run_cache = None  # it holds the old workspaces' pointers
+        super().reset_workspace_buffer(float_workspace_buffer, int_workspace_buffer)
 
     def plan(
         self,
@@ -301,39 +265,14 @@ class BatchDecodeWithPagedKVCacheWrapper:
         The remaining arguments configure the attention variant exactly as in the reference.
         ``plan`` is synchronous host code and must not be captured in a graph.
         """
-        for tensor, name in [(indptr, "indptr"), (indices, "indices"), (last_page_len, "last_page_len")]:
-            if tensor.dtype != torch.int32:
-                raise ValueError(f"{name} must have dtype torch.int32, got {tensor.dtype}")
         _check_pos_encoding_mode(pos_encoding_mode)
         batch_size = len(last_page_len)
         if logits_soft_cap is None:
             logits_soft_cap = 0.0
-        if self.is_cuda_graph_enabled:
-            if batch_size != self._fixed_batch_size:
-                raise ValueError(
-                    "The batch size should be fixed in cudagraph mode, the runtime batch size {} "
-                    " mismatches the batch size set during initialization {}".format(
-                        batch_size, self._fixed_batch_size
-                    )
-                )
-            if len(indices) > len(self._paged_kv_indices_buf):
-                raise ValueError(
-                    "The size of indices should be less than or equal to the allocated buffer"
-                )
-            if not _fast:  # fast_decode_plan: the caller already wrote the graph buffers in place
-                self._paged_kv_indptr_buf.copy_(indptr, non_blocking=non_blocking)
-                self._paged_kv_last_page_len_buf.copy_(last_page_len, non_blocking=non_blocking)
-                self._paged_kv_indices_buf[: len(indices)].copy_(
-                    indices, non_blocking=(indices.device == self.device) and non_blocking
-                )
-        elif _fast:
-            self._paged_kv_indptr_buf = indptr
-            self._paged_kv_indices_buf = indices
-            self._paged_kv_last_page_len_buf = last_page_len
-        else:
-            self._paged_kv_indptr_buf = indptr.to(self.device, non_blocking=non_blocking)
-            self._paged_kv_indices_buf = indices.to(self.device, non_blocking=non_blocking)
-            self._paged_kv_last_page_len_buf = last_page_len.to(self.device, non_blocking=non_blocking)
+        # fast_decode_plan: the caller wrote the graph buffers in place; without a graph its tensors are adopted
+        self._bind_index_tensors(batch_size, non_blocking, prefix=("paged_kv_indices",), adopt=_fast,
+                                 paged_kv_indptr=indptr, paged_kv_indices=indices,
+                                 paged_kv_last_page_len=last_page_len)
         indptr_host = (indptr if _indptr_host is None else _indptr_host).to("cpu").contiguous()
         if indptr_host.dtype != torch.int32 or len(indptr_host) != batch_size + 1:
             raise ValueError("indptr must be int32 with batch_size + 1 entries")
@@ -343,10 +282,7 @@ class BatchDecodeWithPagedKVCacheWrapper:
                 q_data_type = data_type
             if kv_data_type is None:
                 kv_data_type = data_type
-        q_data_type = canonicalize_torch_dtype(q_data_type)
-        if kv_data_type is None:
-            kv_data_type = q_data_type
-        kv_data_type = canonicalize_torch_dtype(kv_data_type)
+        q_data_type, kv_data_type = canonicalize_qkv_dtypes(q_data_type, kv_data_type)
         if fixed_split_size is not None and not self.use_tensor_cores:
             raise ValueError("fixed_split_size is only supported by tensor core decode for now.")
 
@@ -365,44 +301,15 @@ class BatchDecodeWithPagedKVCacheWrapper:
         else:
             self._kv_lens_host = seq_lens.cpu()
 
-        plan_info = (C.c_int64 * _lib.FI_DECODE_PLAN_INFO_LEN)()
-        max_grid_hint = 0
-        if disable_split_kv:
-            max_grid_hint = 1  # batch*heads >= 1 always: the planner never splits
-        with torch.cuda.device(self.device):
-            _lib.check(
-                _lib.lib().fi_batch_decode_plan(
-                    self._float_workspace_buffer.data_ptr(),
-                    self._float_workspace_buffer.numel() * self._float_workspace_buffer.element_size(),
-                    self._int_workspace_buffer.data_ptr(),
-                    self._pin_memory_int_workspace_buffer.data_ptr(),
-                    self._int_workspace_buffer.numel(),
-                    indptr_host.data_ptr(),
-                    batch_size,
-                    num_qo_heads,
-                    num_kv_heads,
-                    page_size,
-                    int(self.is_cuda_graph_enabled),
-                    head_dim,
-                    _lib.fi_dtype(q_data_type),
-                    _lib.fi_dtype(kv_data_type),
-                    max_grid_hint,
-                    window_left,
-                    plan_info,
-                    _lib.current_stream(self.device),
-                ),
-                "BatchDecodeWithPagedKVCacheWrapper.plan",
-            )
-        self._plan_info = list(plan_info)
-        self._plan_info_c = plan_info
-        self._plan_serial = getattr(self, "_plan_serial", 0) + 1
+        # max_grid_hint 1: batch * heads >= 1 always, so the planner never splits
+        self._plan_info = _lib.batch_decode_plan(
+            self._float_workspace_buffer, self._int_workspace_buffer, self._pin_memory_int_workspace_buffer,
+            indptr_host, batch_size, num_qo_heads, num_kv_heads, page_size, self._use_cuda_graph, head_dim,
+            q_data_type, kv_data_type, 1 if disable_split_kv else 0, window_left,
+            "BatchDecodeWithPagedKVCacheWrapper.plan")
+        self._plan_serial += 1
         self._run_cache = None
-        self._pos_encoding_mode = pos_encoding_mode
-        self._window_left = window_left
-        self._logits_soft_cap = logits_soft_cap
-        self._sm_scale = sm_scale
-        self._rope_scale = rope_scale
-        self._rope_theta = rope_theta
+        self._set_run_options(pos_encoding_mode, window_left, logits_soft_cap, sm_scale, rope_scale, rope_theta)
 
     begin_forward = plan
 
@@ -421,12 +328,7 @@ class BatchDecodeWithPagedKVCacheWrapper:
         rope_theta: Optional[float] = None,
     ) -> torch.Tensor:
         r"""Warning: this function is deprecated, please use :meth:`run` instead."""
-        self._pos_encoding_mode = pos_encoding_mode
-        self._window_left = window_left
-        self._logits_soft_cap = logits_soft_cap
-        self._sm_scale = sm_scale
-        self._rope_scale = rope_scale
-        self._rope_theta = rope_theta
+        self._set_run_options(pos_encoding_mode, window_left, logits_soft_cap, sm_scale, rope_scale, rope_theta)
         self._run_cache = None
         return self.run(q, paged_kv_cache, q_scale=q_scale, k_scale=k_scale, v_scale=v_scale)
 
@@ -483,20 +385,17 @@ class BatchDecodeWithPagedKVCacheWrapper:
         dev_index = q.device.index
         if torch.cuda.current_device() == dev_index:
             status = self._lib_run(self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes,
-                                   self._plan_info_c, _lib.FI_DECODE_PLAN_INFO_LEN, params,
+                                   self._plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, params,
                                    torch.cuda.current_stream().cuda_stream)
         else:
             with torch.cuda.device(q.device):
                 status = self._lib_run(self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes,
-                                       self._plan_info_c, _lib.FI_DECODE_PLAN_INFO_LEN, params,
+                                       self._plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, params,
                                        torch.cuda.current_stream().cuda_stream)
         if status != 0:
             _lib.check(status, "BatchDecodeWithPagedKVCacheWrapper.run")
         if v_scale is not None:
-            if is_float8(out):
-                out = (out.to(torch.float32) * v_scale).to(out.dtype)
-            else:
-                out *= v_scale
+            out = _apply_v_scale(out, v_scale)
         return (out, lse) if return_lse else out
 
     def _build_run_params(self, q, paged_kv_cache, q_scale, k_scale, out, lse):
@@ -504,9 +403,9 @@ class BatchDecodeWithPagedKVCacheWrapper:
         _lib.require_gpu_tensor(q, "q")
         k_cache, v_cache = _unpack_paged_kv_cache(paged_kv_cache, self._kv_layout)
         _check_cached_qkv_data_type(q, k_cache, self._cached_q_data_type, self._cached_kv_data_type)
-        page_size, num_kv_heads, head_dim, stride_page, stride_n, stride_h = paged_kv_strides(
-            k_cache, v_cache, self._kv_layout
-        )
+        kv, page_size, num_kv_heads, head_dim = paged_kv(
+            k_cache, v_cache, self._kv_layout, self._paged_kv_indptr_buf, self._paged_kv_indices_buf,
+            self._paged_kv_last_page_len_buf, self._batch_size)
         pos_encoding_mode = self._pos_encoding_mode
         _check_pos_encoding_mode(pos_encoding_mode)
         if q.dim() != 3 or q.shape[0] != self._batch_size or q.shape[1] != self._num_qo_heads:
@@ -529,15 +428,7 @@ class BatchDecodeWithPagedKVCacheWrapper:
             alibi = _get_cache_alibi_slopes_buf(q.shape[1], q.device)
         params = _lib.BatchDecodeParams(
             q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1),
-            kv=_lib.PagedKV(
-                k_data=k_cache.data_ptr(), v_data=v_cache.data_ptr(),
-                indptr=self._paged_kv_indptr_buf.data_ptr(),
-                indices=self._paged_kv_indices_buf.data_ptr(),
-                last_page_len=self._paged_kv_last_page_len_buf.data_ptr(),
-                rope_pos_offset=None, stride_page=stride_page, stride_n=stride_n, stride_h=stride_h,
-                page_size=page_size, num_kv_heads=num_kv_heads, head_dim=head_dim,
-                batch_size=self._batch_size, dtype=_lib.fi_dtype(k_cache.dtype),
-            ),
+            kv=kv,
             o=out.data_ptr(), lse=_lib.ptr(lse),
             alibi_slopes=_lib.ptr(alibi), q_rope_offset=None, num_qo_heads=self._num_qo_heads,
             q_dtype=_lib.fi_dtype(q.dtype), pos_encoding_mode=PosEncodingMode[pos_encoding_mode].value,
@@ -545,10 +436,7 @@ class BatchDecodeWithPagedKVCacheWrapper:
             **_resolve_logits_params(q.shape[-1], self._sm_scale, q_scale, k_scale, self._logits_soft_cap,
                                      self._rope_scale, self._rope_theta),
         )
-        self._fws_ptr = self._float_workspace_buffer.data_ptr()
-        self._fws_bytes = self._float_workspace_buffer.numel() * self._float_workspace_buffer.element_size()
-        self._iws_ptr = self._int_workspace_buffer.data_ptr()
-        self._iws_bytes = self._int_workspace_buffer.numel()
+        self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes = self._workspace_args
         self._lib_run = _lib.lib().fi_batch_decode_run
         return C.byref(params)
 
@@ -567,12 +455,7 @@ class BatchDecodeWithPagedKVCacheWrapper:
         rope_theta: Optional[float] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         r"""Warning: this function is deprecated, please use :meth:`run_return_lse` instead."""
-        self._pos_encoding_mode = pos_encoding_mode
-        self._window_left = window_left
-        self._logits_soft_cap = logits_soft_cap
-        self._sm_scale = sm_scale
-        self._rope_scale = rope_scale
-        self._rope_theta = rope_theta
+        self._set_run_options(pos_encoding_mode, window_left, logits_soft_cap, sm_scale, rope_scale, rope_theta)
         self._run_cache = None
         return self.run(
             q, paged_kv_cache, q_scale=q_scale, k_scale=k_scale, v_scale=v_scale, return_lse=True

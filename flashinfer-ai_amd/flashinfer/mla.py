@@ -12,6 +12,7 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import _lib
+from ._wrapper import BatchAttentionWrapper
 
 _MLA_INT_WORKSPACE_BYTES = 8 * 1024 * 1024
 
@@ -21,7 +22,7 @@ def _last_dim_contiguous(t: torch.Tensor, name: str) -> None:
         raise ValueError(f"{name} must have a contiguous last dimension")
 
 
-class BatchMLAPagedAttentionWrapper:
+class BatchMLAPagedAttentionWrapper(BatchAttentionWrapper):
     r"""Wrapper class for MLA PagedAttention on DeepSeek models, for decode, speculative verify and incremental
     prefill with the matrix-absorbed weights (ref: flashinfer/mla.py:85-420).
 
@@ -45,32 +46,19 @@ class BatchMLAPagedAttentionWrapper:
         kv_len_arr: Optional[torch.Tensor] = None,
         backend: str = "auto",
     ) -> None:
-        if backend == "cutlass":
-            raise ValueError(
-                "BatchMLAPagedAttentionWrapper: backend='cutlass' is not available on MI355X "
-                "(use 'auto', 'fa2' or 'fa3', which all run the HIP kernel)"
-            )
-        if backend not in ("auto", "fa2", "fa3"):
-            raise ValueError(f"BatchMLAPagedAttentionWrapper: unknown backend {backend!r}")
-        _lib.require_gpu_tensor(float_workspace_buffer, "float_workspace_buffer")
-        self._float_workspace_buffer = float_workspace_buffer
-        self.device = float_workspace_buffer.device
-        self._backend = backend
-        self._int_workspace_buffer = torch.empty((_MLA_INT_WORKSPACE_BYTES,), dtype=torch.uint8, device=self.device)
-        self._pin_memory_int_workspace_buffer = torch.empty(
-            (_MLA_INT_WORKSPACE_BYTES,), dtype=torch.uint8, pin_memory=True, device="cpu"
-        )
-        self._use_cuda_graph = use_cuda_graph
+        # of the reference's backend names only "cutlass" is refused: the others all run the one HIP kernel
+        super().__init__(float_workspace_buffer, use_cuda_graph, backend, ("auto", "fa2", "fa3"),
+                         int_workspace_bytes=_MLA_INT_WORKSPACE_BYTES)
         if use_cuda_graph:
             for t, name in ((qo_indptr, "qo_indptr"), (kv_indptr, "kv_indptr"), (kv_indices, "kv_indices"),
                             (kv_len_arr, "kv_len_arr")):
                 if t is None:
                     raise ValueError(f"use_cuda_graph=True needs the {name} buffer")
+            self._fixed_batch_size = qo_indptr.numel() - 1
         self._qo_indptr_buf = qo_indptr
         self._kv_indptr_buf = kv_indptr
         self._kv_indices_buf = kv_indices
         self._kv_len_arr_buf = kv_len_arr
-        self._plan_info = None
         self._graph_rows = None  # (qo_indptr[-1], num_heads) of the first graph plan
 
     def plan(
@@ -96,10 +84,6 @@ class BatchMLAPagedAttentionWrapper:
         """
         if use_profiler:
             raise ValueError("BatchMLAPagedAttentionWrapper: the profiler is not available on MI355X")
-        for t, name in ((kv_len_arr, "kv_len_arr"), (kv_indptr, "kv_indptr"), (qo_indptr, "qo_indptr"),
-                        (kv_indices, "kv_indices")):
-            if t.dtype != torch.int32:
-                raise ValueError(f"Expected {name}.dtype == torch.int32, got {t.dtype}")
         qo_indptr_host = qo_indptr.to("cpu").contiguous()
         kv_indptr_host = kv_indptr.to("cpu").contiguous()
         kv_len_arr_host = kv_len_arr.to("cpu").contiguous()
@@ -107,8 +91,6 @@ class BatchMLAPagedAttentionWrapper:
         if kv_indptr_host.numel() != batch_size + 1 or kv_len_arr_host.numel() != batch_size:
             raise ValueError("qo_indptr, kv_indptr and kv_len_arr disagree on the batch size")
         if self._use_cuda_graph:
-            if batch_size + 1 != self._qo_indptr_buf.numel():
-                raise ValueError("use_cuda_graph: the batch size cannot change after construction")
             # a captured run() holds the q / out tensors and the merge launch of the first plan's packed row count
             # (qo_indptr[-1] x num_heads), and the workspace layout moves with it: every later plan must keep both
             graph_rows = (int(qo_indptr_host[-1]), int(num_heads))
@@ -117,22 +99,13 @@ class BatchMLAPagedAttentionWrapper:
                     "use_cuda_graph: the query count and num_heads cannot change between plans "
                     f"(qo_indptr[-1], num_heads = {graph_rows}; first plan {self._graph_rows})"
                 )
-            if kv_indices.numel() > self._kv_indices_buf.numel():
-                raise ValueError("use_cuda_graph: kv_indices does not fit the kv_indices buffer")
-            self._qo_indptr_buf.copy_(qo_indptr, non_blocking=True)
-            self._kv_indptr_buf.copy_(kv_indptr, non_blocking=True)
-            self._kv_indices_buf[: len(kv_indices)].copy_(kv_indices, non_blocking=True)
-            self._kv_len_arr_buf.copy_(kv_len_arr, non_blocking=True)
-        else:
-            self._qo_indptr_buf = qo_indptr.to(self.device, non_blocking=True)
-            self._kv_indptr_buf = kv_indptr.to(self.device, non_blocking=True)
-            self._kv_indices_buf = kv_indices.to(self.device, non_blocking=True)
-            self._kv_len_arr_buf = kv_len_arr.to(self.device, non_blocking=True)
+        self._bind_index_tensors(batch_size, True, prefix=("kv_indices",), qo_indptr=qo_indptr, kv_indptr=kv_indptr,
+                                 kv_indices=kv_indices, kv_len_arr=kv_len_arr)
         params = _lib.MlaPlanParams(
             int_ws=self._int_workspace_buffer.data_ptr(),
             pinned_int_ws=self._pin_memory_int_workspace_buffer.data_ptr(),
-            int_ws_bytes=self._int_workspace_buffer.numel(),
-            float_ws_bytes=self._float_workspace_buffer.numel() * self._float_workspace_buffer.element_size(),
+            int_ws_bytes=_lib.nbytes(self._int_workspace_buffer),
+            float_ws_bytes=_lib.nbytes(self._float_workspace_buffer),
             qo_indptr_h=qo_indptr_host.data_ptr(), kv_indptr_h=kv_indptr_host.data_ptr(),
             kv_len_arr_h=kv_len_arr_host.data_ptr(), batch_size=batch_size, num_heads=num_heads,
             head_dim_ckv=head_dim_ckv, head_dim_kpe=head_dim_kpe, page_size=page_size, causal=int(bool(causal)),
@@ -178,8 +151,7 @@ class BatchMLAPagedAttentionWrapper:
         if kv_len is not None or page_table is not None:
             raise ValueError("BatchMLAPagedAttentionWrapper: the kv_len / page_table call form is the cutlass "
                              "backend's and is not supported on MI355X")
-        if self._plan_info is None:
-            raise RuntimeError("BatchMLAPagedAttentionWrapper: call plan() before run()")
+        self._check_run_args()
         for t, name in ((q_nope, "q_nope"), (q_pe, "q_pe"), (ckv_cache, "ckv_cache"), (kpe_cache, "kpe_cache")):
             _lib.require_gpu_tensor(t, name)
             _last_dim_contiguous(t, name)
@@ -209,7 +181,7 @@ class BatchMLAPagedAttentionWrapper:
                 lse = torch.empty((nnz, H), dtype=torch.float32, device=q_nope.device)
             elif lse.shape != (nnz, H) or lse.dtype != torch.float32 or not lse.is_contiguous():
                 raise ValueError("lse must be a contiguous float32 [nnz, num_heads] tensor")
-        fw = self._float_workspace_buffer
+        float_ws, float_ws_bytes, int_ws, int_ws_bytes = self._workspace_args
         params = _lib.MlaParams(
             q_nope=q_nope.data_ptr(), q_nope_stride_n=q_nope.stride(0), q_nope_stride_h=q_nope.stride(1),
             q_pe=q_pe.data_ptr(), q_pe_stride_n=q_pe.stride(0), q_pe_stride_h=q_pe.stride(1),
@@ -217,8 +189,7 @@ class BatchMLAPagedAttentionWrapper:
             kpe=kpe3.data_ptr(), kpe_stride_page=kpe3.stride(0), kpe_stride_n=kpe3.stride(1),
             kv_indices=self._kv_indices_buf.data_ptr(), o=out.data_ptr(),
             lse=None if not return_lse else lse.data_ptr(),
-            float_ws=fw.data_ptr(), float_ws_bytes=fw.numel() * fw.element_size(),
-            int_ws=self._int_workspace_buffer.data_ptr(), int_ws_bytes=self._int_workspace_buffer.numel(),
+            float_ws=float_ws, float_ws_bytes=float_ws_bytes, int_ws=int_ws, int_ws_bytes=int_ws_bytes,
             num_rows=nnz * H, num_heads=H, page_size=self._page_size, dtype=_lib.fi_dtype(q_nope.dtype),
             causal=int(self._causal), sm_scale=self._sm_scale,
         )

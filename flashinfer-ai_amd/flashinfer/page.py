@@ -8,7 +8,7 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import _lib
-from .utils import TensorLayout, _check_kv_layout, _unpack_paged_kv_cache, paged_kv_strides
+from .utils import _check_kv_layout, _unpack_paged_kv_cache, paged_kv
 
 
 def get_seq_lens(
@@ -91,27 +91,22 @@ def append_paged_kv_cache(
         raise ValueError("append_key/append_value dtype must match the cache dtype")
     if append_key.dim() != 3 or append_key.shape != append_value.shape:
         raise ValueError("append_key and append_value must be [nnz, num_kv_heads, head_dim]")
-    page_size, num_kv_heads, head_dim, stride_page, stride_n, stride_h = paged_kv_strides(k_cache, v_cache, kv_layout)
+    dev = k_cache.device
+    kv_indices = kv_indices.to(device=dev, dtype=torch.int32).contiguous()
+    kv_indptr = kv_indptr.to(device=dev, dtype=torch.int32).contiguous()
+    kv, _, num_kv_heads, head_dim = paged_kv(k_cache, v_cache, kv_layout, kv_indptr, kv_indices, None,
+                                             kv_indptr.numel() - 1)
     if append_key.shape[1] != num_kv_heads or append_key.shape[2] != head_dim:
         raise ValueError("append_key shape does not match the cache")
     if append_key.stride(-1) != 1:
         append_key = append_key.contiguous()
     if append_value.stride(-1) != 1:
         append_value = append_value.contiguous()
-    dev = k_cache.device
     batch_indices = batch_indices.to(device=dev, dtype=torch.int32).contiguous()
     positions = positions.to(device=dev, dtype=torch.int32).contiguous()
-    kv_indices = kv_indices.to(device=dev, dtype=torch.int32).contiguous()
-    kv_indptr = kv_indptr.to(device=dev, dtype=torch.int32).contiguous()
     nnz = append_key.shape[0]
     if batch_indices.numel() != nnz or positions.numel() != nnz:
         raise ValueError("batch_indices and positions must have nnz entries")
-    kv = _lib.PagedKV(
-        k_data=k_cache.data_ptr(), v_data=v_cache.data_ptr(), indptr=kv_indptr.data_ptr(),
-        indices=kv_indices.data_ptr(), last_page_len=None, rope_pos_offset=None, stride_page=stride_page,
-        stride_n=stride_n, stride_h=stride_h, page_size=page_size, num_kv_heads=num_kv_heads,
-        head_dim=head_dim, batch_size=kv_indptr.numel() - 1, dtype=_lib.fi_dtype(k_cache.dtype),
-    )
     with torch.cuda.device(dev):
         _lib.check(
             _lib.lib().fi_append_paged_kv_cache(
@@ -158,7 +153,11 @@ def apply_rope_append_paged_kv_cache(
         raise ValueError("q and append_key must be float16 or bfloat16")
     if append_key.dim() != 3 or append_key.shape != append_value.shape or q.dim() != 3:
         raise ValueError("q, append_key and append_value must be [nnz, heads, head_dim]")
-    page_size, num_kv_heads, head_dim, stride_page, stride_n, stride_h = paged_kv_strides(k_cache, v_cache, kv_layout)
+    dev = k_cache.device
+    kv_indices = kv_indices.to(device=dev, dtype=torch.int32).contiguous()
+    kv_indptr = kv_indptr.to(device=dev, dtype=torch.int32).contiguous()
+    kv, _, num_kv_heads, head_dim = paged_kv(k_cache, v_cache, kv_layout, kv_indptr, kv_indices, None,
+                                             kv_indptr.numel() - 1)
     if append_key.shape[1] != num_kv_heads or append_key.shape[2] != head_dim or q.shape[2] != head_dim or \
             q.shape[0] != append_key.shape[0]:
         raise ValueError("q / append_key shape does not match the cache")
@@ -172,21 +171,12 @@ def apply_rope_append_paged_kv_cache(
         q_out = torch.empty_like(q)
     elif q_out.shape != q.shape or q_out.dtype != q.dtype or q_out.stride(-1) != 1:
         raise ValueError("q_out must match q")
-    dev = k_cache.device
     batch_indices = batch_indices.to(device=dev, dtype=torch.int32).contiguous()
     positions = positions.to(device=dev, dtype=torch.int32).contiguous()
     pos_ids = positions if pos_ids is None else pos_ids.to(device=dev, dtype=torch.int32).contiguous()
-    kv_indices = kv_indices.to(device=dev, dtype=torch.int32).contiguous()
-    kv_indptr = kv_indptr.to(device=dev, dtype=torch.int32).contiguous()
     nnz = append_key.shape[0]
     if batch_indices.numel() != nnz or positions.numel() != nnz or pos_ids.numel() != nnz:
         raise ValueError("batch_indices, positions and pos_ids must have nnz entries")
-    kv = _lib.PagedKV(
-        k_data=k_cache.data_ptr(), v_data=v_cache.data_ptr(), indptr=kv_indptr.data_ptr(),
-        indices=kv_indices.data_ptr(), last_page_len=None, rope_pos_offset=None, stride_page=stride_page,
-        stride_n=stride_n, stride_h=stride_h, page_size=page_size, num_kv_heads=num_kv_heads,
-        head_dim=head_dim, batch_size=kv_indptr.numel() - 1, dtype=_lib.fi_dtype(k_cache.dtype),
-    )
     params = _lib.RopeParams(
         q=q.data_ptr(), k=append_key.data_ptr(), q_out=q_out.data_ptr(), k_out=None, pos_ids=pos_ids.data_ptr(),
         cos_sin_cache=None, q_stride_n=q.stride(0), q_stride_h=q.stride(1), k_stride_n=append_key.stride(0),

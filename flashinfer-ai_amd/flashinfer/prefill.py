@@ -15,11 +15,13 @@ from typing import Any, List, Optional, Tuple, Union
 import torch
 
 from . import _lib
+from ._wrapper import BatchAttentionWrapper
 from .page import get_seq_lens
 from .quantization import packbits, segment_packbits
 from .utils import (
     MaskMode,
     PosEncodingMode,
+    _apply_v_scale,
     _check_cached_qkv_data_type,
     _check_kv_layout,
     _check_pos_encoding_mode,
@@ -27,10 +29,13 @@ from .utils import (
     _get_cache_buf,
     _resolve_logits_params,
     _unpack_paged_kv_cache,
+    canonicalize_qkv_dtypes,
     canonicalize_torch_dtype,
     check_shape_dtype_device,
+    dense_kv_dims,
     is_float8,
-    paged_kv_strides,
+    paged_kv,
+    ragged_kv,
 )
 
 
@@ -90,7 +95,7 @@ def _mask_mode(wrapper) -> int:
     # ref: flashinfer/prefill.py:2091-2100
     if wrapper._custom_mask_buf is not None:
         return MaskMode.CUSTOM.value
-    if getattr(wrapper, "_prefix_len_ptr", None) is not None:
+    if wrapper._prefix_len_ptr is not None:
         return MaskMode.MULTIITEMSCORING.value
     return MaskMode.CAUSAL.value if wrapper._causal else MaskMode.NON_CAUSAL.value
 
@@ -122,8 +127,7 @@ def _plan_custom_mask(wrapper, custom_mask, packed_custom_mask, qo_indptr_host, 
         if packed_custom_mask.dtype != torch.uint8:
             raise ValueError("packed_custom_mask must be uint8")
     if wrapper.is_cuda_graph_enabled:
-        mask_buf = getattr(wrapper, "_user_custom_mask_buf", None)
-        indptr_buf = getattr(wrapper, "_user_mask_indptr_buf", None)
+        mask_buf, indptr_buf = wrapper._user_custom_mask_buf, wrapper._user_mask_indptr_buf
         if mask_buf is None or indptr_buf is None:
             raise ValueError("custom_mask_buf and mask_indptr_buf are required for custom masks in cuda graph mode")
         if packed_custom_mask.numel() > mask_buf.numel():
@@ -157,7 +161,7 @@ def _run_single_prefill(run_fn, params, device):
     tmp = _get_cache_buf("single_prefill_with_kv_cache_tmp", 32 * 1024 * 1024, device)
     with torch.cuda.device(device):
         _lib.check(
-            run_fn(C.byref(params), tmp.data_ptr(), tmp.numel() * tmp.element_size(), _lib.current_stream(device)),
+            run_fn(C.byref(params), tmp.data_ptr(), _lib.nbytes(tmp), _lib.current_stream(device)),
             "single_prefill_with_kv_cache",
         )
 
@@ -180,25 +184,20 @@ def _run_batch_prefill(wrapper, name, q, kv, o_dtype, out, lse, return_lse, wind
         token_pos_in_items_ptr=_lib.ptr(wrapper._token_pos_in_items_ptr),
         max_item_len_ptr=_lib.ptr(wrapper._max_item_len_ptr), token_pos_in_items_len=wrapper._token_pos_in_items_len,
         mask_mode=_mask_mode(wrapper), pos_encoding_mode=PosEncodingMode[wrapper._pos_encoding_mode].value,
-        window_left=window_left, bf16_pv_mode=getattr(wrapper, "_bf16_pv_mode", 0),
+        window_left=window_left, bf16_pv_mode=wrapper._bf16_pv_mode,
         **_resolve_logits_params(q.size(-1), wrapper._sm_scale, q_scale, k_scale, wrapper._logits_soft_cap,
                                  wrapper._rope_scale, wrapper._rope_theta),
     )
-    fws = wrapper._float_workspace_buffer
     with torch.cuda.device(q.device):
         _lib.check(
             _lib.lib().fi_batch_prefill_paged_run(
-                fws.data_ptr(), fws.numel() * fws.element_size(), wrapper._int_workspace_buffer.data_ptr(),
-                wrapper._int_workspace_buffer.numel(), wrapper._plan_info_c, _lib.FI_PREFILL_PLAN_INFO_LEN,
-                C.byref(params), _lib.current_stream(q.device),
+                *wrapper._workspace_args, wrapper._plan_info, _lib.FI_PREFILL_PLAN_INFO_LEN, C.byref(params),
+                _lib.current_stream(q.device),
             ),
             name,
         )
     if v_scale is not None:
-        if is_float8(out):
-            out = (out.to(torch.float32) * v_scale).to(out.dtype)
-        else:
-            out *= v_scale
+        out = _apply_v_scale(out, v_scale)
     return (out, lse) if return_lse else out
 
 
@@ -228,15 +227,13 @@ def _check_qkvo_config(head_dim_qk, head_dim_vo, q_dtype, kv_dtype, pos_encoding
 def _qkvo_params(q, k, v, kv_layout, out, lse, causal, window_left, sm_scale, bf16_pv_mode, **extra):
     """fi_prefill_qkvo_params_t for q [rows, Hq, 192] and k / v [kv rows, Hkv, 192 / 128] (NHD; HND: heads first),
     k and v each by their own strides."""
-    if kv_layout == "NHD":
-        k_sn, k_sh, v_sn, v_sh = k.stride(0), k.stride(1), v.stride(0), v.stride(1)
-    else:
-        k_sh, k_sn, v_sh, v_sn = k.stride(0), k.stride(1), v.stride(0), v.stride(1)
+    _, num_kv_heads, k_sn, k_sh = dense_kv_dims(k, kv_layout)
+    _, _, v_sn, v_sh = dense_kv_dims(v, kv_layout)
     dt = _lib.fi_dtype(q.dtype)
     return _lib.PrefillQkvoParams(
         q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), k=k.data_ptr(), k_stride_n=k_sn,
         k_stride_h=k_sh, v=v.data_ptr(), v_stride_n=v_sn, v_stride_h=v_sh, o=out.data_ptr(), lse=_lib.ptr(lse),
-        num_qo_heads=q.shape[1], num_kv_heads=k.shape[1] if kv_layout == "NHD" else k.shape[0],
+        num_qo_heads=q.shape[1], num_kv_heads=num_kv_heads,
         head_dim_qk=q.shape[2], head_dim_vo=v.shape[2], q_dtype=dt, kv_dtype=_lib.fi_dtype(k.dtype), o_dtype=dt,
         mask_mode=MaskMode.CAUSAL.value if causal else MaskMode.NON_CAUSAL.value,
         pos_encoding_mode=PosEncodingMode.NONE.value, window_left=window_left, logits_soft_cap=0.0,
@@ -262,7 +259,7 @@ def _single_prefill_qkvo(q, k, v, causal, kv_layout, pos_encoding_mode, sm_scale
     if q.stride(-1) != 1:
         q = q.contiguous()
     qo_len, num_qo_heads = q.shape[0], q.shape[1]
-    kv_len = k.shape[0] if kv_layout == "NHD" else k.shape[1]
+    kv_len = dense_kv_dims(k, kv_layout)[0]
     out, lse = _out_and_lse(q, None, None, return_lse, (qo_len, num_qo_heads, head_dim_vo), q.dtype)
     params = _qkvo_params(q, k, v, kv_layout, out, lse, causal, window_left,
                           1.0 / math.sqrt(head_dim_qk) if sm_scale is None else sm_scale,
@@ -329,12 +326,7 @@ def single_prefill_with_kv_cache(
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape:
         raise ValueError("q must be [qo_len, num_qo_heads, head_dim]; k, v 3-D with equal shapes")
     qo_len, num_qo_heads, head_dim = q.shape
-    if kv_layout == "NHD":
-        kv_len, num_kv_heads = k.shape[0], k.shape[1]
-        stride_n, stride_h = k.stride(0), k.stride(1)
-    else:
-        num_kv_heads, kv_len = k.shape[0], k.shape[1]
-        stride_h, stride_n = k.stride(0), k.stride(1)
+    kv_len, num_kv_heads, stride_n, stride_h = dense_kv_dims(k, kv_layout)
     if k.stride() != v.stride() or k.stride(-1) != 1 or q.stride(-1) != 1:
         raise ValueError("k and v must share strides and q/k/v must be contiguous in head_dim")
     if is_float8(q):
@@ -380,7 +372,7 @@ single_prefill_with_kv_cache_return_lse = functools.partial(
 )
 
 
-class BatchPrefillWithPagedKVCacheWrapper:
+class BatchPrefillWithPagedKVCacheWrapper(BatchAttentionWrapper):
     r"""Prefill / append attention over a paged KV cache for a batch of requests.
 
     >>> prefill_wrapper = flashinfer.BatchPrefillWithPagedKVCacheWrapper(workspace_buffer, "NHD")
@@ -407,19 +399,8 @@ class BatchPrefillWithPagedKVCacheWrapper:
         jit_kwargs: Optional[dict] = None,
     ) -> None:
         _check_kv_layout(kv_layout)
-        if jit_args is not None:
-            raise ValueError("jit_args is not supported: kernels are built ahead of time")
-        if backend not in ("auto", "fa2", "fa3"):
-            raise ValueError(f"backend {backend!r} is not available on MI355X (use 'auto')")
-        _lib.require_gpu_tensor(float_workspace_buffer, "float_workspace_buffer")
+        super().__init__(float_workspace_buffer, use_cuda_graph, backend, ("auto", "fa2", "fa3"), jit_args)
         self._kv_layout = kv_layout
-        self._float_workspace_buffer = float_workspace_buffer
-        self.device = float_workspace_buffer.device
-        self._int_workspace_buffer = torch.empty((8 * 1024 * 1024,), dtype=torch.uint8, device=self.device)
-        self._pin_memory_int_workspace_buffer = torch.empty(
-            self._int_workspace_buffer.shape, dtype=torch.uint8, pin_memory=True, device="cpu"
-        )
-        self._use_cuda_graph = use_cuda_graph
         if use_cuda_graph:
             for buf, name in ((qo_indptr_buf, "qo_indptr_buf"), (paged_kv_indptr_buf, "paged_kv_indptr_buf"),
                               (paged_kv_indices_buf, "paged_kv_indices_buf"),
@@ -431,8 +412,6 @@ class BatchPrefillWithPagedKVCacheWrapper:
                 raise ValueError("The length of paged_kv_indptr_buf should be batch_size + 1.")
             if len(paged_kv_last_page_len_buf) != self._fixed_batch_size:
                 raise ValueError("The length of paged_kv_last_page_len_buf should be batch_size.")
-        else:
-            self._fixed_batch_size = 0
         self._qo_indptr_buf = qo_indptr_buf
         self._paged_kv_indptr_buf = paged_kv_indptr_buf
         self._paged_kv_indices_buf = paged_kv_indices_buf
@@ -440,22 +419,6 @@ class BatchPrefillWithPagedKVCacheWrapper:
         self._user_custom_mask_buf = custom_mask_buf
         self._user_mask_indptr_buf = mask_indptr_buf
         self._custom_mask_buf = self._mask_indptr_buf = None
-        self._backend = backend
-        self._plan_info = None
-
-    @property
-    def is_cuda_graph_enabled(self) -> bool:
-        return self._use_cuda_graph
-
-    def reset_workspace_buffer(
-        self, float_workspace_buffer: torch.Tensor, int_workspace_buffer: torch.Tensor
-    ) -> None:
-        self._float_workspace_buffer = float_workspace_buffer
-        self._int_workspace_buffer = int_workspace_buffer
-        self._pin_memory_int_workspace_buffer = torch.empty(
-            self._int_workspace_buffer.shape, dtype=self._int_workspace_buffer.dtype, device="cpu",
-            pin_memory=True,
-        )
 
     def plan(
         self,
@@ -517,16 +480,8 @@ class BatchPrefillWithPagedKVCacheWrapper:
         self._prefix_len_ptr, self._token_pos_in_items_ptr, self._max_item_len_ptr, self._token_pos_in_items_len = \
             _check_multi_item_args(prefix_len_ptr, token_pos_in_items_ptr, max_item_len_ptr, token_pos_in_items_len,
                                    len(qo_indptr) - 1, self.device)
-        for tensor, name in [(qo_indptr, "qo_indptr"), (paged_kv_indptr, "paged_kv_indptr"),
-                             (paged_kv_indices, "paged_kv_indices"),
-                             (paged_kv_last_page_len, "paged_kv_last_page_len")]:
-            if tensor.dtype != torch.int32:
-                raise ValueError(f"{name} must have dtype torch.int32, got {tensor.dtype}")
         _check_pos_encoding_mode(pos_encoding_mode)
-        q_data_type = canonicalize_torch_dtype(q_data_type)
-        if kv_data_type is None:
-            kv_data_type = q_data_type
-        kv_data_type = canonicalize_torch_dtype(kv_data_type)
+        q_data_type, kv_data_type = canonicalize_qkv_dtypes(q_data_type, kv_data_type)
         if o_data_type is None:
             o_data_type = torch.bfloat16 if q_data_type in (torch.float8_e4m3fn, torch.float8_e5m2) else q_data_type
         o_data_type = canonicalize_torch_dtype(o_data_type)
@@ -557,50 +512,18 @@ class BatchPrefillWithPagedKVCacheWrapper:
         if self._custom_mask_buf is not None:
             causal = False  # mask mode CUSTOM: every kv tile is visited, the bits decide
 
-        if self.is_cuda_graph_enabled:
-            if batch_size != self._fixed_batch_size:
-                raise ValueError(
-                    "The batch size should be fixed during the lifecycle of the wrapper in cuda graph mode, "
-                    f"the runtime batch size {batch_size} mismatches the batch size {self._fixed_batch_size}"
-                )
-            if len(paged_kv_indices) > len(self._paged_kv_indices_buf):
-                raise ValueError("The length of paged_kv_indices exceeds the allocated buffer size.")
-            self._qo_indptr_buf.copy_(qo_indptr, non_blocking=non_blocking)
-            self._paged_kv_indptr_buf.copy_(paged_kv_indptr, non_blocking=non_blocking)
-            self._paged_kv_last_page_len_buf.copy_(paged_kv_last_page_len, non_blocking=non_blocking)
-            self._paged_kv_indices_buf[: len(paged_kv_indices)].copy_(
-                paged_kv_indices, non_blocking=(paged_kv_indices.device == self.device) and non_blocking
-            )
-            if max_token_per_sequence is None:
-                total_rows_bound = total_num_rows
-            else:
-                total_rows_bound = max_token_per_sequence * batch_size
-        else:
-            self._qo_indptr_buf = qo_indptr.to(self.device, non_blocking=non_blocking)
-            self._paged_kv_indptr_buf = paged_kv_indptr.to(self.device, non_blocking=non_blocking)
-            self._paged_kv_indices_buf = paged_kv_indices.to(self.device, non_blocking=non_blocking)
-            self._paged_kv_last_page_len_buf = paged_kv_last_page_len.to(self.device, non_blocking=non_blocking)
-            total_rows_bound = total_num_rows
-
-        plan_info = (C.c_int64 * _lib.FI_PREFILL_PLAN_INFO_LEN)()
-        with torch.cuda.device(self.device):
-            _lib.check(
-                _lib.lib().fi_batch_prefill_plan(
-                    self._float_workspace_buffer.data_ptr(),
-                    self._float_workspace_buffer.numel() * self._float_workspace_buffer.element_size(),
-                    self._int_workspace_buffer.data_ptr(),
-                    self._pin_memory_int_workspace_buffer.data_ptr(),
-                    self._int_workspace_buffer.numel(),
-                    qo_indptr_host.data_ptr(), paged_kv_indptr_host.data_ptr(), kv_lens_arr_host.data_ptr(),
-                    total_rows_bound, batch_size, num_qo_heads, num_kv_heads, page_size,
-                    int(self.is_cuda_graph_enabled), head_dim_qk, head_dim_vo, int(causal), window_left,
-                    -1 if fixed_split_size is None else fixed_split_size, int(disable_split_kv),
-                    plan_info, _lib.current_stream(self.device),
-                ),
-                "BatchPrefillWithPagedKVCacheWrapper.plan",
-            )
-        self._plan_info = list(plan_info)
-        self._plan_info_c = plan_info
+        self._bind_index_tensors(batch_size, non_blocking, prefix=("paged_kv_indices",), qo_indptr=qo_indptr,
+                                 paged_kv_indptr=paged_kv_indptr, paged_kv_indices=paged_kv_indices,
+                                 paged_kv_last_page_len=paged_kv_last_page_len)
+        total_rows_bound = total_num_rows
+        if self._use_cuda_graph and max_token_per_sequence is not None:
+            total_rows_bound = max_token_per_sequence * batch_size
+        self._plan_info = _lib.batch_prefill_plan(
+            self._float_workspace_buffer, self._int_workspace_buffer, self._pin_memory_int_workspace_buffer,
+            qo_indptr_host, paged_kv_indptr_host, kv_lens_arr_host, total_rows_bound, batch_size, num_qo_heads,
+            num_kv_heads, page_size, self._use_cuda_graph, head_dim_qk, head_dim_vo, causal, window_left,
+            -1 if fixed_split_size is None else fixed_split_size, disable_split_kv,
+            "BatchPrefillWithPagedKVCacheWrapper.plan")
         self._batch_size = batch_size
         self._num_qo_heads = num_qo_heads
         self._num_kv_heads = num_kv_heads
@@ -611,12 +534,7 @@ class BatchPrefillWithPagedKVCacheWrapper:
         self._cached_kv_data_type = kv_data_type
         self._cached_o_data_type = o_data_type
         self._causal = causal
-        self._pos_encoding_mode = pos_encoding_mode
-        self._window_left = window_left
-        self._logits_soft_cap = logits_soft_cap
-        self._sm_scale = sm_scale
-        self._rope_scale = rope_scale
-        self._rope_theta = rope_theta
+        self._set_run_options(pos_encoding_mode, window_left, logits_soft_cap, sm_scale, rope_scale, rope_theta)
 
     begin_forward = plan
 
@@ -625,12 +543,7 @@ class BatchPrefillWithPagedKVCacheWrapper:
                 rope_scale=None, rope_theta=None) -> torch.Tensor:
         r"""Warning: This function is deprecated, please use :meth:`run` instead."""
         self._causal = causal
-        self._pos_encoding_mode = pos_encoding_mode
-        self._window_left = window_left
-        self._logits_soft_cap = logits_soft_cap
-        self._sm_scale = sm_scale
-        self._rope_scale = rope_scale
-        self._rope_theta = rope_theta
+        self._set_run_options(pos_encoding_mode, window_left, logits_soft_cap, sm_scale, rope_scale, rope_theta)
         return self.run(q, paged_kv_cache, k_scale=k_scale, v_scale=v_scale)
 
     def run(
@@ -661,18 +574,13 @@ class BatchPrefillWithPagedKVCacheWrapper:
         Returns ``[qo_indptr[-1], num_qo_heads, head_dim]`` (+ base-2 logsumexp ``[nnz, num_qo_heads]``).
         (ref: flashinfer/prefill.py:1979-2206)
         """
-        if self._plan_info is None:
-            raise RuntimeError("plan() must be called before run()")
-        if sinks is not None:
-            raise ValueError("attention sinks are not supported by this backend")
-        if args:
-            raise ValueError("additional kernel arguments require jit_args, which is not supported")
+        self._check_run_args(args, sinks)
         _lib.require_gpu_tensor(q, "q")
         k_cache, v_cache = _unpack_paged_kv_cache(paged_kv_cache, self._kv_layout)
         _check_cached_qkv_data_type(q, k_cache, self._cached_q_data_type, self._cached_kv_data_type)
-        page_size, num_kv_heads, head_dim, stride_page, stride_n, stride_h = paged_kv_strides(
-            k_cache, v_cache, self._kv_layout
-        )
+        kv, page_size, num_kv_heads, head_dim = paged_kv(
+            k_cache, v_cache, self._kv_layout, self._paged_kv_indptr_buf, self._paged_kv_indices_buf,
+            self._paged_kv_last_page_len_buf, self._batch_size)
         window_left = self._window_left if window_left is None else window_left
         assert window_left == self._window_left
         if q.dim() != 3 or q.shape[0] != self._total_num_rows or q.shape[1] != self._num_qo_heads:
@@ -685,14 +593,6 @@ class BatchPrefillWithPagedKVCacheWrapper:
             raise ValueError("kv cache shape does not match the planned num_kv_heads / page_size")
         if out is not None and not out.is_contiguous():
             raise ValueError("out must be contiguous")
-        kv = _lib.PagedKV(
-            k_data=k_cache.data_ptr(), v_data=v_cache.data_ptr(),
-            indptr=self._paged_kv_indptr_buf.data_ptr(), indices=self._paged_kv_indices_buf.data_ptr(),
-            last_page_len=self._paged_kv_last_page_len_buf.data_ptr(), rope_pos_offset=None,
-            stride_page=stride_page, stride_n=stride_n, stride_h=stride_h, page_size=page_size,
-            num_kv_heads=num_kv_heads, head_dim=head_dim, batch_size=self._batch_size,
-            dtype=_lib.fi_dtype(k_cache.dtype),
-        )
         # missing scales are NULL pointers (= 1 in the kernels): run() creates no tensor and stays capturable
         return _run_batch_prefill(
             self, "BatchPrefillWithPagedKVCacheWrapper.run", q, kv, self._cached_o_data_type, out, lse, return_lse,
@@ -706,12 +606,7 @@ class BatchPrefillWithPagedKVCacheWrapper:
                            logits_soft_cap=None, sm_scale=None, rope_scale=None, rope_theta=None):
         r"""Warning: This function is deprecated, please use :meth:`run_return_lse` instead."""
         self._causal = causal
-        self._pos_encoding_mode = pos_encoding_mode
-        self._window_left = window_left
-        self._logits_soft_cap = logits_soft_cap
-        self._sm_scale = sm_scale
-        self._rope_scale = rope_scale
-        self._rope_theta = rope_theta
+        self._set_run_options(pos_encoding_mode, window_left, logits_soft_cap, sm_scale, rope_scale, rope_theta)
         return self.run_return_lse(q, paged_kv_cache, k_scale=k_scale, v_scale=v_scale)
 
     def end_forward(self) -> None:
@@ -719,7 +614,7 @@ class BatchPrefillWithPagedKVCacheWrapper:
         pass
 
 
-class BatchPrefillWithRaggedKVCacheWrapper:
+class BatchPrefillWithRaggedKVCacheWrapper(BatchAttentionWrapper):
     r"""Prefill / append attention with ragged (tensor) KV for a batch of requests: ``k``/``v`` are
     ``[kv_indptr[-1], num_kv_heads, head_dim]`` (``NHD``) or ``[num_kv_heads, kv_indptr[-1], head_dim]`` (``HND``).
 
@@ -741,44 +636,19 @@ class BatchPrefillWithRaggedKVCacheWrapper:
         jit_kwargs: Optional[dict] = None,
     ) -> None:
         _check_kv_layout(kv_layout)
-        if jit_args is not None:
-            raise ValueError("jit_args is not supported: kernels are built ahead of time")
-        if backend not in ("auto", "fa2", "fa3"):
-            raise ValueError(f"backend {backend!r} is not available on MI355X (use 'auto')")
-        _lib.require_gpu_tensor(float_workspace_buffer, "float_workspace_buffer")
+        super().__init__(float_workspace_buffer, use_cuda_graph, backend, ("auto", "fa2", "fa3"), jit_args)
         self._kv_layout = kv_layout
-        self._float_workspace_buffer = float_workspace_buffer
-        self.device = float_workspace_buffer.device
-        self._int_workspace_buffer = torch.empty((8 * 1024 * 1024,), dtype=torch.uint8, device=self.device)
-        self._pin_memory_int_workspace_buffer = torch.empty(
-            self._int_workspace_buffer.shape, dtype=torch.uint8, pin_memory=True, device="cpu"
-        )
-        self._use_cuda_graph = use_cuda_graph
         if use_cuda_graph:
             if not torch.is_tensor(qo_indptr_buf) or not torch.is_tensor(kv_indptr_buf):
                 raise ValueError("qo_indptr_buf and kv_indptr_buf should be torch.Tensor in cuda graph mode")
             self._fixed_batch_size = len(qo_indptr_buf) - 1
             if len(kv_indptr_buf) != self._fixed_batch_size + 1:
                 raise ValueError("The length of kv_indptr_buf should be batch_size + 1.")
-        else:
-            self._fixed_batch_size = 0
         self._qo_indptr_buf = qo_indptr_buf
         self._kv_indptr_buf = kv_indptr_buf
         self._user_custom_mask_buf = custom_mask_buf
         self._user_mask_indptr_buf = mask_indptr_buf
         self._custom_mask_buf = self._mask_indptr_buf = None
-        self._plan_info = None
-
-    @property
-    def is_cuda_graph_enabled(self) -> bool:
-        return self._use_cuda_graph
-
-    def reset_workspace_buffer(self, float_workspace_buffer: torch.Tensor, int_workspace_buffer) -> None:
-        self._float_workspace_buffer = float_workspace_buffer
-        self._int_workspace_buffer = int_workspace_buffer
-        self._pin_memory_int_workspace_buffer = torch.empty(
-            self._int_workspace_buffer.shape, dtype=self._int_workspace_buffer.dtype, device="cpu", pin_memory=True
-        )
 
     def plan(
         self,
@@ -815,14 +685,8 @@ class BatchPrefillWithRaggedKVCacheWrapper:
         self._prefix_len_ptr, self._token_pos_in_items_ptr, self._max_item_len_ptr, self._token_pos_in_items_len = \
             _check_multi_item_args(prefix_len_ptr, token_pos_in_items_ptr, max_item_len_ptr, token_pos_in_items_len,
                                    len(qo_indptr) - 1, self.device)
-        for tensor, name in [(qo_indptr, "qo_indptr"), (kv_indptr, "kv_indptr")]:
-            if tensor.dtype != torch.int32:
-                raise ValueError(f"{name} must have dtype torch.int32, got {tensor.dtype}")
         _check_pos_encoding_mode(pos_encoding_mode)
-        q_data_type = canonicalize_torch_dtype(q_data_type)
-        if kv_data_type is None:
-            kv_data_type = q_data_type
-        kv_data_type = canonicalize_torch_dtype(kv_data_type)
+        q_data_type, kv_data_type = canonicalize_qkv_dtypes(q_data_type, kv_data_type)
         if logits_soft_cap is None:
             logits_soft_cap = 0.0
         if head_dim_vo is None:
@@ -845,31 +709,13 @@ class BatchPrefillWithRaggedKVCacheWrapper:
             self, custom_mask, packed_custom_mask, qo_indptr_host, kv_len_arr, non_blocking)
         if self._custom_mask_buf is not None:
             causal = False
-        if self.is_cuda_graph_enabled:
-            if batch_size != self._fixed_batch_size:
-                raise ValueError("The batch size should be fixed in cuda graph mode")
-            self._qo_indptr_buf.copy_(qo_indptr, non_blocking=non_blocking)
-            self._kv_indptr_buf.copy_(kv_indptr, non_blocking=non_blocking)
-        else:
-            self._qo_indptr_buf = qo_indptr.to(self.device, non_blocking=non_blocking)
-            self._kv_indptr_buf = kv_indptr.to(self.device, non_blocking=non_blocking)
-        plan_info = (C.c_int64 * _lib.FI_PREFILL_PLAN_INFO_LEN)()
-        with torch.cuda.device(self.device):
-            _lib.check(
-                _lib.lib().fi_batch_prefill_plan(
-                    self._float_workspace_buffer.data_ptr(),
-                    self._float_workspace_buffer.numel() * self._float_workspace_buffer.element_size(),
-                    self._int_workspace_buffer.data_ptr(), self._pin_memory_int_workspace_buffer.data_ptr(),
-                    self._int_workspace_buffer.numel(), qo_indptr_host.data_ptr(), kv_indptr_host.data_ptr(),
-                    kv_len_arr.data_ptr(), total_num_rows, batch_size, num_qo_heads, num_kv_heads, 1,
-                    int(self.is_cuda_graph_enabled), head_dim_qk, head_dim_vo, int(causal), window_left,
-                    -1 if fixed_split_size is None else fixed_split_size, int(disable_split_kv), plan_info,
-                    _lib.current_stream(self.device),
-                ),
-                "BatchPrefillWithRaggedKVCacheWrapper.plan",
-            )
-        self._plan_info = list(plan_info)
-        self._plan_info_c = plan_info
+        self._bind_index_tensors(batch_size, non_blocking, qo_indptr=qo_indptr, kv_indptr=kv_indptr)
+        self._plan_info = _lib.batch_prefill_plan(
+            self._float_workspace_buffer, self._int_workspace_buffer, self._pin_memory_int_workspace_buffer,
+            qo_indptr_host, kv_indptr_host, kv_len_arr, total_num_rows, batch_size, num_qo_heads, num_kv_heads, 1,
+            self._use_cuda_graph, head_dim_qk, head_dim_vo, causal, window_left,
+            -1 if fixed_split_size is None else fixed_split_size, disable_split_kv,
+            "BatchPrefillWithRaggedKVCacheWrapper.plan")
         self._batch_size = batch_size
         self._num_qo_heads = num_qo_heads
         self._num_kv_heads = num_kv_heads
@@ -879,12 +725,7 @@ class BatchPrefillWithRaggedKVCacheWrapper:
         self._cached_q_data_type = q_data_type
         self._cached_kv_data_type = kv_data_type
         self._causal = causal
-        self._pos_encoding_mode = pos_encoding_mode
-        self._window_left = window_left
-        self._logits_soft_cap = logits_soft_cap
-        self._sm_scale = sm_scale
-        self._rope_scale = rope_scale
-        self._rope_theta = rope_theta
+        self._set_run_options(pos_encoding_mode, window_left, logits_soft_cap, sm_scale, rope_scale, rope_theta)
 
     begin_forward = plan
 
@@ -903,10 +744,7 @@ class BatchPrefillWithRaggedKVCacheWrapper:
         enable_pdl: Optional[bool] = None,
     ) -> Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
         r"""q ``[qo_indptr[-1], num_qo_heads, head_dim]``; k, v ragged as described in the class docstring."""
-        if self._plan_info is None:
-            raise RuntimeError("plan() must be called before run()")
-        if args:
-            raise ValueError("additional kernel arguments require jit_args, which is not supported")
+        self._check_run_args(args)
         for t, name in ((q, "q"), (k, "k"), (v, "v")):
             _lib.require_gpu_tensor(t, name)
         _check_cached_qkv_data_type(q, k, self._cached_q_data_type, self._cached_kv_data_type)
@@ -916,31 +754,20 @@ class BatchPrefillWithRaggedKVCacheWrapper:
             return self._run_qkvo(q, k, v, q_scale, k_scale, v_scale, out, lse, return_lse)
         if k.shape != v.shape or k.stride() != v.stride() or k.dim() != 3 or k.stride(-1) != 1:
             raise ValueError("k and v must be 3-D with equal shapes/strides, contiguous in head_dim")
-        if self._kv_layout == "NHD":
-            nnz_kv, num_kv_heads, head_dim = k.shape
-            stride_n, stride_h = k.stride(0), k.stride(1)
-        else:
-            num_kv_heads, nnz_kv, head_dim = k.shape
-            stride_h, stride_n = k.stride(0), k.stride(1)
-        if num_kv_heads != self._num_kv_heads or head_dim != self._head_dim or nnz_kv < self._total_kv_rows:
+        kv = ragged_kv(k, v, self._kv_layout, self._kv_indptr_buf, self._batch_size)
+        nnz_kv = dense_kv_dims(k, self._kv_layout)[0]
+        if kv.num_kv_heads != self._num_kv_heads or kv.head_dim != self._head_dim or nnz_kv < self._total_kv_rows:
             raise ValueError("k/v shape does not match the plan")
         if q.dim() != 3 or q.shape[0] != self._total_num_rows or q.shape[1] != self._num_qo_heads:
             raise ValueError("q shape does not match the plan")
-        kv = _lib.PagedKV(
-            k_data=k.data_ptr(), v_data=v.data_ptr(), indptr=self._kv_indptr_buf.data_ptr(), indices=None,
-            last_page_len=None, rope_pos_offset=None, stride_page=stride_n, stride_n=stride_n, stride_h=stride_h,
-            page_size=1, num_kv_heads=num_kv_heads, head_dim=head_dim, batch_size=self._batch_size,
-            dtype=_lib.fi_dtype(k.dtype),
-        )
         return _run_batch_prefill(self, "BatchPrefillWithRaggedKVCacheWrapper.run", q, kv, q.dtype, out, lse,
                                   return_lse, self._window_left, q_scale, k_scale, v_scale)
 
     def _run_qkvo(self, q, k, v, q_scale, k_scale, v_scale, out, lse, return_lse):
         """run() of a head_dim_qk 192 / head_dim_vo 128 plan: k and v by their own strides, no copy."""
         _check_qkvo_kv(k, v)
-        nhd = self._kv_layout == "NHD"
-        nnz_k, hk, dk = (k.shape if nhd else (k.shape[1], k.shape[0], k.shape[2]))
-        nnz_v, hv, dv = (v.shape if nhd else (v.shape[1], v.shape[0], v.shape[2]))
+        (nnz_k, hk, _, _), dk = dense_kv_dims(k, self._kv_layout), k.shape[2]
+        (nnz_v, hv, _, _), dv = dense_kv_dims(v, self._kv_layout), v.shape[2]
         if (hk, dk) != (self._num_kv_heads, self._head_dim) or (hv, dv) != (self._num_kv_heads, self._head_dim_vo):
             raise ValueError(f"k must be [.., {self._num_kv_heads}, {self._head_dim}] and v [.., {self._num_kv_heads}, "
                              f"{self._head_dim_vo}] as planned, got {tuple(k.shape)} / {tuple(v.shape)}")
@@ -957,18 +784,16 @@ class BatchPrefillWithRaggedKVCacheWrapper:
                               self._window_left, sm_scale, self._bf16_pv_mode,
                               qo_indptr=self._qo_indptr_buf.data_ptr(), kv_indptr=self._kv_indptr_buf.data_ptr(),
                               batch_size=self._batch_size)
-        fws = self._float_workspace_buffer
         with torch.cuda.device(q.device):
             _lib.check(
                 _lib.lib().fi_batch_prefill_qkvo_run(
-                    fws.data_ptr(), fws.numel() * fws.element_size(), self._int_workspace_buffer.data_ptr(),
-                    self._int_workspace_buffer.numel(), self._plan_info_c, _lib.FI_PREFILL_PLAN_INFO_LEN,
-                    C.byref(params), _lib.current_stream(q.device),
+                    *self._workspace_args, self._plan_info, _lib.FI_PREFILL_PLAN_INFO_LEN, C.byref(params),
+                    _lib.current_stream(q.device),
                 ),
                 "BatchPrefillWithRaggedKVCacheWrapper.run",
             )
         if v_scale is not None:
-            out *= v_scale
+            out = _apply_v_scale(out, v_scale)
         return (out, lse) if return_lse else out
 
     run_return_lse = functools.partialmethod(run, return_lse=True)

@@ -12,6 +12,8 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
 
+from . import _lib
+
 
 class PosEncodingMode(Enum):
     NONE = 0
@@ -56,6 +58,12 @@ def canonicalize_torch_dtype(dtype: Union[torch.dtype, str]) -> torch.dtype:
     raise TypeError("dtype must be a string or torch.dtype, got {}".format(type(dtype)))
 
 
+def canonicalize_qkv_dtypes(q_data_type, kv_data_type) -> Tuple[torch.dtype, torch.dtype]:
+    """The q and kv dtypes of a plan(); ``kv_data_type`` None means the q dtype."""
+    q_data_type = canonicalize_torch_dtype(q_data_type)
+    return q_data_type, q_data_type if kv_data_type is None else canonicalize_torch_dtype(kv_data_type)
+
+
 def get_indptr(x: torch.Tensor) -> torch.Tensor:
     x = x.to(torch.int64)
     out = torch.zeros(x.shape[0] + 1, dtype=x.dtype, device=x.device)
@@ -93,9 +101,19 @@ def _unpack_paged_kv_cache(
     )
 
 
-def paged_kv_strides(k_cache: torch.Tensor, v_cache: torch.Tensor, kv_layout: str):
-    """(page_size, num_kv_heads, head_dim, stride_page, stride_n, stride_h) of a 4-D cache view.
-    K and V must share strides (ref: csrc/batch_decode.cu:118-129)."""
+def dense_kv_dims(k: torch.Tensor, kv_layout: str) -> Tuple[int, int, int, int]:
+    """(rows, heads, stride_n, stride_h) of a dense 3-D k or v: ``[rows, heads, dim]`` (NHD) or
+    ``[heads, rows, dim]`` (HND)."""
+    if kv_layout == "NHD":
+        return k.shape[0], k.shape[1], k.stride(0), k.stride(1)
+    return k.shape[1], k.shape[0], k.stride(1), k.stride(0)
+
+
+def paged_kv(k_cache: torch.Tensor, v_cache: torch.Tensor, kv_layout: str, indptr: torch.Tensor,
+             indices: Optional[torch.Tensor], last_page_len: Optional[torch.Tensor], batch_size: int):
+    """(fi_paged_kv, page_size, num_kv_heads, head_dim) of 4-D cache views and their page table; the three shape
+    facts are what callers check against their plan.  K and V must share shape and strides
+    (ref: csrc/batch_decode.cu:118-129)."""
     if k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride():
         raise ValueError("k_cache and v_cache must have the same shape and strides")
     if k_cache.stride(-1) != 1:
@@ -106,7 +124,26 @@ def paged_kv_strides(k_cache: torch.Tensor, v_cache: torch.Tensor, kv_layout: st
     else:
         _, num_kv_heads, page_size, head_dim = k_cache.shape
         stride_h, stride_n = k_cache.stride(1), k_cache.stride(2)
-    return page_size, num_kv_heads, head_dim, k_cache.stride(0), stride_n, stride_h
+    kv = _lib.PagedKV(
+        k_data=k_cache.data_ptr(), v_data=v_cache.data_ptr(), indptr=indptr.data_ptr(),
+        indices=None if indices is None else indices.data_ptr(),
+        last_page_len=None if last_page_len is None else last_page_len.data_ptr(), rope_pos_offset=None,
+        stride_page=k_cache.stride(0), stride_n=stride_n, stride_h=stride_h, page_size=page_size,
+        num_kv_heads=num_kv_heads, head_dim=head_dim, batch_size=batch_size, dtype=_lib.fi_dtype(k_cache.dtype),
+    )
+    return kv, page_size, num_kv_heads, head_dim
+
+
+def ragged_kv(k: torch.Tensor, v: torch.Tensor, kv_layout: str, kv_indptr: torch.Tensor,
+              batch_size: int) -> _lib.PagedKV:
+    """fi_paged_kv of ragged 3-D k / v (which share strides): an identity table of one-token pages
+    (see include/fi_mi355.h)."""
+    _, num_kv_heads, stride_n, stride_h = dense_kv_dims(k, kv_layout)
+    return _lib.PagedKV(
+        k_data=k.data_ptr(), v_data=v.data_ptr(), indptr=kv_indptr.data_ptr(), indices=None, last_page_len=None,
+        rope_pos_offset=None, stride_page=stride_n, stride_n=stride_n, stride_h=stride_h, page_size=1,
+        num_kv_heads=num_kv_heads, head_dim=k.shape[2], batch_size=batch_size, dtype=_lib.fi_dtype(k.dtype),
+    )
 
 
 def get_alibi_slopes(n_heads: int) -> torch.Tensor:
@@ -179,6 +216,14 @@ def _resolve_logits_params(
         rope_rcp_scale=1.0 / (1.0 if rope_scale is None else rope_scale),
         rope_rcp_theta=1.0 / (1e4 if rope_theta is None else rope_theta),
     )
+
+
+def _apply_v_scale(out: torch.Tensor, v_scale: float) -> torch.Tensor:
+    """``out`` times the fp8 calibration scale of V: in place, or through float32 for an fp8 ``out``."""
+    if is_float8(out):
+        return (out.to(torch.float32) * v_scale).to(out.dtype)
+    out *= v_scale
+    return out
 
 
 def _check_cached_qkv_data_type(
