@@ -62,6 +62,17 @@ struct OffsetAllocator {
   }
 };
 
+// The planners' chunk search: the smallest value in [lo, hi] for which too_many(value) is false (hi if it never is,
+// lo if the range is empty).  too_many must not turn true again as the value grows.
+template <class Pred>
+inline int64_t smallest_fitting(int64_t lo, int64_t hi, Pred too_many) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) / 2;
+    if (too_many(mid)) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 // Division by a runtime-constant 32-bit divisor using a precomputed multiplier (round-up method,
 // Granlund & Montgomery 1994): q = (umulhi(n, m) + n) >> l, valid for n < 2^31.
 struct FastDiv {

@@ -159,24 +159,43 @@ static int launch_decode(const DecodeKernelParams& kp, const DecodeChoice& c, in
   return 0;
 }
 
-// ref: PartitionPagedKVCacheBinarySearchMinNumPagePerBatch, scheduler.cuh:73-99
-static void partition_pages(uint32_t max_grid, uint32_t gdy, const std::vector<int32_t>& num_pages,
-                            uint32_t min_pages, uint32_t* pages_per_chunk, uint32_t* new_batch) {
-  uint32_t low = min_pages, high = 0;
-  for (int32_t e : num_pages) high = std::max<uint32_t>(high, (uint32_t)e);
-  while (low < high) {
-    uint32_t mid = (low + high) / 2;
+// pages a request's chunks are cut from: all of them, or with a sliding window the ones from the page
+// holding the earliest key the last token can see (kv_len >= (pages - 1) * page_size + 1)
+static int32_t window_pages(const int32_t* indptr_h, int i, int page_size, int window_left) {
+  const int32_t np = indptr_h[i + 1] - indptr_h[i];
+  if (window_left < 0 || np <= 0) return np;
+  const int64_t first = std::max<int64_t>((int64_t)(np - 1) * page_size - window_left, 0) / page_size;
+  return (int32_t)(np - first);
+}
+
+struct DecodeWork {
+  bool split_kv;
+  uint32_t pages_per_chunk;
+  size_t padded;  // work list entries: the (request, chunk) pairs, for a graph plan padded to a fixed count
+};
+
+// work estimation (ref: scheduler.cuh:183-207) for a launch of at most max_grid waves, gdy per list entry
+static DecodeWork estimate_decode_work(const int32_t* indptr_h, int batch_size, int page_size, int window_left,
+                                       uint32_t gdy, uint32_t max_grid, bool enable_cuda_graph) {
+  std::vector<int32_t> num_pages(batch_size);
+  uint32_t max_pages = 0;
+  for (int i = 0; i < batch_size; ++i)
+    max_pages = std::max<uint32_t>(max_pages, num_pages[i] = window_pages(indptr_h, i, page_size, window_left));
+  // whole requests already fill the grid
+  if ((uint64_t)batch_size * gdy >= max_grid) return {false, std::max(max_pages, 1u), (size_t)batch_size};
+  // ref: PartitionPagedKVCacheBinarySearchMinNumPagePerBatch, scheduler.cuh:73-99
+  // chunks no shorter than one tile pair: >= 128 tokens (ref uses 128/page_size too)
+  const uint32_t min_pages = std::max<uint32_t>(128u / (uint32_t)page_size, 1u);
+  const uint32_t pages_per_chunk = (uint32_t)smallest_fitting(min_pages, max_pages, [&](int64_t pages) {
     uint64_t nb = 0;
-    for (int32_t e : num_pages) nb += ceil_div<uint32_t>((uint32_t)e, mid);
-    if (nb * gdy > max_grid)
-      low = mid + 1;
-    else
-      high = mid;
-  }
-  uint32_t nb = 0;
-  for (int32_t e : num_pages) nb += ceil_div<uint32_t>((uint32_t)std::max(e, 1), low);
-  *pages_per_chunk = low;
-  *new_batch = nb;
+    for (int32_t e : num_pages) nb += ceil_div<uint32_t>((uint32_t)e, (uint32_t)pages);
+    return nb * gdy > max_grid;
+  });
+  uint32_t new_batch = 0;
+  for (int32_t e : num_pages) new_batch += ceil_div<uint32_t>((uint32_t)std::max(e, 1), pages_per_chunk);
+  // a graph plan always takes the split path, its list padded to the grid
+  if (enable_cuda_graph) return {true, pages_per_chunk, std::max<size_t>(max_grid / gdy, new_batch)};
+  return {new_batch != (uint32_t)batch_size, pages_per_chunk, new_batch};
 }
 
 }  // namespace fi
@@ -216,34 +235,9 @@ extern "C" FI_API int fi_batch_decode_plan(void* float_ws, size_t float_ws_bytes
       max_grid_hint > 0 ? (uint32_t)max_grid_hint
                         : (uint32_t)(fi_num_compute_units() * decode_waves_per_cu(kv_dtype, true) * (head_tiles > 1 ? 2 : 1));
 
-  // pages a request's chunks are cut from: all of them, or with a sliding window the ones from the page
-  // holding the earliest key the last token can see (kv_len >= (pages - 1) * page_size + 1)
   if (window_left < 0) window_left = -1;
-  auto eff_pages = [&](int i) -> int32_t {
-    const int32_t np = indptr_h[i + 1] - indptr_h[i];
-    if (window_left < 0 || np <= 0) return np;
-    const int64_t first = std::max<int64_t>((int64_t)(np - 1) * page_size - window_left, 0) / page_size;
-    return (int32_t)(np - first);
-  };
-  // ---- work estimation (ref: scheduler.cuh:183-207) ----
-  bool split_kv;
-  uint32_t pages_per_chunk, new_batch;
-  if ((uint64_t)batch_size * gdy >= max_grid) {
-    split_kv = false;
-    pages_per_chunk = 1;
-    for (int i = 0; i < batch_size; ++i) pages_per_chunk = std::max<uint32_t>(pages_per_chunk, eff_pages(i));
-    new_batch = batch_size;
-  } else {
-    std::vector<int32_t> num_pages(batch_size);
-    for (int i = 0; i < batch_size; ++i) num_pages[i] = eff_pages(i);
-    // chunks no shorter than one tile pair: >= 128 tokens (ref uses 128/page_size too)
-    const uint32_t min_pages = std::max<uint32_t>(128u / (uint32_t)page_size, 1u);
-    partition_pages(max_grid, gdy, num_pages, min_pages, &pages_per_chunk, &new_batch);
-    split_kv = !(new_batch == (uint32_t)batch_size && !enable_cuda_graph);
-  }
-  const size_t padded = enable_cuda_graph ? (split_kv ? std::max<size_t>(max_grid / gdy, new_batch)
-                                                      : (size_t)batch_size)
-                                          : (size_t)new_batch;
+  const auto [split_kv, pages_per_chunk, padded] =
+      estimate_decode_work(indptr_h, batch_size, page_size, window_left, gdy, max_grid, enable_cuda_graph);
 
   // ---- work list (ref: DecodeSplitKVIndptr, scheduler.cuh:348-364) ----
   OffsetAllocator ia(int_ws_bytes);
@@ -264,7 +258,7 @@ extern "C" FI_API int fi_batch_decode_plan(void* float_ws, size_t float_ws_bytes
   size_t w = 0;
   oind_h[0] = 0;
   for (int b = 0; b < batch_size; ++b) {
-    const uint32_t np = (uint32_t)std::max(eff_pages(b), 1);
+    const uint32_t np = (uint32_t)std::max(window_pages(indptr_h, b, page_size, window_left), 1);
     const uint32_t nchunks = split_kv ? ceil_div(np, pages_per_chunk) : 1u;
     for (uint32_t t = 0; t < nchunks; ++t) {
       FI_REQUIRE(w < padded, "batch_decode_plan: work list overflow");

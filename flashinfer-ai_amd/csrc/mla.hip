@@ -339,12 +339,9 @@ extern "C" FI_API int fi_batch_mla_plan(const fi_batch_mla_plan_params_t* a, int
   if (a->fixed_split_size > 0) {
     chunk = std::min(whole, ceil_div<int64_t>(a->fixed_split_size, kMlaTileKV) * kMlaTileKV);
   } else if (total_tiles > 0 && total_tiles < max_items) {
-    int64_t lo = kMlaMinChunk / kMlaTileKV, hi = whole / kMlaTileKV;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) / 2;
-      if (items_at(mid * kMlaTileKV) > max_items) lo = mid + 1; else hi = mid;
-    }
-    chunk = std::min(whole, std::max<int64_t>(lo, kMlaMinChunk / kMlaTileKV) * kMlaTileKV);
+    chunk = kMlaTileKV * smallest_fitting(kMlaMinChunk / kMlaTileKV, whole / kMlaTileKV,
+                                          [&](int64_t n) { return items_at(n * kMlaTileKV) > max_items; });
+    chunk = std::min(whole, chunk);
   }
   const int64_t max_entries = mla_max_entries(a->float_ws_bytes);
   while (chunk < whole && entries_at(chunk) > max_entries) chunk *= 2;

@@ -55,32 +55,71 @@ static int compute_type(int q_dt, int o_dt) {
   return o_dt;  // fp8 q: f16 or bf16 output decides
 }
 
-}  // namespace fi
+// A measured batch: per request the q tiles, the kv span its chunks are cut from and the query rows; the totals.
+struct BatchShape {
+  int n;
+  const int64_t *q_tiles, *kv_len, *qo_rows;
+  int64_t total_q_tiles, max_kv_len;
+};
 
-using namespace fi;
+// keys a request's chunks are cut from.  Sliding window: a q tile only walks the keys from its first row's window
+// start on (the kernel skips the rest), so chunks are cut from that span (ref: effective_kv_len_arr,
+// scheduler.cuh:561-567)
+static int64_t kv_span(int64_t kv_len, int64_t qo_len, bool causal, int window_left) {
+  const int64_t span = std::max<int64_t>(kv_len, 1);
+  return window_left < 0 ? span : std::min<int64_t>(span, (int64_t)window_left + (causal ? kTileQ : qo_len) + kTileKV);
+}
 
-// Chunk choice by price (see fi_batch_prefill_plan): the reference chunk, its doublings and "whole" (returned as the
-// kv span rounded up to a kv tile); rounds of workgroups per CU x tokens per item x 20 ns per 256 of head_dim_qk +
-// head_dim_vo, for a split + 6 us + partial-state bytes at 3 TB/s; ties go to the coarser.
-static int64_t price_kv_chunk(int64_t ref_chunk, int64_t max_kv_len, int n, const int64_t* q_tiles, const int64_t* kv_len,
-                              const int64_t* qo_rows, int num_kv_heads, int num_qo_heads, int head_dim_qk,
-                              int head_dim_vo) {
+// resident workgroups (2 per CU) over the kv heads each item is launched for
+// (ref: max_batch_size_if_split = max_grid_size / num_kv_heads, scheduler.cuh:718)
+static int64_t resident_items(int num_kv_heads) {
+  return std::max<int64_t>((int64_t)fi_num_compute_units() * 2 / num_kv_heads, 1);
+}
+
+// q tiles and kv spans (ref: PrefillSplitQOKVIndptr, scheduler.cuh:495-614, with packed_qo_len = qo_len * G and a
+// fixed 128-row q tile).  `store` holds the three per-request arrays `s` points into.
+static int measure_batch(const int32_t* qo_indptr_h, const int32_t* kv_len_arr_h, int batch_size, int group,
+                         bool causal, int window_left, std::vector<int64_t>& store, BatchShape& s) {
+  store.resize((size_t)batch_size * 3);
+  int64_t *q_tiles = store.data(), *kv_len = q_tiles + batch_size, *qo_rows = kv_len + batch_size;
+  s = BatchShape{batch_size, q_tiles, kv_len, qo_rows, 0, 1};
+  for (int b = 0; b < batch_size; ++b) {
+    qo_rows[b] = qo_indptr_h[b + 1] - qo_indptr_h[b];
+    FI_REQUIRE(qo_rows[b] >= 0, "batch_prefill_plan: qo_indptr must be non-decreasing");
+    FI_REQUIRE(kv_len_arr_h[b] >= 0, "batch_prefill_plan: negative kv length");
+    q_tiles[b] = ceil_div<int64_t>(qo_rows[b] * group, kTileQ);
+    kv_len[b] = kv_span(kv_len_arr_h[b], qo_rows[b], causal, window_left);
+    s.total_q_tiles += q_tiles[b];
+    s.max_kv_len = std::max(s.max_kv_len, kv_len[b]);
+  }
+  return 0;
+}
+
+// Chunk choice by price.  The reference rule cuts as fine as max_items allows.  On this part that over-splits whenever
+// the batch has rows to merge: every chunk writes, and the merge reads back, an f32 partial row per query row and head
+// (bs 1, qo = kv = 1024: 82 us split in two against 31 us whole; bs 2, 512 x 4096: 132 against 95), while few-row
+// requests gain a lot (bs 1, 16 x 8192: 28 against 159 us).  So the candidates chunk, 2 x chunk, 4 x chunk ... and
+// "whole" (returned as the kv span rounded up to a kv tile) are priced with a two-term model -- workgroup rounds per CU
+// x tokens per item x 20 ns (per 256 of head_dim_qk + head_dim_vo), plus for a split 6 us + partial-state bytes at
+// 3 TB/s -- and the cheapest wins (ties: the coarser).
+static int64_t price_kv_chunk(int64_t ref_chunk, const BatchShape& s, int num_kv_heads, int num_qo_heads,
+                              int head_dim_qk, int head_dim_vo) {
   const int64_t cus = fi_num_compute_units();
   const int64_t tok_ns = std::max<int64_t>(20 * (head_dim_qk + head_dim_vo) / 256, 1);
   auto cost_ns = [&](int64_t chunk, bool split) {
     int64_t items = 0, entries = 0;
-    for (int b = 0; b < n; ++b) {
-      const int64_t nc = split ? ceil_div<int64_t>(kv_len[b], chunk) : 1;
-      items += q_tiles[b] * nc;
-      entries += qo_rows[b] * nc;
+    for (int b = 0; b < s.n; ++b) {
+      const int64_t nc = split ? ceil_div<int64_t>(s.kv_len[b], chunk) : 1;
+      items += s.q_tiles[b] * nc;
+      entries += s.qo_rows[b] * nc;
     }
-    int64_t t = ceil_div<int64_t>(items * num_kv_heads, cus) * std::min(chunk, max_kv_len) * tok_ns;
+    int64_t t = ceil_div<int64_t>(items * num_kv_heads, cus) * std::min(chunk, s.max_kv_len) * tok_ns;
     if (split) t += 6000 + entries * num_qo_heads * head_dim_vo * 8 / 3000;
     return t;
   };
-  const int64_t whole = ceil_div<int64_t>(max_kv_len, kTileKV) * kTileKV;
+  const int64_t whole = ceil_div<int64_t>(s.max_kv_len, kTileKV) * kTileKV;
   int64_t best = whole, best_cost = cost_ns(whole, false);
-  for (int64_t c = ref_chunk; c < max_kv_len; c *= 2) {
+  for (int64_t c = ref_chunk; c < s.max_kv_len; c *= 2) {
     const int64_t t = cost_ns(c, true);
     if (t < best_cost || (t == best_cost && c > best && best != whole)) {
       best = c;
@@ -89,6 +128,115 @@ static int64_t price_kv_chunk(int64_t ref_chunk, int64_t max_kv_len, int n, cons
   }
   return best;
 }
+
+struct KvChunk { int64_t size; bool split_kv; };  // split_kv: the launch writes partial states and merges them
+
+// The kv chunk of a batch, or of one request (split_single_kv).  graph_items: the items a graph plan's launch is padded
+// to, 0 for a plan that is not captured.
+static KvChunk choose_kv_chunk(const BatchShape& s, int num_qo_heads, int num_kv_heads, int head_dim_qk,
+                               int head_dim_vo, size_t float_ws_bytes, int64_t graph_items, int fixed_split_size,
+                               bool disable_split_kv) {
+  // chunk sizes are multiples of one 64-row kv tile and at least 128 tokens (ref: min_kv_chunk_size)
+  const int64_t chunk_unit = kTileKV;
+  int64_t kv_chunk = ceil_div<int64_t>(s.max_kv_len, chunk_unit) * chunk_unit;  // one chunk = no split
+  if (disable_split_kv || s.n <= 0) return {kv_chunk, false};
+  const int64_t max_items = resident_items(num_kv_heads);
+  auto items_at = [&](int64_t chunk) {
+    int64_t n = 0;
+    for (int b = 0; b < s.n; ++b) n += s.q_tiles[b] * ceil_div<int64_t>(s.kv_len[b], chunk);
+    return n;
+  };
+  if (fixed_split_size > 0) {
+    kv_chunk = ceil_div<int64_t>(fixed_split_size, chunk_unit) * chunk_unit;
+  } else {
+    // ref: PrefillBinarySearchKVChunkSize, scheduler.cuh:101-130 (in units of 64 tokens)
+    kv_chunk = chunk_unit * smallest_fitting(128 / chunk_unit, ceil_div<int64_t>(s.max_kv_len, chunk_unit),
+                                             [&](int64_t n) { return items_at(n * chunk_unit) > max_items; });
+    // Graph plans keep the reference rule (they always split).
+    if (!graph_items) kv_chunk = price_kv_chunk(kv_chunk, s, num_kv_heads, num_qo_heads, head_dim_qk, head_dim_vo);
+  }
+  // Load balance (not in the reference, whose rule above only ever splits a batch of fewer than max_items items): a
+  // mixed batch -- many short requests and a few long ones with few query rows -- otherwise ends in a tail of
+  // single workgroups walking the long requests (reference benchmark bench_batch_attention.py, 122 x (600, 1) + 8 x
+  // (10000, 17): 0.23 ms for 0.3 GB).  With W = sum of q tiles x kv length, the ideal makespan is W / max_items;
+  // chunks of at most half of that (and >= 256 tokens) let the longest-first work list even out.  A batch whose long
+  // requests also have many query rows has a large W and keeps its single chunk; graph plans keep the reference
+  // rule (their item count must stay under the captured bound).
+  // Only where the reference rule left every request whole AND the batch is uneven (longest request >= twice the
+  // mean item): an even batch gains nothing from more items (decode-only 128 x 8192 through this wrapper: -6 %), and
+  // a batch the reference rule already cut is compute-bound prefill (4 x (4096, 128): -12 % when cut finer).
+  if (fixed_split_size <= 0 && !graph_items && kv_chunk >= s.max_kv_len && s.total_q_tiles > 0) {
+    int64_t work = 0;
+    for (int b = 0; b < s.n; ++b) work += s.q_tiles[b] * s.kv_len[b];
+    const int64_t bal = ceil_div<int64_t>(std::max<int64_t>(work / (2 * max_items), 256), chunk_unit) * chunk_unit;
+    if (s.max_kv_len * s.total_q_tiles >= 2 * work && 2 * bal <= s.max_kv_len && items_at(bal) <= 8 * max_items)
+      kv_chunk = bal;
+  }
+  // the partial states must fit the caller's float workspace: grow the chunks until they do (a plan
+  // that cannot split at all is still correct, only less parallel)
+  if (fixed_split_size <= 0) {
+    auto ws_need = [&](int64_t chunk) {
+      int64_t entries = 0;
+      for (int b = 0; b < s.n; ++b) entries += s.qo_rows[b] * ceil_div<int64_t>(s.kv_len[b], chunk);
+      int64_t lse_entries = entries;
+      if (graph_items)  // the fixed lse region of a graph plan (see fi_batch_prefill_plan)
+        lse_entries = std::max(entries, std::max(items_at(chunk), graph_items) *
+                                            (ceil_div<int64_t>(kTileQ, num_qo_heads / num_kv_heads) + 1));
+      return (entries * num_qo_heads * head_dim_vo + lse_entries * num_qo_heads + 64) * (int64_t)sizeof(float);
+    };
+    while (kv_chunk < s.max_kv_len && ws_need(kv_chunk) > (int64_t)float_ws_bytes) kv_chunk *= 2;
+  }
+  // a fixed-shape (graph) launch always takes the split path so that the kernel sequence does not
+  // depend on the page table (ref: scheduler.cuh:129)
+  return {kv_chunk, kv_chunk < s.max_kv_len || graph_items};
+}
+
+struct WorkItem { int32_t req, tile, kvt; };  // request, q tile, kv chunk
+
+// work list, costliest first (requests by rows per q tile x kv_len descending; for causal masks the later = heavier q
+// tiles first) so the tail of the launch is made of the cheapest items (ref LPT idea: scheduler.cuh:900-946)
+static std::vector<WorkItem> build_work_list(const BatchShape& s, const int32_t* kv_len_arr_h, int group, bool causal,
+                                             int64_t kv_chunk, bool split_kv) {
+  std::vector<int> order(s.n);
+  std::iota(order.begin(), order.end(), 0);
+  // (cost of a request's items ~ rows of a q tile x kv length: in a mixed batch the compute-bound full tiles of a
+  // prefill request go out before the memory-bound one-row items of equally long decode requests and run beside
+  // them, instead of forming the tail -- bench_batch_attention.py's 254 x (8192, 1) + (8192, 4096))
+  auto item_cost = [&](int b) {
+    const int64_t rows = std::min<int64_t>(s.qo_rows[b] * group, kTileQ);
+    return (int64_t)kv_len_arr_h[b] * std::max<int64_t>(rows, 1);
+  };
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return item_cost(a) > item_cost(b); });
+  std::vector<WorkItem> w;
+  for (int b : order) {
+    const int64_t ntiles = s.q_tiles[b];
+    const int64_t nchunks = split_kv ? ceil_div<int64_t>(s.kv_len[b], kv_chunk) : 1;
+    for (int64_t t = 0; t < ntiles; ++t)
+      for (int64_t c = 0; c < nchunks; ++c) w.push_back({b, (int32_t)(causal ? ntiles - 1 - t : t), (int32_t)c});
+  }
+  // Mixed batches: a q tile with many rows is compute-bound, one with a few rows (decode-like) streams its keys at
+  // HBM rate.  Listed one kind after the other they run as two phases; interleaved in proportion (each kind keeps its
+  // costliest-first order) the two kinds share the CUs and overlap.  Pure batches (one kind only) are unchanged.
+  std::vector<size_t> wide, narrow;
+  for (size_t i = 0; i < w.size(); ++i) {
+    const int64_t rows_left = s.qo_rows[w[i].req] * group - (int64_t)w[i].tile * kTileQ;
+    (std::min<int64_t>(rows_left, kTileQ) * 2 >= kTileQ ? wide : narrow).push_back(i);
+  }
+  if (wide.empty() || narrow.empty()) return w;
+  std::vector<WorkItem> mixed;
+  const size_t n = w.size();
+  size_t iw = 0, in = 0;
+  for (size_t k = 0; k < n; ++k) {
+    // wide items are due when their share of the first k + 1 slots falls behind
+    const bool take_wide = in >= narrow.size() || (iw < wide.size() && iw * n <= k * wide.size());
+    mixed.push_back(w[take_wide ? wide[iw++] : narrow[in++]]);
+  }
+  return mixed;
+}
+
+}  // namespace fi
+
+using namespace fi;
 
 extern "C" FI_API int fi_batch_prefill_plan(
     void* float_ws, size_t float_ws_bytes, void* int_ws, void* pinned_int_ws, size_t int_ws_bytes,
@@ -114,153 +262,19 @@ extern "C" FI_API int fi_batch_prefill_plan(
   FI_REQUIRE(qo_indptr_h[0] == 0, "batch_prefill_plan: qo_indptr[0] must be 0");
   const int group = num_qo_heads / num_kv_heads;
 
-  // ---- q tiles and kv chunks (ref: PrefillSplitQOKVIndptr, scheduler.cuh:495-614, with
-  // packed_qo_len = qo_len * G and a fixed 128-row q tile) ----
-  std::vector<int64_t> q_tiles(batch_size), kv_len(batch_size);
-  int64_t total_q_tiles = 0, max_kv_len = 1;
-  for (int b = 0; b < batch_size; ++b) {
-    const int64_t qo_len = qo_indptr_h[b + 1] - qo_indptr_h[b];
-    FI_REQUIRE(qo_len >= 0, "batch_prefill_plan: qo_indptr must be non-decreasing");
-    FI_REQUIRE(kv_len_arr_h[b] >= 0, "batch_prefill_plan: negative kv length");
-    q_tiles[b] = ceil_div<int64_t>(qo_len * group, kTileQ);
-    kv_len[b] = std::max<int64_t>(kv_len_arr_h[b], 1);
-    // sliding window: a q tile only walks the keys from its first row's window start on (the kernel
-    // skips the rest), so chunks are cut from that span (ref: effective_kv_len_arr, scheduler.cuh:561-567)
-    if (window_left >= 0)
-      kv_len[b] = std::min<int64_t>(kv_len[b], (int64_t)window_left + (causal ? kTileQ : qo_len) + kTileKV);
-    total_q_tiles += q_tiles[b];
-    max_kv_len = std::max(max_kv_len, kv_len[b]);
-  }
-  // resident workgroups (2 per CU) over the kv heads each item is launched for
-  // (ref: max_batch_size_if_split = max_grid_size / num_kv_heads, scheduler.cuh:718)
-  const int64_t max_items = std::max<int64_t>((int64_t)fi_num_compute_units() * 2 / num_kv_heads, 1);
+  std::vector<int64_t> store;
+  BatchShape shape;
+  if (measure_batch(qo_indptr_h, kv_len_arr_h, batch_size, group, causal, window_left, store, shape)) return 1;
+  // a graph launch is padded to the resident items, or the most items total_num_rows rows can make without a split
   const int64_t graph_bound =
       ceil_div<int64_t>((int64_t)total_num_rows * group, kTileQ) + std::max(batch_size, 1) - 1;
-  // chunk sizes are multiples of one 64-row kv tile and at least 128 tokens (ref: min_kv_chunk_size)
-  auto items_at = [&](int64_t chunk) {
-    int64_t n = 0;
-    for (int b = 0; b < batch_size; ++b) n += q_tiles[b] * ceil_div<int64_t>(kv_len[b], chunk);
-    return n;
-  };
-  const int64_t chunk_unit = kTileKV;
-  int64_t kv_chunk = ceil_div<int64_t>(max_kv_len, chunk_unit) * chunk_unit;  // one chunk = no split
-  bool split_kv = false;
-  if (!disable_split_kv && batch_size > 0) {
-    if (fixed_split_size > 0) {
-      kv_chunk = ceil_div<int64_t>(fixed_split_size, chunk_unit) * chunk_unit;
-    } else {
-      // ref: PrefillBinarySearchKVChunkSize, scheduler.cuh:101-130 (in units of 64 tokens)
-      int64_t low = 128 / chunk_unit, high = ceil_div<int64_t>(max_kv_len, chunk_unit);
-      while (low < high) {
-        const int64_t mid = (low + high) / 2;
-        if (items_at(mid * chunk_unit) > max_items) low = mid + 1; else high = mid;
-      }
-      kv_chunk = std::max<int64_t>(low, 128 / chunk_unit) * chunk_unit;
-      // The reference rule cuts as fine as max_items allows.  On this part that over-splits whenever the batch has
-      // rows to merge: every chunk writes, and the merge reads back, an f32 partial row per query row and head (bs 1,
-      // qo = kv = 1024: 82 us split in two against 31 us whole; bs 2, 512 x 4096: 132 against 95), while few-row
-      // requests gain a lot (bs 1, 16 x 8192: 28 against 159 us).  So the candidates chunk, 2 x chunk, 4 x chunk ...
-      // and "whole" are priced with a two-term model -- workgroup rounds per CU x tokens per item x 20 ns (per 256 of
-      // head_dim_qk + head_dim_vo), plus for a split 6 us + partial-state bytes at 3 TB/s -- and the cheapest wins
-      // (ties: the coarser).  Graph plans keep the reference rule (they always split).
-      if (!enable_cuda_graph) {
-        std::vector<int64_t> rows(batch_size);
-        for (int b = 0; b < batch_size; ++b) rows[b] = qo_indptr_h[b + 1] - qo_indptr_h[b];
-        kv_chunk = price_kv_chunk(kv_chunk, max_kv_len, batch_size, q_tiles.data(), kv_len.data(), rows.data(),
-                                  num_kv_heads, num_qo_heads, head_dim_qk, head_dim_vo);
-      }
-    }
-    // Load balance (not in the reference, whose rule above only ever splits a batch of fewer than max_items items): a
-    // mixed batch -- many short requests and a few long ones with few query rows -- otherwise ends in a tail of
-    // single workgroups walking the long requests (reference benchmark bench_batch_attention.py, 122 x (600, 1) + 8 x
-    // (10000, 17): 0.23 ms for 0.3 GB).  With W = sum of q tiles x kv length, the ideal makespan is W / max_items;
-    // chunks of at most half of that (and >= 256 tokens) let the longest-first work list even out.  A batch whose long
-    // requests also have many query rows has a large W and keeps its single chunk; graph plans keep the reference
-    // rule (their item count must stay under the captured bound).
-    // Only where the reference rule left every request whole AND the batch is uneven (longest request >= twice the
-    // mean item): an even batch gains nothing from more items (decode-only 128 x 8192 through this wrapper: -6 %), and
-    // a batch the reference rule already cut is compute-bound prefill (4 x (4096, 128): -12 % when cut finer).
-    if (fixed_split_size <= 0 && !enable_cuda_graph && kv_chunk >= max_kv_len && total_q_tiles > 0) {
-      int64_t work = 0;
-      for (int b = 0; b < batch_size; ++b) work += q_tiles[b] * kv_len[b];
-      const int64_t bal = ceil_div<int64_t>(std::max<int64_t>(work / (2 * max_items), 256), chunk_unit) * chunk_unit;
-      if (max_kv_len * total_q_tiles >= 2 * work && 2 * bal <= max_kv_len && items_at(bal) <= 8 * max_items)
-        kv_chunk = bal;
-    }
-    // the partial states must fit the caller's float workspace: grow the chunks until they do (a plan
-    // that cannot split at all is still correct, only less parallel)
-    if (fixed_split_size <= 0) {
-      auto ws_need = [&](int64_t chunk) {
-        int64_t entries = 0;
-        for (int b = 0; b < batch_size; ++b)
-          entries += (int64_t)(qo_indptr_h[b + 1] - qo_indptr_h[b]) * ceil_div<int64_t>(kv_len[b], chunk);
-        int64_t lse_entries = entries;
-        if (enable_cuda_graph)  // the fixed lse region of a graph plan (below)
-          lse_entries = std::max(entries, std::max(items_at(chunk), std::max(max_items, graph_bound)) *
-                                              (ceil_div<int64_t>(kTileQ, group) + 1));
-        return (entries * num_qo_heads * head_dim_vo + lse_entries * num_qo_heads + 64) * (int64_t)sizeof(float);
-      };
-      while (kv_chunk < max_kv_len && ws_need(kv_chunk) > (int64_t)float_ws_bytes) kv_chunk *= 2;
-    }
-    split_kv = kv_chunk < max_kv_len;
-    // a fixed-shape (graph) launch always takes the split path so that the kernel sequence does not
-    // depend on the page table (ref: scheduler.cuh:129)
-    if (enable_cuda_graph) split_kv = true;
-  }
+  const int64_t graph_items = enable_cuda_graph ? std::max(resident_items(num_kv_heads), graph_bound) : 0;
+  const auto [kv_chunk, split_kv] = choose_kv_chunk(shape, num_qo_heads, num_kv_heads, head_dim_qk, head_dim_vo,
+                                                    float_ws_bytes, graph_items, fixed_split_size, disable_split_kv);
   FI_REQUIRE(kv_chunk < (1ll << 31), "batch_prefill_plan: kv chunk too large");
+  const std::vector<WorkItem> work = build_work_list(shape, kv_len_arr_h, group, causal, kv_chunk, split_kv);
 
-  // work list, costliest first (requests by rows per q tile x kv_len descending; for causal masks the later = heavier q
-  // tiles first) so the tail of the launch is made of the cheapest items (ref LPT idea: scheduler.cuh:900-946)
-  std::vector<int> order(batch_size);
-  std::iota(order.begin(), order.end(), 0);
-  // (cost of a request's items ~ rows of a q tile x kv length: in a mixed batch the compute-bound full tiles of a
-  // prefill request go out before the memory-bound one-row items of equally long decode requests and run beside
-  // them, instead of forming the tail -- bench_batch_attention.py's 254 x (8192, 1) + (8192, 4096))
-  auto item_cost = [&](int b) {
-    const int64_t rows = std::min<int64_t>((int64_t)(qo_indptr_h[b + 1] - qo_indptr_h[b]) * group, kTileQ);
-    return (int64_t)kv_len_arr_h[b] * std::max<int64_t>(rows, 1);
-  };
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return item_cost(a) > item_cost(b); });
-  std::vector<int32_t> req, tile, kvt;
-  for (int b : order) {
-    const int64_t ntiles = q_tiles[b];
-    const int64_t nchunks = split_kv ? ceil_div<int64_t>(kv_len[b], kv_chunk) : 1;
-    for (int64_t t = 0; t < ntiles; ++t)
-      for (int64_t c = 0; c < nchunks; ++c) {
-        req.push_back(b);
-        tile.push_back((int32_t)(causal ? ntiles - 1 - t : t));
-        kvt.push_back((int32_t)c);
-      }
-  }
-  // Mixed batches: a q tile with many rows is compute-bound, one with a few rows (decode-like) streams its keys at
-  // HBM rate.  Listed one kind after the other they run as two phases; interleaved in proportion (each kind keeps its
-  // costliest-first order) the two kinds share the CUs and overlap.  Pure batches (one kind only) are unchanged.
-  {
-    std::vector<size_t> wide, narrow;
-    for (size_t i = 0; i < req.size(); ++i) {
-      const int b = req[i];
-      const int64_t rows_left = (int64_t)(qo_indptr_h[b + 1] - qo_indptr_h[b]) * group - (int64_t)tile[i] * kTileQ;
-      (std::min<int64_t>(rows_left, kTileQ) * 2 >= kTileQ ? wide : narrow).push_back(i);
-    }
-    if (!wide.empty() && !narrow.empty()) {
-      std::vector<int32_t> r2, t2, k2;
-      const size_t n = req.size();
-      size_t iw = 0, in = 0;
-      for (size_t k = 0; k < n; ++k) {
-        // wide items are due when their share of the first k + 1 slots falls behind
-        const bool take_wide = in >= narrow.size() || (iw < wide.size() && iw * n <= k * wide.size());
-        const size_t src = take_wide ? wide[iw++] : narrow[in++];
-        r2.push_back(req[src]);
-        t2.push_back(tile[src]);
-        k2.push_back(kvt[src]);
-      }
-      req.swap(r2);
-      tile.swap(t2);
-      kvt.swap(k2);
-    }
-  }
-  size_t padded = req.size();
-  if (enable_cuda_graph) padded = std::max<size_t>(padded, (size_t)std::max(max_items, graph_bound));
+  const size_t num_work = work.size(), padded = std::max(num_work, (size_t)graph_items);
   // partial-state ranges per qo row (ref merge_indptr, scheduler.cuh:597-600)
   const int64_t nrows_tab = split_kv ? (int64_t)std::max(total_num_rows, qo_indptr_h[batch_size]) : 0;
   OffsetAllocator ia(int_ws_bytes);
@@ -275,9 +289,9 @@ extern "C" FI_API int fi_batch_prefill_plan(
   int32_t* kvt_h = (int32_t*)((char*)pinned_int_ws + kvt_off);
   int32_t* mrg_h = (int32_t*)((char*)pinned_int_ws + mrg_off);
   for (size_t i = 0; i < padded; ++i) {
-    req_h[i] = i < req.size() ? req[i] : -1;  // -1: padding item, the workgroup exits
-    tile_h[i] = i < tile.size() ? tile[i] : 0;
-    kvt_h[i] = i < kvt.size() ? kvt[i] : 0;
+    req_h[i] = i < num_work ? work[i].req : -1;  // -1: padding item, the workgroup exits
+    tile_h[i] = i < num_work ? work[i].tile : 0;
+    kvt_h[i] = i < num_work ? work[i].kvt : 0;
   }
   *(int32_t*)((char*)pinned_int_ws + chunk_off) = (int32_t)kv_chunk;
   int64_t entries = 0;
@@ -285,7 +299,7 @@ extern "C" FI_API int fi_batch_prefill_plan(
   if (split_kv) {
     int64_t row = 0;
     for (int b = 0; b < batch_size; ++b) {
-      const int64_t nchunks = ceil_div<int64_t>(kv_len[b], kv_chunk);
+      const int64_t nchunks = ceil_div<int64_t>(shape.kv_len[b], kv_chunk);
       for (int64_t r = qo_indptr_h[b]; r < qo_indptr_h[b + 1]; ++r) {
         entries += nchunks;
         mrg_h[++row] = (int32_t)entries;
@@ -323,7 +337,7 @@ extern "C" FI_API int fi_batch_prefill_plan(
   plan_info_out[FI_PP_KV_CHUNK_SIZE] = kv_chunk;
   plan_info_out[FI_PP_V_OFFSET] = v_off;
   plan_info_out[FI_PP_S_OFFSET] = s_off;
-  plan_info_out[FI_PP_NUM_WORK] = (int64_t)req.size();
+  plan_info_out[FI_PP_NUM_WORK] = (int64_t)num_work;
   plan_info_out[FI_PP_ENABLE_CUDA_GRAPH] = enable_cuda_graph ? 1 : 0;
   plan_info_out[FI_PP_SPLIT_KV] = split_kv ? 1 : 0;
   // a (192, 128) plan carries its own tag: its partial states are sized for head_dim_vo 128, and only
@@ -436,35 +450,19 @@ static int bind_batch_plan(const char* who, const int64_t* plan_info, void* floa
 }
 
 // Splits a single request's kv axis when the q tiles alone (kp.num_work) cannot fill the chip, and the partial
-// states ([qo_len, chunks, Hq, head_dim_vo] f32 + lse) fit the caller's scratch buffer: same search as the batch
-// planner (ref: PrefillBinarySearchKVChunkSize, scheduler.cuh:101-130), then the priced chunk, doubled until the
-// partial states fit.  Leaves kp unsplit otherwise.
+// states ([qo_len, chunks, Hq, head_dim_vo] f32 + lse) fit the caller's scratch buffer: the batch planner's chunk
+// choice for a batch of this one request.  Leaves kp unsplit otherwise.
 template <class KP>
 static void split_single_kv(KP& kp, void* tmp, size_t tmp_bytes, int qo_len, int kv_len, int window_left,
                             int head_dim_qk, int head_dim_vo) {
-  const int64_t q_tiles = kp.num_work;
-  const int64_t max_items = std::max<int64_t>((int64_t)fi_num_compute_units() * 2 / kp.num_kv_heads, 1);
-  int64_t span = std::max<int64_t>(kv_len, 1);
-  if (window_left >= 0)
-    span = std::min<int64_t>(span, (int64_t)window_left + (kp.causal ? kTileQ : qo_len) + kTileKV);
-  int64_t low = 128 / kTileKV, high = ceil_div<int64_t>(span, kTileKV);
-  while (low < high) {
-    const int64_t mid = (low + high) / 2;
-    if (q_tiles * ceil_div<int64_t>(span, mid * kTileKV) > max_items) low = mid + 1; else high = mid;
-  }
-  int64_t chunk = std::max<int64_t>(low, 128 / kTileKV) * kTileKV;
-  const int64_t rows = qo_len;
-  chunk = price_kv_chunk(chunk, span, 1, &q_tiles, &span, &rows, kp.num_kv_heads, kp.num_qo_heads, head_dim_qk,
-                         head_dim_vo);
-  auto need = [&](int64_t c) {
-    return ((int64_t)qo_len * ceil_div<int64_t>(span, c) * kp.num_qo_heads * (head_dim_vo + 1) + 64) *
-           (int64_t)sizeof(float);
-  };
-  while (chunk < span && need(chunk) > (int64_t)tmp_bytes) chunk *= 2;
-  const int64_t nchunks = ceil_div<int64_t>(span, chunk);
-  if (nchunks > 1 && q_tiles * nchunks < (1ll << 30)) {
+  const int64_t q_tiles = kp.num_work, rows = qo_len, span = kv_span(kv_len, qo_len, kp.causal, window_left);
+  const KvChunk kc = choose_kv_chunk(BatchShape{1, &q_tiles, &span, &rows, q_tiles, span}, kp.num_qo_heads,
+                                     kp.num_kv_heads, head_dim_qk, head_dim_vo, tmp_bytes, /*graph_items=*/0,
+                                     /*fixed_split_size=*/0, /*disable_split_kv=*/false);
+  const int64_t nchunks = ceil_div<int64_t>(span, kc.size);
+  if (kc.split_kv && q_tiles * nchunks < (1ll << 30)) {
     kp.num_kv_chunks = (int32_t)nchunks;
-    kp.kv_chunk_size = (int32_t)chunk;
+    kp.kv_chunk_size = (int32_t)kc.size;
     kp.num_work = (int32_t)(q_tiles * nchunks);
     kp.tmp_o = (float*)tmp;
     size_t vbytes = (size_t)qo_len * nchunks * kp.num_qo_heads * head_dim_vo * sizeof(float);
