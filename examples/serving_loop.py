@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """A minimal serving loop on the MI355X FlashInfer path: chunked prefill into a paged KV cache, then
-graph-captured batch decode steps (append one token per request, attend, repeat).
+graph-captured batch decode steps (append one token per request, attend, project to logits, sample the next
+token with top-k / top-p, feed it back, repeat).
 
     PYTHONPATH=flashinfer-ai_amd python examples/serving_loop.py
 
-Everything below is the reference's public API (flashinfer.page / prefill / decode); nothing is specific to
+Everything below is the reference's public API (flashinfer.page / prefill / decode / sampling); nothing is specific to
 this build except that it runs on gfx950.  Weights are random: the point is the data flow.
 """
 import os
@@ -18,7 +19,8 @@ import torch  # noqa: E402
 import flashinfer  # noqa: E402
 
 
-def main(batch=8, prompt_len=700, new_tokens=16, hq=32, hkv=8, d=128, page_size=16, dtype=torch.bfloat16):
+def main(batch=8, prompt_len=700, new_tokens=16, hq=32, hkv=8, d=128, page_size=16, dtype=torch.bfloat16,
+         vocab=32000, top_k=50, top_p=0.9):
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     max_len = prompt_len + new_tokens
@@ -65,13 +67,18 @@ def main(batch=8, prompt_len=700, new_tokens=16, hq=32, hkv=8, d=128, page_size=
     o1 = torch.zeros_like(q1)
     graph = None
     one = (torch.arange(batch + 1, dtype=torch.int32)).to(dev)
+    # a stand-in model: a token embedding, per-head q / k / v scalings of it, and an output projection to the vocabulary
+    embed = torch.randn(vocab, d, dtype=dtype, device=dev)
+    wq, wk, wv = (torch.randn(h, d, dtype=dtype, device=dev) for h in (hq, hkv, hkv))
+    lm_head = torch.randn(hq * d, vocab, dtype=dtype, device=dev) / (hq * d) ** 0.5
+    tokens = torch.randint(vocab, (batch,), device=dev)
+    generated = []
     for step in range(new_tokens):
         lens = [prompt_len + step + 1] * batch
         indptr, indices, last = table(lens)
-        # the new token's q / k / v (a model would produce them); rotate at its position and append
-        qn = torch.randn(batch, hq, d, dtype=dtype, device=dev)
-        kn = torch.randn(batch, hkv, d, dtype=dtype, device=dev)
-        vn = torch.randn_like(kn)
+        # the last token's q / k / v; rotate at its position and append
+        x = embed[tokens].unsqueeze(1)
+        qn, kn, vn = x * wq, x * wk, x * wv
         pos1 = torch.full((batch,), prompt_len + step, dtype=torch.int32, device=dev)
         flashinfer.apply_rope_pos_ids_inplace(qn, kn, pos1)
         bi, bp = flashinfer.get_batch_indices_positions(one, flashinfer.get_seq_lens(indptr, last, page_size), batch)
@@ -85,8 +92,13 @@ def main(batch=8, prompt_len=700, new_tokens=16, hq=32, hkv=8, d=128, page_size=
             with torch.cuda.graph(graph):
                 decode.run(q1, cache, out=o1)
         graph.replay()
+        # logits -> next token.  Sampling stays outside the graph: a captured draw would replay its (seed, offset)
+        logits = o1.reshape(batch, hq * d) @ lm_head
+        tokens = flashinfer.top_k_top_p_sampling_from_logits(logits, top_k, top_p).long()
+        generated.append(tokens)
     torch.cuda.synchronize()
     print("decode :", tuple(o1.shape), "finite:", bool(torch.isfinite(o1.float()).all()), "steps:", new_tokens)
+    print("tokens :", torch.stack(generated, dim=1)[0].tolist())
     return out, o1
 
 

@@ -1,11 +1,12 @@
 """flashinfer -- MI355X (gfx950) native implementation of FlashInfer's paged-KV attention hot path.
 
-Drop-in for the ``flashinfer.decode / prefill / cascade / page / gemm`` operator API of FlashInfer
+Drop-in for the ``flashinfer.decode / prefill / cascade / page / gemm / sampling`` operator API of FlashInfer
 v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-written HIP kernels behind the C ABI of
 ``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided.
 """
 from . import _lib as _lib
 from . import mla as mla
+from . import sampling as sampling
 from .cascade import (
     BatchDecodeWithSharedPrefixPagedKVCacheWrapper as BatchDecodeWithSharedPrefixPagedKVCacheWrapper,
 )
@@ -60,6 +61,20 @@ from .rope import apply_rope_with_cos_sin_cache as apply_rope_with_cos_sin_cache
 from .rope import (
     apply_rope_with_cos_sin_cache_inplace as apply_rope_with_cos_sin_cache_inplace,
 )
+from .sampling import chain_speculative_sampling as chain_speculative_sampling
+from .sampling import min_p_sampling_from_probs as min_p_sampling_from_probs
+from .sampling import sampling_from_logits as sampling_from_logits
+from .sampling import sampling_from_probs as sampling_from_probs
+from .sampling import softmax as softmax
+from .sampling import top_k_mask_logits as top_k_mask_logits
+from .sampling import top_k_renorm_probs as top_k_renorm_probs
+from .sampling import top_k_sampling_from_probs as top_k_sampling_from_probs
+from .sampling import (
+    top_k_top_p_sampling_from_logits as top_k_top_p_sampling_from_logits,
+)
+from .sampling import top_k_top_p_sampling_from_probs as top_k_top_p_sampling_from_probs
+from .sampling import top_p_renorm_probs as top_p_renorm_probs
+from .sampling import top_p_sampling_from_probs as top_p_sampling_from_probs
 from .utils import next_positive_power_of_2 as next_positive_power_of_2
 
 __version__ = "0.3.1+mi355x.r2"

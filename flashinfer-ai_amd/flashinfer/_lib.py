@@ -253,6 +253,36 @@ class AppendMlaParams(C.Structure):
     ]
 
 
+class SamplingParams(C.Structure):
+    """fi_sampling_params_t: the draws (plain, from logits, top-k / top-p / min-p / joint)."""
+    _fields_ = [
+        ("probs", C.c_void_p), ("samples", C.c_void_p), ("indices", C.c_void_p),
+        ("top_k_arr", C.c_void_p), ("top_p_arr", C.c_void_p),
+        ("top_k_val", C.c_int32), ("top_p_val", C.c_float),
+        ("batch", C.c_int32), ("num_rows", C.c_int32), ("vocab", C.c_int32), ("param_len", C.c_int32),
+        ("philox_seed", C.c_uint64), ("philox_offset", C.c_uint64),
+    ]
+
+
+class RowTransformParams(C.Structure):
+    """fi_row_transform_params_t: softmax, top-p / top-k renormalisation, top-k logit mask."""
+    _fields_ = [
+        ("in_", C.c_void_p), ("out", C.c_void_p), ("top_k_arr", C.c_void_p), ("scalar_arr", C.c_void_p),
+        ("top_k_val", C.c_int32), ("scalar_val", C.c_float),
+        ("batch", C.c_int32), ("vocab", C.c_int32), ("param_len", C.c_int32),
+    ]
+
+
+class ChainSpeculativeParams(C.Structure):
+    _fields_ = [
+        ("draft_probs", C.c_void_p), ("draft_token_ids", C.c_void_p), ("target_probs", C.c_void_p),
+        ("output_token_ids", C.c_void_p), ("output_accepted_token_num", C.c_void_p),
+        ("output_emitted_draft_token_num", C.c_void_p),
+        ("batch", C.c_int32), ("num_speculative_tokens", C.c_int32), ("vocab", C.c_int32),
+        ("philox_seed", C.c_uint64), ("philox_offset", C.c_uint64),
+    ]
+
+
 FI_PREFILL_PLAN_INFO_LEN = 16
 FI_PREFILL_PLAN_MAGIC = 0x4649505245
 FI_PREFILL_QKVO_PLAN_MAGIC = 0x4649514B564F  # plan_info[15] of a head_dim_qk 192 / head_dim_vo 128 plan
@@ -293,7 +323,23 @@ EXPORTED_SYMBOLS = [
     "fi_batch_mla_plan",
     "fi_batch_mla_run",
     "fi_append_paged_mla_kv_cache",
+    "fi_softmax",
+    "fi_sampling_from_logits",
+    "fi_sampling_from_probs",
+    "fi_top_k_sampling_from_probs",
+    "fi_top_p_sampling_from_probs",
+    "fi_min_p_sampling_from_probs",
+    "fi_top_k_top_p_sampling_from_probs",
+    "fi_top_p_renorm_probs",
+    "fi_top_k_renorm_probs",
+    "fi_top_k_mask_logits",
+    "fi_chain_speculative_sampling",
 ]
+
+SAMPLING_SYMBOLS = ("fi_sampling_from_logits", "fi_sampling_from_probs", "fi_top_k_sampling_from_probs",
+                    "fi_top_p_sampling_from_probs", "fi_min_p_sampling_from_probs",
+                    "fi_top_k_top_p_sampling_from_probs")
+ROW_TRANSFORM_SYMBOLS = ("fi_softmax", "fi_top_p_renorm_probs", "fi_top_k_renorm_probs", "fi_top_k_mask_logits")
 
 
 def lib() -> C.CDLL:
@@ -335,6 +381,11 @@ def lib() -> C.CDLL:
     l.fi_batch_mla_plan.argtypes = [C.POINTER(MlaPlanParams), i64p, vp]
     l.fi_batch_mla_run.argtypes = [i64p, i32, C.POINTER(MlaParams), vp]
     l.fi_append_paged_mla_kv_cache.argtypes = [C.POINTER(AppendMlaParams), vp]
+    for name in SAMPLING_SYMBOLS:
+        getattr(l, name).argtypes = [C.POINTER(SamplingParams), vp]
+    for name in ROW_TRANSFORM_SYMBOLS:
+        getattr(l, name).argtypes = [C.POINTER(RowTransformParams), vp]
+    l.fi_chain_speculative_sampling.argtypes = [C.POINTER(ChainSpeculativeParams), vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(l, name)
         if name not in ("fi_last_error",):

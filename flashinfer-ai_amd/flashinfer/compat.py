@@ -21,6 +21,9 @@ from typing import List, Optional
 import torch
 
 from . import _lib
+# ref getter: flashinfer/sampling.py:60-487; exports csrc/flashinfer_sampling_binding.cu:62-82.  The functions keep the
+# positional signatures of the reference's custom ops (tensors in, tensors out; seed and offset drawn inside).
+from .sampling import get_sampling_module as get_sampling_module
 from .utils import paged_kv, ragged_kv
 
 

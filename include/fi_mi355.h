@@ -1,7 +1,7 @@
 /*
  * fi_mi355.h -- C ABI of libfi_mi355.so, the MI355X (gfx950) implementation of FlashInfer's
- * batch paged-KV attention hot path (decode / prefill / cascade merge / page append) and the fp8
- * groupwise (grouped) GEMM.
+ * batch paged-KV attention hot path (decode / prefill / cascade merge / page append), the fp8
+ * groupwise (grouped) GEMM and the sampling operators.
  *
  * Every entry point replaces one TVM-FFI export of the reference (FlashInfer v0.3.1); the export it
  * stands in for is cited as `ref: file:line` (paths relative to the reference checkout).  The
@@ -531,6 +531,77 @@ FI_API int fi_apply_rope_append_paged_kv_cache(const fi_rope_params_t* params, c
 /* pos_ids[i] = offsets[b] + i - indptr[b] for indptr[b] <= i < indptr[b+1] (ref: pos_enc.cuh:540-575) */
 FI_API int fi_rope_positions_from_indptr(const int32_t* indptr, const int32_t* offsets, int32_t batch_size,
                                   int32_t nnz, int32_t* pos_ids, fi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Sampling: logits -> probabilities -> token.  ref: csrc/flashinfer_sampling_binding.cu:20-82 (exports),
+ * csrc/sampling.cu, csrc/renorm.cu, kernels include/flashinfer/sampling.cuh, Python flashinfer/sampling.py.
+ * All rows are f32 [num_rows, vocab] contiguous; one workgroup works on one output row.  A per-row parameter
+ * is `*_arr[row]` when the array is given (device, `param_len` entries, the index is clamped to it; `row` is the
+ * row drawn from, i.e. indices[i] for output i, which is the output row itself without indices) and the scalar
+ * `*_val` otherwise.  Filters are exact thresholds found by a radix select over the float bit pattern
+ * (no sort, a fixed number of passes); a draw is an inverse-CDF draw over the kept entries with one uniform
+ * number from Philox4x32-10 keyed by (seed, offset, output row).  Defined results for degenerate input: a row
+ * without a positive finite entry gives token 0; top_k == 0 or top_k >= vocab and top_p >= 1 switch that filter
+ * off; top_p <= 0 keeps the maximum only; NaN entries are never kept.  vocab is at most 2^22; top-p expects rows that
+ * sum to about 1 (an entry counts as at most 2.0).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct fi_sampling_params {
+  const float* probs;       /* [num_rows, vocab] probabilities (logits for fi_sampling_from_logits) */
+  int32_t* samples;         /* [batch] out */
+  const int32_t* indices;   /* optional [batch]: output row i draws from row indices[i] (clamped to num_rows) */
+  const int32_t* top_k_arr; /* optional [param_len] */
+  const float* top_p_arr;   /* optional [param_len]; min_p for fi_min_p_sampling_from_probs */
+  int32_t top_k_val;
+  float top_p_val;
+  int32_t batch, num_rows, vocab, param_len;
+  uint64_t philox_seed, philox_offset;
+} fi_sampling_params_t;
+
+/* ref: sampling_from_logits / sampling_from_probs, csrc/flashinfer_sampling_binding.cu:23-27, 64-66 */
+FI_API int fi_sampling_from_logits(const fi_sampling_params_t* params, fi_stream_t stream);
+FI_API int fi_sampling_from_probs(const fi_sampling_params_t* params, fi_stream_t stream);
+/* ref: top_k / top_p / min_p / top_k_top_p _sampling_from_probs, csrc/flashinfer_sampling_binding.cu:29-45, 68-74.
+ * fi_top_k_top_p_sampling_from_probs is the "joint" filter: the intersection of both sets. */
+FI_API int fi_top_k_sampling_from_probs(const fi_sampling_params_t* params, fi_stream_t stream);
+FI_API int fi_top_p_sampling_from_probs(const fi_sampling_params_t* params, fi_stream_t stream);
+FI_API int fi_min_p_sampling_from_probs(const fi_sampling_params_t* params, fi_stream_t stream);
+FI_API int fi_top_k_top_p_sampling_from_probs(const fi_sampling_params_t* params, fi_stream_t stream);
+
+typedef struct fi_row_transform_params {
+  const float* in;   /* [batch, vocab] */
+  float* out;        /* [batch, vocab], may alias in */
+  const int32_t* top_k_arr;
+  const float* scalar_arr; /* top_p (renorm) or temperature (softmax), optional [param_len] */
+  int32_t top_k_val;
+  float scalar_val;
+  int32_t batch, vocab, param_len;
+} fi_row_transform_params_t;
+
+/* out = softmax(in / temperature); rows may hold -inf.  ref: softmax, csrc/flashinfer_sampling_binding.cu:20-21, 62,
+ * include/flashinfer/sampling.cuh:314-435 (the reference's workspace and enable_pdl have no counterpart). */
+FI_API int fi_softmax(const fi_row_transform_params_t* params, fi_stream_t stream);
+/* ref: top_p_renorm_probs / top_k_renorm_probs / top_k_mask_logits, csrc/flashinfer_sampling_binding.cu:47-54, 76-80,
+ * include/flashinfer/sampling.cuh:1592-1850 */
+FI_API int fi_top_p_renorm_probs(const fi_row_transform_params_t* params, fi_stream_t stream);
+FI_API int fi_top_k_renorm_probs(const fi_row_transform_params_t* params, fi_stream_t stream);
+FI_API int fi_top_k_mask_logits(const fi_row_transform_params_t* params, fi_stream_t stream);
+
+/* ref: chain_speculative_sampling, csrc/flashinfer_sampling_binding.cu:56-59, 82, sampling.cuh:2059-2190.
+ * Draft token i is accepted while u_i * p_draft < p_target; the first rejected position is redrawn from
+ * relu(target - draft) (the bonus position from target alone), later positions are -1.  The counters are
+ * ADDED to (accepted: as if every position were tested on its own; emitted: the accepted prefix). */
+typedef struct fi_chain_speculative_params {
+  const float* draft_probs;       /* [batch, n, vocab] */
+  const int32_t* draft_token_ids; /* [batch, n] (clamped to the vocabulary) */
+  const float* target_probs;      /* [batch, n + 1, vocab] */
+  int32_t* output_token_ids;      /* [batch, n + 1] out */
+  int32_t* output_accepted_token_num;      /* [batch] in/out */
+  int32_t* output_emitted_draft_token_num; /* [batch] in/out */
+  int32_t batch, num_speculative_tokens, vocab;
+  uint64_t philox_seed, philox_offset;
+} fi_chain_speculative_params_t;
+
+FI_API int fi_chain_speculative_sampling(const fi_chain_speculative_params_t* params, fi_stream_t stream);
 
 #ifdef __cplusplus
 }
