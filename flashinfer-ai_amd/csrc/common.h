@@ -241,6 +241,44 @@ __device__ __forceinline__ uint16_t f32_to_f16_bits(float x) {
 __device__ __forceinline__ uint16_t f32_to_16bit(float x, int dt) {
   return dt == FI_DTYPE_BF16 ? f32_to_bf16_bits(x) : f32_to_f16_bits(x);
 }
+
+// VEC (8, 4 or 1) consecutive 16-bit values of a compile-time dtype <-> floats, as one access of VEC * 2 bytes; the
+// address must be aligned to that size.  Stores round to nearest even.
+template <int DT, int VEC>
+__device__ __forceinline__ void load_16bit(const uint16_t* p, float* f) {
+  if constexpr (VEC == 1) {
+    f[0] = load_f16_or_bf16(p, 0, DT);
+  } else {
+    using words = __attribute__((ext_vector_type(VEC / 2))) uint32_t;
+    const words r = *(const words*)p;
+#pragma unroll
+    for (int i = 0; i < VEC / 2; ++i) {
+      const uint32_t w = r[i];
+      if constexpr (DT == FI_DTYPE_BF16) {
+        f[2 * i] = __builtin_bit_cast(float, w << 16);
+        f[2 * i + 1] = __builtin_bit_cast(float, w & 0xffff0000u);
+      } else {
+        using h2 = __attribute__((ext_vector_type(2))) _Float16;
+        const h2 h = __builtin_bit_cast(h2, w);
+        f[2 * i] = (float)h[0];
+        f[2 * i + 1] = (float)h[1];
+      }
+    }
+  }
+}
+template <int DT, int VEC>
+__device__ __forceinline__ void store_16bit(uint16_t* p, const float* f) {
+  if constexpr (VEC == 1) {
+    p[0] = f32_to_16bit(f[0], DT);
+  } else {
+    using words = __attribute__((ext_vector_type(VEC / 2))) uint32_t;
+    words r;
+#pragma unroll
+    for (int i = 0; i < VEC / 2; ++i)
+      r[i] = (uint32_t)f32_to_16bit(f[2 * i], DT) | ((uint32_t)f32_to_16bit(f[2 * i + 1], DT) << 16);
+    *(words*)p = r;
+  }
+}
 __device__ __forceinline__ float load_any_float(const void* p, int64_t idx, int dt) {
   if (dt == FI_DTYPE_F32) return ((const float*)p)[idx];
   return load_f16_or_bf16(p, idx, dt);

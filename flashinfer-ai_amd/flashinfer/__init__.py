@@ -1,12 +1,17 @@
 """flashinfer -- MI355X (gfx950) native implementation of FlashInfer's paged-KV attention hot path.
 
-Drop-in for the ``flashinfer.decode / prefill / cascade / page / gemm / sampling`` operator API of FlashInfer
-v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-written HIP kernels behind the C ABI of
+Drop-in for the ``flashinfer.decode / prefill / cascade / page / gemm / sampling / norm / activation`` operator API
+of FlashInfer v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-written HIP kernels behind the C ABI of
 ``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided.
 """
 from . import _lib as _lib
+from . import activation as activation
 from . import mla as mla
+from . import norm as norm
 from . import sampling as sampling
+from .activation import gelu_and_mul as gelu_and_mul
+from .activation import gelu_tanh_and_mul as gelu_tanh_and_mul
+from .activation import silu_and_mul as silu_and_mul
 from .cascade import (
     BatchDecodeWithSharedPrefixPagedKVCacheWrapper as BatchDecodeWithSharedPrefixPagedKVCacheWrapper,
 )
@@ -30,6 +35,10 @@ from .decode import single_decode_with_kv_cache as single_decode_with_kv_cache
 from .gemm import gemm_fp8_nt_groupwise as gemm_fp8_nt_groupwise
 from .gemm import group_gemm_fp8_nt_groupwise as group_gemm_fp8_nt_groupwise
 from .mla import BatchMLAPagedAttentionWrapper as BatchMLAPagedAttentionWrapper
+from .norm import fused_add_rmsnorm as fused_add_rmsnorm
+from .norm import gemma_fused_add_rmsnorm as gemma_fused_add_rmsnorm
+from .norm import gemma_rmsnorm as gemma_rmsnorm
+from .norm import rmsnorm as rmsnorm
 from .page import append_paged_kv_cache as append_paged_kv_cache
 from .page import append_paged_mla_kv_cache as append_paged_mla_kv_cache
 from .page import apply_rope_append_paged_kv_cache as apply_rope_append_paged_kv_cache

@@ -283,6 +283,34 @@ class ChainSpeculativeParams(C.Structure):
     ]
 
 
+class RmsNormParams(C.Structure):
+    """fi_rmsnorm_params_t: RMSNorm over [batch, hidden] (num_heads == 1) or [batch, num_heads, hidden]."""
+    _fields_ = [
+        ("in_", C.c_void_p), ("weight", C.c_void_p), ("out", C.c_void_p),
+        ("batch", C.c_int32), ("num_heads", C.c_int32), ("hidden", C.c_int32),
+        ("in_stride_n", C.c_int64), ("in_stride_h", C.c_int64), ("out_stride_n", C.c_int64), ("out_stride_h", C.c_int64),
+        ("eps", C.c_float), ("weight_bias", C.c_float), ("dtype", C.c_int32),
+    ]
+
+
+class FusedAddRmsNormParams(C.Structure):
+    _fields_ = [
+        ("input", C.c_void_p), ("residual", C.c_void_p), ("weight", C.c_void_p),
+        ("batch", C.c_int32), ("hidden", C.c_int32), ("input_stride", C.c_int64), ("residual_stride", C.c_int64),
+        ("eps", C.c_float), ("weight_bias", C.c_float), ("dtype", C.c_int32),
+    ]
+
+
+class ActAndMulParams(C.Structure):
+    _fields_ = [
+        ("in_", C.c_void_p), ("out", C.c_void_p), ("tokens", C.c_int64), ("d", C.c_int32), ("act", C.c_int32),
+        ("dtype", C.c_int32),
+    ]
+
+
+FI_NORM_MAX_HIDDEN = 65536
+FI_ACT_SILU, FI_ACT_GELU, FI_ACT_GELU_TANH = range(3)
+
 FI_PREFILL_PLAN_INFO_LEN = 16
 FI_PREFILL_PLAN_MAGIC = 0x4649505245
 FI_PREFILL_QKVO_PLAN_MAGIC = 0x4649514B564F  # plan_info[15] of a head_dim_qk 192 / head_dim_vo 128 plan
@@ -334,6 +362,9 @@ EXPORTED_SYMBOLS = [
     "fi_top_k_renorm_probs",
     "fi_top_k_mask_logits",
     "fi_chain_speculative_sampling",
+    "fi_rmsnorm",
+    "fi_fused_add_rmsnorm",
+    "fi_act_and_mul",
 ]
 
 SAMPLING_SYMBOLS = ("fi_sampling_from_logits", "fi_sampling_from_probs", "fi_top_k_sampling_from_probs",
@@ -386,6 +417,9 @@ def lib() -> C.CDLL:
     for name in ROW_TRANSFORM_SYMBOLS:
         getattr(l, name).argtypes = [C.POINTER(RowTransformParams), vp]
     l.fi_chain_speculative_sampling.argtypes = [C.POINTER(ChainSpeculativeParams), vp]
+    l.fi_rmsnorm.argtypes = [C.POINTER(RmsNormParams), vp]
+    l.fi_fused_add_rmsnorm.argtypes = [C.POINTER(FusedAddRmsNormParams), vp]
+    l.fi_act_and_mul.argtypes = [C.POINTER(ActAndMulParams), vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(l, name)
         if name not in ("fi_last_error",):

@@ -21,6 +21,9 @@ from typing import List, Optional
 import torch
 
 from . import _lib
+# ref getters: flashinfer/activation.py:65-88 and flashinfer/norm.py:38-40 (exports csrc/flashinfer_norm_binding.cu).
+from .activation import get_act_and_mul_module as get_act_and_mul_module
+from .norm import get_norm_module as get_norm_module
 # ref getter: flashinfer/sampling.py:60-487; exports csrc/flashinfer_sampling_binding.cu:62-82.  The functions keep the
 # positional signatures of the reference's custom ops (tensors in, tensors out; seed and offset drawn inside).
 from .sampling import get_sampling_module as get_sampling_module

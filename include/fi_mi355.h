@@ -1,7 +1,7 @@
 /*
  * fi_mi355.h -- C ABI of libfi_mi355.so, the MI355X (gfx950) implementation of FlashInfer's
  * batch paged-KV attention hot path (decode / prefill / cascade merge / page append), the fp8
- * groupwise (grouped) GEMM and the sampling operators.
+ * groupwise (grouped) GEMM, the sampling operators and the norm / gated-activation operators.
  *
  * Every entry point replaces one TVM-FFI export of the reference (FlashInfer v0.3.1); the export it
  * stands in for is cited as `ref: file:line` (paths relative to the reference checkout).  The
@@ -602,6 +602,64 @@ typedef struct fi_chain_speculative_params {
 } fi_chain_speculative_params_t;
 
 FI_API int fi_chain_speculative_sampling(const fi_chain_speculative_params_t* params, fi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Normalisation and gated activations: the operators a decoder layer runs around attention.
+ * ref: csrc/norm.cu:24-162, include/flashinfer/norm.cuh, csrc/flashinfer_norm_binding.cu,
+ * flashinfer/activation.py:33-88, include/flashinfer/activation.cuh.
+ * Tensors are f16 or bf16 (`dtype`), the weight has the tensors' dtype and all arithmetic is f32; the only 16-bit
+ * rounding is the final store.  `hidden` (and `d`) go from 1 to 65536.  No entry point keeps host state, so all
+ * of them may be captured into a graph.  An empty batch returns 0 without a launch.
+ * ---------------------------------------------------------------------------------------------- */
+#define FI_NORM_MAX_HIDDEN 65536
+
+/* out = in * rsqrt(mean(in^2) + eps) * (weight_bias + weight) per row of `hidden` contiguous elements.
+ * weight_bias is 0 for RMSNorm and 1 for the Gemma form (ref: norm.cuh:118, 405).  num_heads == 1 is the row form
+ * over [batch, hidden] (one workgroup per row; *_stride_h are ignored); num_heads > 1 is the head form over
+ * [batch, num_heads, hidden] (QK-norm, one wave per (token, head) row; ref: QKRMSNormKernel, norm.cuh:142-260).
+ * Strides are in elements and at least `hidden`.  `out` may be `in`. */
+typedef struct fi_rmsnorm_params {
+  const void* in;
+  const void* weight; /* [hidden] */
+  void* out;
+  int32_t batch, num_heads, hidden;
+  int64_t in_stride_n, in_stride_h, out_stride_n, out_stride_h;
+  float eps, weight_bias;
+  int32_t dtype;
+} fi_rmsnorm_params_t;
+
+FI_API int fi_rmsnorm(const fi_rmsnorm_params_t* params, fi_stream_t stream);
+
+/* In place on both tensors (ref: FusedAddRMSNormKernel, norm.cuh:264-355): s = float(input) + float(residual);
+ * residual = T(s); input = T(s * rsqrt(mean(s^2) + eps) * (weight_bias + weight)), the sum of squares and the output
+ * taken from the unrounded f32 s.  input and residual must not overlap. */
+typedef struct fi_fused_add_rmsnorm_params {
+  void* input;    /* [batch, hidden] in/out */
+  void* residual; /* [batch, hidden] in/out */
+  const void* weight;
+  int32_t batch, hidden;
+  int64_t input_stride, residual_stride;
+  float eps, weight_bias;
+  int32_t dtype;
+} fi_fused_add_rmsnorm_params_t;
+
+FI_API int fi_fused_add_rmsnorm(const fi_fused_add_rmsnorm_params_t* params, fi_stream_t stream);
+
+enum fi_activation { FI_ACT_SILU = 0, FI_ACT_GELU = 1, FI_ACT_GELU_TANH = 2 };
+
+/* out[t, j] = act(in[t, j]) * in[t, d + j]; in [tokens, 2 d] and out [tokens, d] contiguous.
+ * silu(x) = x / (1 + exp(-x)); gelu(x) = x/2 (1 + erf(x / sqrt 2)); gelu_tanh(x) = x/2 (1 + tanh(0.79788456
+ * (x + 0.044715 x^3))) (ref: flashinfer/activation.py:33-52). */
+typedef struct fi_act_and_mul_params {
+  const void* in;
+  void* out;
+  int64_t tokens;
+  int32_t d;
+  int32_t act; /* enum fi_activation */
+  int32_t dtype;
+} fi_act_and_mul_params_t;
+
+FI_API int fi_act_and_mul(const fi_act_and_mul_params_t* params, fi_stream_t stream);
 
 #ifdef __cplusplus
 }
