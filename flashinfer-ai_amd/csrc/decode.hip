@@ -256,10 +256,12 @@ extern "C" FI_API int fi_batch_decode_plan(void* float_ws, size_t float_ws_bytes
   memset(req_h, 0, padded * sizeof(int32_t));
   memset(tile_h, 0, padded * sizeof(int32_t));
   size_t w = 0;
+  uint32_t uniform_chunks = 0;  // the chunk count every request has, 0 when they differ
   oind_h[0] = 0;
   for (int b = 0; b < batch_size; ++b) {
     const uint32_t np = (uint32_t)std::max(window_pages(indptr_h, b, page_size, window_left), 1);
     const uint32_t nchunks = split_kv ? ceil_div(np, pages_per_chunk) : 1u;
+    uniform_chunks = (b == 0 || uniform_chunks == nchunks) ? nchunks : 0u;
     for (uint32_t t = 0; t < nchunks; ++t) {
       FI_REQUIRE(w < padded, "batch_decode_plan: work list overflow");
       req_h[w] = b;
@@ -300,6 +302,11 @@ extern "C" FI_API int fi_batch_decode_plan(void* float_ws, size_t float_ws_bytes
   plan_info_out[FI_DP_INT_BYTES_USED] = (int64_t)ia.used;
   plan_info_out[FI_DP_WINDOW_LEFT] = window_left;
   plan_info_out[FI_DP_MAGIC] = FI_DECODE_PLAN_MAGIC;
+  // 2 or 4 equal chunks per request fit one 4-wave workgroup: run() may merge them in the decode launch
+  plan_info_out[FI_DP_UNIFORM_CHUNKS] =
+      (split_kv && !enable_cuda_graph && window_left < 0 && (uniform_chunks == 2 || uniform_chunks == 4))
+          ? (int64_t)uniform_chunks
+          : 0;
 
   if (int_ws && ia.used)
     FI_HIP_CALL(hipMemcpyAsync(int_ws, pinned_int_ws, ia.used, hipMemcpyHostToDevice,
@@ -423,6 +430,27 @@ extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes,
   }
   // fast path: scalar page ids, no logits transform (see decode_kernel.h)
   kp.fast_path = kp.uniform_page && kp.indices && !kp.use_alibi && kp.logits_soft_cap == 0.f;
+  // Every request cut into the same 2 or 4 chunks: the chunks of a (request, kv head) are waves of one workgroup
+  // of the 16x16x32 kernel's FUSE form, which folds them in LDS and writes the final output.  One launch; the work
+  // list and the partial-state region of the workspace are not touched.
+  // A fused workgroup reads 4 / n heads of a token row where an unfused one reads 4: below 256 contiguous bytes per
+  // row the lost DRAM locality costs more than the merge launch (C2 with an fp8 cache, n = 4, 128 B: 192-204 us
+  // fused against 177 us in two launches), so those plans keep the two launches.
+  const int fuse_n = (int)plan_info[FI_DP_UNIFORM_CHUNKS];
+  const int heads_per_wg = (fuse_n == 2 || fuse_n == 4) ? kDecodeWaves / fuse_n : 0;
+  if (split && heads_per_wg && choice.kind == DecodeKernel::MFMA16 &&
+      a->pos_encoding_mode != FI_POS_ROPE_LLAMA && a->window_left < 0 && kv.indices &&
+      (size_t)heads_per_wg * kv.head_dim * esz >= 256) {
+    const int grid = kv.batch_size * ceil_div(kv.num_kv_heads, heads_per_wg);
+    kp.fuse_chunks = fuse_n;
+    kp.num_items = grid * kDecodeWaves;
+    kp.request_indices = kp.kv_tile_indices = kp.o_indptr = nullptr;
+    kp.block_valid_mask = nullptr;
+    kp.kv_chunk_size_ptr = nullptr;  // not a graph plan: the planned value is the one in plan_info
+    kp.tmp_o = kp.tmp_lse = nullptr;
+    FI_HIP_CALL(decode_mfma16_launch(kp, a->q_dtype, kv.dtype, kv.head_dim, /*rope=*/0, grid, stream));
+    return 0;
+  }
   return launch_decode(kp, choice, a->q_dtype, kv.dtype, kv.head_dim, a->pos_encoding_mode == FI_POS_ROPE_LLAMA,
                        /*merge_n=*/0, kv.batch_size, stream);
 }

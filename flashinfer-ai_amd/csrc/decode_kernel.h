@@ -49,6 +49,9 @@ struct DecodeKernelParams {
   int32_t fast_path;     // launch the FAST instantiation
   FastDiv page_div;
   int32_t kv_chunk_size;  // tokens; only read when split_kv and kv_chunk_size_ptr is null
+  // decode_mfma16_kernel's FUSE form: chunks per request (2 | 4), all folded inside one workgroup; 0 otherwise.
+  // (Sits in what was alignment padding in front of the pointer below: no other field moves.)
+  int32_t fuse_chunks;
   // device copy of the chunk size in the int workspace: plan() rewrites it, so a captured run() replayed
   // after a new plan() sees the new value (ref: *kv_chunk_size_ptr, decode.cuh:424, 926)
   const int32_t* kv_chunk_size_ptr;

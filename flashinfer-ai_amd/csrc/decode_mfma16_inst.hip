@@ -1,5 +1,6 @@
 // 16x16x32 matrix-core decode instantiations (groups of <= 16 query heads): q dtype (f16 | bf16) x cache dtype
-// (same | e4m3 | e5m2) x head_dim (64 | 128) x (paged | identity pages) x (plain | fused RoPE).
+// (same | e4m3 | e5m2) x head_dim (64 | 128) x (paged | identity pages) x (plain | fused RoPE), and the FUSE form
+// (chunks merged in the workgroup) of the paged, plain ones.
 #include "decode_mfma16_kernel.h"
 
 namespace fi {
@@ -7,7 +8,10 @@ namespace fi {
 template <int T16, int KVS, int D>
 static hipError_t launch16(const DecodeKernelParams& p, int rope, int grid, hipStream_t stream) {
   const dim3 g(grid), b(kDecodeThreads);
-  if (rope) {
+  if (p.fuse_chunks) {
+    if (rope || !p.indices) return hipErrorInvalidValue;
+    decode_mfma16_kernel<T16, KVS, D, true, false, true><<<g, b, 0, stream>>>(p);
+  } else if (rope) {
     if (p.indices) decode_mfma16_kernel<T16, KVS, D, true, true><<<g, b, 0, stream>>>(p);
     else decode_mfma16_kernel<T16, KVS, D, false, true><<<g, b, 0, stream>>>(p);
   } else {

@@ -17,7 +17,8 @@ _LIB_PATH = os.environ.get("FI_MI355_LIB", os.path.join(_HERE, "libfi_mi355.so")
 
 FI_DTYPE_F16, FI_DTYPE_BF16, FI_DTYPE_FP8_E4M3, FI_DTYPE_FP8_E5M2, FI_DTYPE_F32 = range(5)
 FI_NEG_INF = -5.0e4
-FI_DECODE_PLAN_INFO_LEN = 16
+FI_DECODE_PLAN_INFO_LEN = 17
+FI_DP_UNIFORM_CHUNKS = 16  # plan_info slot: 2 | 4 when every request is cut into that many chunks, else 0
 
 _TORCH2FI = {
     torch.float16: FI_DTYPE_F16,

@@ -88,7 +88,7 @@ typedef struct fi_paged_kv {
  * Batch decode.  ref: BatchDecodeWithPagedKVCachePlan / Run, csrc/batch_decode.cu:39-79, 81-191;
  * planner DecodePlan, include/flashinfer/attention/scheduler.cuh:424-493.
  * ---------------------------------------------------------------------------------------------- */
-#define FI_DECODE_PLAN_INFO_LEN 16
+#define FI_DECODE_PLAN_INFO_LEN 17
 /* plan_info (int64[FI_DECODE_PLAN_INFO_LEN]); the reference's DecodePlanInfo has 10 entries
  * (scheduler.cuh:391-402); entries 0..9 keep their meaning, 10.. are ours. */
 enum fi_decode_plan_slot {
@@ -107,7 +107,10 @@ enum fi_decode_plan_slot {
   FI_DP_BATCH_SIZE = 12,
   FI_DP_INT_BYTES_USED = 13,
   FI_DP_WINDOW_LEFT = 14,   /* sliding window the chunks were cut for (-1: none); run() must pass the same */
-  FI_DP_MAGIC = 15
+  FI_DP_MAGIC = 15,
+  FI_DP_UNIFORM_CHUNKS = 16 /* n in {2, 4} when the plan is split, not a graph plan, has no planned window
+                               (FI_DP_WINDOW_LEFT < 0) and EVERY request has exactly n chunks; else 0.  run() then
+                               merges the chunks inside the decode launch where its kernel can */
 };
 #define FI_DECODE_PLAN_MAGIC 0x4649444543ll /* "FIDEC" */
 
