@@ -53,6 +53,51 @@ def apply_rope_pos_ids_ref(q, k, pos_ids, rotary_dim=None, interleave=False, rop
     return outs[0], outs[1]
 
 
+# Angle budget of an f32 frequency pipeline (tests/test_rope_budget_cpu.py holds the study behind the constants):
+# the relative error of freq_m = exp2(log2(1/theta) * 2m/rot) computed in f32 with log2 / exp2 good to 2 ulp stays
+# within (A |log2 b_m| + B) 2^-23, b_m = theta^(-2m/rot) the unblended frequency; B also covers the rounding of
+# pos * freq.  The reference computes its angles in f32 the same way, so this is the error any f32 form carries.
+ANGLE_BUDGET_A = 4.0
+ANGLE_BUDGET_B = 3.0
+
+
+def pair_index(rotary_dim: int, interleave: bool) -> torch.Tensor:
+    """Pair index m of every element of the rotary part [rotary_dim] (int64)."""
+    i = torch.arange(rotary_dim)
+    return i // 2 if interleave else i % (rotary_dim // 2)
+
+
+def freq_rel_budget(rotary_dim: int, rope_theta: float) -> torch.Tensor:
+    """(A |log2 b_m| + B) 2^-23 per pair m [rotary_dim // 2] (f64): the relative frequency error allowed."""
+    m = torch.arange(rotary_dim // 2, dtype=torch.float64)
+    log2_b = -(2.0 * m / rotary_dim) * math.log2(rope_theta)
+    return (ANGLE_BUDGET_A * log2_b.abs() + ANGLE_BUDGET_B) * 2.0 ** -23
+
+
+def angle_budget(pos_ids, rotary_dim: int, interleave: bool, rope_scale: float = 1.0, rope_theta: float = 1e4,
+                 smooth_a: float = 0.0, smooth_b: float = 0.0) -> torch.Tensor:
+    """delta_theta(p, m) = p f_m (A |log2 b_m| + B) 2^-23 in per-element layout [nnz, rotary_dim] (f64); f_m is
+    the frequency after scaling and blending, b_m the unblended one."""
+    f = rope_freqs(rotary_dim, interleave, rope_scale, rope_theta, smooth_a, smooth_b)
+    rel = freq_rel_budget(rotary_dim, rope_theta)[pair_index(rotary_dim, interleave)]
+    return pos_ids.to(torch.float64)[:, None] * (f * rel)[None, :]
+
+
+def pair_norm_sq(x: torch.Tensor, rotary_dim: int, interleave: bool) -> torch.Tensor:
+    """x0^2 + x1^2 of every rotation pair of x [..., D], [..., rotary_dim // 2] in pair order; a rotation keeps it.
+    Works in x's dtype and on x's device."""
+    xr = x[..., :rotary_dim]
+    if interleave:
+        return xr[..., 0::2] ** 2 + xr[..., 1::2] ** 2
+    return xr[..., : rotary_dim // 2] ** 2 + xr[..., rotary_dim // 2:] ** 2
+
+
+def pair_hypot(x: torch.Tensor, rotary_dim: int, interleave: bool) -> torch.Tensor:
+    """hypot(x0, x1) of the pair every element belongs to, per-element layout [..., rotary_dim]."""
+    n = pair_norm_sq(x.to(torch.float64), rotary_dim, interleave).sqrt()
+    return n.repeat_interleave(2, -1) if interleave else torch.cat((n, n), -1)
+
+
 def positions_from_indptr(indptr, offsets):
     pos = []
     for b in range(len(indptr) - 1):
