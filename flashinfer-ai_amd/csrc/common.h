@@ -126,6 +126,23 @@ __device__ __forceinline__ float fast_tanh(float x) {
   return 1.0f - 2.0f * fast_rcp(e + 1.0f);
 }
 
+// Attention sink (ref: AttentionSink, flashinfer/jit/attention/variants.py:17-53): one more term 2^sink_log2 in the
+// softmax denominator of a row, without a value vector.  Given the row's final running state (m, l) in base 2 --
+// the accumulators hold sum_j 2^(s_j - m) v_j, l = sum_j 2^(s_j - m) -- this returns what the finalize block of a
+// kernel multiplies the accumulators by and the row's lse, i.e. the state merged with (0, sink_log2):
+//   m' = max(m, sink_log2), sa = 2^(m - m'), l' = l sa + 2^(sink_log2 - m');  inv = sa / l', lse = m' + log2(l').
+// m must be finite (the kernels start it at -1e30).  sink_log2 = -inf gives sa = 1 and l' = l exactly: inv and lse
+// are then bit for bit the values without a sink; an empty row (l = 0) with it gives inv = 0, lse = FI_NEG_INF.
+// A state that carries a power-of-two factor 2^k in l (and in its accumulators) passes sink_log2 + k.
+__device__ __forceinline__ void fold_sink(float m, float l, float sink_log2, float& inv, float& lse) {
+  const float m2 = fmaxf(m, sink_log2);
+  const float sa = fast_exp2(m - m2);
+  const float l2 = __builtin_fmaf(l, sa, fast_exp2(sink_log2 - m2));
+  const bool empty = !(l2 > 0.f);
+  inv = empty ? 0.f : sa * (1.0f / l2);
+  lse = empty ? FI_NEG_INF : m2 + fast_log2(l2);
+}
+
 // ---- cross-lane moves ----
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float x) {

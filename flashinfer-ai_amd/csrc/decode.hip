@@ -154,6 +154,7 @@ static int launch_decode(const DecodeKernelParams& kp, const DecodeChoice& c, in
     // ref: VariableLengthMergeStates after the partition-kv kernel, decode.cuh:798-821
     MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.o_indptr, kp.o, kp.lse, merge_n, merge_rows,
                     kp.num_qo_heads, head_dim, FI_DTYPE_F32, q_dt};
+    mp.sinks = kp.sinks;  // the decode kernels left the partial states without them
     FI_HIP_CALL(launch_merge_n(mp, stream));
   }
   return 0;
@@ -363,7 +364,18 @@ extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes,
                                    size_t int_ws_bytes, const int64_t* plan_info,
                                    int32_t plan_info_len, const fi_batch_decode_params_t* a,
                                    fi_stream_t stream_) {
+  return fi_batch_decode_run_sinks(float_ws, float_ws_bytes, int_ws, int_ws_bytes, plan_info, plan_info_len, a,
+                                   /*sinks=*/nullptr, stream_);
+}
+
+extern "C" FI_API int fi_batch_decode_run_sinks(void* float_ws, size_t float_ws_bytes, void* int_ws,
+                                         size_t int_ws_bytes, const int64_t* plan_info,
+                                         int32_t plan_info_len, const fi_batch_decode_params_t* a,
+                                         const float* sinks, fi_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  // decode takes 16-bit queries only; with sinks that is said first, so before any launch
+  FI_REQUIRE(!sinks || !a || a->q_dtype == FI_DTYPE_F16 || a->q_dtype == FI_DTYPE_BF16,
+             "batch_decode_run: attention sinks need f16 / bf16 queries (q dtype %d)", a->q_dtype);
   FI_REQUIRE(plan_info && plan_info_len == FI_DECODE_PLAN_INFO_LEN &&
                  plan_info[FI_DP_MAGIC] == FI_DECODE_PLAN_MAGIC,
              "batch_decode_run: plan_info is not a decode plan (call plan() first)");
@@ -416,6 +428,7 @@ extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes,
   // the kernels read the chunk size from the slot plan() refreshes (graph replay after a re-plan)
   kp.kv_chunk_size_ptr = (const int32_t*)(ib + plan_info[FI_DP_KV_CHUNK_SIZE_PTR_OFFSET]);
   kp.split_kv = split;
+  kp.sinks = sinks;
   // chunks were cut from the window's pages at plan(): the kernel offsets them by the same first page
   kp.plan_window_left = (int32_t)plan_info[FI_DP_WINDOW_LEFT];
   FI_REQUIRE(kp.plan_window_left < 0 || kp.plan_window_left == a->window_left,

@@ -64,6 +64,10 @@ struct DecodeKernelParams {
   float logits_soft_cap;  // 0: off
   float sm_scale;
   float rope_rcp_scale, rope_rcp_theta;
+  // attention sinks: f32 [num_qo_heads] natural-log logits, NULL = none.  Folded (fold_sink, common.h) where a FINAL
+  // output row is written -- never into a split-KV partial state, whose merge launch folds instead.  Last field: no
+  // other field moves.
+  const float* sinks;
 };
 
 // K/V rows are read once per wave: non-temporal.  When a GQA group is processed as several head tiles the
@@ -478,8 +482,9 @@ struct DecodeWave {
         if (hg >= p.group_size) continue;
         const int head = kv_head * p.group_size + hg;
         const bool empty = !(d[g] > 0.f);
-        const float inv = empty ? 0.f : 1.0f / d[g];
-        const float lse_v = empty ? FI_NEG_INF : m[g] + fast_log2(d[g]);
+        float inv = empty ? 0.f : 1.0f / d[g];
+        float lse_v = empty ? FI_NEG_INF : m[g] + fast_log2(d[g]);
+        if (p.sinks && !p.split_kv) fold_sink(m[g], d[g], p.sinks[head] * kLog2e, inv, lse_v);
         const int64_t ob = (out_row * p.num_qo_heads + head) * HEAD_DIM + c * VEC;
         if (p.split_kv) {
 #pragma unroll

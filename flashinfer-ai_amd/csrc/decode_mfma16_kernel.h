@@ -482,8 +482,11 @@ __global__ void __launch_bounds__(kDecodeThreads, (ROPE && D == 128 && KVS != T1
   }
   const bool split_out = FUSE ? false : (bool)p.split_kv;  // FUSE: split for the kv range, final for the output
   const bool empty = !(l_run > 0.f);
-  const float inv = empty ? 0.f : 1.0f / l_run;
-  const float lse_v = empty ? FI_NEG_INF : m_run + fast_log2(l_run);
+  float inv = empty ? 0.f : 1.0f / l_run;
+  float lse_v = empty ? FI_NEG_INF : m_run + fast_log2(l_run);
+  // attention sink of this lane's head (lanes past the group: a valid head, unused), on a final output only: once
+  // per row, for FUSE after the fold of the chunks
+  if (p.sinks && !split_out) fold_sink(m_run, l_run, p.sinks[min(head0 + lc, p.num_qo_heads - 1)] * kLog2e, inv, lse_v);
   if (lc < G) {
     const int qo_head = head0 + lc;
     const int64_t out_row = split_out ? (int64_t)(p.o_indptr ? p.o_indptr[req] : 0) + kv_tile : req;

@@ -389,8 +389,10 @@ __global__ void __launch_bounds__(kDecodeThreads, (ROPE && D == 128) ? 1 : 2) de
   // ---- finalize and write (partial state or final output) ----
   l_run += swap_halves(l_run);
   const bool empty = !(l_run > 0.f);
-  const float inv = empty ? 0.f : 1.0f / l_run;
-  const float lse_v = empty ? FI_NEG_INF : m_run + fast_log2(l_run);
+  float inv = empty ? 0.f : 1.0f / l_run;
+  float lse_v = empty ? FI_NEG_INF : m_run + fast_log2(l_run);
+  // attention sink of this lane's head (lanes past the group: a valid head, unused), on a final output only
+  if (p.sinks && !p.split_kv) fold_sink(m_run, l_run, p.sinks[min(head0 + lq, p.num_qo_heads - 1)] * kLog2e, inv, lse_v);
   if (lq < G) {
     const int qo_head = head0 + lq;
     const int64_t out_row = p.split_kv ? (int64_t)(p.o_indptr ? p.o_indptr[req] : 0) + kv_tile : req;

@@ -74,14 +74,15 @@ __global__ void __launch_bounds__(kMergeThreads) merge_n_kernel(const MergeNPara
   // n == 0, or nothing but empty partial states -> zeros / -inf sentinel (ref: cascade.cuh:397-405)
   if (n == 0 && p.skip_empty) return;
   const bool empty = !(dsum > 0.f) || mx <= FI_NEG_INF;
-  const float inv = empty ? 0.f : 1.0f / dsum;
+  float inv = empty ? 0.f : 1.0f / dsum;
+  float lse = empty ? FI_NEG_INF : mx + fast_log2(dsum);
+  if (p.sinks) fold_sink(mx, empty ? 0.f : dsum, p.sinks[head] * kLog2e, inv, lse);
 #pragma unroll
   for (int k = 0; k < kMergeMaxPerLane; ++k) {
     const int i = lane + 64 * k;
     if (i < D) store_any_float(p.v_out, ob + i, acc[k] * inv, p.out_dtype);
   }
-  if (lane == 0 && p.s_out)
-    p.s_out[(int64_t)row * p.num_heads + head] = empty ? FI_NEG_INF : mx + fast_log2(dsum);
+  if (lane == 0 && p.s_out) p.s_out[(int64_t)row * p.num_heads + head] = lse;
 }
 
 // The same merge for f32 partial states with head_dim = 64 * VEC (the split-KV partials of decode and
@@ -165,11 +166,12 @@ __global__ void __launch_bounds__(kMergeThreads) merge_n_f32_kernel(const MergeN
   for (int off = 32; off > 0; off >>= 1) dsum += __shfl_xor(dsum, off, 64);
   const int64_t ob = ((int64_t)row * p.num_heads + head) * D + lane * VEC;
   const bool empty = !(dsum > 0.f) || mx <= FI_NEG_INF;
-  const float inv = empty ? 0.f : 1.0f / dsum;
+  float inv = empty ? 0.f : 1.0f / dsum;
+  float lse = empty ? FI_NEG_INF : mx + fast_log2(dsum);
+  if (p.sinks) fold_sink(mx, empty ? 0.f : dsum, p.sinks[head] * kLog2e, inv, lse);
 #pragma unroll
   for (int i = 0; i < VEC; ++i) store_any_float(p.v_out, ob + i, acc[i] * inv, p.out_dtype);
-  if (lane == 0 && p.s_out)
-    p.s_out[(int64_t)row * p.num_heads + head] = empty ? FI_NEG_INF : mx + fast_log2(dsum);
+  if (lane == 0 && p.s_out) p.s_out[(int64_t)row * p.num_heads + head] = lse;
 }
 
 // ref: MergeStateKernel cascade.cuh:44-71 and MergeStateInPlaceKernel cascade.cuh:86-116

@@ -22,6 +22,10 @@ struct MergeNParams {
   int32_t seq_len, num_heads, head_dim;
   int32_t in_dtype, out_dtype;
   int32_t skip_empty;  // rows without entries are left untouched (padding rows of a fixed-shape launch)
+  // attention sinks, f32 [num_heads] natural-log logits (NULL: none): the merge of the split-KV partial states of a
+  // run with sinks folds them (fold_sink, common.h), once per output row; a row of empty partials becomes
+  // (0, sink_log2).  NULL everywhere else.
+  const float* sinks;
 };
 
 struct Merge2Params {

@@ -474,11 +474,14 @@ static void split_single_kv(KP& kp, void* tmp, size_t tmp_bytes, int qo_len, int
 // For a split kv axis (kp.tmp_o set), the n-way merge of the partial states of merge_rows query rows: ragged over
 // kp.merge_indptr (batch), or kp.num_kv_chunks per row (single).  ref: VariableLengthMergeStates after the
 // partition-kv kernel, prefill.cuh:2590-2671; the padding rows of a graph plan have no entries and are left alone.
+// `sinks`: the attention sinks of the run (NULL: none), which the kernel left out of the partial states.
 template <class KP>
-static int merge_split_kv(const KP& kp, int head_dim_vo, int o_dtype, int32_t merge_rows, hipStream_t stream) {
+static int merge_split_kv(const KP& kp, int head_dim_vo, int o_dtype, int32_t merge_rows, const float* sinks,
+                          hipStream_t stream) {
   if (kp.tmp_o) {
     MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.merge_indptr, kp.o, kp.lse, kp.num_kv_chunks, merge_rows,
-                    kp.num_qo_heads, head_dim_vo, FI_DTYPE_F32, o_dtype, /*skip_empty=*/kp.merge_indptr != nullptr};
+                    kp.num_qo_heads, head_dim_vo, FI_DTYPE_F32, o_dtype, /*skip_empty=*/kp.merge_indptr != nullptr,
+                    sinks};
     FI_HIP_CALL(launch_merge_n(mp, stream));
   }
   return 0;
@@ -491,7 +494,7 @@ static int launch_prefill(const PrefillKernelParams& kp, const PrefillLaunch& la
     FI_HIP_CALL(prefill_fp8_launch(kp, kp.o_dtype, launch.q_dtype == FI_DTYPE_FP8_E5M2, launch.head_dim, stream));
   else
     FI_HIP_CALL(launch.fn(kp, launch.rope, stream));
-  return merge_split_kv(kp, launch.head_dim, kp.o_dtype, merge_rows, stream);
+  return merge_split_kv(kp, launch.head_dim, kp.o_dtype, merge_rows, kp.sinks, stream);
 }
 
 }  // namespace fi
@@ -501,7 +504,20 @@ extern "C" FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws
                                                  int32_t plan_info_len,
                                                  const fi_batch_prefill_params_t* a,
                                                  fi_stream_t stream_) {
+  return fi_batch_prefill_paged_run_sinks(float_ws, float_ws_bytes, int_ws, int_ws_bytes, plan_info, plan_info_len, a,
+                                          /*sinks=*/nullptr, stream_);
+}
+
+extern "C" FI_API int fi_batch_prefill_paged_run_sinks(void* float_ws, size_t float_ws_bytes, void* int_ws,
+                                                       size_t int_ws_bytes, const int64_t* plan_info,
+                                                       int32_t plan_info_len,
+                                                       const fi_batch_prefill_params_t* a, const float* sinks,
+                                                       fi_stream_t stream_) {
   (void)int_ws_bytes;
+  // attention sinks exist for 16-bit queries only (the fp8-query kernels have no sink term): refused before anything
+  // else, so before any launch
+  FI_REQUIRE(!sinks || !a || a->q_dtype == FI_DTYPE_F16 || a->q_dtype == FI_DTYPE_BF16,
+             "batch_prefill_paged_run: attention sinks need f16 / bf16 queries (q dtype %d)", a->q_dtype);
   FI_REQUIRE(!plan_info || plan_info_len != FI_PREFILL_PLAN_INFO_LEN ||
                  plan_info[FI_PP_MAGIC] != FI_PREFILL_QKVO_PLAN_MAGIC,
              "batch_prefill_paged_run: the plan is for head_dim_qk 192 / head_dim_vo 128, which runs through "
@@ -540,6 +556,7 @@ extern "C" FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws
   kp.kv_last_page_len = kv.last_page_len;
   if (bind_batch_plan("batch_prefill_paged_run", plan_info, float_ws, float_ws_bytes, int_ws, kp)) return 1;
   kp.num_work = (int32_t)num_work;
+  kp.sinks = sinks;
   if (a->mask_mode == FI_MASK_CUSTOM) kp.mask_indptr = a->mask_indptr;
   if (a->mask_mode == FI_MASK_MULTIITEMSCORING) {
     kp.prefix_len_ptr = a->prefix_len_ptr;
@@ -632,7 +649,7 @@ static int launch_qkvo(const PrefillQkvoParams& kp, const fi_prefill_qkvo_params
   // bf16: P.V on the f16 MFMA by default; bf16_pv_mode 1 = hi + lo bf16 P, 3 = one bf16 rounding of P
   const int pmode = a.bf16_pv_mode == 1 ? 1 : a.bf16_pv_mode == 3 ? 0 : 2;
   FI_HIP_CALL(prefill_qkvo_launch(kp, a.q_dtype, pmode, stream));
-  return merge_split_kv(kp, kQkvoDimVO, a.o_dtype, merge_rows, stream);
+  return merge_split_kv(kp, kQkvoDimVO, a.o_dtype, merge_rows, /*sinks=*/nullptr, stream);
 }
 
 }  // namespace fi

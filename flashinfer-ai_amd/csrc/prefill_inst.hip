@@ -8,9 +8,9 @@
 
 namespace fi {
 
-template <bool ROPE, int GEN, int PMODE = 0>
+template <bool ROPE, int GEN, int PMODE = 0, bool SINK = false>
 static hipError_t launch(const PrefillKernelParams& p, hipStream_t stream) {
-  auto kern = batch_prefill_kernel<FI_PF_T16, FI_PF_KVS, FI_PF_QS, FI_PF_D, ROPE, GEN, PMODE>;
+  auto kern = batch_prefill_kernel<FI_PF_T16, FI_PF_KVS, FI_PF_QS, FI_PF_D, ROPE, GEN, PMODE, SINK>;
   constexpr int smem = 2 * 2 * kTileKV * FI_PF_D * 2;
   static bool attr_set = false;
   if (!attr_set) {
@@ -30,6 +30,17 @@ template <int PMODE>
 static hipError_t launch_features(const PrefillKernelParams& p, int rope, hipStream_t stream) {
   const int gen = (p.use_alibi ? 1 : 0) | (p.logits_soft_cap > 0.f ? 2 : 0) | (p.custom_mask != nullptr ? 4 : 0) |
                   (p.prefix_len_ptr != nullptr ? 8 : 0);
+#if FI_PF_QS <= 1  // 16-bit queries (enumerators are not visible to the preprocessor)
+  static_assert(FI_DTYPE_F16 == 0 && FI_DTYPE_BF16 == 1, "16-bit tags");
+  // attention sinks on a final output (the partial states of a split kv axis get them in their merge): the SINK
+  // kernels, which exist in the plain and the all-features form
+  if (p.sinks && !p.kv_tile_indices && p.num_kv_chunks <= 1) {
+    if (rope) return gen ? launch<true, 15, PMODE, true>(p, stream) : launch<true, 0, PMODE, true>(p, stream);
+    return gen ? launch<false, 15, PMODE, true>(p, stream) : launch<false, 0, PMODE, true>(p, stream);
+  }
+#else
+  if (p.sinks) return hipErrorInvalidValue;  // refused on the host before it gets here
+#endif
   if (rope) return gen ? launch<true, 15, PMODE>(p, stream) : launch<true, 0, PMODE>(p, stream);
   switch (gen) {
     case 0: return launch<false, 0, PMODE>(p, stream);

@@ -86,6 +86,10 @@ struct PrefillKernelParams {
   float logits_soft_cap;
   float sm_scale;
   float rope_rcp_scale, rope_rcp_theta;
+  // attention sinks: f32 [num_qo_heads] natural-log logits, NULL = none (16-bit queries only; the host refuses them
+  // with fp8 queries).  Folded (fold_sink, common.h) where a FINAL output row is written; the partial states of a split
+  // kv axis are left alone and their merge launch folds.  Last field: no other field moves.
+  const float* sinks;
 };
 
 template <int T16>
@@ -203,7 +207,10 @@ __device__ __forceinline__ float round_through_e4m3(float x) {
 //      it is staged (exact for |v| < 65504 -- larger values saturate there -- and free for an fp8 cache, which is
 //      converted anyway); QK^T stays on the bf16 MFMA.  The default: the 1e-3 bar at the cost of ~48 conversions
 //      per tile instead of 16 MFMAs + 80 vector instructions.
-template <int T16, int KVS, int QS, int D, bool ROPE, int GEN, int PMODE>
+// SINK: the run has attention sinks (p.sinks set; 16-bit queries only).  A template parameter, picked on the host, and
+//   not a test of p.sinks: the fold's values live beside the whole of o_acc, and kernels that sit on a register step
+//   must not pay for them in runs without sinks -- with SINK false the kernel is the one without the feature.
+template <int T16, int KVS, int QS, int D, bool ROPE, int GEN, int PMODE, bool SINK = false>
 // head_dim 256 keeps 128 accumulator + 64 query-fragment registers per lane: one wave per SIMD (512 registers)
 __global__ void __launch_bounds__(kPrefillThreads, D == 256 ? 1 : 2)
     batch_prefill_kernel(const PrefillKernelParams p) {
@@ -211,6 +218,7 @@ __global__ void __launch_bounds__(kPrefillThreads, D == 256 ? 1 : 2)
   using frag_t = typename M::frag;
   constexpr bool KV_FP8 = (KVS == FI_DTYPE_FP8_E4M3 || KVS == FI_DTYPE_FP8_E5M2);
   constexpr bool Q_FP8 = (QS == FI_DTYPE_FP8_E4M3 || QS == FI_DTYPE_FP8_E5M2);
+  static_assert(!SINK || !Q_FP8, "attention sinks need 16-bit queries");
   constexpr bool GENERAL = GEN != 0;
   static_assert(GEN == 0 || GEN == 1 || GEN == 2 || GEN == 4 || GEN == 8 || GEN == 15, "feature mask");
   // feature f is on: compiled in, and (only in the all-features form) asked for at run time
@@ -920,6 +928,17 @@ __global__ void __launch_bounds__(kPrefillThreads, D == 256 ? 1 : 2)
   l_run += swap_halves(l_run);
   const bool empty = !(l_run > 0.f);
   float inv = empty ? 0.f : 1.0f / l_run;
+  [[maybe_unused]] float lse_sink = 0.f;  // the row's lse with its sink folded in; read only where fold is set
+  [[maybe_unused]] bool fold = false;
+  if constexpr (SINK) {
+    // attention sink of this lane's head, on a final output only.  PV_F16: l_run and the accumulators carry 2^9, so
+    // the sink term does too, and the lse drops the factor as it does below.
+    fold = !split;
+    if (fold) {
+      fold_sink(m_run, l_run, __builtin_fmaf(p.sinks[qo_head], kLog2e, PV_F16 ? 9.f : 0.f), inv, lse_sink);
+      if (PV_F16 && lse_sink > FI_NEG_INF) lse_sink -= 9.f;  // an empty row with its sink off stays FI_NEG_INF
+    }
+  }
   if constexpr (Q_FP8) inv *= (p.scale_v ? p.scale_v[kv_head] : 1.f) / kPScale;
   else if (p.scale_v) inv *= p.scale_v[kv_head];
   if (row_valid && split) {
@@ -953,7 +972,7 @@ __global__ void __launch_bounds__(kPrefillThreads, D == 256 ? 1 : 2)
     }
     if (p.lse && lh == 0)
       p.lse[(int64_t)(qo_start + qo_idx) * p.num_qo_heads + qo_head] =
-          empty ? FI_NEG_INF : m_run + fast_log2(l_run) - (PV_F16 ? 9.f : 0.f);
+          SINK && fold ? lse_sink : empty ? FI_NEG_INF : m_run + fast_log2(l_run) - (PV_F16 ? 9.f : 0.f);
   }
 }
 

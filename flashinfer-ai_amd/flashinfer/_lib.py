@@ -330,6 +330,7 @@ EXPORTED_SYMBOLS = [
     "fi_num_compute_units",
     "fi_batch_decode_plan",
     "fi_batch_decode_run",
+    "fi_batch_decode_run_sinks",
     "fi_single_decode_run",
     "fi_merge_state",
     "fi_merge_state_in_place",
@@ -337,6 +338,7 @@ EXPORTED_SYMBOLS = [
     "fi_variable_length_merge_states",
     "fi_batch_prefill_plan",
     "fi_batch_prefill_paged_run",
+    "fi_batch_prefill_paged_run_sinks",
     "fi_single_prefill_run",
     "fi_batch_prefill_qkvo_run",
     "fi_single_prefill_qkvo_run",
@@ -391,6 +393,7 @@ def lib() -> C.CDLL:
     vp, i32, i64p, sz = C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_size_t
     l.fi_batch_decode_plan.argtypes = [vp, sz, vp, vp, sz, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64p, vp]
     l.fi_batch_decode_run.argtypes = [vp, sz, vp, sz, i64p, i32, C.POINTER(BatchDecodeParams), vp]
+    l.fi_batch_decode_run_sinks.argtypes = [vp, sz, vp, sz, i64p, i32, C.POINTER(BatchDecodeParams), vp, vp]
     l.fi_single_decode_run.argtypes = [C.POINTER(SingleDecodeParams), vp, sz, vp]
     l.fi_merge_state.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     l.fi_merge_state_in_place.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -398,6 +401,7 @@ def lib() -> C.CDLL:
     l.fi_variable_length_merge_states.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     l.fi_batch_prefill_plan.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp] + [i32] * 12 + [i64p, vp]
     l.fi_batch_prefill_paged_run.argtypes = [vp, sz, vp, sz, i64p, i32, C.POINTER(BatchPrefillParams), vp]
+    l.fi_batch_prefill_paged_run_sinks.argtypes = [vp, sz, vp, sz, i64p, i32, C.POINTER(BatchPrefillParams), vp, vp]
     l.fi_single_prefill_run.argtypes = [C.POINTER(SinglePrefillParams), vp, sz, vp]
     l.fi_batch_prefill_qkvo_run.argtypes = [vp, sz, vp, sz, i64p, i32, C.POINTER(PrefillQkvoParams), vp]
     l.fi_single_prefill_qkvo_run.argtypes = [C.POINTER(PrefillQkvoParams), vp, sz, vp]

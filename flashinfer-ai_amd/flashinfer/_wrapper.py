@@ -2,11 +2,30 @@
 of a plan's index tensors (CUDA-graph buffers or fresh device copies), and the per-run options."""
 from __future__ import annotations
 
+import functools
 from typing import Any, List, Optional, Sequence
 
 import torch
 
 from . import _lib
+
+
+def is_attention_sink_variant(jit_args: Optional[Sequence[Any]]) -> bool:
+    """True for the reference's jit_args list of the attention-sink variant (entry 11, the variant name, is
+    ``"AttentionSink"``: flashinfer/attention.py:241-255); the CUDA declaration in entry 12 is ignored, the kernels
+    here being built ahead of time."""
+    return jit_args is not None and len(jit_args) > 11 and jit_args[11] == "AttentionSink"
+
+
+def refuses_sinks(run):
+    """For the run() of a wrapper whose kernels have no attention-sink term (MLA): ``sinks=`` is answered with a
+    ValueError that says so.  The method keeps the reference's signature, which has no such parameter."""
+    @functools.wraps(run)
+    def run_without_sinks(self, *args, **kwargs):
+        if kwargs.pop("sinks", None) is not None:
+            raise ValueError(f"{type(self).__name__} does not support attention sinks")
+        return run(self, *args, **kwargs)
+    return run_without_sinks
 
 
 class BatchAttentionWrapper:
@@ -15,8 +34,11 @@ class BatchAttentionWrapper:
 
     def __init__(self, float_workspace_buffer: torch.Tensor, use_cuda_graph: bool, backend: str,
                  backends: Sequence[str], jit_args: Optional[List[Any]] = None,
-                 int_workspace_bytes: int = 8 * 1024 * 1024) -> None:
-        if jit_args is not None:
+                 int_workspace_bytes: int = 8 * 1024 * 1024, sink_variant: bool = False) -> None:
+        # sink_variant: the wrapper takes the reference's "AttentionSink" jit_args (the prefill wrappers); its run()
+        # is then run(q, <kv>, sink, sm_scale), as the reference's generated module is called
+        self._sink_variant = sink_variant and is_attention_sink_variant(jit_args)
+        if jit_args is not None and not self._sink_variant:
             raise ValueError("jit_args is not supported: kernels are built ahead of time")
         if backend not in backends:
             raise ValueError(f"backend {backend!r} is not available on MI355X (use 'auto')")
@@ -87,10 +109,33 @@ class BatchAttentionWrapper:
         self._rope_scale = rope_scale
         self._rope_theta = rope_theta
 
-    def _check_run_args(self, args=(), sinks=None) -> None:
+    def _check_run_args(self, args=()) -> None:
         if self._plan_info is None:
             raise RuntimeError("plan() must be called before run()")
-        if sinks is not None:
-            raise ValueError("attention sinks are not supported by this backend")
         if args:
             raise ValueError("additional kernel arguments require jit_args, which is not supported")
+
+    def _sink_variant_args(self, args, sinks):
+        """(args, sinks, sm_scale) of a run(): a wrapper built with the "AttentionSink" jit_args takes the sink tensor
+        and the softmax scale as its two additional positional arguments (ref: additional_tensor_names ``sink``,
+        additional_scalar_names ``sm_scale``); any other wrapper passes its arguments through, sm_scale None."""
+        if not self._sink_variant:
+            return args, sinks, None
+        if len(args) != 2 or sinks is not None:
+            raise ValueError("a wrapper built with the AttentionSink jit_args is run as run(q, <kv>, sink, sm_scale)")
+        return (), args[0], float(args[1])
+
+    def _sinks_ptr(self, sinks: Optional[torch.Tensor], q: torch.Tensor) -> int:
+        """Device pointer of the per-head attention sinks (0 for None) once they are float32, contiguous,
+        ``[num_qo_heads]`` and on the wrapper's device.  No tensor is created: run() stays capturable."""
+        if sinks is None:
+            return 0
+        if (not torch.is_tensor(sinks) or sinks.dtype != torch.float32 or sinks.dim() != 1
+                or sinks.shape[0] != self._num_qo_heads or not sinks.is_contiguous() or sinks.device != self.device):
+            raise ValueError(
+                f"sinks must be a contiguous float32 tensor of shape [{self._num_qo_heads}] (num_qo_heads) on "
+                f"{self.device}; got {getattr(sinks, 'dtype', type(sinks))} {tuple(getattr(sinks, 'shape', ()))} on "
+                f"{getattr(sinks, 'device', None)}")
+        if q.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"attention sinks need float16 or bfloat16 queries (got {q.dtype})")
+        return sinks.data_ptr()

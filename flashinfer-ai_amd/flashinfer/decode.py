@@ -197,7 +197,7 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
             the three ``paged_kv_*_buffer`` tensors are then required and the batch size is fixed.
         use_tensor_cores : accepted; selects the MFMA path when available.
         backend : ``auto`` / ``fa2`` (one native backend exists; NVIDIA-only names are rejected).
-        jit_args : must be None -- there is no JIT in this build.
+        jit_args : must be None -- there is no JIT in this build (attention sinks go through ``run(sinks=)``).
         """
         _check_kv_layout(kv_layout)
         super().__init__(float_workspace_buffer, use_cuda_graph, backend, ("auto", "fa2"), jit_args)
@@ -354,13 +354,18 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
         paged_kv_cache : a 5-D tensor ``[max_num_pages, 2, page_size, num_kv_heads, head_dim]`` (NHD) /
             ``[max_num_pages, 2, num_kv_heads, page_size, head_dim]`` (HND), or a ``(k_cache, v_cache)``
             tuple of 4-D tensors.
+        sinks : optional float32 ``[num_qo_heads]`` on the wrapper's device, contiguous: one attention-sink logit per
+            head (natural-log units, not multiplied by ``sm_scale``) that joins the softmax denominator without a
+            value vector (ref: flashinfer/jit/attention/variants.py:17-53).  ``-inf`` switches a head's sink off.  The
+            returned logsumexp includes the sink, so a state with a folded sink must not be merged again
+            (``merge_state`` and the cascade wrappers would count it twice).  The tensor is read when the kernels
+            run: a captured ``run`` sees the values it holds at replay.
         Returns the output ``[batch_size, num_qo_heads, head_dim]`` (and the base-2 logsumexp
         ``[batch_size, num_qo_heads]`` when ``return_lse``).  (ref: flashinfer/decode.py:1163-1374)
         """
         if self._plan_info is None:
             raise RuntimeError("plan() must be called before run()")
-        if sinks is not None:
-            raise ValueError("attention sinks are not supported by this backend")
+        sinks_ptr = 0 if sinks is None else self._sinks_ptr(sinks, q)
         if args:
             raise ValueError("additional kernel arguments require jit_args, which is not supported")
         window_left = self._window_left if window_left is None else window_left
@@ -375,7 +380,7 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
         cache_t = paged_kv_cache if torch.is_tensor(paged_kv_cache) else paged_kv_cache[0]
         key = (q.data_ptr(), q.stride(), q.shape, cache_t.data_ptr(), cache_t.stride(), cache_t.shape,
                None if torch.is_tensor(paged_kv_cache) else paged_kv_cache[1].data_ptr(),
-               out.data_ptr(), lse.data_ptr() if return_lse else 0, q_scale, k_scale, self._plan_serial)
+               out.data_ptr(), lse.data_ptr() if return_lse else 0, q_scale, k_scale, self._plan_serial, sinks_ptr)
         cached = self._run_cache
         if cached is not None and cached[0] == key:
             params = cached[1]
@@ -383,7 +388,17 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
             params = self._build_run_params(q, paged_kv_cache, q_scale, k_scale, out, lse if return_lse else None)
             self._run_cache = (key, params, q, paged_kv_cache)  # keep the tensors alive with the pointers
         dev_index = q.device.index
-        if torch.cuda.current_device() == dev_index:
+        if sinks_ptr:
+            if torch.cuda.current_device() == dev_index:
+                status = self._lib_run_sinks(self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes,
+                                             self._plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, params, sinks_ptr,
+                                             torch.cuda.current_stream().cuda_stream)
+            else:
+                with torch.cuda.device(q.device):
+                    status = self._lib_run_sinks(self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes,
+                                                 self._plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, params, sinks_ptr,
+                                                 torch.cuda.current_stream().cuda_stream)
+        elif torch.cuda.current_device() == dev_index:
             status = self._lib_run(self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes,
                                    self._plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, params,
                                    torch.cuda.current_stream().cuda_stream)
@@ -438,6 +453,7 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
         )
         self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes = self._workspace_args
         self._lib_run = _lib.lib().fi_batch_decode_run
+        self._lib_run_sinks = _lib.lib().fi_batch_decode_run_sinks
         return C.byref(params)
 
     def forward_return_lse(

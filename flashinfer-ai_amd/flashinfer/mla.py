@@ -12,7 +12,7 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import _lib
-from ._wrapper import BatchAttentionWrapper
+from ._wrapper import BatchAttentionWrapper, refuses_sinks
 
 _MLA_INT_WORKSPACE_BYTES = 8 * 1024 * 1024
 
@@ -128,6 +128,7 @@ class BatchMLAPagedAttentionWrapper(BatchAttentionWrapper):
         self._q_data_type = q_data_type
         self._kv_data_type = kv_data_type
 
+    @refuses_sinks
     def run(
         self,
         q_nope: torch.Tensor,

@@ -167,9 +167,12 @@ def _run_single_prefill(run_fn, params, device):
 
 
 def _run_batch_prefill(wrapper, name, q, kv, o_dtype, out, lse, return_lse, window_left, q_scale, k_scale, v_scale,
-                       scale_q=None, scale_k=None, scale_v=None):
+                       scale_q=None, scale_k=None, scale_v=None, sinks=None, sm_scale=None):
     """run() of the paged and ragged wrappers once the kv view ``kv`` (a ``_lib.PagedKV``; ragged: an identity table
-    of one-token pages) is resolved and checked against the plan: out / lse, fi_batch_prefill_paged_run, v_scale."""
+    of one-token pages) is resolved and checked against the plan: out / lse, fi_batch_prefill_paged_run, v_scale.
+    ``sinks``: the per-head attention sinks (then fi_batch_prefill_paged_run_sinks); ``sm_scale``: a softmax scale
+    given to this run() in place of the planned one (the AttentionSink call form)."""
+    sinks_ptr = wrapper._sinks_ptr(sinks, q)
     if q.stride(-1) != 1:
         q = q.contiguous()
     out, lse = _out_and_lse(q, out, lse, return_lse, q.shape[:-1] + (kv.head_dim,), o_dtype)
@@ -185,17 +188,18 @@ def _run_batch_prefill(wrapper, name, q, kv, o_dtype, out, lse, return_lse, wind
         max_item_len_ptr=_lib.ptr(wrapper._max_item_len_ptr), token_pos_in_items_len=wrapper._token_pos_in_items_len,
         mask_mode=_mask_mode(wrapper), pos_encoding_mode=PosEncodingMode[wrapper._pos_encoding_mode].value,
         window_left=window_left, bf16_pv_mode=wrapper._bf16_pv_mode,
-        **_resolve_logits_params(q.size(-1), wrapper._sm_scale, q_scale, k_scale, wrapper._logits_soft_cap,
-                                 wrapper._rope_scale, wrapper._rope_theta),
+        **_resolve_logits_params(q.size(-1), wrapper._sm_scale if sm_scale is None else sm_scale, q_scale, k_scale,
+                                 wrapper._logits_soft_cap, wrapper._rope_scale, wrapper._rope_theta),
     )
     with torch.cuda.device(q.device):
-        _lib.check(
-            _lib.lib().fi_batch_prefill_paged_run(
-                *wrapper._workspace_args, wrapper._plan_info, _lib.FI_PREFILL_PLAN_INFO_LEN, C.byref(params),
-                _lib.current_stream(q.device),
-            ),
-            name,
-        )
+        plan_and_params = (wrapper._plan_info, _lib.FI_PREFILL_PLAN_INFO_LEN, C.byref(params))
+        if sinks_ptr:
+            status = _lib.lib().fi_batch_prefill_paged_run_sinks(
+                *wrapper._workspace_args, *plan_and_params, sinks_ptr, _lib.current_stream(q.device))
+        else:
+            status = _lib.lib().fi_batch_prefill_paged_run(
+                *wrapper._workspace_args, *plan_and_params, _lib.current_stream(q.device))
+        _lib.check(status, name)
     if v_scale is not None:
         out = _apply_v_scale(out, v_scale)
     return (out, lse) if return_lse else out
@@ -399,7 +403,10 @@ class BatchPrefillWithPagedKVCacheWrapper(BatchAttentionWrapper):
         jit_kwargs: Optional[dict] = None,
     ) -> None:
         _check_kv_layout(kv_layout)
-        super().__init__(float_workspace_buffer, use_cuda_graph, backend, ("auto", "fa2", "fa3"), jit_args)
+        # jit_args: None, or the reference's list for the "AttentionSink" variant (flashinfer/attention.py:241-255),
+        # which makes run() take (q, paged_kv_cache, sink, sm_scale); jit_kwargs is accepted and unused
+        super().__init__(float_workspace_buffer, use_cuda_graph, backend, ("auto", "fa2", "fa3"), jit_args,
+                         sink_variant=True)
         self._kv_layout = kv_layout
         if use_cuda_graph:
             for buf, name in ((qo_indptr_buf, "qo_indptr_buf"), (paged_kv_indptr_buf, "paged_kv_indptr_buf"),
@@ -571,10 +578,18 @@ class BatchPrefillWithPagedKVCacheWrapper(BatchAttentionWrapper):
         scale_q / scale_k / scale_v : (extension) per-head fp8 scales ``[num_qo_heads]`` / ``[num_kv_heads]``
             for fp8 attention (the reference's FA3 kernel takes them, csrc/batch_prefill_fp8_sm90.cu:81-185,
             but its wrapper passes None).
+        sinks : optional float32 ``[num_qo_heads]`` on the wrapper's device, contiguous: one attention-sink logit per
+            head (natural-log units, not multiplied by ``sm_scale``) that joins the softmax denominator of every query
+            row without a value vector (ref: flashinfer/jit/attention/variants.py:17-53); float16 / bfloat16 queries
+            only.  ``-inf`` switches a head's sink off.  The returned logsumexp includes the sink, so a state with a
+            folded sink must not be merged again (``merge_state`` and the cascade wrappers would count it twice).
+        A wrapper built with the reference's "AttentionSink" ``jit_args`` is called as
+        ``run(q, paged_kv_cache, sink, sm_scale)``.
         Returns ``[qo_indptr[-1], num_qo_heads, head_dim]`` (+ base-2 logsumexp ``[nnz, num_qo_heads]``).
         (ref: flashinfer/prefill.py:1979-2206)
         """
-        self._check_run_args(args, sinks)
+        args, sinks, sm_scale = self._sink_variant_args(args, sinks)
+        self._check_run_args(args)
         _lib.require_gpu_tensor(q, "q")
         k_cache, v_cache = _unpack_paged_kv_cache(paged_kv_cache, self._kv_layout)
         _check_cached_qkv_data_type(q, k_cache, self._cached_q_data_type, self._cached_kv_data_type)
@@ -597,7 +612,8 @@ class BatchPrefillWithPagedKVCacheWrapper(BatchAttentionWrapper):
         return _run_batch_prefill(
             self, "BatchPrefillWithPagedKVCacheWrapper.run", q, kv, self._cached_o_data_type, out, lse, return_lse,
             window_left, q_scale, k_scale, v_scale, _scale_tensor(scale_q, self._num_qo_heads, q.device),
-            _scale_tensor(scale_k, num_kv_heads, q.device), _scale_tensor(scale_v, num_kv_heads, q.device))
+            _scale_tensor(scale_k, num_kv_heads, q.device), _scale_tensor(scale_v, num_kv_heads, q.device),
+            sinks=sinks, sm_scale=sm_scale)
 
     run_return_lse = functools.partialmethod(run, return_lse=True)
 
@@ -636,7 +652,9 @@ class BatchPrefillWithRaggedKVCacheWrapper(BatchAttentionWrapper):
         jit_kwargs: Optional[dict] = None,
     ) -> None:
         _check_kv_layout(kv_layout)
-        super().__init__(float_workspace_buffer, use_cuda_graph, backend, ("auto", "fa2", "fa3"), jit_args)
+        # jit_args: None, or the reference's "AttentionSink" list: run() is then run(q, k, v, sink, sm_scale)
+        super().__init__(float_workspace_buffer, use_cuda_graph, backend, ("auto", "fa2", "fa3"), jit_args,
+                         sink_variant=True)
         self._kv_layout = kv_layout
         if use_cuda_graph:
             if not torch.is_tensor(qo_indptr_buf) or not torch.is_tensor(kv_indptr_buf):
@@ -743,7 +761,13 @@ class BatchPrefillWithRaggedKVCacheWrapper(BatchAttentionWrapper):
         return_lse: bool = False,
         enable_pdl: Optional[bool] = None,
     ) -> Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
-        r"""q ``[qo_indptr[-1], num_qo_heads, head_dim]``; k, v ragged as described in the class docstring."""
+        r"""q ``[qo_indptr[-1], num_qo_heads, head_dim]``; k, v ragged as described in the class docstring.
+
+        A wrapper built with the reference's "AttentionSink" ``jit_args`` (tests/attention/test_attention_sink.py
+        :162-235) is called as ``run(q, k, v, sink, sm_scale)``: ``sink`` is float32 ``[num_qo_heads]``, one logit per
+        head that joins the softmax denominator (see :meth:`BatchPrefillWithPagedKVCacheWrapper.run`); the returned
+        state must not be merged again.  Not at head_dim_qk 192 / head_dim_vo 128."""
+        args, sinks, sm_scale = self._sink_variant_args(args, None)
         self._check_run_args(args)
         for t, name in ((q, "q"), (k, "k"), (v, "v")):
             _lib.require_gpu_tensor(t, name)
@@ -751,6 +775,8 @@ class BatchPrefillWithRaggedKVCacheWrapper(BatchAttentionWrapper):
         if is_float8(q):
             raise ValueError("fp8 queries are supported by the paged wrapper only")
         if self._qkvo:
+            if sinks is not None:
+                raise ValueError("attention sinks are not supported at head_dim_qk 192 / head_dim_vo 128")
             return self._run_qkvo(q, k, v, q_scale, k_scale, v_scale, out, lse, return_lse)
         if k.shape != v.shape or k.stride() != v.stride() or k.dim() != 3 or k.stride(-1) != 1:
             raise ValueError("k and v must be 3-D with equal shapes/strides, contiguous in head_dim")
@@ -761,7 +787,8 @@ class BatchPrefillWithRaggedKVCacheWrapper(BatchAttentionWrapper):
         if q.dim() != 3 or q.shape[0] != self._total_num_rows or q.shape[1] != self._num_qo_heads:
             raise ValueError("q shape does not match the plan")
         return _run_batch_prefill(self, "BatchPrefillWithRaggedKVCacheWrapper.run", q, kv, q.dtype, out, lse,
-                                  return_lse, self._window_left, q_scale, k_scale, v_scale)
+                                  return_lse, self._window_left, q_scale, k_scale, v_scale, sinks=sinks,
+                                  sm_scale=sm_scale)
 
     def _run_qkvo(self, q, k, v, q_scale, k_scale, v_scale, out, lse, return_lse):
         """run() of a head_dim_qk 192 / head_dim_vo 128 plan: k and v by their own strides, no copy."""

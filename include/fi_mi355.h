@@ -18,6 +18,15 @@
  *   - strides are in ELEMENTS, not bytes (as paged_kv_t, ref: include/flashinfer/page.cuh:127-145).
  *   - log-sum-exp values are base 2 (ref: include/flashinfer/attention/state.cuh:45), and an empty
  *     KV range yields o = 0, lse = FI_NEG_INF (-5e4, ref: include/flashinfer/math.cuh:32).
+ *   - attention sinks (the *_run_sinks entry points; ref: AttentionSink, flashinfer/jit/attention/variants.py:17-53):
+ *     `sinks` is f32 [num_qo_heads] on the device, one logit per head in natural-log units, NOT multiplied by
+ *     sm_scale.  Row probabilities become p_j = exp(s_j) / (sum_k exp(s_k) + exp(sink_h)) over the final logits s
+ *     (after sm_scale, soft cap, mask and window); the sink has no value vector.  The result is the state (o, lse)
+ *     merged with (0, sink_h * log2(e)), and the returned lse includes the sink:
+ *     lse' = log2(2^lse + 2^(sink_h * log2(e))).  Such a state must not be merged with others again.  What the
+ *     reference does not pin: an empty KV range with a finite sink gives o = 0, lse = sink_h * log2(e);
+ *     sink_h = -inf switches the sink off for that head (o and lse are bit for bit those of the run without sinks);
+ *     an empty KV range with sink_h = -inf gives o = 0, lse = FI_NEG_INF.  sinks == NULL is the plain run.
  */
 #ifndef FI_MI355_H_
 #define FI_MI355_H_
@@ -149,6 +158,13 @@ typedef struct fi_batch_decode_params {
 FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes, void* int_ws, size_t int_ws_bytes,
                         const int64_t* plan_info, int32_t plan_info_len,
                         const fi_batch_decode_params_t* params, fi_stream_t stream);
+/* fi_batch_decode_run with attention sinks (see Conventions; ref: flashinfer/jit/attention/variants.py:17-53, the
+ * `sinks` argument of BatchDecodeWithPagedKVCacheWrapper.run, flashinfer/decode.py:1163-1374).  The sink is folded
+ * once per output row, in the launch that writes the final output (the merge launch of a split plan): no extra
+ * launch.  sinks == NULL is fi_batch_decode_run. */
+FI_API int fi_batch_decode_run_sinks(void* float_ws, size_t float_ws_bytes, void* int_ws, size_t int_ws_bytes,
+                              const int64_t* plan_info, int32_t plan_info_len,
+                              const fi_batch_decode_params_t* params, const float* sinks, fi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Single-request decode over a dense KV tensor.
@@ -289,6 +305,14 @@ typedef struct fi_batch_prefill_params {
 FI_API int fi_batch_prefill_paged_run(void* float_ws, size_t float_ws_bytes, void* int_ws, size_t int_ws_bytes,
                                const int64_t* plan_info, int32_t plan_info_len,
                                const fi_batch_prefill_params_t* params, fi_stream_t stream);
+/* fi_batch_prefill_paged_run (paged, or ragged K / V in the page_size = 1 form above) with attention sinks (see
+ * Conventions; ref: flashinfer/jit/attention/variants.py:17-53, BatchAttentionWithAttentionSinkWrapper,
+ * flashinfer/attention.py:201-275).  f16 / bf16 queries only: fp8 queries with sinks != NULL are refused before any
+ * launch, and so is a head_dim_qk 192 / head_dim_vo 128 plan.  sinks == NULL is fi_batch_prefill_paged_run. */
+FI_API int fi_batch_prefill_paged_run_sinks(void* float_ws, size_t float_ws_bytes, void* int_ws, size_t int_ws_bytes,
+                                     const int64_t* plan_info, int32_t plan_info_len,
+                                     const fi_batch_prefill_params_t* params, const float* sinks,
+                                     fi_stream_t stream);
 
 /* Single-request prefill over dense K/V.  ref: csrc/single_prefill.cu, flashinfer/prefill.py:960-1194. */
 typedef struct fi_single_prefill_params {
