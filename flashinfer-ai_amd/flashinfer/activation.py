@@ -43,7 +43,7 @@ def get_act_and_mul_module(act_func_name: str):
             raise ValueError(f"out has shape {tuple(out.shape)}, expected {tuple(input.shape[:-1]) + (d,)}")
         x = input.contiguous()
         o = out if out.is_contiguous() else torch.empty_like(out, memory_format=torch.contiguous_format)
-        p = _lib.ActAndMulParams(in_=x.data_ptr(), out=o.data_ptr(), tokens=o.numel() // d if d else 0, d=d, act=code,
+        p = _lib.fi_act_and_mul_params_t(in_=x.data_ptr(), out=o.data_ptr(), tokens=o.numel() // d if d else 0, d=d, act=code,
                                  dtype=_lib.fi_dtype(input.dtype))
         with torch.cuda.device(input.device):
             _lib.check(_lib.lib().fi_act_and_mul(C.byref(p), _lib.current_stream(input.device)), fname)

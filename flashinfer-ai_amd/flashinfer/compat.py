@@ -66,7 +66,7 @@ def get_batch_decode_module(dtype_q, dtype_kv, dtype_o, idtype, head_dim_qk, hea
         1/rope_theta here (flashinfer/decode.py:264-268)."""
         kv = paged_kv(paged_k_cache, paged_v_cache, _kv_layout(kv_layout_code), paged_kv_indptr, paged_kv_indices,
                       paged_kv_last_page_len, q.shape[0])[0]
-        p = _lib.BatchDecodeParams(
+        p = _lib.fi_batch_decode_params_t(
             q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), kv=kv, o=o.data_ptr(),
             lse=_lib.ptr(maybe_lse), alibi_slopes=_lib.ptr(maybe_alibi_slopes), q_rope_offset=None,
             num_qo_heads=q.shape[1], q_dtype=_lib.fi_dtype(q.dtype), pos_encoding_mode=pos_encoding_mode,
@@ -107,7 +107,7 @@ def get_batch_prefill_module(backend, dtype_q, dtype_kv, dtype_o, idtype, head_d
              window_left, custom_mask, mask_indptr, alibi_slopes, prefix_len_ptr, token_pos_in_items_ptr,
              max_item_len_ptr, token_pos_in_items_len, logits_soft_cap, sm_scale, rope_rcp_scale, rope_rcp_theta,
              scale_q, scale_k, scale_v, what):
-        p = _lib.BatchPrefillParams(
+        p = _lib.fi_batch_prefill_params_t(
             q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), qo_indptr=qo_indptr.data_ptr(), kv=kv,
             o=o.data_ptr(), lse=_lib.ptr(maybe_lse), alibi_slopes=_lib.ptr(alibi_slopes), scale_q=_lib.ptr(scale_q),
             scale_k=_lib.ptr(scale_k), scale_v=_lib.ptr(scale_v), custom_mask=_lib.ptr(custom_mask),

@@ -142,7 +142,7 @@ def single_decode_with_kv_cache(
     if pos_encoding_mode == "ALIBI":
         alibi = _get_cache_alibi_slopes_buf(num_qo_heads, q.device)
 
-    params = _lib.SingleDecodeParams(
+    params = _lib.fi_single_decode_params_t(
         q=q.data_ptr(), q_stride_h=q.stride(0), k=k.data_ptr(), v=v.data_ptr(),
         kv_stride_n=stride_n, kv_stride_h=stride_h, o=out.data_ptr(), lse=_lib.ptr(lse),
         alibi_slopes=_lib.ptr(alibi), kv_len=kv_len, num_qo_heads=num_qo_heads,
@@ -441,7 +441,7 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
         alibi = None
         if pos_encoding_mode == "ALIBI":
             alibi = _get_cache_alibi_slopes_buf(q.shape[1], q.device)
-        params = _lib.BatchDecodeParams(
+        params = _lib.fi_batch_decode_params_t(
             q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1),
             kv=kv,
             o=out.data_ptr(), lse=_lib.ptr(lse),

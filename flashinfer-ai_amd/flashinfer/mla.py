@@ -101,7 +101,7 @@ class BatchMLAPagedAttentionWrapper(BatchAttentionWrapper):
                 )
         self._bind_index_tensors(batch_size, True, prefix=("kv_indices",), qo_indptr=qo_indptr, kv_indptr=kv_indptr,
                                  kv_indices=kv_indices, kv_len_arr=kv_len_arr)
-        params = _lib.MlaPlanParams(
+        params = _lib.fi_batch_mla_plan_params_t(
             int_ws=self._int_workspace_buffer.data_ptr(),
             pinned_int_ws=self._pin_memory_int_workspace_buffer.data_ptr(),
             int_ws_bytes=_lib.nbytes(self._int_workspace_buffer),
@@ -183,7 +183,7 @@ class BatchMLAPagedAttentionWrapper(BatchAttentionWrapper):
             elif lse.shape != (nnz, H) or lse.dtype != torch.float32 or not lse.is_contiguous():
                 raise ValueError("lse must be a contiguous float32 [nnz, num_heads] tensor")
         float_ws, float_ws_bytes, int_ws, int_ws_bytes = self._workspace_args
-        params = _lib.MlaParams(
+        params = _lib.fi_batch_mla_params_t(
             q_nope=q_nope.data_ptr(), q_nope_stride_n=q_nope.stride(0), q_nope_stride_h=q_nope.stride(1),
             q_pe=q_pe.data_ptr(), q_pe_stride_n=q_pe.stride(0), q_pe_stride_h=q_pe.stride(1),
             ckv=ckv3.data_ptr(), ckv_stride_page=ckv3.stride(0), ckv_stride_n=ckv3.stride(1),

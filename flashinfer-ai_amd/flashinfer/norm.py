@@ -65,7 +65,7 @@ def _rmsnorm_into(out: torch.Tensor, input: torch.Tensor, weight: torch.Tensor, 
         heads, packed_n = input.shape[1], input.shape[1] * hidden
         strides = (_stride(input, 0, packed_n), _stride(input, 1, hidden), _stride(out, 0, packed_n),
                    _stride(out, 1, hidden))
-    p = _lib.RmsNormParams(
+    p = _lib.fi_rmsnorm_params_t(
         in_=input.data_ptr(), weight=weight.data_ptr(), out=out.data_ptr(), batch=input.shape[0], num_heads=heads,
         hidden=hidden, in_stride_n=strides[0], in_stride_h=strides[1], out_stride_n=strides[2],
         out_stride_h=strides[3], eps=float(eps), weight_bias=weight_bias, dtype=_lib.fi_dtype(input.dtype))
@@ -83,7 +83,7 @@ def _fused_add_rmsnorm(input: torch.Tensor, residual: torch.Tensor, weight: torc
     _check_weight(weight, input)
     weight = weight.contiguous()
     hidden = input.shape[1]
-    p = _lib.FusedAddRmsNormParams(
+    p = _lib.fi_fused_add_rmsnorm_params_t(
         input=input.data_ptr(), residual=residual.data_ptr(), weight=weight.data_ptr(), batch=input.shape[0],
         hidden=hidden, input_stride=_stride(input, 0, hidden), residual_stride=_stride(residual, 0, hidden),
         eps=float(eps), weight_bias=weight_bias, dtype=_lib.fi_dtype(input.dtype))

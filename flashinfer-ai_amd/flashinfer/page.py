@@ -177,7 +177,7 @@ def apply_rope_append_paged_kv_cache(
     nnz = append_key.shape[0]
     if batch_indices.numel() != nnz or positions.numel() != nnz or pos_ids.numel() != nnz:
         raise ValueError("batch_indices, positions and pos_ids must have nnz entries")
-    params = _lib.RopeParams(
+    params = _lib.fi_rope_params_t(
         q=q.data_ptr(), k=append_key.data_ptr(), q_out=q_out.data_ptr(), k_out=None, pos_ids=pos_ids.data_ptr(),
         cos_sin_cache=None, q_stride_n=q.stride(0), q_stride_h=q.stride(1), k_stride_n=append_key.stride(0),
         k_stride_h=append_key.stride(1), qo_stride_n=q_out.stride(0), qo_stride_h=q_out.stride(1), ko_stride_n=0,
@@ -242,7 +242,7 @@ def append_paged_mla_kv_cache(
     kv_indptr = kv_indptr.to(device=dev, dtype=torch.int32).contiguous()
     if batch_indices.numel() != nnz or positions.numel() != nnz:
         raise ValueError("batch_indices and positions must have nnz entries")
-    p = _lib.AppendMlaParams(
+    p = _lib.fi_append_paged_mla_kv_params_t(
         append_ckv=append_ckv.data_ptr(), append_ckv_stride_n=append_ckv.stride(0),
         append_kpe=append_kpe.data_ptr(), append_kpe_stride_n=append_kpe.stride(0),
         batch_indices=batch_indices.data_ptr(), positions=positions.data_ptr(),

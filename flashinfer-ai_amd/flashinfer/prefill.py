@@ -168,8 +168,8 @@ def _run_single_prefill(run_fn, params, device):
 
 def _run_batch_prefill(wrapper, name, q, kv, o_dtype, out, lse, return_lse, window_left, q_scale, k_scale, v_scale,
                        scale_q=None, scale_k=None, scale_v=None, sinks=None, sm_scale=None):
-    """run() of the paged and ragged wrappers once the kv view ``kv`` (a ``_lib.PagedKV``; ragged: an identity table
-    of one-token pages) is resolved and checked against the plan: out / lse, fi_batch_prefill_paged_run, v_scale.
+    """run() of the paged and ragged wrappers once the kv view ``kv`` (a ``_lib.fi_paged_kv_t``; ragged: an identity
+    table of one-token pages) is resolved and checked against the plan: out / lse, fi_batch_prefill_paged_run, v_scale.
     ``sinks``: the per-head attention sinks (then fi_batch_prefill_paged_run_sinks); ``sm_scale``: a softmax scale
     given to this run() in place of the planned one (the AttentionSink call form)."""
     sinks_ptr = wrapper._sinks_ptr(sinks, q)
@@ -177,7 +177,7 @@ def _run_batch_prefill(wrapper, name, q, kv, o_dtype, out, lse, return_lse, wind
         q = q.contiguous()
     out, lse = _out_and_lse(q, out, lse, return_lse, q.shape[:-1] + (kv.head_dim,), o_dtype)
     alibi = _get_cache_alibi_slopes_buf(q.shape[1], q.device) if wrapper._pos_encoding_mode == "ALIBI" else None
-    params = _lib.BatchPrefillParams(
+    params = _lib.fi_batch_prefill_params_t(
         q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), qo_indptr=wrapper._qo_indptr_buf.data_ptr(),
         kv=kv, o=out.data_ptr(), lse=_lib.ptr(lse), alibi_slopes=_lib.ptr(alibi),
         scale_q=_lib.ptr(scale_q), scale_k=_lib.ptr(scale_k), scale_v=_lib.ptr(scale_v),
@@ -234,7 +234,7 @@ def _qkvo_params(q, k, v, kv_layout, out, lse, causal, window_left, sm_scale, bf
     _, num_kv_heads, k_sn, k_sh = dense_kv_dims(k, kv_layout)
     _, _, v_sn, v_sh = dense_kv_dims(v, kv_layout)
     dt = _lib.fi_dtype(q.dtype)
-    return _lib.PrefillQkvoParams(
+    return _lib.fi_prefill_qkvo_params_t(
         q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), k=k.data_ptr(), k_stride_n=k_sn,
         k_stride_h=k_sh, v=v.data_ptr(), v_stride_n=v_sn, v_stride_h=v_sh, o=out.data_ptr(), lse=_lib.ptr(lse),
         num_qo_heads=q.shape[1], num_kv_heads=num_kv_heads,
@@ -353,7 +353,7 @@ def single_prefill_with_kv_cache(
             raise ValueError("packed_custom_mask must be uint8 with at least qo_len * kv_len bits")
         packed_custom_mask = packed_custom_mask.contiguous()
     alibi = _get_cache_alibi_slopes_buf(num_qo_heads, q.device) if pos_encoding_mode == "ALIBI" else None
-    params = _lib.SinglePrefillParams(
+    params = _lib.fi_single_prefill_params_t(
         q=q.data_ptr(), q_stride_n=q.stride(0), q_stride_h=q.stride(1), k=k.data_ptr(), v=v.data_ptr(),
         kv_stride_n=stride_n, kv_stride_h=stride_h, o=out.data_ptr(), lse=_lib.ptr(lse),
         alibi_slopes=_lib.ptr(alibi), scale_q=_lib.ptr(scale_q), scale_k=_lib.ptr(scale_k),

@@ -31,7 +31,7 @@ def _run(q, k, q_out, k_out, pos_ids, rotary_dim, interleave, rope_scale, rope_t
     pos_ids = pos_ids.to(device=q.device, dtype=torch.int32).contiguous()
     if pos_ids.numel() != q.shape[0]:
         raise ValueError("pos_ids must have nnz entries")
-    params = _lib.RopeParams(
+    params = _lib.fi_rope_params_t(
         q=q.data_ptr(), k=k.data_ptr(), q_out=q_out.data_ptr(), k_out=k_out.data_ptr(), pos_ids=pos_ids.data_ptr(),
         cos_sin_cache=_lib.ptr(cos_sin_cache), q_stride_n=q.stride(0), q_stride_h=q.stride(1),
         k_stride_n=k.stride(0), k_stride_h=k.stride(1), qo_stride_n=q_out.stride(0), qo_stride_h=q_out.stride(1),

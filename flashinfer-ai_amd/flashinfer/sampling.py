@@ -84,7 +84,7 @@ def _draw(symbol: str, probs: torch.Tensor, indices: Optional[torch.Tensor], inc
     param_len = max([a.numel() for a in (k_arr, p_arr) if a is not None], default=0)
     samples = torch.empty(batch, dtype=torch.int32, device=dev)
     seed, offset = _seed_and_offset(batch * increment_per_row, generator, dev)
-    p = _lib.SamplingParams(
+    p = _lib.fi_sampling_params_t(
         probs=probs.data_ptr(), samples=samples.data_ptr(), indices=_lib.ptr(idx), top_k_arr=_lib.ptr(k_arr),
         top_p_arr=_lib.ptr(p_arr), top_k_val=int(top_k_val), top_p_val=float(top_p_val), batch=batch,
         num_rows=probs.shape[0], vocab=probs.shape[1], param_len=param_len, philox_seed=_u64(seed),
@@ -101,7 +101,7 @@ def _transform(symbol: str, x: torch.Tensor, name: str, top_k_arr=None, top_k_va
     out = torch.empty_like(x)
     k_arr, s_arr = _arr(top_k_arr, torch.int32, dev), _arr(scalar_arr, torch.float32, dev)
     param_len = max([a.numel() for a in (k_arr, s_arr) if a is not None], default=0)
-    p = _lib.RowTransformParams(
+    p = _lib.fi_row_transform_params_t(
         in_=x.data_ptr(), out=out.data_ptr(), top_k_arr=_lib.ptr(k_arr), scalar_arr=_lib.ptr(s_arr),
         top_k_val=int(top_k_val), scalar_val=float(scalar_val), batch=x.shape[0], vocab=x.shape[1],
         param_len=param_len)
@@ -184,7 +184,7 @@ def get_sampling_module():
         emi = output_emitted_draft_token_num.int().contiguous()
         out = torch.empty((b, n + 1), dtype=torch.int32, device=dev)
         seed, offset = _seed_and_offset(b * (n + 1), generator, dev)
-        p = _lib.ChainSpeculativeParams(
+        p = _lib.fi_chain_speculative_params_t(
             draft_probs=draft.data_ptr(), draft_token_ids=ids.data_ptr(), target_probs=target.data_ptr(),
             output_token_ids=out.data_ptr(), output_accepted_token_num=acc.data_ptr(),
             output_emitted_draft_token_num=emi.data_ptr(), batch=b, num_speculative_tokens=n, vocab=d,

@@ -124,7 +124,7 @@ def paged_kv(k_cache: torch.Tensor, v_cache: torch.Tensor, kv_layout: str, indpt
     else:
         _, num_kv_heads, page_size, head_dim = k_cache.shape
         stride_h, stride_n = k_cache.stride(1), k_cache.stride(2)
-    kv = _lib.PagedKV(
+    kv = _lib.fi_paged_kv_t(
         k_data=k_cache.data_ptr(), v_data=v_cache.data_ptr(), indptr=indptr.data_ptr(),
         indices=None if indices is None else indices.data_ptr(),
         last_page_len=None if last_page_len is None else last_page_len.data_ptr(), rope_pos_offset=None,
@@ -135,11 +135,11 @@ def paged_kv(k_cache: torch.Tensor, v_cache: torch.Tensor, kv_layout: str, indpt
 
 
 def ragged_kv(k: torch.Tensor, v: torch.Tensor, kv_layout: str, kv_indptr: torch.Tensor,
-              batch_size: int) -> _lib.PagedKV:
+              batch_size: int) -> _lib.fi_paged_kv_t:
     """fi_paged_kv of ragged 3-D k / v (which share strides): an identity table of one-token pages
     (see include/fi_mi355.h)."""
     _, num_kv_heads, stride_n, stride_h = dense_kv_dims(k, kv_layout)
-    return _lib.PagedKV(
+    return _lib.fi_paged_kv_t(
         k_data=k.data_ptr(), v_data=v.data_ptr(), indptr=kv_indptr.data_ptr(), indices=None, last_page_len=None,
         rope_pos_offset=None, stride_page=stride_n, stride_n=stride_n, stride_h=stride_h, page_size=1,
         num_kv_heads=num_kv_heads, head_dim=k.shape[2], batch_size=batch_size, dtype=_lib.fi_dtype(k.dtype),

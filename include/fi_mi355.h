@@ -27,6 +27,12 @@
  *     reference does not pin: an empty KV range with a finite sink gives o = 0, lse = sink_h * log2(e);
  *     sink_h = -inf switches the sink off for that head (o and lse are bit for bit those of the run without sinks);
  *     an empty KV range with sink_h = -inf gives o = 0, lse = FI_NEG_INF.  sinks == NULL is the plain run.
+ *
+ * This file is also the source of the Python binding: flashinfer/_abi.py parses it at import into the ctypes
+ * structures, prototypes and constants (there is no second copy to edit).  Keep declarations in the forms already
+ * used here -- `typedef struct tag { ... } tag_t;` with scalar, pointer and struct-typed fields, `FI_API <ret>
+ * fi_xxx(<params>);`, `#define FI_NAME <integer or float literal>`, enums with an explicit value for every
+ * enumerator -- and no arrays, bit-fields, unions or function pointers: the parser refuses what it does not know.
  */
 #ifndef FI_MI355_H_
 #define FI_MI355_H_

@@ -1,8 +1,12 @@
 """CPU: the C-ABI library loads and exports every symbol include/fi_mi355.h declares; host-side argument
-validation reports through fi_last_error().  No kernel is launched here."""
+validation reports through fi_last_error(); the ctypes binding read from the header lays every struct out as the
+compiler does.  No kernel is launched here."""
 import ctypes as C
+import keyword
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -75,3 +79,71 @@ def test_ops_fail_loudly_on_cpu_tensors():
         flashinfer.single_decode_with_kv_cache(q, k, k)
     with pytest.raises(RuntimeError, match="GPU"):
         flashinfer.merge_state(torch.zeros(1, 1, 64), torch.zeros(1, 1), torch.zeros(1, 1, 64), torch.zeros(1, 1))
+
+
+def host_clang():
+    """The clang beside hipcc: the compiler the library itself is built with."""
+    hipcc = shutil.which("hipcc")
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    if hipcc:
+        rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
+    for cand in (os.path.join(rocm, "llvm", "bin", "clang"), os.path.join(rocm, "lib", "llvm", "bin", "clang")):
+        if os.path.exists(cand):
+            return cand
+    pytest.fail(f"no clang under {rocm}: the library cannot be built without it either")
+
+
+def compiler_layouts(tmp_path, names):
+    """{struct tag: ([(byte offset, field name), ...] top level in order, sizeof)} from clang's record-layout dump."""
+    src = tmp_path / "layouts.c"
+    src.write_text(f'#include "{HEADER}"\n' + "".join(f"{n} var_{n};\n" for n in names))
+    cmd = [host_clang(), "-c", "-Xclang", "-fdump-record-layouts", str(src), "-o", str(tmp_path / "layouts.o")]
+    dump = subprocess.run(cmd, check=True, capture_output=True, text=True).stdout
+    layouts = {}
+    for record in dump.split("*** Dumping AST Record Layout")[1:]:
+        lines = record.strip().splitlines()
+        tag = re.match(r"\s*0 \| struct (\w+)$", lines[0]).group(1)
+        # a top-level member is indented by exactly three columns after the bar; a nested record's own fields by more
+        fields = [(int(off), name) for off, name in re.findall(r"^\s*(\d+) \|   \S.*?(\w+)$", record, re.M)]
+        size = int(re.search(r"\[sizeof=(\d+)", record).group(1))
+        layouts[tag] = (fields, size)
+    return layouts
+
+
+def test_struct_layouts_match_the_compiler(tmp_path):
+    from flashinfer import _lib
+
+    structs = _lib._ABI.structs
+    assert "fi_paged_kv_t" in structs and "fi_batch_prefill_params_t" in structs
+    layouts = compiler_layouts(tmp_path, list(structs))
+    for name, cls in structs.items():
+        fields, size = layouts[name[:-2]]  # the header names every typedef <struct tag>_t
+        ours = [(getattr(cls, f).offset, f) for f, _ in cls._fields_]
+        assert ours == [(off, f + "_" if keyword.iskeyword(f) else f) for off, f in fields], name
+        assert C.sizeof(cls) == size, name
+
+
+@pytest.mark.parametrize("snippet,offender", [
+    ("typedef struct fi_x { int32_t a; fi_unknown_t b; } fi_x_t;", "fi_unknown_t"),
+    ("FI_API int fi_f(int32_t a, const fi_missing_t* params);", "fi_missing_t"),
+    ("enum fi_e { FI_E_A = 0, FI_E_B };", "FI_E_B"),
+    ("FI_API int fi_unfinished(int32_t a)\nFI_API int fi_next(void);", "fi_unfinished"),
+])
+def test_parser_refuses_what_it_cannot_read(snippet, offender):
+    from flashinfer import _abi
+
+    with pytest.raises(_abi.HeaderError, match=offender):
+        _abi.parse(snippet)
+
+
+def test_every_parsed_prototype_is_bound(fi_lib):
+    from flashinfer import _lib
+
+    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    counts = {name: 0 if params.strip() == "void" else params.count(",") + 1
+              for name, params in re.findall(r"FI_API\s[^;(]*?\b(fi_\w+)\s*\(([^)]*)\)\s*;", text)}
+    assert sorted(counts) == sorted(_lib.EXPORTED_SYMBOLS)
+    for name, count in counts.items():
+        fn = getattr(fi_lib, name)
+        assert len(fn.argtypes) == count, name
+        assert fn.restype is (C.c_char_p if name == "fi_last_error" else C.c_int), name

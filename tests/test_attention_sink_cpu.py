@@ -126,12 +126,12 @@ def test_run_sinks_entry_points_refuse_fp8_queries_before_any_launch(fi_lib, q_d
     from flashinfer import _lib
 
     sink = (C.c_float * 8)()
-    dp = _lib.BatchDecodeParams(num_qo_heads=8, q_dtype=q_dtype)
+    dp = _lib.fi_batch_decode_params_t(num_qo_heads=8, q_dtype=q_dtype)
     assert fi_lib.fi_batch_decode_run_sinks(None, 0, None, 0, None, 0, C.byref(dp), sink, None) != 0
     assert b"attention sinks need f16 / bf16 queries" in fi_lib.fi_last_error()
     assert fi_lib.fi_batch_decode_run_sinks(None, 0, None, 0, None, 0, C.byref(dp), None, None) != 0
     assert b"not a decode plan" in fi_lib.fi_last_error()
-    pp = _lib.BatchPrefillParams(num_qo_heads=8, q_dtype=q_dtype, o_dtype=1)
+    pp = _lib.fi_batch_prefill_params_t(num_qo_heads=8, q_dtype=q_dtype, o_dtype=1)
     assert fi_lib.fi_batch_prefill_paged_run_sinks(None, 0, None, 0, None, 0, C.byref(pp), sink, None) != 0
     assert b"attention sinks need f16 / bf16 queries" in fi_lib.fi_last_error()
     assert fi_lib.fi_batch_prefill_paged_run_sinks(None, 0, None, 0, None, 0, C.byref(pp), None, None) != 0
@@ -144,6 +144,6 @@ def test_run_sinks_refuses_a_192_128_plan(fi_lib):
     info = (C.c_int64 * _lib.FI_PREFILL_PLAN_INFO_LEN)()
     info[15] = 0x4649514b564f  # FI_PREFILL_QKVO_PLAN_MAGIC
     sink = (C.c_float * 8)()
-    pp = _lib.BatchPrefillParams(num_qo_heads=8, q_dtype=1, o_dtype=1)
+    pp = _lib.fi_batch_prefill_params_t(num_qo_heads=8, q_dtype=1, o_dtype=1)
     assert fi_lib.fi_batch_prefill_paged_run_sinks(None, 0, None, 0, info, len(info), C.byref(pp), sink, None) != 0
     assert b"192 / head_dim_vo 128" in fi_lib.fi_last_error()

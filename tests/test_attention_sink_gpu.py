@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import sink_ref as S
+from flashinfer import _lib
 from oracle import attention_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -92,7 +93,7 @@ ONE_LAUNCH = [(8, 2, 64, 16), (8, 2, 128, 16),  # 16x16x32 matrix-core kernel
 def test_decode_one_launch(hq, hkv, d, page, dtype):
     c = decode_case((54, 97, 1, 0, 513), hq, hkv, d, page, dtype, seed=1)
     w = decode_wrapper(c, hq, hkv, d, page, disable_split_kv=True)
-    assert w._plan_info[9] == 0
+    assert w._plan_info[_lib.FI_DP_SPLIT_KV] == 0
     o, lse = w.run(c[0].to(DEV), c[1].to(DEV), sinks=c[5].to(DEV), return_lse=True)
     check_decode(c, o, lse, dtype)
     # the empty request: o = 0 and lse = sink log2 e, or FI_NEG_INF for the head whose sink is off
@@ -115,7 +116,7 @@ def run_split_and_unsplit(kv_lens, dtype, window_left=-1, d=128, seed=2):
     untouched = bool((w._float_workspace_buffer == 0xFF).all())
     check_decode(c, o, lse, dtype)
     w1 = decode_wrapper(c, 8, 2, d, 16, window_left=window_left, disable_split_kv=True)
-    assert w1._plan_info[9] == 0
+    assert w1._plan_info[_lib.FI_DP_SPLIT_KV] == 0
     o1, lse1 = w1.run(q, cache, sinks=sinks, return_lse=True)
     check_decode(c, o1, lse1, dtype)
     # a sink folded once per chunk instead of once per row fails here (and above)
@@ -126,8 +127,6 @@ def run_split_and_unsplit(kv_lens, dtype, window_left=-1, d=128, seed=2):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_decode_uniform_two_chunks_fold_in_the_fused_launch(dtype):
-    from flashinfer import _lib
-
     w, untouched = run_split_and_unsplit((130, 200, 256), dtype)
     assert w._plan_info[_lib.FI_DP_UNIFORM_CHUNKS] == 2 and _lib.FI_DP_UNIFORM_CHUNKS == 16
     assert untouched, "the fused launch writes no partial states, with sinks as without"
@@ -136,21 +135,22 @@ def test_decode_uniform_two_chunks_fold_in_the_fused_launch(dtype):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_decode_ragged_split_folds_in_the_merge_launch(dtype):
     w, untouched = run_split_and_unsplit((130, 700), dtype)
-    assert w._plan_info[9] == 1 and w._plan_info[16] == 0 and not untouched
+    assert w._plan_info[_lib.FI_DP_SPLIT_KV] == 1 and w._plan_info[_lib.FI_DP_UNIFORM_CHUNKS] == 0 and not untouched
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_decode_window_64(dtype):
     # the window leaves every request 5 pages, under the planner's smallest chunk: this windowed plan is not split
     w, _ = run_split_and_unsplit((130, 200, 256), dtype, window_left=64)
-    assert w._plan_info[14] == 64
+    assert w._plan_info[_lib.FI_DP_WINDOW_LEFT] == 64
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_decode_windowed_split_plan(dtype):
     # a window wide enough to be cut into chunks: two launches (a windowed plan has no fused form)
     w, untouched = run_split_and_unsplit((600, 700, 800), dtype, window_left=300, seed=3)
-    assert w._plan_info[9] == 1 and w._plan_info[14] == 300 and w._plan_info[16] == 0 and not untouched
+    assert w._plan_info[_lib.FI_DP_SPLIT_KV] == 1 and w._plan_info[_lib.FI_DP_WINDOW_LEFT] == 300
+    assert w._plan_info[_lib.FI_DP_UNIFORM_CHUNKS] == 0 and not untouched
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -161,7 +161,7 @@ def test_decode_fp8_e4m3_cache(dtype, split):
     kv_lens = (130, 200, 256) if split else (54, 97, 1, 0, 513)
     c = decode_case(kv_lens, 8, 2, 128, 16, dtype, kv_dtype=torch.float8_e4m3fn, seed=4)
     w = decode_wrapper(c, 8, 2, 128, 16, disable_split_kv=not split)
-    assert bool(w._plan_info[9]) == split
+    assert bool(w._plan_info[_lib.FI_DP_SPLIT_KV]) == split
     o, lse = w.run(c[0].to(DEV), c[1].to(DEV), sinks=c[5].to(DEV), return_lse=True)
     check_decode(c, o, lse, dtype)
 
@@ -239,7 +239,7 @@ def run_ragged_prefill(c, dtype, causal, window_left, **plan_kw):
 def test_prefill_paged_unsplit_and_split(d, causal, window_left, dtype):
     c = prefill_case(d, dtype, causal, window_left)
     w1, o1, lse1 = run_paged_prefill(c, dtype, causal, window_left, c["sinks"].to(DEV), disable_split_kv=True)
-    assert w1._plan_info[14] == 0
+    assert w1._plan_info[_lib.FI_PP_SPLIT_KV] == 0
     check_prefill(c, o1, lse1, dtype)
     # rows of the request without keys: o = 0, lse = sink log2 e (FI_NEG_INF where the sink is off)
     empty = slice(int(c["qo_indptr"][3]), int(c["qo_indptr"][4]))
@@ -248,7 +248,7 @@ def test_prefill_paged_unsplit_and_split(d, causal, window_left, dtype):
     torch.testing.assert_close(lse1[empty].cpu(), want.expand(5, -1), rtol=1e-6, atol=1e-5)
     # 64-token chunks: partial states without the sink, folded once by the merge launch
     w2, o2, lse2 = run_paged_prefill(c, dtype, causal, window_left, c["sinks"].to(DEV), fixed_split_size=64)
-    assert w2._plan_info[14] == 1
+    assert w2._plan_info[_lib.FI_PP_SPLIT_KV] == 1
     check_prefill(c, o2, lse2, dtype)
     torch.testing.assert_close(o2.float(), o1.float(), **tol(dtype))
     torch.testing.assert_close(lse2, lse1, rtol=1e-3, atol=1e-3)
@@ -263,7 +263,7 @@ def test_prefill_ragged_reference_call_form(d, causal, window_left, dtype):
     _, o1, lse1 = run_ragged_prefill(c, dtype, causal, window_left, disable_split_kv=True)
     check_prefill(c, o1, lse1, dtype)
     w2, o2, lse2 = run_ragged_prefill(c, dtype, causal, window_left, fixed_split_size=64)
-    assert w2._plan_info[14] == 1
+    assert w2._plan_info[_lib.FI_PP_SPLIT_KV] == 1
     check_prefill(c, o2, lse2, dtype)
 
 
@@ -310,7 +310,7 @@ def test_decode_minus_inf_sinks_are_no_sinks(kv_lens, plan_kw, fused, dtype):
     o0, lse0 = w.run(q, cache, return_lse=True)
     torch.cuda.synchronize()
     if fused:
-        assert w._plan_info[16] == 2
+        assert w._plan_info[_lib.FI_DP_UNIFORM_CHUNKS] == 2
         assert bool((w._float_workspace_buffer == 0xFF).all()), "sinks=None: the fused plan writes no partial states"
     off = torch.full((8,), float("-inf"), device=DEV)
     o1, lse1 = w.run(q, cache, sinks=off, return_lse=True)

@@ -13,6 +13,7 @@ import functools
 import pytest
 import torch
 
+from flashinfer import _lib
 from oracle import attention_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -59,8 +60,6 @@ def plan_wrapper(c, hq, hkv, d, layout="NHD", **plan_kw):
 def run_checked(c, hq, hkv, d, dtype, expect_slot, fused, layout="NHD", lse_tol=1e-3, o_tol=None, **plan_kw):
     """plan, poison the float workspace, run, compare with the oracle.  ``fused``: the workspace must come back
     untouched; otherwise (two launches on a split plan) the partial states must have been written to it."""
-    from flashinfer import _lib
-
     q, cache, _, _, _, o_ref, lse_ref = c
     w = plan_wrapper(c, hq, hkv, d, layout, **plan_kw)
     assert w._plan_info[_lib.FI_DP_UNIFORM_CHUNKS] == expect_slot and _lib.FI_DP_UNIFORM_CHUNKS == 16
@@ -70,7 +69,7 @@ def run_checked(c, hq, hkv, d, dtype, expect_slot, fused, layout="NHD", lse_tol=
     untouched = bool((w._float_workspace_buffer == 0xFF).all())
     if fused:
         assert untouched, "the fused launch must not write partial states"
-    elif w._plan_info[9]:
+    elif w._plan_info[_lib.FI_DP_SPLIT_KV]:
         assert not untouched, "a split plan on the two-launch path writes its partial states"
     torch.testing.assert_close(o.float().cpu(), o_ref, **(o_tol or tol(dtype)))
     torch.testing.assert_close(lse.cpu(), lse_ref, rtol=lse_tol, atol=lse_tol)
@@ -101,8 +100,6 @@ def test_kv_heads_not_a_multiple_of_the_heads_per_workgroup(hq, hkv):
 
 
 def test_caller_output_without_lse():
-    from flashinfer import _lib
-
     q, cache, _, _, _, o_ref, _ = c = case((256,) * 3, 8, 2, 128, torch.bfloat16, seed=4)
     w = plan_wrapper(c, 8, 2, 128)
     assert w._plan_info[_lib.FI_DP_UNIFORM_CHUNKS] == 2
@@ -141,7 +138,7 @@ def test_fused_equals_unsplit():
     q, cache = (c := case((130, 200, 256), 8, 2, 128, torch.bfloat16, seed=1))[:2]
     _, o_fused, lse_fused = run_checked(c, 8, 2, 128, torch.bfloat16, expect_slot=2, fused=True)
     w = plan_wrapper(c, 8, 2, 128, disable_split_kv=True)
-    assert w._plan_info[9] == 0 and w._plan_info[16] == 0
+    assert w._plan_info[_lib.FI_DP_SPLIT_KV] == 0 and w._plan_info[_lib.FI_DP_UNIFORM_CHUNKS] == 0
     o_one, lse_one = w.run(q.to(DEV), cache.to(DEV), return_lse=True)
     torch.testing.assert_close(o_fused.float(), o_one.float(), **tol(torch.bfloat16))
     torch.testing.assert_close(lse_fused, lse_one, rtol=1e-4, atol=1e-4)
@@ -182,7 +179,7 @@ def test_graph_plan_takes_two_launches():
         ws, torch.empty(4, dtype=torch.int32, device=DEV), torch.empty(64, dtype=torch.int32, device=DEV),
         torch.empty(3, dtype=torch.int32, device=DEV), "NHD")
     w.plan(indptr, indices, last, 8, 2, 128, PAGE, q_data_type=torch.float16, kv_data_type=torch.float16)
-    assert w._plan_info[9] == 1 and w._plan_info[16] == 0
+    assert w._plan_info[_lib.FI_DP_SPLIT_KV] == 1 and w._plan_info[_lib.FI_DP_UNIFORM_CHUNKS] == 0
     w._float_workspace_buffer.fill_(0xFF)
     o, lse = w.run(q.to(DEV), cache.to(DEV), return_lse=True)
     torch.cuda.synchronize()

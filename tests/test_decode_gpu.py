@@ -7,6 +7,7 @@ import math
 import pytest
 import torch
 
+from flashinfer import _lib
 from oracle import attention_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -114,7 +115,7 @@ def test_batch_decode_wide_group_no_split_and_graph_padding():
     q = torch.randn(len(kv_lens), hq, d).half()
     o_ref, lse_ref = R.batch_decode_ref(q.float(), cache.float(), "NHD", indptr, indices, last)
     (o, lse), w = run_batch_decode(q, cache, "NHD", indptr, indices, last, hq, hkv, d, page_size)
-    assert w._plan_info[9] == 0  # split_kv off
+    assert w._plan_info[_lib.FI_DP_SPLIT_KV] == 0  # split_kv off
     torch.testing.assert_close(o.float().cpu(), o_ref.float(), rtol=1e-3, atol=1e-3)
     torch.testing.assert_close(lse.cpu(), lse_ref.float(), rtol=1e-3, atol=1e-3)
 
@@ -307,9 +308,9 @@ def test_full_size_c2_split_invariance():
     w = flashinfer.BatchDecodeWithPagedKVCacheWrapper(ws, "NHD")
     w.plan(indptr, indices, last, hq, hkv, d, ps, q_data_type=torch.bfloat16, kv_data_type=torch.bfloat16)
     o_split, lse_split = w.run(q, cache, return_lse=True)
-    assert w._plan_info[9] == 1  # split-kv on a 256-CU chip
+    assert w._plan_info[_lib.FI_DP_SPLIT_KV] == 1  # split-kv on a 256-CU chip
     w.plan(indptr, indices, last, hq, hkv, d, ps, q_data_type=torch.bfloat16, kv_data_type=torch.bfloat16, disable_split_kv=True)
-    assert w._plan_info[9] == 0
+    assert w._plan_info[_lib.FI_DP_SPLIT_KV] == 0
     o_one, lse_one = w.run(q, cache, return_lse=True)
     torch.testing.assert_close(o_split.float(), o_one.float(), **tol(torch.bfloat16))
     torch.testing.assert_close(lse_split, lse_one, rtol=1e-4, atol=1e-4)

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from flashinfer import _lib
 from oracle.plan_ref import decode_plan_ref
 
 MAX_GRID = 1024
@@ -23,8 +24,6 @@ def indptr_of(pages):
 
 
 def run_plan(fi_lib, pages, hq, hkv, cuda_graph=False, window_left=-1):
-    from flashinfer import _lib
-
     indptr = indptr_of(pages)
     n = len(pages)
     pinned = (C.c_char * (1 << 20))()
@@ -39,9 +38,12 @@ def run_plan(fi_lib, pages, hq, hkv, cuda_graph=False, window_left=-1):
     def i32(off, count):
         return raw[off: off + 4 * count].view(np.int32).tolist()
 
-    nwork = info[11]
-    got = dict(split_kv=bool(info[9]), kv_chunk_size=info[10], padded_batch_size=info[0], num_work=nwork,
-               request_indices=i32(info[3], nwork), kv_tile_indices=i32(info[4], nwork), o_indptr=i32(info[5], n + 1))
+    nwork = info[_lib.FI_DP_NUM_WORK]
+    got = dict(split_kv=bool(info[_lib.FI_DP_SPLIT_KV]), kv_chunk_size=info[_lib.FI_DP_KV_CHUNK_SIZE],
+               padded_batch_size=info[_lib.FI_DP_PADDED_BATCH_SIZE], num_work=nwork,
+               request_indices=i32(info[_lib.FI_DP_REQUEST_INDICES_OFFSET], nwork),
+               kv_tile_indices=i32(info[_lib.FI_DP_KV_TILE_INDICES_OFFSET], nwork),
+               o_indptr=i32(info[_lib.FI_DP_O_INDPTR_OFFSET], n + 1))
     return info, got
 
 
@@ -71,8 +73,6 @@ CASES = [
 
 @pytest.mark.parametrize("pages,hq,hkv,slot,chunks", CASES)
 def test_uniform_chunks_slot(fi_lib, pages, hq, hkv, slot, chunks):
-    from flashinfer import _lib
-
     info, got = run_plan(fi_lib, pages, hq, hkv)
     check_against_oracle(got, pages, hq, hkv)
     per_request = [b - a for a, b in zip(got["o_indptr"], got["o_indptr"][1:])]
@@ -80,22 +80,22 @@ def test_uniform_chunks_slot(fi_lib, pages, hq, hkv, slot, chunks):
     assert len(info) == 17 and _lib.FI_DP_UNIFORM_CHUNKS == 16
     assert info[_lib.FI_DP_UNIFORM_CHUNKS] == slot
     if slot:
-        assert got["split_kv"] and info[8] == 0 and info[14] == -1
+        assert got["split_kv"] and info[_lib.FI_DP_ENABLE_CUDA_GRAPH] == 0 and info[_lib.FI_DP_WINDOW_LEFT] == -1
 
 
 def test_c2_plan_is_unchanged_and_uniform(fi_lib):
     info, got = run_plan(fi_lib, [512] * 64, 32, 8)
     assert got["split_kv"] and got["kv_chunk_size"] == 4096 and got["num_work"] == 128
-    assert info[16] == 2
+    assert info[_lib.FI_DP_UNIFORM_CHUNKS] == 2
     # the partial-state region is still reserved: the two-launch path needs it
-    assert info[2] - info[1] >= 32 * 128 * 128 * 4
+    assert info[_lib.FI_DP_S_OFFSET] - info[_lib.FI_DP_V_OFFSET] >= 32 * 128 * 128 * 4
 
 
 @pytest.mark.parametrize("pages,hq,hkv", [([16, 16, 16], 8, 2), ([32, 32], 8, 2), ([512] * 64, 32, 8)])
 def test_graph_plans_never_report_uniform_chunks(fi_lib, pages, hq, hkv):
     info, got = run_plan(fi_lib, pages, hq, hkv, cuda_graph=True)
     check_against_oracle(got, pages, hq, hkv, cuda_graph=True)
-    assert got["split_kv"] and info[16] == 0
+    assert got["split_kv"] and info[_lib.FI_DP_UNIFORM_CHUNKS] == 0
 
 
 @pytest.mark.parametrize("window_left", [0, 100, 255, 100000])
@@ -103,7 +103,7 @@ def test_window_plans_never_report_uniform_chunks(fi_lib, window_left):
     pages = [16, 16, 16]
     info, got = run_plan(fi_lib, pages, 8, 2, window_left=window_left)
     check_against_oracle(got, pages, 8, 2, window_left=window_left)
-    assert info[14] == window_left and info[16] == 0
+    assert info[_lib.FI_DP_WINDOW_LEFT] == window_left and info[_lib.FI_DP_UNIFORM_CHUNKS] == 0
 
 
 def test_slots_0_to_15_do_not_depend_on_the_new_slot(fi_lib):
@@ -112,7 +112,9 @@ def test_slots_0_to_15_do_not_depend_on_the_new_slot(fi_lib):
     workspace offsets follow from it."""
     info, got = run_plan(fi_lib, [16, 16, 16], 8, 2)
     padded = got["padded_batch_size"]
-    assert info[0] == padded == 6 and info[11] == 6 and info[12] == 3
-    assert info[1] == 0 and info[2] == 8 * padded * 128 * 4          # tmp_v, then tmp_s
-    assert info[3] == 0 and info[4] >= 4 * padded and info[5] >= info[4] + 4 * padded
+    assert info[_lib.FI_DP_PADDED_BATCH_SIZE] == padded == 6
+    assert info[_lib.FI_DP_NUM_WORK] == 6 and info[_lib.FI_DP_BATCH_SIZE] == 3
+    assert info[_lib.FI_DP_V_OFFSET] == 0 and info[_lib.FI_DP_S_OFFSET] == 8 * padded * 128 * 4  # tmp_v, then tmp_s
+    assert info[_lib.FI_DP_REQUEST_INDICES_OFFSET] == 0 and info[_lib.FI_DP_KV_TILE_INDICES_OFFSET] >= 4 * padded
+    assert info[_lib.FI_DP_O_INDPTR_OFFSET] >= info[_lib.FI_DP_KV_TILE_INDICES_OFFSET] + 4 * padded
     assert info[15] == 0x4649444543

@@ -9,6 +9,7 @@ import math
 import pytest
 import torch
 
+from flashinfer import _lib
 from oracle import attention_ref as R
 from oracle import gemm_ref as G
 
@@ -63,10 +64,10 @@ def test_full_size_c3_fp8_prefill():
         return o, lse, w
 
     o, lse, w = run()  # the plan bench.py times
-    assert w._plan_info[14] == 0  # 1024 q tiles per kv head fill the chip: no split
+    assert w._plan_info[_lib.FI_PP_SPLIT_KV] == 0  # 1024 q tiles per kv head fill the chip: no split
     # (1) split-KV invariance over the whole output: two 4096-token chunks merged == one pass
     o_s, lse_s, w_s = run(fixed_split_size=4096)
-    assert w_s._plan_info[14] == 1
+    assert w_s._plan_info[_lib.FI_PP_SPLIT_KV] == 1
     diff = (o.float() - o_s.float()).abs()
     assert diff.max() < 5e-2 and diff.mean() < 1e-3  # e4m3 rounding of P follows the running max: not bit-equal
     torch.testing.assert_close(lse, lse_s, rtol=1e-3, atol=2e-3)

@@ -5,6 +5,7 @@ this reason, decode.cuh:424, prefill.cuh:2058; serving pattern: capture once, pl
 import pytest
 import torch
 
+from flashinfer import _lib
 from oracle import attention_ref as R
 from test_decode_gpu import make_paged
 
@@ -40,7 +41,7 @@ def test_decode_graph_replay_after_replan_with_other_chunk_size():
         return q
 
     plan(0)
-    chunk_a = w._plan_info[10]
+    chunk_a = w._plan_info[_lib.FI_DP_KV_CHUNK_SIZE]
     w.run(q_dev, cache_dev, out=out, lse=lse, return_lse=True)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
@@ -49,7 +50,7 @@ def test_decode_graph_replay_after_replan_with_other_chunk_size():
     chunks = set()
     for i in (1, 0, 2, 1):
         q = plan(i)
-        chunks.add(w._plan_info[10])
+        chunks.add(w._plan_info[_lib.FI_DP_KV_CHUNK_SIZE])
         out.zero_()
         torch.cuda.synchronize()
         g.replay()
@@ -95,18 +96,19 @@ def test_prefill_graph_replay_after_replan_with_other_chunk_size_and_more_partia
         return q, qo_indptr
 
     plan(0)
-    offsets = (w._plan_info[10], w._plan_info[11], w._plan_info[0])  # v_off, s_off, padded items
+    frozen_slots = (_lib.FI_PP_V_OFFSET, _lib.FI_PP_S_OFFSET, _lib.FI_PP_PADDED_BATCH_SIZE)
+    offsets = [w._plan_info[s] for s in frozen_slots]
     w.run(q_dev, cache_dev, out=out, lse=lse, return_lse=True)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         w.run(q_dev, cache_dev, out=out, lse=lse, return_lse=True)
-    chunks = {w._plan_info[9]}
+    chunks = {w._plan_info[_lib.FI_PP_KV_CHUNK_SIZE]}
     for i in (1, 0, 3, 2, 1):
         q, qo_indptr = plan(i)
-        chunks.add(w._plan_info[9])
+        chunks.add(w._plan_info[_lib.FI_PP_KV_CHUNK_SIZE])
         # what a captured launch froze must be the same for every plan of this wrapper
-        assert (w._plan_info[10], w._plan_info[11], w._plan_info[0]) == offsets
+        assert [w._plan_info[s] for s in frozen_slots] == offsets
         out.zero_()
         torch.cuda.synchronize()
         g.replay()

@@ -36,7 +36,7 @@ def plan(fi_lib, qo_lens, kv_lens, H, page_size=16, ckv=512, kpe=64, q_dt=BF16, 
     kv_indptr = (C.c_int32 * (B + 1))(*np.concatenate([[0], np.cumsum(pages)]).astype(int).tolist())
     kv_len = (C.c_int32 * max(B, 1))(*kv_lens)
     pinned = (C.c_char * int_bytes)()
-    p = _lib.MlaPlanParams(int_ws=None, pinned_int_ws=C.addressof(pinned), int_ws_bytes=int_bytes,
+    p = _lib.fi_batch_mla_plan_params_t(int_ws=None, pinned_int_ws=C.addressof(pinned), int_ws_bytes=int_bytes,
                            float_ws_bytes=float_bytes, qo_indptr_h=C.addressof(qo_indptr),
                            kv_indptr_h=C.addressof(kv_indptr), kv_len_arr_h=C.addressof(kv_len), batch_size=B,
                            num_heads=H, head_dim_ckv=ckv, head_dim_kpe=kpe, page_size=page_size, causal=0,
@@ -178,7 +178,7 @@ def test_run_rejects_rows_other_than_planned(fi_lib):
     plan_info = (C.c_int64 * _lib.FI_MLA_PLAN_INFO_LEN)(*info)
     fake = 1 << 20  # 16-byte aligned, non-null
     for rows in (3 * 16 - 16, 3 * 16 + 16):
-        p = _lib.MlaParams(q_nope=fake, q_nope_stride_n=16 * 512, q_nope_stride_h=512, q_pe=fake, q_pe_stride_n=16 * 64,
+        p = _lib.fi_batch_mla_params_t(q_nope=fake, q_nope_stride_n=16 * 512, q_nope_stride_h=512, q_pe=fake, q_pe_stride_n=16 * 64,
                            q_pe_stride_h=64, ckv=fake, ckv_stride_page=16 * 512, ckv_stride_n=512, kpe=fake,
                            kpe_stride_page=16 * 64, kpe_stride_n=64, kv_indices=fake, o=fake, lse=None, float_ws=fake,
                            float_ws_bytes=128 << 20, int_ws=fake, int_ws_bytes=8 << 20, num_rows=rows, num_heads=16,

@@ -88,7 +88,7 @@ def test_host_validation_without_a_launch(fi_lib):
         base = dict(in_=a, weight=a, out=a, batch=1, num_heads=1, hidden=8, in_stride_n=8, in_stride_h=8,
                     out_stride_n=8, out_stride_h=8, eps=1e-6, weight_bias=0.0, dtype=_lib.FI_DTYPE_F16)
         base.update(kw)
-        return _lib.RmsNormParams(**base)
+        return _lib.fi_rmsnorm_params_t(**base)
 
     fn = fi_lib.fi_rmsnorm
     assert fn(None, None) != 0 and b"null" in err()
@@ -109,7 +109,7 @@ def test_host_validation_without_a_launch(fi_lib):
         base = dict(input=a, residual=a, weight=a, batch=1, hidden=8, input_stride=8, residual_stride=8, eps=1e-6,
                     weight_bias=0.0, dtype=_lib.FI_DTYPE_BF16)
         base.update(kw)
-        return _lib.FusedAddRmsNormParams(**base)
+        return _lib.fi_fused_add_rmsnorm_params_t(**base)
 
     fn = fi_lib.fi_fused_add_rmsnorm
     assert fn(None, None) != 0 and b"null" in err()
@@ -126,7 +126,7 @@ def test_host_validation_without_a_launch(fi_lib):
     def act_params(**kw):
         base = dict(in_=a, out=a, tokens=1, d=8, act=_lib.FI_ACT_SILU, dtype=_lib.FI_DTYPE_F16)
         base.update(kw)
-        return _lib.ActAndMulParams(**base)
+        return _lib.fi_act_and_mul_params_t(**base)
 
     fn = fi_lib.fi_act_and_mul
     assert fn(None, None) != 0 and b"null" in err()

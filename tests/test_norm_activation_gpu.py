@@ -270,7 +270,7 @@ def test_act_and_mul_layouts_and_extremes(dtype):
         # d that allows no vector access, reached through the C ABI (the Python layer keeps the 16-byte rule)
         x = randn((6, 2 * 5), dtype, g, scale=3.0)
         out = torch.empty(6, 5, dtype=dtype, device=DEV)
-        p = _lib.ActAndMulParams(in_=x.data_ptr(), out=out.data_ptr(), tokens=6, d=5, act=codes[act],
+        p = _lib.fi_act_and_mul_params_t(in_=x.data_ptr(), out=out.data_ptr(), tokens=6, d=5, act=codes[act],
                                  dtype=_lib.fi_dtype(dtype))
         _lib.check(_lib.lib().fi_act_and_mul(C.byref(p), _lib.current_stream(x.device)), fn_name)
         assert_close(out, R.act_and_mul_ref(x, act), dtype, f"{fn_name} d=5")

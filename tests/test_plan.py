@@ -6,13 +6,12 @@ import random
 import numpy as np
 import pytest
 
+from flashinfer import _lib
 from oracle.plan_ref import decode_plan_ref
 
 
 def run_plan(fi_lib, indptr, hq, hkv, page_size, max_grid, cuda_graph=False, head_dim=128,
              float_bytes=1 << 30, window_left=-1):
-    from flashinfer import _lib
-
     n = len(indptr) - 1
     pinned = (C.c_char * (8 << 20))()
     arr = (C.c_int32 * len(indptr))(*indptr)
@@ -26,12 +25,16 @@ def run_plan(fi_lib, indptr, hq, hkv, page_size, max_grid, cuda_graph=False, hea
     def i32(off, count):
         return raw[off: off + 4 * count].view(np.int32).tolist()
 
-    padded, nwork = info[0], info[11]
-    out = dict(split_kv=bool(info[9]), kv_chunk_size=info[10], padded_batch_size=padded, num_work=nwork,
-               request_indices=i32(info[3], nwork), kv_tile_indices=i32(info[4], nwork),
-               o_indptr=i32(info[5], n + 1), chunk_ptr=i32(info[7], 1)[0], info=info)
+    padded, nwork = info[_lib.FI_DP_PADDED_BATCH_SIZE], info[_lib.FI_DP_NUM_WORK]
+    out = dict(split_kv=bool(info[_lib.FI_DP_SPLIT_KV]), kv_chunk_size=info[_lib.FI_DP_KV_CHUNK_SIZE],
+               padded_batch_size=padded, num_work=nwork,
+               request_indices=i32(info[_lib.FI_DP_REQUEST_INDICES_OFFSET], nwork),
+               kv_tile_indices=i32(info[_lib.FI_DP_KV_TILE_INDICES_OFFSET], nwork),
+               o_indptr=i32(info[_lib.FI_DP_O_INDPTR_OFFSET], n + 1),
+               chunk_ptr=i32(info[_lib.FI_DP_KV_CHUNK_SIZE_PTR_OFFSET], 1)[0], info=info)
     if out["split_kv"]:
-        out["mask"] = raw[info[6]: info[6] + padded].tolist()
+        mask_off = info[_lib.FI_DP_BLOCK_VALID_MASK_OFFSET]
+        out["mask"] = raw[mask_off: mask_off + padded].tolist()
     return out
 
 
@@ -91,8 +94,6 @@ def test_planner_random_page_tables(fi_lib):
 
 
 def test_workspace_too_small_is_an_error(fi_lib):
-    from flashinfer import _lib
-
     indptr = (C.c_int32 * 2)(0, 4096)
     pinned = (C.c_char * 4096)()
     info = (C.c_int64 * _lib.FI_DECODE_PLAN_INFO_LEN)()
@@ -104,8 +105,6 @@ def test_workspace_too_small_is_an_error(fi_lib):
 # ---- prefill planner (split-KV work list) -------------------------------------------------------------
 def run_prefill_plan(fi_lib, qo_indptr, kv_lens, hq, hkv, causal=False, cuda_graph=False, fixed=-1, disable=False,
                      page_size=16, float_bytes=1 << 32, window_left=-1):
-    from flashinfer import _lib
-
     n = len(kv_lens)
     pinned = (C.c_char * (8 << 20))()
     qo = (C.c_int32 * (n + 1))(*qo_indptr)
@@ -125,11 +124,17 @@ def run_prefill_plan(fi_lib, qo_indptr, kv_lens, hq, hkv, causal=False, cuda_gra
     def i32(off, count):
         return raw[off: off + 4 * count].view(np.int32).tolist()
 
-    nwork = info[12]
-    out = dict(split_kv=bool(info[14]), kv_chunk_size=info[9], padded_batch_size=info[0], num_work=nwork,
-               request_indices=i32(info[4], nwork), qo_tile_indices=i32(info[5], nwork),
-               kv_tile_indices=i32(info[6], nwork), padding=i32(info[4], info[0])[nwork:])
-    out["merge_indptr"] = i32(info[7], info[1] + 1) if out["split_kv"] else [0]
+    nwork = info[_lib.FI_PP_NUM_WORK]
+    padded = info[_lib.FI_PP_PADDED_BATCH_SIZE]
+    out = dict(split_kv=bool(info[_lib.FI_PP_SPLIT_KV]), kv_chunk_size=info[_lib.FI_PP_KV_CHUNK_SIZE],
+               padded_batch_size=padded, num_work=nwork,
+               request_indices=i32(info[_lib.FI_PP_REQUEST_INDICES_OFFSET], nwork),
+               qo_tile_indices=i32(info[_lib.FI_PP_QO_TILE_INDICES_OFFSET], nwork),
+               kv_tile_indices=i32(info[_lib.FI_PP_KV_TILE_INDICES_OFFSET], nwork),
+               padding=i32(info[_lib.FI_PP_REQUEST_INDICES_OFFSET], padded)[nwork:])
+    out["merge_indptr"] = [0]
+    if out["split_kv"]:
+        out["merge_indptr"] = i32(info[_lib.FI_PP_MERGE_INDPTR_OFFSET], info[_lib.FI_PP_TOTAL_NUM_ROWS] + 1)
     return out
 
 

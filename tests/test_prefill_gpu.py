@@ -4,6 +4,7 @@ test_fp8_prefill.py:23-191 and test_hopper_fp8_attention.py:64-108."""
 import pytest
 import torch
 
+from flashinfer import _lib
 from oracle import attention_ref as R
 from test_decode_gpu import make_paged, tol
 
@@ -334,7 +335,7 @@ def test_batch_prefill_split_kv_matches_oracle_and_unsplit(dtype, causal, qo_len
                                                                       causal, seed=50)
     # few q tiles x 2 kv heads cannot fill 256 CUs: the planner must have split long kv
     if max(kv_lens) >= 3000:
-        assert w._plan_info[14] == 1 and w._plan_info[9] % 64 == 0
+        assert w._plan_info[_lib.FI_PP_SPLIT_KV] == 1 and w._plan_info[_lib.FI_PP_KV_CHUNK_SIZE] % 64 == 0
     o_ref, lse_ref = R.batch_prefill_ref(q.float(), qo_indptr, cache.float(), "NHD", indptr, indices, last,
                                          causal=causal)
     torch.testing.assert_close(o.float().cpu(), o_ref.float(), **ptol(dtype))
@@ -342,7 +343,7 @@ def test_batch_prefill_split_kv_matches_oracle_and_unsplit(dtype, causal, qo_len
     # disable_split_kv (batch-invariant mode) and a fixed split size give the same answer
     for kw in (dict(disable_split_kv=True), dict(fixed_split_size=512)):
         w2, *_, o2, lse2 = _plan_run(qo_lens, kv_lens, hq, hkv, d, ps, dtype, causal, seed=50, **kw)
-        assert w2._plan_info[14] == (0 if "disable_split_kv" in kw else int(max(kv_lens) > 512))
+        assert w2._plan_info[_lib.FI_PP_SPLIT_KV] == (0 if "disable_split_kv" in kw else int(max(kv_lens) > 512))
         # against the ORACLE at the same bar (two bf16 outputs rounded from nearly equal f32 values may differ by a
         # whole ulp from each other, 2^-8 ... 2^-7 relative, while each is within half an ulp of the oracle)
         torch.testing.assert_close(o2.float().cpu(), o_ref.float(), **ptol(dtype))
@@ -360,12 +361,13 @@ def test_batch_prefill_mixed_batch_balance_rule_and_idle_waves(dtype):
     kv_lens = [200 + 3 * i for i in range(132)] + [5000, 4321, 4097, 3500] + [700]
     qo_lens = [1] * 132 + [17] * 4 + [300]
     w, q, cache, qo_indptr, indptr, indices, last, o, lse = _plan_run(qo_lens, kv_lens, hq, hkv, d, ps, dtype, True, seed=77)
-    assert w._plan_info[14] == 1 and w._plan_info[9] < 4097 and w._plan_info[12] > 132 + 4 + 17  # split, extra items
+    assert w._plan_info[_lib.FI_PP_SPLIT_KV] == 1 and w._plan_info[_lib.FI_PP_KV_CHUNK_SIZE] < 4097
+    assert w._plan_info[_lib.FI_PP_NUM_WORK] > 132 + 4 + 17  # split, extra items
     o_ref, lse_ref = R.batch_prefill_ref(q.float(), qo_indptr, cache.float(), "NHD", indptr, indices, last, causal=True)
     torch.testing.assert_close(o.float().cpu(), o_ref.float(), **ptol(dtype))
     torch.testing.assert_close(lse.cpu(), lse_ref.float(), rtol=1e-3, atol=1e-3)
     w2, *_, o2, lse2 = _plan_run(qo_lens, kv_lens, hq, hkv, d, ps, dtype, True, seed=77, disable_split_kv=True)
-    assert w2._plan_info[14] == 0
+    assert w2._plan_info[_lib.FI_PP_SPLIT_KV] == 0
     torch.testing.assert_close(o2.float().cpu(), o_ref.float(), **ptol(dtype))
     torch.testing.assert_close(lse2, lse, rtol=1e-3, atol=1e-3)
 
@@ -376,10 +378,10 @@ def test_batch_prefill_split_kv_fp8_native_and_rows_without_keys():
     qo_lens, kv_lens = [100], [8192]
     w, q, cache, qo_indptr, indptr, indices, last, o, lse = _plan_run(
         qo_lens, kv_lens, hq, hkv, d, ps, torch.float8_e4m3fn, True, seed=60, o_data_type=torch.bfloat16)
-    assert w._plan_info[14] == 1
+    assert w._plan_info[_lib.FI_PP_SPLIT_KV] == 1
     w2, *_, o2, lse2 = _plan_run(qo_lens, kv_lens, hq, hkv, d, ps, torch.float8_e4m3fn, True, seed=60,
                                  o_data_type=torch.bfloat16, disable_split_kv=True)
-    assert w2._plan_info[14] == 0
+    assert w2._plan_info[_lib.FI_PP_SPLIT_KV] == 0
     torch.testing.assert_close(o.float(), o2.float(), rtol=5e-2, atol=5e-2)
     torch.testing.assert_close(lse, lse2, rtol=1e-2, atol=1e-2)
     # causal with qo_len > kv_len: the first rows see no key in any chunk -> o = 0, lse = -5e4 exactly
@@ -387,7 +389,7 @@ def test_batch_prefill_split_kv_fp8_native_and_rows_without_keys():
     w, q, cache, qo_indptr, indptr, indices, last, o, lse = _plan_run(qo_lens, kv_lens, 4, 1, 128, 16,
                                                                       torch.float16, True, seed=61,
                                                                       fixed_split_size=128)
-    assert w._plan_info[14] == 1
+    assert w._plan_info[_lib.FI_PP_SPLIT_KV] == 1
     o_ref, lse_ref = R.batch_prefill_ref(q.float(), qo_indptr, cache.float(), "NHD", indptr, indices, last,
                                          causal=True)
     assert torch.all(o[:100] == 0) and torch.all(lse[:100].cpu() == R.NEG_INF_SENTINEL)
@@ -395,7 +397,7 @@ def test_batch_prefill_split_kv_fp8_native_and_rows_without_keys():
     torch.testing.assert_close(lse.cpu(), lse_ref.float(), rtol=1e-3, atol=1e-3)
     # the same rows through the unsplit kernel
     w, *_, o, lse = _plan_run(qo_lens, kv_lens, 4, 1, 128, 16, torch.float16, True, seed=61, disable_split_kv=True)
-    assert w._plan_info[14] == 0
+    assert w._plan_info[_lib.FI_PP_SPLIT_KV] == 0
     assert torch.all(o[:100] == 0) and torch.all(lse[:100].cpu() == R.NEG_INF_SENTINEL)
     torch.testing.assert_close(o.float().cpu(), o_ref.float(), rtol=1e-3, atol=1e-3)
 

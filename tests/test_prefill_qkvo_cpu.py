@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from flashinfer import _lib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "prefill_plans_equal_dims.json")
 ENTRY_ALIGN = 256  # slack for the workspace allocator's alignment of the two partial-state regions
@@ -15,8 +17,6 @@ ENTRY_ALIGN = 256  # slack for the workspace allocator's alignment of the two pa
 def plan(fi_lib, qo_lens, kv_lens, hq, hkv, dqk, dvo, causal=True, float_bytes=1 << 30, graph=False,
          fixed_split=-1, disable_split=False, window_left=-1, page_size=1):
     """fi_batch_prefill_plan on the host: (rc, plan_info, request / q tile / kv tile / merge_indptr lists)."""
-    from flashinfer import _lib
-
     n = len(qo_lens)
     qo = np.concatenate([[0], np.cumsum(qo_lens)]).astype(np.int32)
     kvp = np.concatenate([[0], np.cumsum([-(-k // page_size) for k in kv_lens])]).astype(np.int32)
@@ -34,9 +34,12 @@ def plan(fi_lib, qo_lens, kv_lens, hq, hkv, dqk, dvo, causal=True, float_bytes=1
     def i32(off, count):
         return raw[off: off + 4 * count].view(np.int32).tolist()
 
-    padded, rows = info[0], info[1]
-    lists = dict(req=i32(info[4], padded), tile=i32(info[5], padded), kvt=i32(info[6], padded),
-                 merge=i32(info[7], rows + 1) if info[14] else [], chunk=i32(info[2], 1))
+    padded, rows = info[_lib.FI_PP_PADDED_BATCH_SIZE], info[_lib.FI_PP_TOTAL_NUM_ROWS]
+    lists = dict(req=i32(info[_lib.FI_PP_REQUEST_INDICES_OFFSET], padded),
+                 tile=i32(info[_lib.FI_PP_QO_TILE_INDICES_OFFSET], padded),
+                 kvt=i32(info[_lib.FI_PP_KV_TILE_INDICES_OFFSET], padded),
+                 merge=i32(info[_lib.FI_PP_MERGE_INDPTR_OFFSET], rows + 1) if info[_lib.FI_PP_SPLIT_KV] else [],
+                 chunk=i32(info[_lib.FI_PP_KV_CHUNK_SIZE_PTR_OFFSET], 1))
     return rc, info, lists
 
 
@@ -45,8 +48,6 @@ def entries(qo_lens, kv_lens, chunk):
 
 
 def test_new_symbols_are_exported(fi_lib):
-    from flashinfer import _lib
-
     for s in ("fi_batch_prefill_qkvo_run", "fi_single_prefill_qkvo_run"):
         assert s in _lib.EXPORTED_SYMBOLS and hasattr(fi_lib, s)
 
@@ -55,13 +56,11 @@ def test_new_symbols_are_exported(fi_lib):
 @pytest.mark.parametrize("shape", [([1024] * 16, [1024] * 16, 128, 128), ([377, 177, 1], [544, 977, 0], 32, 8),
                                    ([8192], [8192], 16, 16), ([3928], [7563], 128, 128)])
 def test_plan_192_128_succeeds_and_is_tagged(fi_lib, shape, graph):
-    from flashinfer import _lib
-
     qo_lens, kv_lens, hq, hkv = shape
     rc, info, lists = plan(fi_lib, qo_lens, kv_lens, hq, hkv, 192, 128, graph=graph, float_bytes=1 << 34)
     assert rc == 0, fi_lib.fi_last_error()
-    assert info[15] == _lib.FI_PREFILL_QKVO_PLAN_MAGIC != _lib.FI_PREFILL_PLAN_MAGIC
-    assert info[3] == 128  # q tile
+    assert info[_lib.FI_PP_MAGIC] == _lib.FI_PREFILL_QKVO_PLAN_MAGIC != _lib.FI_PREFILL_PLAN_MAGIC
+    assert info[_lib.FI_PP_CTA_TILE_Q] == 128  # q tile
     # every (request, q tile) appears, once per kv chunk
     g = hq // hkv
     items = {(r, t) for r, t in zip(lists["req"], lists["tile"]) if r >= 0}
@@ -76,7 +75,7 @@ def test_forced_split_workspace_is_sized_by_head_dim_vo(fi_lib):
     rc, info, _ = plan(fi_lib, qo_lens, kv_lens, hq, hkv, 192, 128, float_bytes=need + ENTRY_ALIGN,
                        fixed_split=chunk)
     assert rc == 0, fi_lib.fi_last_error()
-    assert info[14] == 1 and info[9] == chunk
+    assert info[_lib.FI_PP_SPLIT_KV] == 1 and info[_lib.FI_PP_KV_CHUNK_SIZE] == chunk
     rc, _, _ = plan(fi_lib, qo_lens, kv_lens, hq, hkv, 192, 128, float_bytes=need - 4, fixed_split=chunk)
     assert rc != 0 and b"float workspace too small" in fi_lib.fi_last_error()
     # the bound is head_dim_vo's: 128 / 128 needs the same bytes (refused just below), 256 / 256 more
@@ -94,14 +93,12 @@ def test_unsupported_pairs_are_refused(fi_lib, pair):
 
 
 def _params(**kw):
-    from flashinfer import _lib
-
     base = dict(q=16, k=16, v=16, o=16, q_stride_n=4 * 192, q_stride_h=192, k_stride_n=4 * 192, k_stride_h=192,
                 v_stride_n=4 * 128, v_stride_h=128, qo_len=10, kv_len=20, num_qo_heads=4, num_kv_heads=4,
                 head_dim_qk=192, head_dim_vo=128, q_dtype=_lib.FI_DTYPE_BF16, kv_dtype=_lib.FI_DTYPE_BF16,
                 o_dtype=_lib.FI_DTYPE_BF16, mask_mode=1, sm_scale=0.07)
     base.update(kw)
-    return _lib.PrefillQkvoParams(**base)
+    return _lib.fi_prefill_qkvo_params_t(**base)
 
 
 @pytest.mark.parametrize("kw,msg", [
@@ -128,15 +125,13 @@ def test_single_run_refusals_report_errors(fi_lib, kw, msg):
 def test_runs_refuse_foreign_plans(fi_lib):
     """fi_batch_prefill_qkvo_run takes only a 192 / 128 plan (its partial states are head_dim_vo wide); the paged run
     refuses a 192 / 128 plan."""
-    from flashinfer import _lib
-
     _, info_eq, _ = plan(fi_lib, [10], [20], 4, 4, 128, 128)
     _, info_qkvo, _ = plan(fi_lib, [10], [20], 4, 4, 192, 128)
     p = _params(batch_size=1, qo_indptr=16, kv_indptr=16)
     arr = (C.c_int64 * 16)(*info_eq)
     rc = fi_lib.fi_batch_prefill_qkvo_run(None, 0, 16, 0, arr, 16, C.byref(p), None)
     assert rc != 0 and b"not made for head_dim_qk 192" in fi_lib.fi_last_error()
-    bp = _lib.BatchPrefillParams()
+    bp = _lib.fi_batch_prefill_params_t()
     arr = (C.c_int64 * 16)(*info_qkvo)
     rc = fi_lib.fi_batch_prefill_paged_run(None, 0, 16, 0, arr, 16, C.byref(bp), None)
     assert rc != 0 and b"fi_batch_prefill_qkvo_run" in fi_lib.fi_last_error()

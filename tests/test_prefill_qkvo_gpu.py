@@ -7,6 +7,7 @@ import random
 import pytest
 import torch
 
+from flashinfer import _lib
 from oracle import attention_ref as R
 from test_prefill_gpu import ptol
 
@@ -153,7 +154,7 @@ def test_splits_and_empty_requests(dtype):
     qd, kd, vd = q.to(DEV), k.to(DEV), v.to(DEV)
     o0, lse0, w0 = _ragged(qo_lens, kv_lens, hq, hkv, dtype, False, qd, kd, vd, disable_split_kv=True)
     o1, lse1, w1 = _ragged(qo_lens, kv_lens, hq, hkv, dtype, False, qd, kd, vd, fixed_split_size=256)
-    assert w0._plan_info[14] == 0 and w1._plan_info[14] == 1
+    assert w0._plan_info[_lib.FI_PP_SPLIT_KV] == 0 and w1._plan_info[_lib.FI_PP_SPLIT_KV] == 1
     o_ref, lse_ref = _ref(q, k, v, qo_lens, kv_lens, False)
     for o, lse in ((o0, lse0), (o1, lse1)):
         _check(o, lse, o_ref, lse_ref, dtype)

@@ -61,31 +61,31 @@ def test_host_validation_without_a_launch(fi_lib):
     for name in _lib.SAMPLING_SYMBOLS:
         fn = getattr(fi_lib, name)
         assert fn(None, None) != 0 and b"null" in fi_lib.fi_last_error()
-        p = _lib.SamplingParams(probs=None, samples=oaddr, batch=1, num_rows=1, vocab=4)
+        p = _lib.fi_sampling_params_t(probs=None, samples=oaddr, batch=1, num_rows=1, vocab=4)
         assert fn(C.byref(p), None) != 0 and b"null" in fi_lib.fi_last_error(), name
-        p = _lib.SamplingParams(probs=addr, samples=oaddr, batch=1, num_rows=1, vocab=0)
+        p = _lib.fi_sampling_params_t(probs=addr, samples=oaddr, batch=1, num_rows=1, vocab=0)
         assert fn(C.byref(p), None) != 0 and b"vocab" in fi_lib.fi_last_error(), name
-        p = _lib.SamplingParams(probs=addr, samples=oaddr, batch=1, num_rows=1, vocab=(1 << 22) + 1)
+        p = _lib.fi_sampling_params_t(probs=addr, samples=oaddr, batch=1, num_rows=1, vocab=(1 << 22) + 1)
         assert fn(C.byref(p), None) != 0 and b"vocab" in fi_lib.fi_last_error(), name
-        p = _lib.SamplingParams(probs=addr, samples=oaddr, batch=-1, num_rows=1, vocab=4)
+        p = _lib.fi_sampling_params_t(probs=addr, samples=oaddr, batch=-1, num_rows=1, vocab=4)
         assert fn(C.byref(p), None) != 0 and b"negative" in fi_lib.fi_last_error(), name
-        p = _lib.SamplingParams(probs=addr, samples=oaddr, batch=2, num_rows=1, vocab=4)
+        p = _lib.fi_sampling_params_t(probs=addr, samples=oaddr, batch=2, num_rows=1, vocab=4)
         assert fn(C.byref(p), None) != 0 and b"indices" in fi_lib.fi_last_error(), name
         # an empty batch is a no-op, not a launch
-        p = _lib.SamplingParams(probs=None, samples=None, batch=0, num_rows=0, vocab=4)
+        p = _lib.fi_sampling_params_t(probs=None, samples=None, batch=0, num_rows=0, vocab=4)
         assert fn(C.byref(p), None) == 0, name
     for name in _lib.ROW_TRANSFORM_SYMBOLS:
         fn = getattr(fi_lib, name)
         assert fn(None, None) != 0 and b"null" in fi_lib.fi_last_error()
-        p = _lib.RowTransformParams(in_=addr, out=None, batch=1, vocab=4)
+        p = _lib.fi_row_transform_params_t(in_=addr, out=None, batch=1, vocab=4)
         assert fn(C.byref(p), None) != 0 and b"null" in fi_lib.fi_last_error(), name
-        p = _lib.RowTransformParams(in_=addr, out=addr, batch=1, vocab=0)
+        p = _lib.fi_row_transform_params_t(in_=addr, out=addr, batch=1, vocab=0)
         assert fn(C.byref(p), None) != 0 and b"vocab" in fi_lib.fi_last_error(), name
-        p = _lib.RowTransformParams(in_=None, out=None, batch=0, vocab=4)
+        p = _lib.fi_row_transform_params_t(in_=None, out=None, batch=0, vocab=4)
         assert fn(C.byref(p), None) == 0, name
     fn = fi_lib.fi_chain_speculative_sampling
     assert fn(None, None) != 0 and b"null" in fi_lib.fi_last_error()
-    p = _lib.ChainSpeculativeParams(draft_probs=addr, draft_token_ids=oaddr, target_probs=addr, output_token_ids=oaddr,
+    p = _lib.fi_chain_speculative_params_t(draft_probs=addr, draft_token_ids=oaddr, target_probs=addr, output_token_ids=oaddr,
                                     output_accepted_token_num=None, output_emitted_draft_token_num=oaddr, batch=1,
                                     num_speculative_tokens=1, vocab=4)
     assert fn(C.byref(p), None) != 0 and b"null" in fi_lib.fi_last_error()
