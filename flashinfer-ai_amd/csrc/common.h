@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <optional>
+
 #include "fi_mi355.h"
 
 namespace fi {
@@ -23,6 +25,23 @@ const char* last_error();
       return ::fi::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, \
                              __LINE__);                                                   \
   } while (0)
+
+// ---- kernel-choice switches (lib.hip): the FI_* variables of INTEGRATION.md ----
+// Each starts as the environment gave it when the library was loaded; fi_set_option changes it in the running process.
+enum Option {
+  OPT_NUM_CUS,
+  OPT_DECODE_MFMA16,
+  OPT_GEMM_WS_MIN_TILES,
+  OPT_GEMM_DMA_TM,
+  OPT_GEMM_BIG,
+  OPT_GEMM_BIG_MIN_TILES,
+  OPT_GEMM_BIG_FOLD_MIN_TILES,
+  OPT_GEMM_HW_SCALES,
+  OPT_COUNT
+};
+// The switch's value; none when neither fi_set_option nor the environment gave it one.  One atomic load: a call
+// that must not see a switch change under it reads each switch once, at its top.
+std::optional<int> option(Option o);
 
 inline size_t dtype_size(int dt) {
   switch (dt) {

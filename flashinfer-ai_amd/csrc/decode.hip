@@ -48,17 +48,6 @@ static decode_launch_fn find_launcher(int kv_dt, int head_dim) {
 #undef FI_ROW
 }
 
-// FI_DECODE_MFMA16=0: the r1 kernel choice (see choose_decode), read once per process.  The decode suite runs
-// through both choices: by default the 16x16x32 kernel takes the shapes the VALU kernel and the 32x32x16 kernel
-// serve under r1.
-static bool decode_mfma16() {
-  static const bool on = [] {
-    const char* e = getenv("FI_DECODE_MFMA16");
-    return !e || atoi(e) != 0;
-  }();
-  return on;
-}
-
 // work items per CU the planner cuts the batch into.  r3 sweep over the reference
 // benchmark's grid (tools/bench_ref_grids.py and a one-off r3 sweep; bf16 32 / 4 and 32 / 8 heads, random and identity
 // page order): with a 16-bit cache 4 per CU is level with 8 at C2 (6.72 against 6.65 TB/s) and ahead on everything
@@ -114,7 +103,9 @@ static DecodeChoice choose_decode(int group, int q_dt, int kv_dt, int head_dim, 
   // the matrix-core kernels: 16-bit q, K/V in the q dtype or fp8, head_dim 64 / 128, 32-bit element offsets
   const bool mfma = (q_dt == FI_DTYPE_F16 || q_dt == FI_DTYPE_BF16) && (kv_dt == q_dt || fp8) &&
                     (head_dim == 64 || head_dim == 128) && strides_fit_31_bits;
-  if (decode_mfma16()) {
+  // FI_DECODE_MFMA16=0: the r1 kernel choice.  The decode suite runs through both choices: by default the 16x16x32
+  // kernel takes the shapes the VALU kernel and the 32x32x16 kernel serve under r1.
+  if (option(OPT_DECODE_MFMA16).value_or(1) != 0) {
     // the 16x16x32 form (decode_mfma16_kernel.h) serves every group of <= 16 heads: measured >= the VALU kernel
     // (G <= 4) and >= the 32x32x16 form (G 5..16) on every shape of tools/bench_decode_kernels.py (C2 6.35 -> 6.52
     // TB/s, bs 8 x 1024 20.3 -> 16.1 us), and the only one with room for the fused-RoPE rotation.  ALiBi and the

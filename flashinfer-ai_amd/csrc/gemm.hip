@@ -552,12 +552,7 @@ __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const
   if (have_out) store_tile();
 }
 
-static int env_int(const char* name, int unset) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : unset;
-}
-
-// The FI_GEMM_* knobs, read once per process; the tests force kernels through them.
+// The FI_GEMM_* switches as one call sees them; the tests force kernels through them.
 struct GemmKnobs {
   int ws_min_tiles;        // FI_GEMM_WS_MIN_TILES: fewest tiles for the persistent kernels (-1: never; default 2 x CUs)
   int forced_tm;           // FI_GEMM_DMA_TM = 128 / 256: force the LDS-DMA kernel's tile shape (0: by the group sizes)
@@ -566,18 +561,16 @@ struct GemmKnobs {
   bool hw_scales;          // FI_GEMM_HW_SCALES=0: never the hardware-scale variant (A/B runs)
 };
 
-static const GemmKnobs& gemm_knobs() {
-  static const GemmKnobs k = [] {
-    GemmKnobs k;
-    const int cus = fi_num_compute_units();
-    k.ws_min_tiles = env_int("FI_GEMM_WS_MIN_TILES", 2 * cus);
-    k.forced_tm = env_int("FI_GEMM_DMA_TM", 0);
-    k.big_hws_min_tiles = env_int("FI_GEMM_BIG", 1) == 0 ? -1 : env_int("FI_GEMM_BIG_MIN_TILES", cus / 2);
-    // a forced FI_GEMM_BIG_MIN_TILES (tests, A/B runs) applies to both variants
-    k.big_fold_min_tiles = env_int("FI_GEMM_BIG_FOLD_MIN_TILES", env_int("FI_GEMM_BIG_MIN_TILES", 4 * cus));
-    k.hw_scales = env_int("FI_GEMM_HW_SCALES", 1) != 0;
-    return k;
-  }();
+// Each switch read once, the defaults from the CU count of this call.
+static GemmKnobs read_gemm_knobs(int cus) {
+  GemmKnobs k;
+  k.ws_min_tiles = option(OPT_GEMM_WS_MIN_TILES).value_or(2 * cus);
+  k.forced_tm = option(OPT_GEMM_DMA_TM).value_or(0);
+  const std::optional<int> big_min_tiles = option(OPT_GEMM_BIG_MIN_TILES);
+  k.big_hws_min_tiles = option(OPT_GEMM_BIG).value_or(1) == 0 ? -1 : big_min_tiles.value_or(cus / 2);
+  // a forced FI_GEMM_BIG_MIN_TILES (tests, A/B runs) applies to both variants
+  k.big_fold_min_tiles = option(OPT_GEMM_BIG_FOLD_MIN_TILES).value_or(big_min_tiles.value_or(4 * cus));
+  k.hw_scales = option(OPT_GEMM_HW_SCALES).value_or(1) != 0;
   return k;
 }
 
@@ -590,11 +583,13 @@ struct GemmChoice {
   GemmBig big;
   GemmNext next;
   int persistent_grid;  // the persistent kernels' grid: one workgroup per CU, XCD-aligned
+  bool hw_scales;       // big != NONE: the scale check and the hardware-scale variant may run (FI_GEMM_HW_SCALES)
 };
 
 static GemmChoice choose_gemm(const GemmParams& p) {
-  const GemmKnobs& k = gemm_knobs();
-  GemmChoice c{GemmBig::NONE, GemmNext::TILE_128x128, (fi_num_compute_units() / 8) * 8};
+  const int cus = fi_num_compute_units();
+  const GemmKnobs k = read_gemm_knobs(cus);
+  GemmChoice c{GemmBig::NONE, GemmNext::TILE_128x128, (cus / 8) * 8, k.hw_scales};
   const bool persistent = k.ws_min_tiles >= 0 && c.persistent_grid >= 8;
   // 128 x 256 tiles for grouped problems whose groups have few rows (a <= 128-row group fills half of a
   // 256-row tile); FI_GEMM_DMA_TM = 128 / 256 forces the shape
@@ -615,7 +610,7 @@ static GemmChoice choose_gemm(const GemmParams& p) {
   if (persistent && big_rows && k.big_hws_min_tiles >= 0 && big_tiles >= k.big_hws_min_tiles) {
     //  * arbitrary scales (the fold variant): mixed below four tiles per CU (8 x 1024 x 4096 x 7168 1.57 against 1.32,
     //    4 x 1024 x 7168 x 2048 0.88 against 1.18) -> from 4 x CUs tiles on, as in r2.
-    if (big_tiles >= k.big_fold_min_tiles) return {GemmBig::BOTH, GemmNext::NONE, c.persistent_grid};
+    if (big_tiles >= k.big_fold_min_tiles) return {GemmBig::BOTH, GemmNext::NONE, c.persistent_grid, k.hw_scales};
     c.big = GemmBig::HWS_ONLY;
   }
   // producer/consumer kernel: enough 256 x 128 tiles to give every CU a few
@@ -635,7 +630,7 @@ static hipError_t launch_gemm(const GemmParams& p_in, hipStream_t stream) {
   if (c.big != GemmBig::NONE) {
     // the pow2 check and the hardware-scale variant need a flag slot: none under a stream capture before the first
     // eager call, or with FI_GEMM_HW_SCALES=0.  HWS_ONLY then launches nothing and the following kernel does the call.
-    ws.pow2_flag = gemm_knobs().hw_scales ? pow2_flag_slot(stream) : nullptr;
+    ws.pow2_flag = c.hw_scales ? pow2_flag_slot(stream) : nullptr;
     if (ws.pow2_flag != nullptr) {
       launch_pow2_check(ws, stream);
       launch_gemm_big(ws, /*hws=*/true, c.persistent_grid, stream);

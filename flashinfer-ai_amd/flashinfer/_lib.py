@@ -85,6 +85,12 @@ def check(status: int, what: str) -> None:
         raise RuntimeError(f"{what} failed: {msg}")
 
 
+def set_option(name: str, value: Optional[int]) -> None:
+    """fi_set_option: give a kernel-choice switch of this process (``FI_DECODE_MFMA16``, ``FI_GEMM_*``,
+    ``FI_NUM_CUS``) a value; None returns it to what the environment gave it when the library loaded."""
+    check(lib().fi_set_option(name.encode(), None if value is None else str(value).encode()), f"set_option({name})")
+
+
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 

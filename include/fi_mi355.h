@@ -74,8 +74,12 @@ enum fi_mask_mode { FI_MASK_NON_CAUSAL = 0, FI_MASK_CAUSAL = 1, FI_MASK_CUSTOM =
 FI_API const char* fi_last_error(void);
 FI_API int fi_abi_version(void);
 /* number of compute units the planner balances for (hipDeviceProp.multiProcessorCount of the current
- * device, or FI_NUM_CUS from the environment, or 256 when no device is visible). */
+ * device, or the switch FI_NUM_CUS when it is positive, or 256 when no device is visible). */
 FI_API int fi_num_compute_units(void);
+/* Set a kernel-choice switch of this process (names and values as the environment variables of INTEGRATION.md);
+ * value == NULL returns the switch to what the environment gave it at load.  A set value wins over the environment.
+ * Returns non-zero (fi_last_error) for an unknown name or a value that is not an integer. */
+FI_API int fi_set_option(const char* name, const char* value);
 
 /* ------------------------------------------------------------------------------------------------
  * Paged KV cache view.  ref: paged_kv_t, include/flashinfer/page.cuh:37-210.

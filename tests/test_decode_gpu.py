@@ -1,7 +1,12 @@
 """GPU parity: HIP batch / single decode (through the C ABI) against the CPU oracle on the same seeded
 inputs.  Grid modelled on the reference's tests/attention/test_batch_decode_kernels.py:58-70,
 test_decode_prefill_lse.py:22-71 and test_non_contiguous_*.py.  Tolerance: rtol = atol = 1e-3 for
-16-bit kv (the reference's own bar, test_batch_decode_kernels.py:144-184)."""
+16-bit kv (the reference's own bar, test_batch_decode_kernels.py:144-184).
+
+Every test here runs once per entry of VARIANTS, in this process (_lib.set_option before the test, back to the
+environment's value after it; the plain functions are the default run, TestKernelVariants at the end repeats them
+for r1): the default kernel choice, which sends every group of <= 16 heads to decode_mfma16_kernel.h, and r1
+(FI_DECODE_MFMA16=0): groups of <= 4 heads back on the VALU kernel, wider ones on the 32x32x16 matrix-core kernel."""
 import math
 
 import pytest
@@ -12,6 +17,22 @@ from oracle import attention_ref as R
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+
+VARIANTS = {"default": {}, "r1": {"FI_DECODE_MFMA16": 0}}
+
+
+@pytest.fixture(autouse=True)
+def kernel_variant(request):
+    """Sets the switches of a VARIANTS entry for the test (TestKernelVariants names it; a plain test runs "default")
+    and returns every one of them to the environment's value afterwards."""
+    options = VARIANTS[getattr(request, "param", "default")]
+    try:
+        for name, value in options.items():
+            _lib.set_option(name, value)
+        yield
+    finally:
+        for name in options:
+            _lib.set_option(name, None)
 
 
 def tol(dtype):
@@ -399,19 +420,8 @@ def test_single_decode_head_dim_512():
     torch.testing.assert_close(lse.cpu(), lse_ref.float(), rtol=1e-3, atol=1e-3)
 
 
-def test_decode_suite_through_r1_kernel_choice():
-    """FI_DECODE_MFMA16=0: groups of <= 4 heads back on the VALU kernel, wider ones on the 32x32x16 matrix-core
-    kernel (the default sends every group of <= 16 heads to decode_mfma16_kernel.h).  The switch is read once per
-    process, so the suite runs in a child."""
-    import os
-    import subprocess
-    import sys
-
-    if os.environ.get("FI_DECODE_MFMA16") == "0":
-        pytest.skip("already the child")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, FI_DECODE_MFMA16="0")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_decode_gpu.py"), "-x", "-q",
-                        "-p", "no:cacheprovider"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout
+# Every test function above once more per non-default entry of VARIANTS; the functions themselves are the default run
+# and keep their ids.
+TestKernelVariants = pytest.mark.parametrize("kernel_variant", [v for v in VARIANTS if v != "default"], indirect=True)(
+    type("TestKernelVariants", (), {name: staticmethod(fn) for name, fn in list(globals().items())
+                                    if name.startswith("test_") and callable(fn)}))

@@ -1,14 +1,48 @@
 """GPU parity: fp8 groupwise (grouped) GEMM against dequantise-then-matmul, the reference's own check
-(tests/GEMM/test_groupwise_scaled_gemm_fp8.py:35-71, 135-192; atol = rtol = 1e-2 in bf16 output)."""
+(tests/GEMM/test_groupwise_scaled_gemm_fp8.py:35-71, 135-192; atol = rtol = 1e-2 in bf16 output).
+
+The library picks the kernel by problem size (256 x 256 tiles from half a tile per CU on, 128 x 256 tiles for groups
+of few rows, the 128 x 128 kernel below that).  Every test here runs once per entry of VARIANTS, in this process (the plain
+functions are the default run, TestKernelVariants at the end of the file repeats them for the other entries): the
+switches are set through _lib.set_option before the test and returned to the environment's values after it.
+  default -> the 128 x 128 kernel and the size-based choice
+  FI_GEMM_WS_MIN_TILES=0 FI_GEMM_BIG_MIN_TILES=0 -> every shape takes the 256 x 256 kernel (gemm_big.hip)
+  FI_GEMM_WS_MIN_TILES=0 FI_GEMM_DMA_TM=256 / 128 -> every shape takes the persistent LDS-DMA kernel with
+                                       256 x 128 / 128 x 256 tiles
+  ... FI_GEMM_HW_SCALES=0 -> the 256 x 256 kernel without its hardware-scale path (power-of-two scales, which the
+                                       reference's quantiser produces, otherwise ride the MFMA's E8M0 block scales)"""
 import math
 
 import pytest
 import torch
 
+from flashinfer import _lib
 from oracle import gemm_ref as G
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+
+VARIANTS = {
+    "default": {},
+    "dma-256x256": {"FI_GEMM_WS_MIN_TILES": 0, "FI_GEMM_BIG_MIN_TILES": 0},
+    "dma-256x128": {"FI_GEMM_WS_MIN_TILES": 0, "FI_GEMM_DMA_TM": 256, "FI_GEMM_BIG": 0},
+    "dma-128x256": {"FI_GEMM_WS_MIN_TILES": 0, "FI_GEMM_DMA_TM": 128},
+    "dma-256x256-fold-only": {"FI_GEMM_WS_MIN_TILES": 0, "FI_GEMM_BIG_MIN_TILES": 0, "FI_GEMM_HW_SCALES": 0},
+}
+
+
+@pytest.fixture(autouse=True)
+def kernel_variant(request):
+    """Sets the switches of a VARIANTS entry for the test (TestKernelVariants names it; a plain test runs "default")
+    and returns every one of them to the environment's value afterwards."""
+    options = VARIANTS[getattr(request, "param", "default")]
+    try:
+        for name, value in options.items():
+            _lib.set_option(name, value)
+        yield
+    finally:
+        for name in options:
+            _lib.set_option(name, None)
 
 
 @pytest.mark.parametrize("m", [4, 128, 300, 1024])
@@ -78,7 +112,7 @@ def test_group_gemm_scales_that_are_not_powers_of_two(scales, mode):
     """The reference takes any f32 scale (csrc/group_gemm_fp8_groupwise_sm100.cu:89-124); its own quantiser happens to
     produce powers of two (flashinfer/testing/utils.py:96-98).  The 256 x 256 kernel feeds power-of-two scales to the
     MFMA's hardware block scales and must fall back to the general fold when a single scale is not one -- checked on
-    the device, per call.  (tests/test_gemm_variants_gpu.py sends this case through every large-problem kernel.)"""
+    the device, per call.  (TestKernelVariants sends this case through every large-problem kernel.)"""
     import flashinfer
 
     torch.manual_seed(5)
@@ -270,3 +304,10 @@ def test_group_gemm_graph_replay_follows_the_scale_kind():
         graph.replay()
         torch.cuda.synchronize()
         torch.testing.assert_close(out.float().cpu(), reference(sa_h), atol=0, rtol=0)
+
+
+# Every test function above once more per non-default entry of VARIANTS; the functions themselves are the default run
+# and keep their ids.
+TestKernelVariants = pytest.mark.parametrize("kernel_variant", [v for v in VARIANTS if v != "default"], indirect=True)(
+    type("TestKernelVariants", (), {name: staticmethod(fn) for name, fn in list(globals().items())
+                                    if name.startswith("test_") and callable(fn)}))

@@ -138,6 +138,14 @@ def run_prefill_plan(fi_lib, qo_indptr, kv_lens, hq, hkv, causal=False, cuda_gra
     return out
 
 
+@pytest.fixture
+def cus_256():
+    """The oracle's prefill plans are for 256 compute units, whatever device is current."""
+    _lib.set_option("FI_NUM_CUS", 256)
+    yield
+    _lib.set_option("FI_NUM_CUS", None)
+
+
 PREFILL_CASES = [
     # (qo_indptr, kv_lens, hq, hkv)
     ([0, 2048 * 1], [8192], 32, 8),                                   # one C3 request: 64 q tiles, no split
@@ -157,10 +165,9 @@ PREFILL_CASES = [
 @pytest.mark.parametrize("case", PREFILL_CASES)
 @pytest.mark.parametrize("causal", [False, True])
 @pytest.mark.parametrize("mode", ["auto", "graph", "fixed", "disabled"])
-def test_prefill_planner_matches_oracle(fi_lib, monkeypatch, case, causal, mode):
+def test_prefill_planner_matches_oracle(fi_lib, cus_256, case, causal, mode):
     from oracle.plan_ref import prefill_plan_ref
 
-    monkeypatch.setenv("FI_NUM_CUS", "256")
     qo_indptr, kv_lens, hq, hkv = case
     kw = dict(cuda_graph=mode == "graph", fixed=512 if mode == "fixed" else -1, disable=mode == "disabled")
     got = run_prefill_plan(fi_lib, qo_indptr, kv_lens, hq, hkv, causal=causal, **kw)
@@ -176,10 +183,9 @@ def test_prefill_planner_matches_oracle(fi_lib, monkeypatch, case, causal, mode)
         assert got["kv_chunk_size"] % 64 == 0 and got["kv_chunk_size"] >= 128
 
 
-def test_prefill_planner_grows_chunks_to_fit_the_float_workspace(fi_lib, monkeypatch):
+def test_prefill_planner_grows_chunks_to_fit_the_float_workspace(fi_lib, cus_256):
     from oracle.plan_ref import prefill_plan_ref
 
-    monkeypatch.setenv("FI_NUM_CUS", "256")
     qo_indptr, kv_lens, hq, hkv = [0, 64], [65536], 32, 8
     roomy = run_prefill_plan(fi_lib, qo_indptr, kv_lens, hq, hkv)
     tight_bytes = roomy["merge_indptr"][-1] * hq * 129 * 4 * 3 // 4   # three quarters of what the roomy plan's states take
@@ -192,10 +198,9 @@ def test_prefill_planner_grows_chunks_to_fit_the_float_workspace(fi_lib, monkeyp
 
 
 @pytest.mark.parametrize("causal", [False, True])
-def test_prefill_planner_sliding_window_uses_the_effective_kv_span(fi_lib, monkeypatch, causal):
+def test_prefill_planner_sliding_window_uses_the_effective_kv_span(fi_lib, cus_256, causal):
     from oracle.plan_ref import prefill_plan_ref
 
-    monkeypatch.setenv("FI_NUM_CUS", "256")
     qo_indptr, kv_lens, hq, hkv = [0, 64, 128], [40000, 300], 8, 8
     got = run_prefill_plan(fi_lib, qo_indptr, kv_lens, hq, hkv, causal=causal, window_left=1000)
     exp = prefill_plan_ref(qo_indptr, kv_lens, hq, hkv, causal=causal, window_left=1000)
@@ -217,11 +222,10 @@ def test_decode_planner_sliding_window_partitions_only_the_window_pages(fi_lib):
     assert got["kv_chunk_size"] < full["kv_chunk_size"]  # 64 window pages, not 4096, are spread over the grid
 
 
-def test_prefill_planner_balances_a_mixed_batch(fi_lib, monkeypatch):
+def test_prefill_planner_balances_a_mixed_batch(fi_lib, cus_256):
     """122 one-row requests of 600 keys + 8 requests of 10 000 keys and 17 rows (bench_batch_attention.py's hybrid):
     130 q tiles > 128 resident items, so the reference's binary search leaves every request whole and the launch ends
     in eight lone workgroups walking 10 000 keys.  The balance rule cuts chunks of about W / (2 x 128) tokens."""
-    monkeypatch.setenv("FI_NUM_CUS", "256")
     qo_indptr = list(range(123)) + [122 + 17 * (i + 1) for i in range(8)]
     kv_lens = [600] * 122 + [10000] * 8
     got = run_prefill_plan(fi_lib, qo_indptr, kv_lens, 28, 4, causal=True)
