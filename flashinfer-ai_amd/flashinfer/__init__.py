@@ -1,11 +1,12 @@
 """flashinfer -- MI355X (gfx950) native implementation of FlashInfer's paged-KV attention hot path.
 
-Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / gemm / sampling / norm / activation`` operator API
+Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / gemm / fp8_quantization / sampling / norm / activation`` operator API
 of FlashInfer v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-written HIP kernels behind the C ABI of
 ``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided.
 """
 from . import _lib as _lib
 from . import activation as activation
+from . import fp8_quantization as fp8_quantization
 from . import mla as mla
 from . import norm as norm
 from . import sampling as sampling
@@ -35,6 +36,8 @@ from .decode import (
 )
 from .decode import fast_decode_plan as fast_decode_plan
 from .decode import single_decode_with_kv_cache as single_decode_with_kv_cache
+from .fp8_quantization import mxfp8_dequantize_host as mxfp8_dequantize_host
+from .fp8_quantization import mxfp8_quantize as mxfp8_quantize
 from .gemm import gemm_fp8_nt_groupwise as gemm_fp8_nt_groupwise
 from .gemm import group_gemm_fp8_nt_groupwise as group_gemm_fp8_nt_groupwise
 from .mla import BatchMLAPagedAttentionWrapper as BatchMLAPagedAttentionWrapper

@@ -23,6 +23,7 @@ import torch
 from . import _lib
 # ref getters: flashinfer/activation.py:65-88 and flashinfer/norm.py:38-40 (exports csrc/flashinfer_norm_binding.cu).
 from .activation import get_act_and_mul_module as get_act_and_mul_module
+from .gemm import _group_gemm_mxfp4_into
 from .norm import get_norm_module as get_norm_module
 # ref getter: flashinfer/sampling.py:60-487; exports csrc/flashinfer_sampling_binding.cu:62-82.  The functions keep the
 # positional signatures of the reference's custom ops (tensors in, tensors out; seed and offset drawn inside).
@@ -257,5 +258,12 @@ def get_gemm_sm100_module():
                 scale_granularity_n, scale_granularity_k, int(scale_major_mode == "K"), _lib.fi_dtype(a.dtype),
                 _lib.fi_dtype(b.dtype), _lib.fi_dtype(out.dtype), _stream(a)), "group_gemm_fp8_nt_groupwise")
 
+    def group_gemm_mxfp4_nt_groupwise(int_workspace_buffer, float_workspace_buffer, a, b, a_scale, b_scale, out,
+                                      m_indptr, n, k, mma_sm, tile_m, tile_n, tile_k, swap_ab) -> None:
+        """ref: CutlassGroupGemmMXFP4GroupwiseScaledSM100, csrc/group_gemm_mxfp4_groupwise_sm100.cu
+        (flashinfer/gemm.py:2928-2944: 15 positional arguments).  The workspaces and the tuning knobs are unused."""
+        _group_gemm_mxfp4_into(a, b, a_scale, b_scale, out, m_indptr, n, k)
+
     return SimpleNamespace(gemm_fp8_nt_groupwise=gemm_fp8_nt_groupwise,
-                           group_gemm_fp8_nt_groupwise=group_gemm_fp8_nt_groupwise)
+                           group_gemm_fp8_nt_groupwise=group_gemm_fp8_nt_groupwise,
+                           group_gemm_mxfp4_nt_groupwise=group_gemm_mxfp4_nt_groupwise)

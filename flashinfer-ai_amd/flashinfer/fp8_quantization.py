@@ -1,0 +1,141 @@
+"""MXFP8 quantisation: ``mxfp8_quantize`` and ``mxfp8_dequantize_host`` of the reference's flashinfer/fp8_quantization.py
+(:179-239), and ``mxfp8_quantize_grouped``, this project's own extension that writes the scales where the grouped
+MXFP4 GEMM reads them.  The kernel is csrc/mxfp8_quantize.hip behind fi_mxfp8_quantize (include/fi_mi355.h).
+
+An MXFP8 tensor is e4m3 values plus one E8M0 byte (value ``2^(byte - 127)``) per 32 consecutive elements of a row.
+The scale of a block is the smallest power of two ``2^e`` with ``448 * 2^e >= amax``; the compare is exact (the
+reference's approximate reciprocal may give ``e + 1`` at ``amax == 448 * 2^e``).  ``enable_pdl`` is accepted and
+ignored: there is no programmatic dependent launch on this hardware.  Nothing here keeps host state or synchronises,
+so every call can be captured into a graph.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+
+_BLOCK = 32
+
+
+def _ceil_to(x: int, m: int) -> int:
+    return (x + m - 1) // m * m
+
+
+def _sf_offset(r: torch.Tensor, kb: torch.Tensor, nkb: int) -> torch.Tensor:
+    """Byte of (row, k block) in the swizzled "128x4" layout (include/fi_mi355.h, csrc/mx_layout.h)."""
+    return (r // 128) * ((nkb + 3) // 4) * 512 + (kb // 4) * 512 + (r % 32) * 16 + ((r % 128) // 32) * 4 + kb % 4
+
+
+def sf_row_offset(m_begin: int, group: int) -> int:
+    """First scale row of ``group`` whose rows start at ``m_begin`` in the grouped layout; ``sf_row_offset(cum_m, G)`` is
+    the row count of the whole scale tensor."""
+    return (m_begin + 127 * group) // 128 * 128
+
+
+def _check_input(input: torch.Tensor, alignment: int) -> None:
+    _lib.require_gpu_tensor(input, "input")
+    if input.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"input has dtype {input.dtype}, expected float16 or bfloat16")
+    if input.dim() < 1:
+        raise ValueError("input must have at least one dim")
+    assert input.shape[-1] % _BLOCK == 0
+    if alignment <= 0 or alignment % _BLOCK != 0:
+        raise ValueError(f"alignment {alignment} must be a positive multiple of {_BLOCK}")
+
+
+def _quantize_into(x: torch.Tensor, q: torch.Tensor, sf: torch.Tensor, swizzled: bool, alignment: int,
+                   m_indptr: Optional[torch.Tensor] = None) -> None:
+    """fi_mxfp8_quantize on a 2-D ``x``; ``q`` and ``sf`` are the pre-allocated outputs (every byte of both is written)."""
+    if x.shape[1] > 1 and x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    p = _lib.fi_mxfp8_quantize_params_t(
+        input=x.data_ptr(), q=q.data_ptr(), sf=sf.data_ptr(), m_indptr=_lib.ptr(m_indptr),
+        input_stride=x.stride(0) if x.shape[0] > 1 else x.shape[1], sf_bytes=sf.numel(), m=x.shape[0], k=x.shape[1],
+        alignment=alignment, num_groups=0 if m_indptr is None else m_indptr.shape[0] - 1,
+        sf_layout=_lib.FI_MX_SF_SWIZZLED_128X4 if swizzled else _lib.FI_MX_SF_LINEAR, dtype=_lib.fi_dtype(x.dtype))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().fi_mxfp8_quantize(C.byref(p), _lib.current_stream(x.device)), "mxfp8_quantize")
+
+
+def mxfp8_quantize(
+    input: torch.Tensor,
+    is_sf_swizzled_layout: bool = True,
+    alignment: int = 32,
+    enable_pdl: Optional[bool] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Quantise ``input`` (f16 / bf16 ``[..., k]``, ``k % 32 == 0``) to MXFP8 (ref: fp8_quantization.py:179-212).
+
+    Returns ``(x_q, sf)``: ``x_q`` is float8_e4m3fn ``[..., k_pad]`` with ``k_pad`` = ``k`` rounded up to ``alignment``
+    (a multiple of 32) and zeros in the padded columns; ``sf`` is a flat uint8 tensor, ``m * k_pad / 32`` bytes in the
+    linear layout ``[m, k_pad / 32]`` or the swizzled "128x4" layout with rows padded to 128 and blocks to 4 (padding is
+    0), where ``m`` is the product of the leading dims.
+    """
+    _check_input(input, alignment)
+    k = input.shape[-1]
+    m = input.numel() // k if k else 0
+    k_pad = _ceil_to(k, alignment)
+    nkb = k_pad // _BLOCK
+    x_q = torch.empty((*input.shape[:-1], k_pad), dtype=torch.float8_e4m3fn, device=input.device)
+    sf_size = _ceil_to(m, 128) * _ceil_to(nkb, 4) if is_sf_swizzled_layout else m * nkb
+    sf = torch.empty((sf_size,), dtype=torch.uint8, device=input.device)
+    _quantize_into(input.reshape(m, k), x_q.view(m, k_pad), sf, bool(is_sf_swizzled_layout), alignment)
+    return x_q, sf
+
+
+def mxfp8_quantize_grouped(input: torch.Tensor, m_indptr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Quantise the row operand of ``group_gemm_mxfp8_mxfp4_nt_groupwise``.  Not part of the reference: there the caller
+    swizzles every group's scales and pads them to the grouped placement by hand.
+
+    ``input`` is f16 / bf16 ``(cum_m, k)`` with ``k % 128 == 0``, ``m_indptr`` int32 ``(G + 1,)`` on the device (it is not
+    read on the host).  Returns ``(x_q, a_scale)``: float8_e4m3fn ``(cum_m, k)`` and uint8
+    ``((cum_m + 127 G) // 128 * 128, k // 32)`` in the grouped swizzled layout, padding as 0.
+    Rows of no group (below ``m_indptr[0]``, at or past ``m_indptr[-1]``) are quantised too; they have no scale row.
+    """
+    _check_input(input, _BLOCK)
+    _lib.require_gpu_tensor(m_indptr, "m_indptr")
+    if input.dim() != 2:
+        raise ValueError(f"input must be 2D (cum_m, k), got shape {tuple(input.shape)}")
+    if input.shape[1] % 128 != 0:
+        raise ValueError(f"k = {input.shape[1]} must be a multiple of 128 for the grouped layout")
+    if m_indptr.dtype != torch.int32 or m_indptr.dim() != 1 or m_indptr.shape[0] < 2:
+        raise ValueError("m_indptr must be a 1D int32 tensor of G + 1 >= 2 entries")
+    cum_m, k = input.shape
+    rows = sf_row_offset(cum_m, m_indptr.shape[0] - 1)
+    x_q = torch.empty((cum_m, k), dtype=torch.float8_e4m3fn, device=input.device)
+    a_scale = torch.empty((rows, k // _BLOCK), dtype=torch.uint8, device=input.device)
+    _quantize_into(input, x_q, a_scale, True, _BLOCK, m_indptr.contiguous())
+    return x_q, a_scale
+
+
+def mxfp8_dequantize_host(
+    input: torch.Tensor,
+    scale_tensor: torch.Tensor,
+    is_sf_swizzled_layout: bool = True,
+) -> torch.Tensor:
+    """``input`` (float8_e4m3fn, or its bytes as uint8, ``[m, k]``) times its block scales, as float32; pure torch on
+    CPU tensors (ref: fp8_quantization.py:215-239)."""
+    if input.is_cuda or scale_tensor.is_cuda:
+        raise RuntimeError("mxfp8_dequantize_host works on CPU tensors (move them with .cpu())")
+    if input.dim() != 2 or input.shape[1] % _BLOCK != 0:
+        raise ValueError(f"input must be 2D (m, k) with k a multiple of {_BLOCK}, got shape {tuple(input.shape)}")
+    if scale_tensor.dtype != torch.uint8:
+        raise ValueError(f"scale_tensor has dtype {scale_tensor.dtype}, expected uint8")
+    if input.dtype == torch.uint8:
+        input = input.view(torch.float8_e4m3fn)
+    m, k = input.shape
+    nkb = k // _BLOCK
+    flat = scale_tensor.reshape(-1)
+    need = _ceil_to(m, 128) * _ceil_to(nkb, 4) if is_sf_swizzled_layout else m * nkb
+    if flat.numel() < need:
+        raise ValueError(f"scale_tensor holds {flat.numel()} bytes, {need} needed")
+    if is_sf_swizzled_layout:
+        r = torch.arange(m).view(-1, 1).expand(m, nkb)
+        kb = torch.arange(nkb).view(1, -1).expand(m, nkb)
+        sf = flat[_sf_offset(r, kb, nkb).reshape(-1)].view(m, nkb)
+    else:
+        sf = flat[: m * nkb].view(m, nkb)
+    scale = torch.exp2(sf.double() - 127.0).unsqueeze(-1)
+    return (input.to(torch.float32).double().view(m, nkb, _BLOCK) * scale).view(m, k).to(torch.float32)

@@ -1,11 +1,14 @@
-"""fp8 groupwise-scaled GEMM operators (``gemm_fp8_nt_groupwise``, ``group_gemm_fp8_nt_groupwise``).
+"""fp8 groupwise-scaled GEMM operators (``gemm_fp8_nt_groupwise``, ``group_gemm_fp8_nt_groupwise``) and the grouped
+GEMM with MXFP8 activations and MXFP4 weights (``group_gemm_mxfp8_mxfp4_nt_groupwise``).
 
-API of the reference's ``flashinfer/gemm.py`` (:2321-2484, :2657-2811); the kernel is csrc/gemm.hip
-(MFMA fp8, two-level accumulation per 128-wide K block).  NVIDIA-only knobs (``mma_sm``, ``backend``)
+API of the reference's ``flashinfer/gemm.py`` (:2321-2484, :2657-2811, :2814-2949); the kernels are csrc/gemm.hip
+(MFMA fp8, two-level accumulation per 128-wide K block) and csrc/gemm_mxfp4.hip (block-scaled MFMA, the E8M0 scale
+bytes ride the instruction's scale operands).  NVIDIA-only knobs (``mma_sm``, ``backend``, tile shapes, ``swap_ab``)
 are accepted and ignored.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Literal, Optional, Tuple
 
 import torch
@@ -144,3 +147,90 @@ def group_gemm_fp8_nt_groupwise(
             "group_gemm_fp8_nt_groupwise",
         )
     return out
+
+
+def _group_gemm_mxfp4_into(a: torch.Tensor, b: torch.Tensor, a_scale: torch.Tensor, b_scale: torch.Tensor,
+                           out: torch.Tensor, m_indptr: torch.Tensor, n: int, k: int) -> None:
+    """fi_group_gemm_mxfp8_mxfp4_nt_groupwise on checked tensors; the scale buffers' sizes go along and are checked on
+    the host against (cum_m + 127 G) // 128 * 128 rows and n padded to 128, without reading m_indptr."""
+    a, b = a.contiguous(), b.contiguous()
+    a_scale, b_scale, m_indptr = a_scale.contiguous(), b_scale.contiguous(), m_indptr.contiguous()
+    if not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+    p = _lib.fi_group_gemm_mxfp4_params_t(
+        a=a.data_ptr(), b=b.data_ptr(), a_scale=a_scale.data_ptr(), b_scale=b_scale.data_ptr(), d=out.data_ptr(),
+        m_indptr=m_indptr.data_ptr(), a_scale_bytes=a_scale.numel(), b_scale_bytes=b_scale.numel(),
+        num_groups=m_indptr.shape[0] - 1, cum_m=a.shape[0], n=n, k=k, a_dtype=_lib.fi_dtype(a.dtype),
+        d_dtype=_lib.fi_dtype(out.dtype))
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.lib().fi_group_gemm_mxfp8_mxfp4_nt_groupwise(C.byref(p), _lib.current_stream(a.device)),
+                   "group_gemm_mxfp8_mxfp4_nt_groupwise")
+
+
+def group_gemm_mxfp8_mxfp4_nt_groupwise(
+    a: torch.Tensor,  # (cum_m, k)
+    b: torch.Tensor,  # (batch_size, n, k // 2)
+    a_scale: torch.Tensor,  # (cum_m_padded, k // 32)
+    b_scale: torch.Tensor,  # (batch_size, n_padded, k // 32)
+    m_indptr: torch.Tensor,  # (batch_size + 1, )
+    mma_sm: int = 1,
+    tile_m: int = 128,
+    tile_n: int = 128,
+    tile_k: int = 128,
+    swap_ab: bool = True,
+    out: Optional[torch.Tensor] = None,  # (cum_m, n)
+    out_dtype: Optional[torch.dtype] = None,
+) -> torch.Tensor:
+    r"""Grouped GEMM with MXFP8 activations and MXFP4 weights (ref: flashinfer/gemm.py:2814-2945): rows
+    ``m_indptr[g]:m_indptr[g+1]`` of ``a`` are multiplied with ``b[g]^T``; every 32 consecutive k elements of a row of
+    either operand carry one E8M0 scale byte.  The kernel is csrc/gemm_mxfp4.hip (block-scaled MFMA, no dequantisation).
+
+    a : ``(cum_m, k)`` float8_e4m3fn or float8_e5m2.
+    b : ``(batch_size, n, k // 2)`` uint8, two e2m1 codes per byte, element ``2 i`` in the low nibble of byte ``i``.
+    a_scale : uint8, ``((cum_m + 127 * batch_size) // 128 * 128, k // 32)``: the rows of group ``g`` start at scale row
+        ``(m_indptr[g] + 127 g) // 128 * 128`` and are in the swizzled "128x4" layout from there
+        (``flashinfer.fp8_quantization.mxfp8_quantize_grouped`` produces it).
+    b_scale : uint8, ``(batch_size, ceil(n / 128) * 128, k // 32)``, every group swizzled on its own.
+    m_indptr : ``(batch_size + 1,)`` int32 on the device; it is not read on the host.
+    mma_sm, tile_m, tile_n, tile_k, swap_ab : the reference's NVIDIA tuning knobs; validated as there, then ignored.
+    out : ``(cum_m, n)`` bf16 (default) / fp16; rows at or past ``m_indptr[-1]`` are not written.
+    ``n % 8 == 0`` and ``k % 128 == 0``.
+    """
+    for t, name in ((a, "a"), (b, "b"), (a_scale, "a_scale"), (b_scale, "b_scale"), (m_indptr, "m_indptr")):
+        _lib.require_gpu_tensor(t, name)
+    assert a.dtype in [torch.float8_e4m3fn, torch.float8_e5m2]
+    assert b.dtype == torch.uint8
+    assert a_scale.dtype == torch.uint8
+    assert b_scale.dtype == torch.uint8
+    assert m_indptr.dtype == torch.int32
+    assert mma_sm in [1, 2]
+    assert tile_m in [128]
+    assert tile_n in [64, 128, 192, 256]
+    assert tile_k in [128, 256]
+    assert swap_ab in [True, False]
+    if out is None:
+        if out_dtype is None:
+            out_dtype = torch.bfloat16
+    else:
+        if out_dtype is None:
+            out_dtype = out.dtype
+    assert out_dtype in [torch.bfloat16, torch.float16]
+    num_groups = m_indptr.shape[0] - 1
+    assert b.shape[0] == num_groups
+    n = b.shape[1]
+    k = b.shape[2] * 2  # two e2m1 codes per byte
+    assert a.shape[1] == k
+    assert n % 8 == 0
+    assert k % 128 == 0
+    out_shape = (a.shape[0], n)
+    if out is None:
+        out = torch.empty(out_shape, dtype=out_dtype, device=a.device)
+    else:
+        assert out.shape == out_shape
+        assert out.dtype == out_dtype
+    _group_gemm_mxfp4_into(a, b, a_scale, b_scale, out, m_indptr, n, k)
+    return out
+
+
+# the reference keeps the old name (gemm.py:2948-2949)
+group_gemm_mxfp4_nt_groupwise = group_gemm_mxfp8_mxfp4_nt_groupwise

@@ -698,6 +698,70 @@ typedef struct fi_act_and_mul_params {
 
 FI_API int fi_act_and_mul(const fi_act_and_mul_params_t* params, fi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * MX (microscaling) operands: e4m3 / e5m2 / e2m1 values with one E8M0 scale byte (value 2^(byte - 127)) per 32
+ * consecutive k elements of a row.  ref: mxfp8_quantize flashinfer/fp8_quantization.py:179-212,
+ * csrc/nv_internal/tensorrt_llm/kernels/quantization.cuh:586-688; group_gemm_mxfp8_mxfp4_nt_groupwise
+ * flashinfer/gemm.py:2814-2949, include/flashinfer/gemm/group_gemm_mxfp4_groupwise_sm100.cuh:54-90.
+ * Both entry points keep no host state and never synchronise (m_indptr stays on the device), so both may be captured
+ * into a graph; an empty problem returns 0 without a launch.
+ *
+ * Scale layouts.  Linear: [rows, nkb] bytes, nkb = k blocks per row.  Swizzled "128x4" (quantization.cuh:649-688):
+ * rows pad to 128 and k blocks to 4, and the byte of (row r, block kb) is at
+ *   (r/128)*ceil(nkb/4)*512 + (kb/4)*512 + (r%32)*16 + ((r%128)/32)*4 + kb%4.
+ * Grouped swizzled (the a_scale of the grouped GEMM; group_gemm_mxfp4_groupwise_sm100.cuh:66-68): the rows of group
+ * g start at scale row sf_off(g) = (m_indptr[g] + g*127)/128*128 and are swizzled on their own from there; the tensor
+ * has sf_off(G) = (cum_m + G*127)/128*128 rows.  The b_scale of group g starts at byte g * ceil(n/128)*128 * (k/32).
+ * ---------------------------------------------------------------------------------------------- */
+enum fi_mx_sf_layout { FI_MX_SF_LINEAR = 0, FI_MX_SF_SWIZZLED_128X4 = 1 };
+
+/* q = e4m3(x * 2^-e), sf = e + 127 per block of 32, where e is the smallest integer in [-127, 127] with
+ * 448 * 2^e >= amax (an all-zero block: e = -127, byte 0, q = 0).  The scaling is exact and the conversion rounds to
+ * nearest even.  One deliberate pin: the reference multiplies amax by an approximate reciprocal of 448, so at amax
+ * exactly 448 * 2^e its hardware may pick e + 1; here the compare is exact and such a block gets e.
+ * input: f16 / bf16 [m, k], k % 32 == 0, row stride in elements (a multiple of 8, base 16-byte aligned).
+ * q: [m, k_pad] e4m3 contiguous, k_pad = k rounded up to `alignment` (a multiple of 32); padded columns are 0.
+ * sf: sf_layout linear [m, k_pad/32] or swizzled (rows padded to 128, blocks to 4); with m_indptr != NULL
+ * (device, [num_groups + 1], ascending, 0 <= m_indptr[0], m_indptr[num_groups] <= m) the grouped swizzled layout of
+ * sf_off(num_groups) rows with m as cum_m, which needs k_pad % 128 == 0 to be read by the GEMM; rows of no group (below
+ * m_indptr[0], at or past m_indptr[num_groups]) get their q and no scale row.  EVERY byte of sf is written, padding as 0. */
+typedef struct fi_mxfp8_quantize_params {
+  const void* input;
+  void* q;
+  void* sf;
+  const int32_t* m_indptr; /* optional, device */
+  int64_t input_stride;
+  int64_t sf_bytes; /* size of the sf buffer */
+  int32_t m, k, alignment, num_groups;
+  int32_t sf_layout; /* enum fi_mx_sf_layout */
+  int32_t dtype;     /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+} fi_mxfp8_quantize_params_t;
+
+FI_API int fi_mxfp8_quantize(const fi_mxfp8_quantize_params_t* params, fi_stream_t stream);
+
+/* d[r, j] = sum_k a[r, k] 2^(sa[r, k/32] - 127) * e2m1(b[g, j, k]) 2^(sb[g, j, k/32] - 127) for the rows r of group g
+ * (m_indptr[g] <= r < m_indptr[g+1]); f32 accumulation, one round-to-nearest to the output dtype.
+ *   a: (cum_m, k) e4m3 / e5m2;  b: (G, n, k/2) bytes, element k = 2i in the low nibble of byte i; e2m1 codes 0..7 are
+ *   {0, .5, 1, 1.5, 2, 3, 4, 6}, bit 3 is the sign;  a_scale: grouped swizzled, at least sf_off(G) * k/32 bytes;
+ *   b_scale: swizzled per group, G * ceil(n/128)*128 * k/32 bytes;  m_indptr: int32 [G+1] on the DEVICE, ascending,
+ *   m_indptr[G] <= cum_m;  d: (cum_m, n) f16 / bf16 contiguous.  n % 8 == 0, k % 128 == 0.
+ * Empty groups are legal; rows of d at or past m_indptr[G] are not written; padding bytes of the scale tensors are
+ * never read.  Scale byte 255 (the E8M0 NaN) and non-finite inputs are unspecified.  No workspace. */
+typedef struct fi_group_gemm_mxfp4_params {
+  const void* a;
+  const void* b;
+  const void* a_scale;
+  const void* b_scale;
+  void* d;
+  const int32_t* m_indptr;
+  int64_t a_scale_bytes, b_scale_bytes; /* sizes of the scale buffers, checked on the host */
+  int32_t num_groups, cum_m, n, k;
+  int32_t a_dtype; /* FI_DTYPE_FP8_E4M3 / FI_DTYPE_FP8_E5M2 */
+  int32_t d_dtype; /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+} fi_group_gemm_mxfp4_params_t;
+
+FI_API int fi_group_gemm_mxfp8_mxfp4_nt_groupwise(const fi_group_gemm_mxfp4_params_t* params, fi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
