@@ -17,6 +17,11 @@ def tolerances(dtype: torch.dtype) -> dict:
     return {"rtol": 1e-3 + half_ulp(dtype), "atol": 1e-3}
 
 
+def assert_close(got, want, dtype, what=""):
+    assert got.dtype == dtype, what
+    torch.testing.assert_close(got.double(), want, **tolerances(dtype), msg=lambda m: f"{what}: {m}")
+
+
 def rmsnorm_ref(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-6, weight_bias: float = 0.0) -> torch.Tensor:
     """x * rsqrt(mean(x^2) + eps) * (weight_bias + w) over the last dim, in fp64."""
     x = x.double()

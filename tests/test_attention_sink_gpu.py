@@ -1,7 +1,7 @@
 """GPU: attention sinks (per-head softmax sink) in batch decode and batch prefill.
 
 The oracle is tests/sink_ref.py (the attention oracle, then a merge with (0, sink log2 e)), held to the reference's own
-statement by tests/test_attention_sink_cpu.py.  Tolerances are the decode suite's ``tol(dtype)`` on o and 1e-3 on the
+statement by tests/test_attention_sink_cpu.py.  Tolerances are the decode bar ``tol(dtype)`` on o and 1e-3 on the
 lse: the sink is folded where the kernels normalise a row, so it adds no rounding of its own.  Sinks are distinct per
 head (linspace(-4, 6)) so that a head mix-up shows; one head is -inf (sink off) and one +60 (the sink takes nearly
 all of the mass: o ~ 0, lse ~ 60 log2 e).
@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import sink_ref as S
+from attn_inputs import indptr_of, page_table, planned_decode_wrapper, planned_prefill_wrapper, scatter_to_pages, tol
 from flashinfer import _lib
 from oracle import attention_ref as R
 
@@ -27,14 +28,6 @@ WS_BYTES = 16 << 20
 DTYPES = [torch.float16, torch.bfloat16]
 
 
-def tol(dtype):
-    """tests/test_decode_gpu.py: rtol = atol = 1e-3 for fp16 outputs; half a bf16 ulp (2^-9 relative) of output
-    rounding on top for bf16."""
-    if dtype == torch.bfloat16:
-        return dict(rtol=1e-3 + 2.0 ** -8, atol=2e-3)
-    return dict(rtol=1e-3, atol=1e-3)
-
-
 def make_sinks(hq):
     s = torch.linspace(-4.0, 6.0, hq)
     s[1] = float("-inf")
@@ -42,20 +35,11 @@ def make_sinks(hq):
     return s
 
 
-def page_table(kv_lens, page, g, extra=3):
-    pages = [-(-l // page) for l in kv_lens]
-    total = sum(pages)
-    indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0)), dtype=torch.int32)
-    last = torch.tensor([(l - 1) % page + 1 if l > 0 else 0 for l in kv_lens], dtype=torch.int32)
-    indices = torch.randperm(total + extra, generator=g)[:total].to(torch.int32)
-    return indptr, indices, last, total + extra
-
-
 @functools.lru_cache(maxsize=None)
 def decode_case(kv_lens, hq, hkv, d, page, dtype, kv_dtype=None, window_left=-1, seed=0):
     """Seeded inputs and the oracle's answer with sinks, computed once per case and never modified."""
     g = torch.Generator().manual_seed(4000 + seed)
-    indptr, indices, last, npages = page_table(kv_lens, page, g)
+    indptr, indices, last, npages = page_table(kv_lens, page, g, extra_pages=3)
     cache = torch.randn(npages, 2, page, hkv, d, generator=g).to(kv_dtype or dtype)
     q = torch.randn(len(kv_lens), hq, d, generator=g).to(dtype)
     sinks = make_sinks(hq)
@@ -65,13 +49,9 @@ def decode_case(kv_lens, hq, hkv, d, page, dtype, kv_dtype=None, window_left=-1,
 
 
 def decode_wrapper(c, hq, hkv, d, page, **plan_kw):
-    import flashinfer
-
     q, cache, indptr, indices, last = c[:5]
-    w = flashinfer.BatchDecodeWithPagedKVCacheWrapper(torch.zeros(WS_BYTES, dtype=torch.uint8, device=DEV), "NHD")
-    w.plan(indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, page, q_data_type=q.dtype,
-           kv_data_type=cache.dtype, **plan_kw)
-    return w
+    return planned_decode_wrapper(WS_BYTES, "NHD", indptr, indices, last, hq, hkv, d, page, q_data_type=q.dtype,
+                                  kv_data_type=cache.dtype, **plan_kw)
 
 
 def check_decode(c, o, lse, dtype):
@@ -177,18 +157,13 @@ def prefill_case(d, dtype, causal, window_left, page=PAGE, seed=0):
     hq, hkv = 8, 2
     g = torch.Generator().manual_seed(5000 + seed)
     qo_lens, kv_lens = [a for a, _ in QO_KV], [b for _, b in QO_KV]
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
-    kv_indptr = torch.tensor([0] + list(torch.tensor(kv_lens).cumsum(0)), dtype=torch.int32)
+    qo_indptr = indptr_of(qo_lens)
+    kv_indptr = indptr_of(kv_lens)
     q = torch.randn(sum(qo_lens), hq, d, generator=g).to(dtype)
     k = torch.randn(sum(kv_lens), hkv, d, generator=g).to(dtype)
     v = torch.randn(sum(kv_lens), hkv, d, generator=g).to(dtype)
-    indptr, indices, last, npages = page_table(kv_lens, page, g)
-    cache = torch.zeros(npages, 2, page, hkv, d, dtype=dtype)
-    for b, n in enumerate(kv_lens):
-        for t in range(n):
-            pg = int(indices[int(indptr[b]) + t // page])
-            cache[pg, 0, t % page] = k[int(kv_indptr[b]) + t]
-            cache[pg, 1, t % page] = v[int(kv_indptr[b]) + t]
+    indptr, indices, last, npages = page_table(kv_lens, page, g, extra_pages=3)
+    cache = scatter_to_pages(k, v, kv_lens, indptr, indices, page, npages)
     sinks = make_sinks(hq)
     o_ref, lse_ref = S.batch_prefill_sink_ref(q.float(), qo_indptr, cache.float(), "NHD", indptr, indices, last, sinks,
                                               causal=causal, window_left=window_left)
@@ -202,11 +177,9 @@ def check_prefill(c, o, lse, dtype):
 
 
 def run_paged_prefill(c, dtype, causal, window_left, sinks, **plan_kw):
-    import flashinfer
-
-    w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(torch.zeros(WS_BYTES, dtype=torch.uint8, device=DEV), "NHD")
-    w.plan(c["qo_indptr"].to(DEV), c["indptr"].to(DEV), c["indices"].to(DEV), c["last"].to(DEV), c["hq"], c["hkv"],
-           c["d"], PAGE, causal=causal, window_left=window_left, q_data_type=dtype, kv_data_type=dtype, **plan_kw)
+    w = planned_prefill_wrapper(WS_BYTES, "NHD", c["qo_indptr"], c["indptr"], c["indices"], c["last"], c["hq"], c["hkv"],
+                                c["d"], PAGE, causal=causal, window_left=window_left, q_data_type=dtype,
+                                kv_data_type=dtype, **plan_kw)
     o, lse = w.run(c["q"].to(DEV), c["cache"].to(DEV), sinks=sinks, return_lse=True)
     return w, o, lse
 

@@ -2,13 +2,11 @@
 Modelled on the reference's tests/utils/test_quantization.py:33-75 (numpy.packbits is the definition) and
 tests/attention/test_batch_prefill_kernels.py:734-839 / test_single_prefill.py (custom mask == causal mask
 must reproduce the causal run; random masks against the oracle)."""
-import numpy as np
 import pytest
 import torch
 
+from attn_inputs import indptr_of, make_paged, planned_prefill_wrapper, ptol
 from oracle import attention_ref as R
-from test_decode_gpu import make_paged
-from test_prefill_gpu import ptol
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -49,7 +47,7 @@ def test_segment_packbits_matches_oracle(bitorder):
 
     torch.manual_seed(2)
     seglens = [0, 1, 8, 9, 0, 63, 4096, 17, 5]
-    indptr = torch.tensor([0] + list(np.cumsum(seglens)), dtype=torch.int32)
+    indptr = indptr_of(seglens)
     x = torch.rand(int(indptr[-1])) < 0.3
     y, new_indptr = flashinfer.segment_packbits(x.to(DEV), indptr.to(DEV), bitorder)
     y_ref, ind_ref = R.segment_packbits_ref(x, indptr, bitorder)
@@ -120,18 +118,17 @@ def test_batch_prefill_paged_custom_mask(ps, layout, logits_soft_cap):
             m[:, 0] = True
         masks.append(m.view(-1))
     mask = torch.cat(masks)
-    qo_indptr = torch.tensor([0] + list(np.cumsum(qo_lens)), dtype=torch.int32)
-    ws = torch.zeros(32 << 20, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(ws, layout)
-    w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, ps, custom_mask=mask.to(DEV),
-           causal=True, logits_soft_cap=logits_soft_cap, q_data_type=torch.float16)
+    qo_indptr = indptr_of(qo_lens)
+    w = planned_prefill_wrapper(32 << 20, layout, qo_indptr, indptr, indices, last, hq, hkv, d, ps,
+                                custom_mask=mask.to(DEV), causal=True, logits_soft_cap=logits_soft_cap,
+                                q_data_type=torch.float16)
     o, lse = w.run(q.to(DEV), cache.to(DEV), return_lse=True)
     o_ref, lse_ref = R.batch_prefill_ref(q.float(), qo_indptr, cache.float(), layout, indptr, indices, last,
                                          custom_mask=mask, logits_soft_cap=logits_soft_cap)
     torch.testing.assert_close(o.float().cpu(), o_ref.float(), rtol=1e-3, atol=1e-3)
     torch.testing.assert_close(lse.cpu(), lse_ref.float(), rtol=1e-3, atol=1e-3)
     # packed form (segment_packbits layout) gives the same bits
-    bit_indptr = torch.tensor([0] + list(np.cumsum([a * b for a, b in zip(qo_lens, kv_lens)])), dtype=torch.int32)
+    bit_indptr = indptr_of([a * b for a, b in zip(qo_lens, kv_lens)])
     packed, _ = flashinfer.segment_packbits(mask.to(DEV), bit_indptr.to(DEV), bitorder="little")
     w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, ps,
            packed_custom_mask=packed, logits_soft_cap=logits_soft_cap, q_data_type=torch.float16)
@@ -156,8 +153,8 @@ def test_batch_prefill_ragged_custom_mask():
     q = torch.randn(sum(qo_lens), hq, d).half()
     k = torch.randn(sum(kv_lens), hkv, d).half()
     v = torch.randn(sum(kv_lens), hkv, d).half()
-    qo_indptr = torch.tensor([0] + list(np.cumsum(qo_lens)), dtype=torch.int32)
-    kv_indptr = torch.tensor([0] + list(np.cumsum(kv_lens)), dtype=torch.int32)
+    qo_indptr = indptr_of(qo_lens)
+    kv_indptr = indptr_of(kv_lens)
     masks = [torch.rand(a, b) < 0.5 for a, b in zip(qo_lens, kv_lens)]
     for m in masks:
         m[:, -1] = True

@@ -13,6 +13,7 @@ import functools
 import pytest
 import torch
 
+from attn_inputs import page_table, planned_decode_wrapper, tol
 from flashinfer import _lib
 from oracle import attention_ref as R
 
@@ -22,24 +23,12 @@ PAGE = 16
 WS_BYTES = 8 << 20
 
 
-def tol(dtype):
-    """tests/test_decode_gpu.py: rtol = atol = 1e-3 for fp16 outputs; half a bf16 ulp (2^-9 relative) of output
-    rounding on top for bf16."""
-    if dtype == torch.bfloat16:
-        return dict(rtol=1e-3 + 2.0 ** -8, atol=2e-3)
-    return dict(rtol=1e-3, atol=1e-3)
-
-
 @functools.lru_cache(maxsize=None)
 def case(kv_lens, hq, hkv, d, dtype, kv_dtype=None, layout="NHD", seed=0, q_gain=1.0, **ref_kw_items):
     """Seeded inputs and the oracle's answer, computed once per distinct case and never modified."""
     g = torch.Generator().manual_seed(1000 + seed)
-    pages = [-(-l // PAGE) for l in kv_lens]
-    total = sum(pages)
-    indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0)), dtype=torch.int32)
-    last = torch.tensor([(l - 1) % PAGE + 1 if l > 0 else 0 for l in kv_lens], dtype=torch.int32)
-    indices = torch.randperm(total + 3, generator=g)[:total].to(torch.int32)
-    shape = (total + 3, 2, PAGE, hkv, d) if layout == "NHD" else (total + 3, 2, hkv, PAGE, d)
+    indptr, indices, last, npages = page_table(kv_lens, PAGE, g, extra_pages=3)
+    shape = (npages, 2, PAGE, hkv, d) if layout == "NHD" else (npages, 2, hkv, PAGE, d)
     cache = torch.randn(shape, generator=g).to(kv_dtype or dtype)
     q = (torch.randn(len(kv_lens), hq, d, generator=g) * q_gain).to(dtype)
     o_ref, lse_ref = R.batch_decode_ref(q.float(), cache.float(), layout, indptr, indices, last, **ref_kw_items)
@@ -47,14 +36,9 @@ def case(kv_lens, hq, hkv, d, dtype, kv_dtype=None, layout="NHD", seed=0, q_gain
 
 
 def plan_wrapper(c, hq, hkv, d, layout="NHD", **plan_kw):
-    import flashinfer
-
     q, cache, indptr, indices, last = c[:5]
-    ws = torch.zeros(WS_BYTES, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchDecodeWithPagedKVCacheWrapper(ws, layout)
-    w.plan(indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, PAGE, q_data_type=q.dtype,
-           kv_data_type=cache.dtype, **plan_kw)
-    return w
+    return planned_decode_wrapper(WS_BYTES, layout, indptr, indices, last, hq, hkv, d, PAGE, q_data_type=q.dtype,
+                                  kv_data_type=cache.dtype, **plan_kw)
 
 
 def run_checked(c, hq, hkv, d, dtype, expect_slot, fused, layout="NHD", lse_tol=1e-3, o_tol=None, **plan_kw):

@@ -7,11 +7,10 @@ Every test here runs once per entry of VARIANTS, in this process (_lib.set_optio
 environment's value after it; the plain functions are the default run, TestKernelVariants at the end repeats them
 for r1): the default kernel choice, which sends every group of <= 16 heads to decode_mfma16_kernel.h, and r1
 (FI_DECODE_MFMA16=0): groups of <= 4 heads back on the VALU kernel, wider ones on the 32x32x16 matrix-core kernel."""
-import math
-
 import pytest
 import torch
 
+from attn_inputs import make_paged, planned_decode_wrapper, rope_rt, tol
 from flashinfer import _lib
 from oracle import attention_ref as R
 
@@ -35,45 +34,9 @@ def kernel_variant(request):
             _lib.set_option(name, None)
 
 
-def tol(dtype):
-    """rtol = atol = 1e-3 (the reference's bar) for fp16 outputs.  A bf16 output cannot carry 1e-3: its
-    own rounding is half an ulp = 2^-9 relative, so that is added on top for bf16."""
-    if dtype == torch.bfloat16:
-        return dict(rtol=1e-3 + 2.0 ** -8, atol=2e-3)
-    return dict(rtol=1e-3, atol=1e-3)
-
-
-def rope_rt(q_dtype, head_dim):
-    """rope_round_dtype for the oracle: decode with fused RoPE runs on the matrix-core kernel for head_dim 64 / 128,
-    which rounds the rotated q / k to the 16-bit type (as the reference's tensor-core decode = its prefill kernel
-    does, prefill.cuh:465-612); other head dims stay on the VALU kernel, which rotates in f32 (decode.cuh:445-466)."""
-    return q_dtype if head_dim in (64, 128) else None
-
-
-def make_paged(batch, kv_lens, page_size, hkv, d, dtype, layout, seed, shuffle=True, extra_pages=3):
-    g = torch.Generator().manual_seed(seed)
-    pages = [max(0, -(-l // page_size)) for l in kv_lens]
-    total = sum(pages)
-    indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0)), dtype=torch.int32)
-    last = torch.tensor([(l - 1) % page_size + 1 if l > 0 else 0 for l in kv_lens], dtype=torch.int32)
-    perm = torch.randperm(total + extra_pages, generator=g)[:total] if shuffle else torch.arange(total)
-    indices = perm.to(torch.int32)
-    shape = (total + extra_pages, 2, page_size, hkv, d) if layout == "NHD" else (total + extra_pages, 2, hkv, page_size, d)
-    cache = torch.randn(shape, generator=g)
-    if dtype in (torch.float8_e4m3fn, torch.float8_e5m2):
-        cache = cache.to(dtype)
-    else:
-        cache = cache.to(dtype)
-    return cache, indptr, indices, last
-
-
 def run_batch_decode(q, cache, layout, indptr, indices, last, hq, hkv, d, page_size, return_lse=True, **plan_kw):
-    import flashinfer
-
-    ws = torch.zeros(64 * 1024 * 1024, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchDecodeWithPagedKVCacheWrapper(ws, layout)
-    w.plan(indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, page_size,
-           q_data_type=q.dtype, kv_data_type=cache.dtype, **plan_kw)
+    w = planned_decode_wrapper(64 << 20, layout, indptr, indices, last, hq, hkv, d, page_size,
+                               q_data_type=q.dtype, kv_data_type=cache.dtype, **plan_kw)
     return w.run(q.to(DEV), cache.to(DEV), return_lse=return_lse), w
 
 
@@ -235,11 +198,8 @@ def test_tuple_cache_noncontiguous_q_and_out_args():
     # non-contiguous q: a slice of a packed qkv tensor (ref: tests/attention/test_non_contiguous_decode.py)
     qkv = torch.randn(2, hq + 2 * hkv, d).half().to(DEV)
     q = qkv[:, :hq]
-    import flashinfer
-
-    ws = torch.zeros(32 * 1024 * 1024, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchDecodeWithPagedKVCacheWrapper(ws, "NHD")
-    w.plan(indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, page_size, q_data_type=torch.float16, kv_data_type=torch.float16)
+    w = planned_decode_wrapper(32 << 20, "NHD", indptr, indices, last, hq, hkv, d, page_size,
+                               q_data_type=torch.float16, kv_data_type=torch.float16)
     cd = cache.to(DEV)
     out = torch.empty(2, hq, d, dtype=torch.float16, device=DEV)
     lse = torch.empty(2, hq, dtype=torch.float32, device=DEV)

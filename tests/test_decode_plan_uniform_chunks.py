@@ -4,11 +4,10 @@ The slot is n in {2, 4} when the plan is split, is no graph plan, has no planned
 exactly n chunks; else 0.  run() uses it to merge the chunks inside the decode launch.  Slots 0-15 and the work list
 stay what the Python restatement of the planner (oracle/plan_ref.py) gives.  All plans are made for the MI355X grid of
 a 16-bit cache: 256 CUs x 4 waves = 1024, page 16 (chunks of 128 tokens unless stated)."""
-import ctypes as C
-
-import numpy as np
 import pytest
 
+import plan_calls
+from attn_inputs import indptr_of
 from flashinfer import _lib
 from oracle.plan_ref import decode_plan_ref
 
@@ -16,39 +15,14 @@ MAX_GRID = 1024
 PAGE = 16
 
 
-def indptr_of(pages):
-    out = [0]
-    for p in pages:
-        out.append(out[-1] + p)
-    return out
-
-
 def run_plan(fi_lib, pages, hq, hkv, cuda_graph=False, window_left=-1):
-    indptr = indptr_of(pages)
-    n = len(pages)
-    pinned = (C.c_char * (1 << 20))()
-    arr = (C.c_int32 * len(indptr))(*indptr)
-    info = (C.c_int64 * _lib.FI_DECODE_PLAN_INFO_LEN)()
-    rc = fi_lib.fi_batch_decode_plan(None, 1 << 30, None, pinned, len(pinned), arr, n, hq, hkv, PAGE, int(cuda_graph),
-                                     128, 1, 1, MAX_GRID, window_left, info, None)
-    assert rc == 0, fi_lib.fi_last_error()
-    info = list(info)
-    raw = np.frombuffer(pinned, dtype=np.uint8)
-
-    def i32(off, count):
-        return raw[off: off + 4 * count].view(np.int32).tolist()
-
-    nwork = info[_lib.FI_DP_NUM_WORK]
-    got = dict(split_kv=bool(info[_lib.FI_DP_SPLIT_KV]), kv_chunk_size=info[_lib.FI_DP_KV_CHUNK_SIZE],
-               padded_batch_size=info[_lib.FI_DP_PADDED_BATCH_SIZE], num_work=nwork,
-               request_indices=i32(info[_lib.FI_DP_REQUEST_INDICES_OFFSET], nwork),
-               kv_tile_indices=i32(info[_lib.FI_DP_KV_TILE_INDICES_OFFSET], nwork),
-               o_indptr=i32(info[_lib.FI_DP_O_INDPTR_OFFSET], n + 1))
-    return info, got
+    got = plan_calls.run_plan(fi_lib, indptr_of(pages).tolist(), hq, hkv, PAGE, MAX_GRID, cuda_graph,
+                              window_left=window_left)
+    return got["info"], got
 
 
 def check_against_oracle(got, pages, hq, hkv, cuda_graph=False, window_left=-1):
-    exp = decode_plan_ref(indptr_of(pages), hq, hkv, PAGE, MAX_GRID, cuda_graph, window_left=window_left)
+    exp = decode_plan_ref(indptr_of(pages).tolist(), hq, hkv, PAGE, MAX_GRID, cuda_graph, window_left=window_left)
     for key in ("split_kv", "kv_chunk_size", "padded_batch_size", "num_work", "request_indices", "kv_tile_indices",
                 "o_indptr"):
         assert got[key] == exp[key], key

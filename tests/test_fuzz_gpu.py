@@ -8,10 +8,8 @@ import random
 import pytest
 import torch
 
+from attn_inputs import indptr_of, make_paged, page_table, planned_prefill_wrapper, ptol, rope_rt, scatter_to_pages, tol
 from oracle import attention_ref as R
-from test_decode_gpu import make_paged, tol
-from test_prefill_gpu import ptol
-from test_decode_gpu import rope_rt
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -78,8 +76,6 @@ def test_fuzz_batch_decode(seed):
 
 @pytest.mark.parametrize("seed", SEEDS)
 def test_fuzz_batch_prefill(seed):
-    import flashinfer
-
     rng = random.Random(2000 + seed)
     d = rng.choice([64, 128, 128, 256])
     hkv = rng.choice([1, 2, 4])
@@ -115,15 +111,13 @@ def test_fuzz_batch_prefill(seed):
     cache, indptr, indices, last = make_paged(batch, kv_lens, ps, hkv, d, kvdt, layout, seed=seed)
     torch.manual_seed(seed)
     q = torch.randn(sum(qo_lens), hq, d).to(qdt)
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
+    qo_indptr = indptr_of(qo_lens)
     mask = None
     if variant == "mask":
         mask = torch.cat([(torch.rand(a, b) < 0.7).view(-1) for a, b in zip(qo_lens, kv_lens)])
         kw["custom_mask"] = mask.to(DEV)
-    ws = torch.zeros(256 << 20, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(ws, layout)
-    w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, ps, causal=causal,
-           q_data_type=qdt, kv_data_type=kvdt, **kw)
+    w = planned_prefill_wrapper(256 << 20, layout, qo_indptr, indptr, indices, last, hq, hkv, d, ps, causal=causal,
+                                q_data_type=qdt, kv_data_type=kvdt, **kw)
     o, lse = w.run(q.to(DEV), cache.to(DEV), return_lse=True)
     o_ref, lse_ref = R.batch_prefill_ref(q.float(), qo_indptr, cache.float(), layout, indptr, indices, last,
                                          causal=causal, custom_mask=mask, **okw)
@@ -149,8 +143,6 @@ def test_fuzz_fp8_attention_prefill(seed):
     groups that do and do not divide a wave, any page size, both layouts, causal or not, automatic / disabled /
     fixed kv split, rows without visible keys -- against the oracle's restatement of the reference's FA3 arithmetic
     (hopper/variants.cuh:71-90) at the fp8 bars of tests/test_prefill_gpu.py."""
-    import flashinfer
-
     rng = random.Random(7000 + seed)
     f8 = rng.choice([torch.float8_e4m3fn, torch.float8_e4m3fn, torch.float8_e5m2])
     d = rng.choice([64, 128, 128, 256])
@@ -177,25 +169,12 @@ def test_fuzz_fp8_attention_prefill(seed):
     q8, sq = R.per_head_symmetric_quant(q16, f8)
     k8, sk = R.per_head_symmetric_quant(k16, f8)
     v8, sv = R.per_head_symmetric_quant(v16, f8)
-    pages = [-(-l // ps) for l in kv_lens]
-    total = sum(pages) + 2
-    indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0)), dtype=torch.int32)
-    indices = torch.randperm(total)[: sum(pages)].to(torch.int32)
-    last = torch.tensor([(l - 1) % ps + 1 for l in kv_lens], dtype=torch.int32)
-    cache_f = torch.zeros(total, 2, ps, hkv, d)  # NHD mirror in f32 (fp8 values are exact in it)
-    off = 0
-    for b, l in enumerate(kv_lens):
-        for t in range(l):
-            pg = int(indices[int(indptr[b]) + t // ps])
-            cache_f[pg, 0, t % ps] = k8[off + t].float()
-            cache_f[pg, 1, t % ps] = v8[off + t].float()
-        off += l
-    cache = (cache_f if layout == "NHD" else cache_f.transpose(2, 3).contiguous()).to(f8)
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
-    ws = torch.zeros(64 << 20, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(ws, layout)
-    w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, ps, causal=causal,
-           q_data_type=f8, kv_data_type=f8, o_data_type=o_dtype, **kw)
+    indptr, indices, last, total = page_table(kv_lens, ps, extra_pages=2)
+    # scattered in f32 (fp8 values are exact in it)
+    cache = scatter_to_pages(k8.float(), v8.float(), kv_lens, indptr, indices, ps, total, layout).to(f8)
+    qo_indptr = indptr_of(qo_lens)
+    w = planned_prefill_wrapper(64 << 20, layout, qo_indptr, indptr, indices, last, hq, hkv, d, ps, causal=causal,
+                                q_data_type=f8, kv_data_type=f8, o_data_type=o_dtype, **kw)
     o, lse = w.run(q8.to(DEV), cache.to(DEV), return_lse=True, scale_q=sq.to(DEV), scale_k=sk.to(DEV),
                    scale_v=sv.to(DEV))
     assert o.dtype == o_dtype

@@ -16,6 +16,7 @@ import math
 import pytest
 import torch
 
+from attn_inputs import indptr_of
 from flashinfer import _lib
 from oracle import gemm_ref as G
 
@@ -98,7 +99,7 @@ def test_group_gemm_fp8_nt_groupwise(ms, n, k, mode):
     b = torch.randn(g, n, k) / math.sqrt(k)
     a8, sa = G.quantize_fp8(a, (1, 128), mode)
     b8, sb = G.quantize_fp8(b, (1, 128, 128), mode)
-    m_indptr = torch.tensor([0] + list(torch.tensor(ms).cumsum(0)), dtype=torch.int32)
+    m_indptr = indptr_of(ms)
     out = flashinfer.group_gemm_fp8_nt_groupwise(a8.to(DEV), b8.to(DEV), sa.to(DEV), sb.to(DEV), m_indptr.to(DEV),
                                                  scale_major_mode=mode)
     ref = G.group_gemm_fp8_nt_groupwise_ref(a8, b8, sa, sb, m_indptr, mode)
@@ -134,7 +135,7 @@ def test_group_gemm_scales_that_are_not_powers_of_two(scales, mode):
         sa[2, 300] = -2.0        # negative
     if mode == "K":
         sa, sb = sa.t().contiguous(), sb.transpose(1, 2).contiguous()
-    m_indptr = torch.tensor([0] + list(torch.tensor(ms).cumsum(0)), dtype=torch.int32)
+    m_indptr = indptr_of(ms)
     out = flashinfer.group_gemm_fp8_nt_groupwise(a8.to(DEV), b8.to(DEV), sa.to(DEV), sb.to(DEV), m_indptr.to(DEV),
                                                  scale_major_mode=mode)
     ref = G.group_gemm_fp8_nt_groupwise_ref(a8, b8, sa, sb, m_indptr, mode)
@@ -213,7 +214,7 @@ def _exact_many_tiles(ms, n, k, odd_scale):
     sb = torch.pow(2.0, torch.randint(-1, 2, (g, k // 128, -(-n // 128))).float())
     if odd_scale:
         sa[0, cum // 2] = 1.5
-    m_indptr = torch.tensor([0] + list(torch.tensor(ms).cumsum(0)), dtype=torch.int32)
+    m_indptr = indptr_of(ms)
     out = flashinfer.group_gemm_fp8_nt_groupwise(a.to(torch.float8_e4m3fn).to(DEV), b.to(torch.float8_e4m3fn).to(DEV),
                                                  sa.to(DEV), sb.to(DEV), m_indptr.to(DEV), out_dtype=torch.float16)
     ref = torch.zeros(cum, n, dtype=torch.float64)
@@ -251,7 +252,7 @@ def test_group_gemm_random_shapes_exact(seed):
     b = torch.randint(-1, 2, (g, n, k)).float()
     sa = torch.pow(2.0, torch.randint(-1, 1, (k // 128, cum)).float())
     sb = torch.pow(2.0, torch.randint(-1, 1, (g, k // 128, -(-n // 128))).float())
-    m_indptr = torch.tensor([0] + list(torch.tensor(ms).cumsum(0)), dtype=torch.int32)
+    m_indptr = indptr_of(ms)
     sa_dev = sa if mode == "MN" else sa.t().contiguous()
     sb_dev = sb if mode == "MN" else sb.permute(0, 2, 1).contiguous()
     out = flashinfer.group_gemm_fp8_nt_groupwise(a.to(torch.float8_e4m3fn).to(DEV), b.to(torch.float8_e4m3fn).to(DEV),

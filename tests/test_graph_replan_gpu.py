@@ -5,9 +5,9 @@ this reason, decode.cuh:424, prefill.cuh:2058; serving pattern: capture once, pl
 import pytest
 import torch
 
+from attn_inputs import indptr_of, make_paged, planned_prefill_wrapper
 from flashinfer import _lib
 from oracle import attention_ref as R
-from test_decode_gpu import make_paged
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -87,7 +87,7 @@ def test_prefill_graph_replay_after_replan_with_other_chunk_size_and_more_partia
 
     def plan(i):
         cache, indptr, indices, last, qo_lens = data[i]
-        qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
+        qo_indptr = indptr_of(qo_lens)
         w.plan(qo_indptr, indptr, indices, last, hq, hkv, d, ps, causal=True, max_token_per_sequence=rows // b)
         cache_dev.copy_(cache)
         torch.manual_seed(i)
@@ -125,18 +125,15 @@ def test_prefill_graph_replay_after_replan_with_other_chunk_size_and_more_partia
 def test_fp8_prefill_run_without_scales_is_graph_capturable():
     """fp8 q/k/v with no scale arguments: run() must not create tensors on the host (a pageable copy is illegal
     while capturing and syncs otherwise); a missing scale is a NULL pointer (= 1)."""
-    import flashinfer
-
     hq, hkv, d, ps = 8, 2, 128, 16
     kv_lens, qo_lens = [300, 64], [200, 64]
     cache, indptr, indices, last = make_paged(2, kv_lens, ps, hkv, d, torch.float8_e4m3fn, "NHD", seed=5)
     torch.manual_seed(6)
     q8 = torch.randn(sum(qo_lens), hq, d).to(torch.float8_e4m3fn)
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
-    ws = torch.zeros(32 << 20, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(ws, "NHD")
-    w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, ps, causal=True,
-           q_data_type=torch.float8_e4m3fn, kv_data_type=torch.float8_e4m3fn, o_data_type=torch.float16)
+    qo_indptr = indptr_of(qo_lens)
+    w = planned_prefill_wrapper(32 << 20, "NHD", qo_indptr, indptr, indices, last, hq, hkv, d, ps, causal=True,
+                                q_data_type=torch.float8_e4m3fn, kv_data_type=torch.float8_e4m3fn,
+                                o_data_type=torch.float16)
     qd, cd = q8.to(DEV), cache.to(DEV)
     out = torch.zeros(sum(qo_lens), hq, d, dtype=torch.float16, device=DEV)
     w.run(qd, cd, out=out)

@@ -9,9 +9,9 @@ import math
 import pytest
 import torch
 
+from attn_inputs import indptr_of, make_paged, page_table, planned_prefill_wrapper
 from oracle import attention_ref as R
 from oracle import gemm_ref as G
-from test_decode_gpu import make_paged
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -75,7 +75,7 @@ def test_batch_prefill_module_reference_call_sequence(causal):
     cache, indptr, indices, last = make_paged(b, kv_lens, ps, hkv, d, torch.float16, "NHD", seed=21)
     torch.manual_seed(1)
     q = torch.randn(sum(qo_lens), hq, d).half()
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
+    qo_indptr = indptr_of(qo_lens)
     kv_len_arr = torch.tensor(kv_lens, dtype=torch.int32)
     float_ws, int_ws, pinned = _workspaces()
     mod = compat.get_batch_prefill_module("fa2", torch.float16, torch.float16, torch.float16, torch.int32, d, d, 0,
@@ -97,7 +97,7 @@ def test_batch_prefill_module_reference_call_sequence(causal):
     ks = [R.gather_paged_kv(cache, "NHD", indptr, indices, last, r) for r in range(b)]
     k_r = torch.cat([k for k, _ in ks]).to(DEV)
     v_r = torch.cat([v for _, v in ks]).to(DEV)
-    kv_indptr_r = torch.tensor([0] + list(torch.tensor(kv_lens).cumsum(0)), dtype=torch.int32)
+    kv_indptr_r = indptr_of(kv_lens)
     plan_info = mod.plan(float_ws, int_ws, pinned, qo_indptr, kv_indptr_r, kv_len_arr, int(qo_indptr[-1]), b, hq, hkv, 1,
                          False, d, d, causal, -1, -1, False)
     out2 = torch.empty_like(qd)
@@ -119,7 +119,7 @@ def test_batch_prefill_module_fa3_six_argument_tail():
     cache, indptr, indices, last = make_paged(b, kv_lens, ps, hkv, d, torch.float16, "NHD", seed=23)
     torch.manual_seed(2)
     q = torch.randn(sum(qo_lens), hq, d).half()
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
+    qo_indptr = indptr_of(qo_lens)
     float_ws, int_ws, pinned = _workspaces()
     mod = compat.get_batch_prefill_module("fa3", torch.float16, torch.float16, torch.float16, torch.int32, d, d, 0,
                                           False, False, False)
@@ -171,7 +171,7 @@ def test_batch_prefill_fp8_module_reference_call_sequence():
     torch.manual_seed(2)
     q8 = torch.randn(sum(qo_lens), hq, d).to(torch.float8_e4m3fn)
     sq, sk, sv = torch.rand(hq) + 0.5, torch.rand(hkv) + 0.5, torch.rand(hkv) + 0.5
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
+    qo_indptr = indptr_of(qo_lens)
     float_ws, int_ws, pinned = _workspaces()
     mod = compat.get_batch_prefill_module("fa3", torch.float8_e4m3fn, torch.float8_e4m3fn, torch.float16, torch.int32,
                                           d, d, 0, False, False, False)
@@ -222,11 +222,8 @@ def test_cascade_page_gemm_modules_reference_call_sequences():
     # ---- page append (flashinfer/page.py:411-424) then decode over the appended cache ----
     hkv, ps = 2, 16
     kv_lens = [40, 7, 100]
-    pages = [-(-l // ps) for l in kv_lens]
-    kv_indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0)), dtype=torch.int32)
-    kv_indices = torch.randperm(sum(pages)).to(torch.int32)
-    kv_last = torch.tensor([(l - 1) % ps + 1 for l in kv_lens], dtype=torch.int32)
-    cache = torch.zeros(sum(pages), 2, ps, hkv, d, dtype=torch.float16, device=DEV)
+    kv_indptr, kv_indices, kv_last, total = page_table(kv_lens, ps)
+    cache = torch.zeros(total, 2, ps, hkv, d, dtype=torch.float16, device=DEV)
     nnz = sum(kv_lens)
     k_new, v_new = torch.randn(nnz, hkv, d).half(), torch.randn(nnz, hkv, d).half()
     batch_indices = torch.cat([torch.full((l,), i, dtype=torch.int32) for i, l in enumerate(kv_lens)])
@@ -274,8 +271,6 @@ def test_multi_item_scoring_matches_custom_mask(kv_len, qo_len, prefix_len, toke
     """ref: tests/attention/test_batch_prefill_kernels.py:810-1010 -- multi-item scoring equals attention under the
     dense mask: a query at p >= prefix sees the prefix and the keys of its own item after its delimiter
     (token_pos == 0 marks a delimiter, which sees only the prefix); checked against the oracle with that mask."""
-    import flashinfer
-
     hkv, d, b = 4, 128, 2
     kv_lens = [kv_len] * b
     cache, indptr, indices, last = make_paged(b, kv_lens, page_size, hkv, d, torch.float16, "NHD", seed=7)
@@ -284,13 +279,11 @@ def test_multi_item_scoring_matches_custom_mask(kv_len, qo_len, prefix_len, toke
     qo_indptr = (torch.arange(b + 1) * qo_len).to(torch.int32)
     tp = torch.zeros(b, tp_len, dtype=torch.int32)
     tp[:, : len(token_pos)] = torch.tensor(token_pos)
-    ws = torch.zeros(64 << 20, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(ws, "NHD")
-    w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, page_size, causal=True,
-           logits_soft_cap=soft_cap,
-           prefix_len_ptr=torch.tensor([prefix_len] * b).to(torch.uint32).to(DEV),
-           token_pos_in_items_ptr=tp.reshape(-1).to(torch.uint16).to(DEV), token_pos_in_items_len=tp_len,
-           max_item_len_ptr=torch.tensor([max_item_len] * b).to(torch.uint16).to(DEV))
+    w = planned_prefill_wrapper(
+        64 << 20, "NHD", qo_indptr, indptr, indices, last, hq, hkv, d, page_size, causal=True,
+        logits_soft_cap=soft_cap, prefix_len_ptr=torch.tensor([prefix_len] * b).to(torch.uint32).to(DEV),
+        token_pos_in_items_ptr=tp.reshape(-1).to(torch.uint16).to(DEV), token_pos_in_items_len=tp_len,
+        max_item_len_ptr=torch.tensor([max_item_len] * b).to(torch.uint16).to(DEV))
     o, lse = w.run(q.to(DEV), cache.to(DEV), return_lse=True)
     # dense mask of the same rule
     qi = torch.arange(qo_len)[:, None] + (kv_len - qo_len)  # position of each query on the kv axis

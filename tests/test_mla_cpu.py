@@ -10,11 +10,13 @@ import re
 import numpy as np
 import pytest
 
+from attn_inputs import indptr_of
+from plan_calls import BF16, F16, mla_plan as plan
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "fi_mi355.h")
 MLA_SYMBOLS = ["fi_batch_mla_plan", "fi_batch_mla_run", "fi_append_paged_mla_kv_cache"]
 ROWS_PER_ITEM = 16
-F16, BF16 = 0, 1
 
 
 def test_mla_symbols_everywhere(fi_lib):
@@ -24,26 +26,6 @@ def test_mla_symbols_everywhere(fi_lib):
     for s in MLA_SYMBOLS:
         assert s in declared and s in _lib.EXPORTED_SYMBOLS and hasattr(fi_lib, s), s
     assert fi_lib.fi_abi_version() == 2
-
-
-def plan(fi_lib, qo_lens, kv_lens, H, page_size=16, ckv=512, kpe=64, q_dt=BF16, kv_dt=BF16, int_bytes=8 << 20,
-         float_bytes=128 << 20, graph=0, fixed_split=0):
-    from flashinfer import _lib
-
-    B = len(qo_lens)
-    qo_indptr = (C.c_int32 * (B + 1))(*np.concatenate([[0], np.cumsum(qo_lens)]).astype(int).tolist())
-    pages = [-(-k // page_size) for k in kv_lens]
-    kv_indptr = (C.c_int32 * (B + 1))(*np.concatenate([[0], np.cumsum(pages)]).astype(int).tolist())
-    kv_len = (C.c_int32 * max(B, 1))(*kv_lens)
-    pinned = (C.c_char * int_bytes)()
-    p = _lib.fi_batch_mla_plan_params_t(int_ws=None, pinned_int_ws=C.addressof(pinned), int_ws_bytes=int_bytes,
-                           float_ws_bytes=float_bytes, qo_indptr_h=C.addressof(qo_indptr),
-                           kv_indptr_h=C.addressof(kv_indptr), kv_len_arr_h=C.addressof(kv_len), batch_size=B,
-                           num_heads=H, head_dim_ckv=ckv, head_dim_kpe=kpe, page_size=page_size, causal=0,
-                           q_dtype=q_dt, kv_dtype=kv_dt, enable_cuda_graph=graph, fixed_split_size=fixed_split)
-    info = (C.c_int64 * _lib.FI_MLA_PLAN_INFO_LEN)()
-    rc = fi_lib.fi_batch_mla_plan(C.byref(p), info, None)
-    return rc, list(info), pinned
 
 
 def test_plan_rejects_unsupported(fi_lib):
@@ -93,7 +75,7 @@ def test_plan_invariants_sweep(fi_lib, graph):
         indptr, items = decode_plan(info, pinned, qo_lens, H)
         chunk = info[_lib.FI_MLA_KV_CHUNK_SIZE]
         assert chunk > 0 and chunk % 64 == 0
-        qo_starts = np.concatenate([[0], np.cumsum(qo_lens)])
+        qo_starts = indptr_of(qo_lens).numpy()
         # every (request, packed row, kv token) exactly once
         cover = {}
         for qo_start, row0, qo_len, k0, k1, kv_len, page_base, ch in items.tolist():

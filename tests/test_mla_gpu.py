@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import flashinfer
+from attn_inputs import indptr_of, page_table, tol
 from oracle.attention_ref import attention_ref
 
 pytestmark = pytest.mark.gpu
@@ -18,19 +19,14 @@ DEV = "cuda:0"
 CKV, KPE = 512, 64
 
 
-def _tol(dtype):
-    # bf16 output: the smoke() bar (1e-3 + half a bf16 ulp of output rounding)
-    return dict(rtol=1e-3, atol=1e-3) if dtype == torch.float16 else dict(rtol=1e-3 + 2.0 ** -8, atol=2e-3)
-
-
 def make_case(kv_lens, qo_lens, H, page_size, dtype, seed=0, nan_fill=False):
     g = torch.Generator().manual_seed(seed)
     B = len(kv_lens)
     pages = [-(-l // page_size) for l in kv_lens]
-    kv_indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0).tolist()), dtype=torch.int32)
+    kv_indptr = indptr_of(pages)
     total_pages = int(kv_indptr[-1])
     kv_indices = torch.randperm(max(total_pages, 1), generator=g)[:total_pages].to(torch.int32)
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0).tolist()), dtype=torch.int32)
+    qo_indptr = indptr_of(qo_lens)
     nnz = int(qo_indptr[-1])
     ckv = (torch.randn(max(total_pages, 1), page_size, CKV, generator=g) * 0.5).to(dtype)
     kpe = (torch.randn(max(total_pages, 1), page_size, KPE, generator=g) * 0.5).to(dtype)
@@ -78,7 +74,7 @@ def plan_run(c, causal, sm_scale, ws=None, q_nope=None, q_pe=None, ckv=None, kpe
 
 def check(c, o, lse, causal, sm_scale):
     o_ref, lse_ref = oracle(c, causal, sm_scale)
-    torch.testing.assert_close(o.float(), o_ref, **_tol(c["dtype"]))
+    torch.testing.assert_close(o.float(), o_ref, **tol(c["dtype"]))
     # lse wherever the row sees at least one key
     rows = []
     for kl, ql in zip(c["kv_lens"], c["qo_lens"]):
@@ -223,16 +219,13 @@ def test_append_paged_mla_kv_cache(dtype):
     hist = [5, 40, 0]          # tokens already in the cache
     new = [3, 1, 20]           # tokens appended now
     kv_lens = [h + n for h, n in zip(hist, new)]
-    pages = [-(-l // ps) for l in kv_lens]
-    kv_indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0).tolist()), dtype=torch.int32, device=DEV)
-    total = int(kv_indptr[-1])
-    kv_indices = torch.randperm(total).to(torch.int32).to(DEV)
-    last = torch.tensor([(l - 1) % ps + 1 for l in kv_lens], dtype=torch.int32, device=DEV)
+    kv_indptr, kv_indices, last, total = page_table(kv_lens, ps)
+    kv_indptr, kv_indices, last = kv_indptr.to(DEV), kv_indices.to(DEV), last.to(DEV)
     ckv_full = (torch.randn(sum(kv_lens), CKV) * 0.5).to(dtype).to(DEV)   # the whole history, request-major
     kpe_full = (torch.randn(sum(kv_lens), KPE) * 0.5).to(dtype).to(DEV)
     ckv_cache = torch.full((total, ps, CKV), float("nan"), dtype=dtype, device=DEV)
     kpe_cache = torch.full((total, ps, KPE), float("nan"), dtype=dtype, device=DEV)
-    starts = [0] + list(torch.tensor(kv_lens).cumsum(0).tolist())
+    starts = indptr_of(kv_lens).tolist()
 
     def scatter(rows):  # torch index scatter of (request, position) rows
         for b, pos in rows:
@@ -242,7 +235,7 @@ def test_append_paged_mla_kv_cache(dtype):
 
     scatter([(b, p) for b in range(3) for p in range(hist[b])])
     ref_ckv, ref_kpe = ckv_cache.clone(), kpe_cache.clone()
-    append_indptr = torch.tensor([0] + list(torch.tensor(new).cumsum(0).tolist()), dtype=torch.int32, device=DEV)
+    append_indptr = indptr_of(new, DEV)
     bi, pos = flashinfer.get_batch_indices_positions(append_indptr, flashinfer.get_seq_lens(kv_indptr, last, ps),
                                                      sum(new))
     rows = [(b, hist[b] + i) for b in range(3) for i in range(new[b])]

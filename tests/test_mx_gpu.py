@@ -11,18 +11,13 @@ import pytest
 import torch
 
 import mx_ref as R
+from attn_inputs import indptr_of
 
 pytestmark = pytest.mark.gpu
 
 GROUPED = (4, 132, 0, 260)
 FP8 = {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
 OUT = {"bf16": torch.bfloat16, "f16": torch.float16}
-
-
-def _indptr(ms):
-    t = torch.zeros(len(ms) + 1, dtype=torch.int32)
-    t[1:] = torch.tensor(ms, dtype=torch.int32).cumsum(0)
-    return t
 
 
 def _run(a, sa, b, sb, ms, out_dtype, fill=0, extra_rows=0, out=None):
@@ -39,7 +34,7 @@ def _run(a, sa, b, sb, ms, out_dtype, fill=0, extra_rows=0, out=None):
         a_scale = torch.cat([a_scale, torch.full((need_rows - a_scale.shape[0], a_scale.shape[1]), fill, dtype=torch.uint8)])
     b_scale = R.swizzle_b(sb, fill)
     res = flashinfer.gemm.group_gemm_mxfp8_mxfp4_nt_groupwise(
-        a.to(dev), b.to(dev), a_scale.to(dev), b_scale.to(dev), _indptr(ms).to(dev), out=out,
+        a.to(dev), b.to(dev), a_scale.to(dev), b_scale.to(dev), indptr_of(ms).to(dev), out=out,
         out_dtype=None if out is not None else out_dtype)
     torch.cuda.synchronize()
     return res.cpu()
@@ -225,7 +220,7 @@ def test_quantiser_grouped_layout(dtype):
 
     ms, k = GROUPED, 384
     x = _quant_input(sum(ms) + 8, k, dtype, 11)  # 8 rows past m_indptr[G]: quantised, without scales
-    q, a_scale = Q.mxfp8_quantize_grouped(x.cuda(), _indptr(ms).cuda())
+    q, a_scale = Q.mxfp8_quantize_grouped(x.cuda(), indptr_of(ms).cuda())
     rows = (sum(ms) + 8 + 127 * len(ms)) // 128 * 128
     assert a_scale.shape == (rows, k // 32) and a_scale.dtype == torch.uint8 and q.shape == x.shape
     q, a_scale = q.cpu(), a_scale.cpu()
@@ -271,7 +266,7 @@ def test_pipeline_quantise_then_gemm():
     from flashinfer import fp8_quantization as Q
 
     ms, x, b, sb = _pipeline_inputs()
-    indptr = _indptr(ms).cuda()
+    indptr = indptr_of(ms).cuda()
     q, a_scale = Q.mxfp8_quantize_grouped(x.cuda(), indptr)
     out = flashinfer.gemm.group_gemm_mxfp4_nt_groupwise(q, b.cuda(), a_scale, R.swizzle_b(sb).cuda(), indptr)
     torch.cuda.synchronize()
@@ -286,7 +281,7 @@ def test_graph_capture_replays_the_eager_result():
     from flashinfer import fp8_quantization as Q
 
     ms, x, b, sb = _pipeline_inputs()
-    indptr = _indptr(ms).cuda()
+    indptr = indptr_of(ms).cuda()
     xd, bd, sbd = x.cuda(), b.cuda(), R.swizzle_b(sb).cuda()
 
     def step():

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import norm_ref as R
+from norm_ref import assert_close
 
 pytestmark = pytest.mark.gpu
 
@@ -46,11 +47,6 @@ def empty_rows(rows, hidden, dtype, strided):
     if strided:
         return torch.empty(rows, hidden * 2, dtype=dtype, device=DEV)[:, :hidden]
     return torch.empty(rows, hidden, dtype=dtype, device=DEV)
-
-
-def assert_close(got, want, dtype, what=""):
-    assert got.dtype == dtype, what
-    torch.testing.assert_close(got.double(), want, **R.tolerances(dtype), msg=lambda m: f"{what}: {m}")
 
 
 def assert_residual_bits(got, x, r, what=""):

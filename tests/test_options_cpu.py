@@ -9,7 +9,7 @@ import pytest
 
 from flashinfer import _lib
 from oracle.plan_ref import decode_plan_ref
-from test_plan import run_plan
+from plan_calls import run_plan
 
 
 @pytest.fixture

@@ -3,8 +3,8 @@ ref: tests/attention/test_page.py:8, tests/attention/test_shared_prefix_kernels.
 import pytest
 import torch
 
+from attn_inputs import indptr_of, planned_decode_wrapper
 from oracle import attention_ref as R
-from test_decode_gpu import make_paged
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -39,7 +39,7 @@ def test_append_paged_kv_cache_then_decode(layout, dtype):
     perm = torch.randperm(max_pages)
     final = [l + 1 for l in lens0]
     pages = [-(-l // ps) for l in final]
-    indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0)), dtype=torch.int32)
+    indptr = indptr_of(pages)
     indices = perm[: int(indptr[-1])].to(torch.int32)
     seq_so_far = [0] * b
     for step_lens in (lens0, [1] * b):
@@ -47,7 +47,7 @@ def test_append_paged_kv_cache_then_decode(layout, dtype):
         k_new = torch.randn(nnz, hkv, d).half().to(dtype)
         v_new = torch.randn(nnz, hkv, d).half().to(dtype)
         seq_after = [s + a for s, a in zip(seq_so_far, step_lens)]
-        append_indptr = torch.tensor([0] + list(torch.tensor(step_lens).cumsum(0)), dtype=torch.int32, device=DEV)
+        append_indptr = indptr_of(step_lens, DEV)
         bi, pos = flashinfer.get_batch_indices_positions(append_indptr, torch.tensor(seq_after), nnz)
         last = torch.tensor([(l - 1) % ps + 1 for l in seq_after], dtype=torch.int32)
         flashinfer.append_paged_kv_cache(k_new.to(DEV), v_new.to(DEV), bi, pos, cache, indices.to(DEV),
@@ -68,9 +68,8 @@ def test_append_paged_kv_cache_then_decode(layout, dtype):
     # decode over the appended cache
     last = torch.tensor([(l - 1) % ps + 1 for l in final], dtype=torch.int32)
     q = torch.randn(b, hq, d).half()
-    ws = torch.zeros(16 << 20, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchDecodeWithPagedKVCacheWrapper(ws, layout)
-    w.plan(indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, ps, q_data_type=torch.float16, kv_data_type=dtype)
+    w = planned_decode_wrapper(16 << 20, layout, indptr, indices, last, hq, hkv, d, ps, q_data_type=torch.float16,
+                               kv_data_type=dtype)
     o = w.run(q.to(DEV), cache)
     o_ref, _ = R.batch_decode_ref(q.float(), host, "NHD", indptr, indices, last)
     torch.testing.assert_close(o.float().cpu(), o_ref.float(), rtol=1e-3, atol=1e-3)
@@ -86,7 +85,7 @@ def _two_level_problem(batch, prefix_len, suffix_lens, hq, hkv, d, ps, seed):
     perm = torch.randperm(total + 2, generator=g).to(torch.int32)
     shared_indices = perm[:ppages]
     unique_indices = perm[ppages:total]
-    unique_indptr = torch.tensor([0] + list(torch.tensor(upages).cumsum(0)), dtype=torch.int32)
+    unique_indptr = indptr_of(upages)
     unique_last = torch.tensor([(l - 1) % ps + 1 for l in suffix_lens], dtype=torch.int32)
     q = torch.randn(batch, hq, d, generator=g).half()
     return cache, shared_indices, unique_indices, unique_indptr, unique_last, q
@@ -207,8 +206,8 @@ def test_three_level_cascade_random_shapes_match_flat_attention(seed):
     qo_indptr = [torch.tensor([0, qo_cum[-1]], dtype=torch.int32), torch.tensor(grp_rows, dtype=torch.int32),
                  torch.tensor(qo_cum, dtype=torch.int32)]
     kv_indptr = [torch.tensor([0, len(glob_idx)], dtype=torch.int32),
-                 torch.tensor([0] + list(torch.tensor([len(x) for x in grp_idx]).cumsum(0)), dtype=torch.int32),
-                 torch.tensor([0] + list(torch.tensor([len(x) for x in unq_idx]).cumsum(0)), dtype=torch.int32)]
+                 indptr_of([len(x) for x in grp_idx]),
+                 indptr_of([len(x) for x in unq_idx])]
     kv_indices = [glob_idx, torch.cat(grp_idx), torch.cat(unq_idx)]
     last = [torch.tensor([ps], dtype=torch.int32), torch.full((n_groups,), ps, dtype=torch.int32),
             torch.tensor([(u - 1) % ps + 1 for u in uniq_lens], dtype=torch.int32)]
@@ -245,7 +244,7 @@ def test_batch_prefill_shared_prefix_wrapper():
     cache, sh_idx, un_idx, un_indptr, un_last, _ = _two_level_problem(batch, prefix_len, suffix_lens, hq, hkv, d, ps, 9)
     torch.manual_seed(10)
     q = torch.randn(sum(qo_lens), hq, d).half()
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
+    qo_indptr = indptr_of(qo_lens)
     k_shared = cache[sh_idx.long(), 0].reshape(-1, hkv, d).contiguous()
     v_shared = cache[sh_idx.long(), 1].reshape(-1, hkv, d).contiguous()
     w = flashinfer.BatchPrefillWithSharedPrefixPagedKVCacheWrapper(torch.zeros(32 << 20, dtype=torch.uint8, device=DEV), "NHD")
@@ -292,7 +291,7 @@ def test_fused_rope_append_equals_rope_then_append(layout, dtype, rotary_dim, in
     cache_b = torch.zeros(shape, dtype=dtype, device=DEV)
     final = [l + 1 for l in lens0]
     pages = [-(-l // ps) for l in final]
-    indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0)), dtype=torch.int32, device=DEV)
+    indptr = indptr_of(pages, DEV)
     indices = torch.randperm(max_pages)[: int(indptr[-1])].to(torch.int32).to(DEV)
     seq_so_far = [0] * b
     for step_lens in (lens0, [1] * b):
@@ -301,7 +300,7 @@ def test_fused_rope_append_equals_rope_then_append(layout, dtype, rotary_dim, in
         k_new = torch.randn(nnz, hkv, d).to(dtype).to(DEV)
         v_new = torch.randn(nnz, hkv, d).to(dtype).to(DEV)
         seq_after = [s + a for s, a in zip(seq_so_far, step_lens)]
-        append_indptr = torch.tensor([0] + list(torch.tensor(step_lens).cumsum(0)), dtype=torch.int32, device=DEV)
+        append_indptr = indptr_of(step_lens, DEV)
         bi, pos = flashinfer.get_batch_indices_positions(append_indptr, torch.tensor(seq_after), nnz)
         last = torch.tensor([(l - 1) % ps + 1 for l in seq_after], dtype=torch.int32, device=DEV)
         q_ref, k_rot = flashinfer.apply_rope_pos_ids(q, k_new, pos, rotary_dim=rotary_dim, interleave=interleave,

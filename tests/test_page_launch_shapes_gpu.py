@@ -15,9 +15,8 @@ import pytest
 import torch
 
 import norm_ref as NR
+from attn_inputs import append_problem, indptr_of
 from oracle import rope_ref as RR
-from test_norm_activation_gpu import assert_close
-from test_rope_launch_shapes_gpu import append_problem
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -50,13 +49,9 @@ def _expected_expansion(lens, first_pos):
     """(batch index, position) of every appended token by repeat_interleave / arange."""
     lens_t = torch.tensor(lens)
     bi = torch.repeat_interleave(torch.arange(len(lens)), lens_t)
-    starts = torch.cat((torch.zeros(1, dtype=torch.int64), lens_t.cumsum(0)))[:-1]
+    starts = indptr_of(lens)[:-1].long()
     pos = torch.arange(int(lens_t.sum())) - starts[bi] + torch.tensor(first_pos)[bi]
     return bi.to(torch.int32), pos.to(torch.int32)
-
-
-def _indptr(lens):
-    return torch.tensor([0] + torch.tensor(lens).cumsum(0).tolist(), dtype=torch.int32, device=DEV)
 
 
 def test_get_batch_indices_positions_beyond_one_pass():
@@ -67,7 +62,7 @@ def test_get_batch_indices_positions_beyond_one_pass():
     assert 0 in LENS
     hist = [3, 17, 40, 5, 100, 7, 9, 64]  # tokens each request already holds: nonzero and all different
     nnz = sum(LENS)
-    indptr = _indptr(LENS)
+    indptr = indptr_of(LENS, DEV)
     seq_lens = torch.tensor([h + n for h, n in zip(hist, LENS)], dtype=torch.int32, device=DEV)
     want_bi, want_pos = _expected_expansion(LENS, hist)
     assert int(want_pos.min()) >= 1
@@ -91,7 +86,7 @@ def test_rope_indptr_form_beyond_one_pass():
     assert max(LENS) > 3 * POSITION_THREADS
     offsets = [1, 50, 7, 300, 2, 1000, 11, 4]
     nnz = sum(LENS)
-    indptr = _indptr(LENS)
+    indptr = indptr_of(LENS, DEV)
     offs = torch.tensor(offsets, dtype=torch.int32, device=DEV)
     _, want_pos = _expected_expansion(LENS, offsets)
     assert torch.equal(want_pos.long(), RR.positions_from_indptr(indptr.cpu(), offs.cpu()))
@@ -250,7 +245,7 @@ def test_segment_packbits_past_grid_cap(big_bits, bitorder):
     assert sum(out_lens) > PACK_GRID_BYTES
     want = torch.from_numpy(np.concatenate([np.packbits(host[int(indptr[i]): int(indptr[i + 1])], bitorder=bitorder)
                                             for i in range(3)]))
-    out_indptr = torch.tensor([0] + np.cumsum(out_lens).tolist(), dtype=torch.int32, device=DEV)
+    out_indptr = indptr_of(out_lens, DEV)
     y = torch.full((sum(out_lens),), FILL_BYTE, dtype=torch.uint8, device=DEV)
     _lib.check(_lib.lib().fi_segment_packbits(x.view(torch.uint8).data_ptr(), indptr.data_ptr(), out_indptr.data_ptr(), 3,
                                               y.numel(), int(bitorder == "little"), y.data_ptr(),
@@ -276,5 +271,5 @@ def test_act_and_mul_past_grid_y_cap(act, dtype):
     fn = getattr(flashinfer, f"{act}_and_mul")
     assert fn(x, out=out) is out
     want = NR.act_and_mul_ref(x, act)
-    assert_close(out[-5:], want[-5:], dtype, f"{act}_and_mul, the rows past {ACT_MAX_GRID_Y}")
-    assert_close(out, want, dtype, f"{act}_and_mul")
+    NR.assert_close(out[-5:], want[-5:], dtype, f"{act}_and_mul, the rows past {ACT_MAX_GRID_Y}")
+    NR.assert_close(out, want, dtype, f"{act}_and_mul")

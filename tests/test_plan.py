@@ -3,39 +3,11 @@ restatement of the reference scheduler (oracle/plan_ref.py)."""
 import ctypes as C
 import random
 
-import numpy as np
 import pytest
 
 from flashinfer import _lib
 from oracle.plan_ref import decode_plan_ref
-
-
-def run_plan(fi_lib, indptr, hq, hkv, page_size, max_grid, cuda_graph=False, head_dim=128,
-             float_bytes=1 << 30, window_left=-1):
-    n = len(indptr) - 1
-    pinned = (C.c_char * (8 << 20))()
-    arr = (C.c_int32 * len(indptr))(*indptr)
-    info = (C.c_int64 * _lib.FI_DECODE_PLAN_INFO_LEN)()
-    rc = fi_lib.fi_batch_decode_plan(None, float_bytes, None, pinned, len(pinned), arr, n, hq, hkv,
-                                     page_size, int(cuda_graph), head_dim, 1, 1, max_grid, window_left, info, None)
-    assert rc == 0, fi_lib.fi_last_error()
-    info = list(info)
-    raw = np.frombuffer(pinned, dtype=np.uint8)
-
-    def i32(off, count):
-        return raw[off: off + 4 * count].view(np.int32).tolist()
-
-    padded, nwork = info[_lib.FI_DP_PADDED_BATCH_SIZE], info[_lib.FI_DP_NUM_WORK]
-    out = dict(split_kv=bool(info[_lib.FI_DP_SPLIT_KV]), kv_chunk_size=info[_lib.FI_DP_KV_CHUNK_SIZE],
-               padded_batch_size=padded, num_work=nwork,
-               request_indices=i32(info[_lib.FI_DP_REQUEST_INDICES_OFFSET], nwork),
-               kv_tile_indices=i32(info[_lib.FI_DP_KV_TILE_INDICES_OFFSET], nwork),
-               o_indptr=i32(info[_lib.FI_DP_O_INDPTR_OFFSET], n + 1),
-               chunk_ptr=i32(info[_lib.FI_DP_KV_CHUNK_SIZE_PTR_OFFSET], 1)[0], info=info)
-    if out["split_kv"]:
-        mask_off = info[_lib.FI_DP_BLOCK_VALID_MASK_OFFSET]
-        out["mask"] = raw[mask_off: mask_off + padded].tolist()
-    return out
+from plan_calls import run_plan, run_prefill_plan
 
 
 CASES = [
@@ -103,41 +75,6 @@ def test_workspace_too_small_is_an_error(fi_lib):
 
 
 # ---- prefill planner (split-KV work list) -------------------------------------------------------------
-def run_prefill_plan(fi_lib, qo_indptr, kv_lens, hq, hkv, causal=False, cuda_graph=False, fixed=-1, disable=False,
-                     page_size=16, float_bytes=1 << 32, window_left=-1):
-    n = len(kv_lens)
-    pinned = (C.c_char * (8 << 20))()
-    qo = (C.c_int32 * (n + 1))(*qo_indptr)
-    kvp = [0]
-    for k in kv_lens:
-        kvp.append(kvp[-1] + -(-k // page_size))
-    kvi = (C.c_int32 * (n + 1))(*kvp)
-    kvl = (C.c_int32 * max(n, 1))(*kv_lens)
-    info = (C.c_int64 * _lib.FI_PREFILL_PLAN_INFO_LEN)()
-    rc = fi_lib.fi_batch_prefill_plan(None, float_bytes, None, pinned, len(pinned), qo, kvi, kvl, qo_indptr[-1], n,
-                                      hq, hkv, page_size, int(cuda_graph), 128, 128, int(causal), window_left, fixed,
-                                      int(disable), info, None)
-    assert rc == 0, fi_lib.fi_last_error()
-    info = list(info)
-    raw = np.frombuffer(pinned, dtype=np.uint8)
-
-    def i32(off, count):
-        return raw[off: off + 4 * count].view(np.int32).tolist()
-
-    nwork = info[_lib.FI_PP_NUM_WORK]
-    padded = info[_lib.FI_PP_PADDED_BATCH_SIZE]
-    out = dict(split_kv=bool(info[_lib.FI_PP_SPLIT_KV]), kv_chunk_size=info[_lib.FI_PP_KV_CHUNK_SIZE],
-               padded_batch_size=padded, num_work=nwork,
-               request_indices=i32(info[_lib.FI_PP_REQUEST_INDICES_OFFSET], nwork),
-               qo_tile_indices=i32(info[_lib.FI_PP_QO_TILE_INDICES_OFFSET], nwork),
-               kv_tile_indices=i32(info[_lib.FI_PP_KV_TILE_INDICES_OFFSET], nwork),
-               padding=i32(info[_lib.FI_PP_REQUEST_INDICES_OFFSET], padded)[nwork:])
-    out["merge_indptr"] = [0]
-    if out["split_kv"]:
-        out["merge_indptr"] = i32(info[_lib.FI_PP_MERGE_INDPTR_OFFSET], info[_lib.FI_PP_TOTAL_NUM_ROWS] + 1)
-    return out
-
-
 @pytest.fixture
 def cus_256():
     """The oracle's prefill plans are for 256 compute units, whatever device is current."""

@@ -4,35 +4,18 @@ test_fp8_prefill.py:23-191 and test_hopper_fp8_attention.py:64-108."""
 import pytest
 import torch
 
+from attn_inputs import indptr_of, make_paged, page_table, planned_prefill_wrapper, ptol, scatter_to_pages
 from flashinfer import _lib
 from oracle import attention_ref as R
-from test_decode_gpu import make_paged, tol
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def ptol(dtype):
-    """fp16: rtol = atol = 1e-3 (the reference's bar).  bf16: the same bar plus the rounding of the bf16 output
-    itself (half an ulp = 2^-9 relative; 2^-8 granted).  The bf16 kernel runs P.V on the f16 MFMA (P rounded to
-    f16, 11 mantissa bits, V converted while staged; bf16_pv_mode = 1 selects hi + lo bf16 halves instead); with
-    the reference's single bf16 rounding of P (prefill.cuh:962-985; bf16_pv_mode = 3) 83 of the 383 bf16 cases of
-    the 900-seed fuzz sweep exceed even rtol 2^-7 / atol 2e-3, all on cancelling rows (|o| << |v|: the error is
-    ~2^-9 sum |p v|; worst 4.6e-3 at seed 637, request 1, row 544, head 16 -- tools/bf16_error_scan.py prints the
-    census)."""
-    if dtype == torch.bfloat16:
-        return dict(rtol=1e-3 + 2.0 ** -8, atol=1e-3)
-    return dict(rtol=1e-3, atol=1e-3)
-
-
 def run_batch_prefill(q, qo_lens, cache, layout, indptr, indices, last, hq, hkv, d, ps, **plan_kw):
-    import flashinfer
-
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
-    ws = torch.zeros(32 << 20, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(ws, layout)
-    w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, ps,
-           q_data_type=q.dtype, kv_data_type=cache.dtype, **plan_kw)
+    qo_indptr = indptr_of(qo_lens)
+    w = planned_prefill_wrapper(32 << 20, layout, qo_indptr, indptr, indices, last, hq, hkv, d, ps,
+                                q_data_type=q.dtype, kv_data_type=cache.dtype, **plan_kw)
     o, lse = w.run(q.to(DEV), cache.to(DEV), return_lse=True)
     return o, lse, qo_indptr
 
@@ -175,29 +158,13 @@ def test_batch_prefill_fp8_qkv_paged_c3_shape_small():
     vcat = torch.cat([x[:, 1] for x in kv16])
     k8, sk = R.per_head_symmetric_quant(kcat)
     v8, sv = R.per_head_symmetric_quant(vcat)
-    # build the paged cache from the quantised rows
-    import flashinfer
-
-    pages = [-(-l // ps) for l in kv_lens]
-    total = sum(pages)
-    cache = torch.zeros(total, 2, ps, hkv, d, dtype=torch.float8_e4m3fn)
-    indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0)), dtype=torch.int32)
-    indices = torch.randperm(total).to(torch.int32)
-    last = torch.tensor([(l - 1) % ps + 1 for l in kv_lens], dtype=torch.int32)
-    off = 0
-    cache_f = cache.float()
-    for b, l in enumerate(kv_lens):
-        for t in range(l):
-            pg = int(indices[int(indptr[b]) + t // ps])
-            cache_f[pg, 0, t % ps] = k8[off + t].float()
-            cache_f[pg, 1, t % ps] = v8[off + t].float()
-        off += l
-    cache = cache_f.to(torch.float8_e4m3fn)
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
-    ws = torch.zeros(32 << 20, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(ws, "NHD")
-    w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, ps, causal=True,
-           q_data_type=torch.float8_e4m3fn, kv_data_type=torch.float8_e4m3fn, o_data_type=torch.bfloat16)
+    # build the paged cache from the quantised rows (fp8 values are exact in f32)
+    indptr, indices, last, total = page_table(kv_lens, ps)
+    cache = scatter_to_pages(k8.float(), v8.float(), kv_lens, indptr, indices, ps, total).to(torch.float8_e4m3fn)
+    qo_indptr = indptr_of(qo_lens)
+    w = planned_prefill_wrapper(32 << 20, "NHD", qo_indptr, indptr, indices, last, hq, hkv, d, ps, causal=True,
+                                q_data_type=torch.float8_e4m3fn, kv_data_type=torch.float8_e4m3fn,
+                                o_data_type=torch.bfloat16)
     o, lse = w.run(q8.to(DEV), cache.to(DEV), return_lse=True, scale_q=sq.to(DEV), scale_k=sk.to(DEV),
                    scale_v=sv.to(DEV))
     assert o.dtype == torch.bfloat16
@@ -226,7 +193,7 @@ def test_prefill_cuda_graph_mode_and_errors():
     for seed, (kv_lens, qo_lens) in enumerate([([100, 40, 300], [10, 40, 6]), ([5, 500, 64], [5, 16, 35])]):
         cache, indptr, indices, last = make_paged(b, kv_lens, ps, hkv, d, torch.float16, "NHD", seed=seed)
         q = torch.randn(56, hq, d).half()
-        qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
+        qo_indptr = indptr_of(qo_lens)
         w.plan(qo_indptr, indptr, indices, last, hq, hkv, d, ps, causal=True, max_token_per_sequence=64)
         o = w.run(q.to(DEV), cache.to(DEV))
         o_ref, _ = R.batch_prefill_ref(q.float(), qo_indptr, cache.float(), "NHD", indptr, indices, last, causal=True)
@@ -243,27 +210,19 @@ def test_fp8_native_kernel_matches_upcast_kernel(f8, d):
     """The fp8-native kernel (MX-scaled MFMA, transposed V image) and the upcast-to-bf16 kernel implement
     the same arithmetic with the same 64-row tiles, so they must agree far tighter than the fp8 bar:
     a sliding window wider than the sequence selects the upcast kernel without changing the result."""
-    import flashinfer
-
     hq, hkv, ps = 16, 4, 16
     kv_lens, qo_lens = [700, 130], [300, 130]
     torch.manual_seed(3)
     cache16 = [torch.randn(-(-l // ps), 2, ps, hkv, d) for l in kv_lens]
     cache = torch.cat(cache16).to(f8)
-    pages = [c.shape[0] for c in cache16]
-    indptr = torch.tensor([0] + list(torch.tensor(pages).cumsum(0)), dtype=torch.int32)
-    indices = torch.arange(sum(pages), dtype=torch.int32)
-    last = torch.tensor([(l - 1) % ps + 1 for l in kv_lens], dtype=torch.int32)
+    indptr, indices, last, _ = page_table(kv_lens, ps, shuffle=False)
     q8 = torch.randn(sum(qo_lens), hq, d).to(f8)
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
+    qo_indptr = indptr_of(qo_lens)
     sq, sk, sv = torch.rand(hq) + 0.5, torch.rand(hkv) + 0.5, torch.rand(hkv) + 0.5
     outs = []
     for window in (-1, 1 << 30):
-        ws = torch.zeros(32 << 20, dtype=torch.uint8, device=DEV)
-        w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(ws, "NHD")
-        w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, ps, causal=True,
-               window_left=window, q_data_type=f8, kv_data_type=f8,
-               o_data_type=torch.float16)
+        w = planned_prefill_wrapper(32 << 20, "NHD", qo_indptr, indptr, indices, last, hq, hkv, d, ps, causal=True,
+                                    window_left=window, q_data_type=f8, kv_data_type=f8, o_data_type=torch.float16)
         outs.append(w.run(q8.to(DEV), cache.to(DEV), return_lse=True, scale_q=sq.to(DEV), scale_k=sk.to(DEV),
                           scale_v=sv.to(DEV)))
     # identical up to e4m3 rounding flips of single probabilities: the native kernel folds the x448 into the
@@ -294,8 +253,8 @@ def test_ragged_kv_prefill_wrapper(layout, causal):
     q = torch.randn(sum(qo_lens), hq, d).half()
     k = torch.randn(sum(kv_lens), hkv, d).half()
     v = torch.randn(sum(kv_lens), hkv, d).half()
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
-    kv_indptr = torch.tensor([0] + list(torch.tensor(kv_lens).cumsum(0)), dtype=torch.int32)
+    qo_indptr = indptr_of(qo_lens)
+    kv_indptr = indptr_of(kv_lens)
     ws = torch.zeros(16 << 20, dtype=torch.uint8, device=DEV)
     w = flashinfer.BatchPrefillWithRaggedKVCacheWrapper(ws, layout)
     w.plan(qo_indptr.to(DEV), kv_indptr.to(DEV), hq, hkv, d, causal=causal)
@@ -312,16 +271,12 @@ def test_ragged_kv_prefill_wrapper(layout, causal):
 
 # ---- split-KV prefill (ref planner: PrefillSplitQOKVIndptr, scheduler.cuh:495-614) -----------------------
 def _plan_run(qo_lens, kv_lens, hq, hkv, d, ps, dtype, causal, seed, layout="NHD", **plan_kw):
-    import flashinfer
-
     cache, indptr, indices, last = make_paged(len(kv_lens), kv_lens, ps, hkv, d, dtype, layout, seed=seed)
     torch.manual_seed(seed + 1)
     q = torch.randn(sum(qo_lens), hq, d).to(dtype)
-    qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
-    ws = torch.zeros(256 << 20, dtype=torch.uint8, device=DEV)
-    w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(ws, layout)
-    w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), hq, hkv, d, ps, causal=causal,
-           q_data_type=dtype, kv_data_type=cache.dtype, **plan_kw)
+    qo_indptr = indptr_of(qo_lens)
+    w = planned_prefill_wrapper(256 << 20, layout, qo_indptr, indptr, indices, last, hq, hkv, d, ps, causal=causal,
+                                q_data_type=dtype, kv_data_type=cache.dtype, **plan_kw)
     o, lse = w.run(q.to(DEV), cache.to(DEV), return_lse=True)
     return w, q, cache, qo_indptr, indptr, indices, last, o, lse
 
@@ -456,7 +411,7 @@ def test_prefill_run_is_graph_capturable_and_replays_after_replan():
 
     def plan(i):
         cache, indptr, indices, last, qo_lens = data[i]
-        qo_indptr = torch.tensor([0] + list(torch.tensor(qo_lens).cumsum(0)), dtype=torch.int32)
+        qo_indptr = indptr_of(qo_lens)
         w.plan(qo_indptr, indptr, indices, last, hq, hkv, d, ps, causal=True, max_token_per_sequence=rows // b)
         cache_dev.copy_(cache)
         torch.manual_seed(i)

@@ -4,43 +4,14 @@ import ctypes as C
 import json
 import os
 
-import numpy as np
 import pytest
 
 from flashinfer import _lib
+from plan_calls import prefill_qkvo_plan as plan
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "prefill_plans_equal_dims.json")
 ENTRY_ALIGN = 256  # slack for the workspace allocator's alignment of the two partial-state regions
-
-
-def plan(fi_lib, qo_lens, kv_lens, hq, hkv, dqk, dvo, causal=True, float_bytes=1 << 30, graph=False,
-         fixed_split=-1, disable_split=False, window_left=-1, page_size=1):
-    """fi_batch_prefill_plan on the host: (rc, plan_info, request / q tile / kv tile / merge_indptr lists)."""
-    n = len(qo_lens)
-    qo = np.concatenate([[0], np.cumsum(qo_lens)]).astype(np.int32)
-    kvp = np.concatenate([[0], np.cumsum([-(-k // page_size) for k in kv_lens])]).astype(np.int32)
-    kl = np.array(kv_lens, dtype=np.int32)
-    pinned = (C.c_char * (8 << 20))()
-    info = (C.c_int64 * _lib.FI_PREFILL_PLAN_INFO_LEN)()
-    rc = fi_lib.fi_batch_prefill_plan(None, float_bytes, None, pinned, len(pinned), qo.ctypes.data, kvp.ctypes.data,
-                                      kl.ctypes.data, int(qo[-1]), n, hq, hkv, page_size, int(graph), dqk, dvo,
-                                      int(causal), window_left, fixed_split, int(disable_split), info, None)
-    if rc != 0:
-        return rc, None, None
-    info = list(info)
-    raw = np.frombuffer(pinned, dtype=np.uint8)
-
-    def i32(off, count):
-        return raw[off: off + 4 * count].view(np.int32).tolist()
-
-    padded, rows = info[_lib.FI_PP_PADDED_BATCH_SIZE], info[_lib.FI_PP_TOTAL_NUM_ROWS]
-    lists = dict(req=i32(info[_lib.FI_PP_REQUEST_INDICES_OFFSET], padded),
-                 tile=i32(info[_lib.FI_PP_QO_TILE_INDICES_OFFSET], padded),
-                 kvt=i32(info[_lib.FI_PP_KV_TILE_INDICES_OFFSET], padded),
-                 merge=i32(info[_lib.FI_PP_MERGE_INDPTR_OFFSET], rows + 1) if info[_lib.FI_PP_SPLIT_KV] else [],
-                 chunk=i32(info[_lib.FI_PP_KV_CHUNK_SIZE_PTR_OFFSET], 1))
-    return rc, info, lists
 
 
 def entries(qo_lens, kv_lens, chunk):

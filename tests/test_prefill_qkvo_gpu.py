@@ -7,19 +7,15 @@ import random
 import pytest
 import torch
 
+from attn_inputs import indptr_of, ptol
 from flashinfer import _lib
 from oracle import attention_ref as R
-from test_prefill_gpu import ptol
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 DQK, DVO = 192, 128
 SEEDS = range(int(os.environ.get("FI_FUZZ_SEEDS", "24")))
 LSE_TOL = dict(rtol=1e-3, atol=1e-3)
-
-
-def _indptr(lens):
-    return torch.tensor([0] + list(torch.tensor(lens, dtype=torch.int64).cumsum(0)), dtype=torch.int32)
 
 
 def _data(qo_lens, kv_lens, hq, hkv, dtype, seed):
@@ -37,7 +33,7 @@ def _ref(q, k, v, qo_lens, kv_lens, causal, kv_heads=None, **kw):
     if kv_heads is not None:
         qh = [h * G + j for h in kv_heads for j in range(G)]
         q, k, v = q[:, qh], k[:, kv_heads], v[:, kv_heads]
-    qi, ki = _indptr(qo_lens), _indptr(kv_lens)
+    qi, ki = indptr_of(qo_lens), indptr_of(kv_lens)
     outs, lses = [], []
     for b in range(len(qo_lens)):
         o, s = R.attention_ref(q[qi[b]:qi[b + 1]].float(), k[ki[b]:ki[b + 1]].float(), v[ki[b]:ki[b + 1]].float(),
@@ -59,7 +55,7 @@ def _ragged(qo_lens, kv_lens, hq, hkv, dtype, causal, q, k, v, layout="NHD", ws_
 
     ws = torch.zeros(ws_mb << 20, dtype=torch.uint8, device=DEV)
     w = flashinfer.BatchPrefillWithRaggedKVCacheWrapper(ws, layout)
-    w.plan(_indptr(qo_lens).to(DEV), _indptr(kv_lens).to(DEV), hq, hkv, DQK, head_dim_vo=DVO, causal=causal,
+    w.plan(indptr_of(qo_lens).to(DEV), indptr_of(kv_lens).to(DEV), hq, hkv, DQK, head_dim_vo=DVO, causal=causal,
            q_data_type=dtype, **plan_kw)
     o, lse = w.run(q, k, v, return_lse=True)
     torch.cuda.synchronize()
@@ -227,12 +223,12 @@ def test_chunked_prefill_composition(n_prefix):
         o, s = flashinfer.merge_states(torch.stack([x[0] for x in states], 1), torch.stack([x[1] for x in states], 1))
     torch.cuda.synchronize()
     # reference: per request, keys = the prefix chunks then the new tokens, causal (queries are the last rows)
-    qi, ni = _indptr(new_lens), _indptr(new_lens)
+    qi, ni = indptr_of(new_lens), indptr_of(new_lens)
     outs, lses = [], []
     for b in range(len(new_lens)):
         ks, vs = [], []
         for ck, cv, pl in zip(chunks_k, chunks_v, prefix_lens):
-            pi = _indptr(pl)
+            pi = indptr_of(pl)
             ks.append(ck[pi[b]:pi[b + 1]])
             vs.append(cv[pi[b]:pi[b + 1]])
         ks.append(k_new[ni[b]:ni[b + 1]])
@@ -266,7 +262,7 @@ def test_graph_replay_after_replan():
 
     def plan(i):
         qo_lens, kv_lens, split = cases[i]
-        w.plan(_indptr(qo_lens).to(DEV), _indptr(kv_lens).to(DEV), hq, hkv, DQK, head_dim_vo=DVO, causal=True,
+        w.plan(indptr_of(qo_lens).to(DEV), indptr_of(kv_lens).to(DEV), hq, hkv, DQK, head_dim_vo=DVO, causal=True,
                q_data_type=dtype, fixed_split_size=split)
         q, k, v = _data(qo_lens, kv_lens, hq, hkv, dtype, seed=40 + i)
         q_dev.copy_(q.to(DEV))
@@ -294,7 +290,7 @@ def test_refusals():
     import flashinfer
 
     ws = torch.zeros(16 << 20, dtype=torch.uint8, device=DEV)
-    qi, ki = _indptr([10]).to(DEV), _indptr([20]).to(DEV)
+    qi, ki = indptr_of([10]).to(DEV), indptr_of([20]).to(DEV)
     w = flashinfer.BatchPrefillWithRaggedKVCacheWrapper(ws)
     with pytest.raises(ValueError, match="fp8"):
         w.plan(qi, ki, 4, 4, DQK, head_dim_vo=DVO, q_data_type=torch.float8_e4m3fn)
@@ -312,7 +308,7 @@ def test_refusals():
             w.plan(qi, ki, 4, 4, qk, head_dim_vo=vo, q_data_type=torch.float16)
     pw = flashinfer.BatchPrefillWithPagedKVCacheWrapper(ws)
     with pytest.raises(ValueError, match="head_dim_qk == head_dim_vo"):
-        pw.plan(qi, _indptr([2]).to(DEV), torch.arange(2, dtype=torch.int32, device=DEV),
+        pw.plan(qi, indptr_of([2]).to(DEV), torch.arange(2, dtype=torch.int32, device=DEV),
                 torch.tensor([4], dtype=torch.int32, device=DEV), 4, 4, DQK, 16, head_dim_vo=DVO,
                 q_data_type=torch.float16)
     q = torch.randn(10, 4, DQK, device=DEV).half()

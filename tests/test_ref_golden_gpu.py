@@ -4,12 +4,13 @@ Inputs are fp16-exact, so the kernels see precisely the values the reference fun
 Tolerances: the reference's bars -- rtol = atol = 1e-3 for 16-bit attention / merge
 (tests/attention/test_batch_decode_kernels.py:144-184), 1e-2 for the fp8 groupwise GEMM
 (tests/GEMM/test_groupwise_scaled_gemm_fp8.py:71)."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 import torch
+
+from attn_inputs import indptr_of, page_table, scatter_to_pages
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -33,18 +34,9 @@ def t(a):
 
 def paged_from_dense(k, v, page_size, seed):
     """[kv, H, D] rows scattered into shuffled pages of an NHD cache."""
-    kv_len, h, d = k.shape
-    n_pages = -(-kv_len // page_size)
-    g = torch.Generator().manual_seed(seed)
-    indices = torch.randperm(n_pages + 2, generator=g)[:n_pages].to(torch.int32)
-    cache = torch.zeros(n_pages + 2, 2, page_size, h, d, dtype=k.dtype)
-    for p in range(n_pages):
-        rows = slice(p * page_size, min((p + 1) * page_size, kv_len))
-        n = rows.stop - rows.start
-        cache[int(indices[p]), 0, :n] = k[rows]
-        cache[int(indices[p]), 1, :n] = v[rows]
-    last = (kv_len - 1) % page_size + 1
-    return cache, indices, last
+    kv_lens = [k.shape[0]]
+    indptr, indices, last, n_pages = page_table(kv_lens, page_size, torch.Generator().manual_seed(seed), extra_pages=2)
+    return scatter_to_pages(k, v, kv_lens, indptr, indices, page_size, n_pages), indices, int(last[0])
 
 
 @pytest.mark.parametrize("tag", ["gqa_a", "gqa_b", "dec", "gqa_c"])
@@ -191,7 +183,7 @@ def test_variable_length_merge_states_matches_oracle_ragged():
 
     g = torch.Generator().manual_seed(5)
     counts = [1, 9, 2, 0, 5, 3, 1, 7]
-    indptr = torch.tensor([0] + list(torch.tensor(counts).cumsum(0)), dtype=torch.int32)
+    indptr = indptr_of(counts)
     nnz, h, d = int(indptr[-1]), 6, 128
     for dt, tol in ((torch.float16, 1e-3), (torch.bfloat16, 8e-3)):
         v = torch.randn(nnz, h, d, generator=g).to(dt)

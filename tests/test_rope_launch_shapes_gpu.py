@@ -12,6 +12,7 @@ Tolerances are those of tests/test_rope_gpu.py.
 import pytest
 import torch
 
+from attn_inputs import append_problem
 from oracle import rope_ref as RR
 
 pytestmark = pytest.mark.gpu
@@ -198,26 +199,6 @@ def test_odd_pass_through_chunk_count(d, rot, nnz, dtype, interleave):
 
 
 # ---- A5: the fused append in the multi-head regime ------------------------------------------------------------------
-
-def append_problem(lens, hist, ps, spare_pages, seed):
-    """Page table (shuffled, with spare pages) and per-token (batch index, position) of appending lens[r] tokens to
-    requests that already hold hist[r] tokens.  Everything by tensor ops."""
-    lens_t, hist_t = torch.tensor(lens), torch.tensor(hist)
-    pages = (lens_t + hist_t + ps - 1) // ps
-    kv_indptr = torch.cat((torch.zeros(1, dtype=torch.int64), pages.cumsum(0))).to(torch.int32)
-    total_pages = int(kv_indptr[-1]) + spare_pages
-    perm = torch.randperm(total_pages, generator=torch.Generator().manual_seed(seed))
-    kv_indices = perm[: int(kv_indptr[-1])].to(torch.int32)
-    batch_indices = torch.repeat_interleave(torch.arange(len(lens)), lens_t)
-    starts = torch.cat((torch.zeros(1, dtype=torch.int64), lens_t.cumsum(0)))[:-1]
-    positions = torch.arange(int(lens_t.sum())) - starts[batch_indices] + hist_t[batch_indices]
-    slot_page = kv_indices[(kv_indptr[batch_indices].long() + positions // ps)].long()
-    slot = slot_page * ps + positions % ps  # flat (page, entry) slot every token lands in
-    last = ((lens_t + hist_t - 1) % ps + 1).to(torch.int32)
-    return dict(kv_indptr=kv_indptr.to(DEV), kv_indices=kv_indices.to(DEV), last=last.to(DEV), total_pages=total_pages,
-                batch_indices=batch_indices.to(torch.int32).to(DEV), positions=positions.to(torch.int32).to(DEV),
-                slot=slot.to(DEV))
-
 
 def slots_view(cache, layout):
     """5-D cache -> [pages * page_size, 2, heads, d] (a copy), one row per slot."""
