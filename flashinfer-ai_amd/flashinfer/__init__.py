@@ -1,6 +1,6 @@
 """flashinfer -- MI355X (gfx950) native implementation of FlashInfer's paged-KV attention hot path.
 
-Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / gemm / fp8_quantization / sampling / norm / activation`` operator API
+Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / sparse / gemm / fp8_quantization / sampling / norm / activation`` operator API
 of FlashInfer v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-written HIP kernels behind the C ABI of
 ``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided.
 """
@@ -10,6 +10,7 @@ from . import fp8_quantization as fp8_quantization
 from . import mla as mla
 from . import norm as norm
 from . import sampling as sampling
+from . import sparse as sparse
 from .activation import gelu_and_mul as gelu_and_mul
 from .activation import gelu_tanh_and_mul as gelu_tanh_and_mul
 from .activation import silu_and_mul as silu_and_mul
@@ -48,6 +49,9 @@ from .norm import rmsnorm as rmsnorm
 from .page import append_paged_kv_cache as append_paged_kv_cache
 from .page import append_paged_mla_kv_cache as append_paged_mla_kv_cache
 from .page import apply_rope_append_paged_kv_cache as apply_rope_append_paged_kv_cache
+from .page import (
+    block_sparse_indices_to_vector_sparse_offsets as block_sparse_indices_to_vector_sparse_offsets,
+)
 from .page import get_batch_indices_positions as get_batch_indices_positions
 from .page import get_seq_lens as get_seq_lens
 from .prefill import (
@@ -90,6 +94,10 @@ from .sampling import (
 from .sampling import top_k_top_p_sampling_from_probs as top_k_top_p_sampling_from_probs
 from .sampling import top_p_renorm_probs as top_p_renorm_probs
 from .sampling import top_p_sampling_from_probs as top_p_sampling_from_probs
+from .sparse import BlockSparseAttentionWrapper as BlockSparseAttentionWrapper
+from .sparse import (
+    VariableBlockSparseAttentionWrapper as VariableBlockSparseAttentionWrapper,
+)
 from .utils import next_positive_power_of_2 as next_positive_power_of_2
 
 __version__ = "0.3.1+mi355x.r2"

@@ -64,6 +64,51 @@ def get_batch_indices_positions(
     return batch_indices, positions
 
 
+def block_sparse_indices_to_vector_sparse_offsets(
+    block_sparse_indices: torch.Tensor,
+    block_sparse_indptr: torch.Tensor,
+    vector_sparse_offsets: torch.Tensor,
+    vector_sparse_indptr: torch.Tensor,
+    kv_lens: torch.Tensor,
+    stride_block: int,
+    stride_n: int,
+    block_size: int,
+) -> torch.Tensor:
+    r"""Expand the block indices of a block-sparse KV selection into one offset per token, written to
+    ``vector_sparse_offsets`` (which is returned): for request ``b`` and ``pos < kv_lens[b]``
+
+    ``vector_sparse_offsets[vector_sparse_indptr[b] + pos] =
+    block_sparse_indices[block_sparse_indptr[b] + pos // block_size] * stride_block + (pos % block_size) * stride_n``
+
+    All five tensors are int32 on one device; ``block_sparse_indptr`` has ``batch_size + 1`` entries.  With
+    ``block_size == 1`` nothing is launched: the indices (times ``stride_block``) are the offsets.
+    (ref: flashinfer/page.py:49-82, include/flashinfer/page.cuh:287-302)
+    """
+    if block_size == 1:
+        return block_sparse_indices if stride_block == 1 else block_sparse_indices * stride_block
+    tensors = (("block_sparse_indices", block_sparse_indices), ("block_sparse_indptr", block_sparse_indptr),
+               ("vector_sparse_offsets", vector_sparse_offsets), ("vector_sparse_indptr", vector_sparse_indptr),
+               ("kv_lens", kv_lens))
+    dev = block_sparse_indices.device
+    for name, t in tensors:
+        _lib.require_gpu_tensor(t, name)
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous int32 tensor on {dev}")
+    batch_size = block_sparse_indptr.size(0) - 1
+    if vector_sparse_indptr.numel() < batch_size or kv_lens.numel() < batch_size:
+        raise ValueError("vector_sparse_indptr and kv_lens must hold an entry for every request")
+    with torch.cuda.device(dev):
+        _lib.check(
+            _lib.lib().fi_block_sparse_indices_to_vector_sparse_offsets(
+                block_sparse_indices.data_ptr(), block_sparse_indptr.data_ptr(), vector_sparse_offsets.data_ptr(),
+                vector_sparse_indptr.data_ptr(), kv_lens.data_ptr(), stride_block, stride_n, batch_size, block_size,
+                block_sparse_indices.numel(), vector_sparse_offsets.numel(), _lib.current_stream(dev),
+            ),
+            "block_sparse_indices_to_vector_sparse_offsets",
+        )
+    return vector_sparse_offsets
+
+
 def append_paged_kv_cache(
     append_key: torch.Tensor,
     append_value: torch.Tensor,

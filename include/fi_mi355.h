@@ -442,6 +442,45 @@ FI_API int fi_append_paged_kv_cache(const void* append_key, const void* append_v
                              const fi_paged_kv_t* kv, fi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Block-sparse index plumbing (csrc/sparse.hip).  ref: the torch expansion of
+ * VariableBlockSparseAttentionWrapper.plan, flashinfer/sparse.py:929-974;
+ * BlockSparseIndicesToVectorSparseOffsetsKernel, include/flashinfer/page.cuh:287-302.
+ *
+ * A per-head block map `block_mask_map` [H, MB, NB] (one byte per entry, non-zero = selected) over column blocks
+ * of `block_col_sz` [H, NB] tokens becomes a page table of `granule`-token pages; `granule` divides every column
+ * size.  Head h owns tokens [h * kv_len, (h + 1) * kv_len), kv_len = sum_c block_col_sz[h, c] for every h; column
+ * block c of head h starts at token h * kv_len + sum_{c' < c} block_col_sz[h, c'].
+ *   row_pages[h * MB + i] = sum_c (mask[h, i, c] != 0) * block_col_sz[h, c] / granule
+ *   fi_block_mask_to_page_indices: with kv_indptr [H * MB + 1] the exclusive scan of row_pages (device), row (h, i)
+ *   writes, for its selected blocks in increasing c, the pages start / granule ... start / granule +
+ *   block_col_sz / granule - 1 to kv_indices[kv_indptr[h * MB + i] ...].
+ * Both refuse H * kv_len / granule >= 2^31 (page numbers are int32).  `num_pages` is kv_indptr[H * MB] as the host
+ * knows it and `capacity` the number of int32 entries kv_indices holds: capacity < num_pages is refused before any
+ * launch, and no row writes past its own end of kv_indptr or past `capacity`.
+ *
+ *   fi_block_sparse_indices_to_vector_sparse_offsets, for b < batch_size and pos < kv_lens[b]:
+ *   vector_sparse_offsets[vector_sparse_indptr[b] + pos] =
+ *       block_sparse_indices[block_sparse_indptr[b] + pos / block_size] * stride_block + (pos % block_size) * stride_n
+ *   `num_indices` / `capacity` are the entries block_sparse_indices / vector_sparse_offsets hold: nothing is read or
+ *   written past them.
+ * ---------------------------------------------------------------------------------------------- */
+FI_API int fi_block_mask_row_pages(const uint8_t* block_mask_map, const int32_t* block_col_sz, int32_t num_heads,
+                                   int32_t num_block_rows, int32_t num_block_cols, int32_t granule, int64_t kv_len,
+                                   int32_t* row_pages, fi_stream_t stream);
+FI_API int fi_block_mask_to_page_indices(const uint8_t* block_mask_map, const int32_t* block_col_sz,
+                                         const int32_t* kv_indptr, int32_t num_heads, int32_t num_block_rows,
+                                         int32_t num_block_cols, int32_t granule, int64_t kv_len, int64_t num_pages,
+                                         int64_t capacity, int32_t* kv_indices, fi_stream_t stream);
+FI_API int fi_block_sparse_indices_to_vector_sparse_offsets(const int32_t* block_sparse_indices,
+                                                            const int32_t* block_sparse_indptr,
+                                                            int32_t* vector_sparse_offsets,
+                                                            const int32_t* vector_sparse_indptr,
+                                                            const int32_t* kv_lens, int64_t stride_block,
+                                                            int64_t stride_n, int32_t batch_size, int32_t block_size,
+                                                            int64_t num_indices, int64_t capacity,
+                                                            fi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Multi-head Latent Attention (absorbed form) over a paged cache.  ref: BatchMLAPagedAttentionWrapper,
  * flashinfer/mla.py:85-420; append_paged_mla_kv_cache flashinfer/page.py:250-298.
  *   one shared KV head; K = [ckv | kpe] (512 + 64 dims), V = ckv (512 dims)
