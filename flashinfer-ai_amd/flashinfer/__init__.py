@@ -1,11 +1,12 @@
 """flashinfer -- MI355X (gfx950) native implementation of FlashInfer's paged-KV attention hot path.
 
-Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / sparse / gemm / fp8_quantization / sampling / norm / activation`` operator API
+Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / sparse / gemm / fp8_quantization / fp4_quantization / sampling / norm / activation`` operator API
 of FlashInfer v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-written HIP kernels behind the C ABI of
 ``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided.
 """
 from . import _lib as _lib
 from . import activation as activation
+from . import fp4_quantization as fp4_quantization
 from . import fp8_quantization as fp8_quantization
 from . import mla as mla
 from . import norm as norm
@@ -37,6 +38,14 @@ from .decode import (
 )
 from .decode import fast_decode_plan as fast_decode_plan
 from .decode import single_decode_with_kv_cache as single_decode_with_kv_cache
+from .fp4_quantization import block_scale_interleave as block_scale_interleave
+from .fp4_quantization import e2m1_and_ufp8sf_scale_to_float as e2m1_and_ufp8sf_scale_to_float
+from .fp4_quantization import fp4_quantize as fp4_quantize
+from .fp4_quantization import mxfp4_dequantize as mxfp4_dequantize
+from .fp4_quantization import mxfp4_dequantize_host as mxfp4_dequantize_host
+from .fp4_quantization import mxfp4_quantize as mxfp4_quantize
+from .fp4_quantization import mxfp4_quantize_grouped as mxfp4_quantize_grouped
+from .fp4_quantization import nvfp4_block_scale_interleave as nvfp4_block_scale_interleave
 from .fp8_quantization import mxfp8_dequantize_host as mxfp8_dequantize_host
 from .fp8_quantization import mxfp8_quantize as mxfp8_quantize
 from .gemm import gemm_fp8_nt_groupwise as gemm_fp8_nt_groupwise

@@ -29,6 +29,19 @@ def _sf_offset(r: torch.Tensor, kb: torch.Tensor, nkb: int) -> torch.Tensor:
     return (r // 128) * ((nkb + 3) // 4) * 512 + (kb // 4) * 512 + (r % 32) * 16 + ((r % 128) // 32) * 4 + kb % 4
 
 
+def _linear_scales(scale_tensor: torch.Tensor, m: int, nkb: int, swizzled: bool) -> torch.Tensor:
+    """The ``[m, nkb]`` scale bytes of a CPU scale tensor in the linear or the swizzled layout (padding is not read)."""
+    flat = scale_tensor.reshape(-1)
+    need = _ceil_to(m, 128) * _ceil_to(nkb, 4) if swizzled else m * nkb
+    if flat.numel() < need:
+        raise ValueError(f"the scale tensor holds {flat.numel()} bytes, {need} needed")
+    if not swizzled:
+        return flat[: m * nkb].view(m, nkb)
+    r = torch.arange(m).view(-1, 1).expand(m, nkb)
+    kb = torch.arange(nkb).view(1, -1).expand(m, nkb)
+    return flat[_sf_offset(r, kb, nkb).reshape(-1)].view(m, nkb)
+
+
 def sf_row_offset(m_begin: int, group: int) -> int:
     """First scale row of ``group`` whose rows start at ``m_begin`` in the grouped layout; ``sf_row_offset(cum_m, G)`` is
     the row count of the whole scale tensor."""
@@ -127,15 +140,6 @@ def mxfp8_dequantize_host(
         input = input.view(torch.float8_e4m3fn)
     m, k = input.shape
     nkb = k // _BLOCK
-    flat = scale_tensor.reshape(-1)
-    need = _ceil_to(m, 128) * _ceil_to(nkb, 4) if is_sf_swizzled_layout else m * nkb
-    if flat.numel() < need:
-        raise ValueError(f"scale_tensor holds {flat.numel()} bytes, {need} needed")
-    if is_sf_swizzled_layout:
-        r = torch.arange(m).view(-1, 1).expand(m, nkb)
-        kb = torch.arange(nkb).view(1, -1).expand(m, nkb)
-        sf = flat[_sf_offset(r, kb, nkb).reshape(-1)].view(m, nkb)
-    else:
-        sf = flat[: m * nkb].view(m, nkb)
+    sf = _linear_scales(scale_tensor, m, nkb, is_sf_swizzled_layout)
     scale = torch.exp2(sf.double() - 127.0).unsqueeze(-1)
     return (input.to(torch.float32).double().view(m, nkb, _BLOCK) * scale).view(m, k).to(torch.float32)

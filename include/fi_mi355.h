@@ -742,7 +742,7 @@ FI_API int fi_act_and_mul(const fi_act_and_mul_params_t* params, fi_stream_t str
  * consecutive k elements of a row.  ref: mxfp8_quantize flashinfer/fp8_quantization.py:179-212,
  * csrc/nv_internal/tensorrt_llm/kernels/quantization.cuh:586-688; group_gemm_mxfp8_mxfp4_nt_groupwise
  * flashinfer/gemm.py:2814-2949, include/flashinfer/gemm/group_gemm_mxfp4_groupwise_sm100.cuh:54-90.
- * Both entry points keep no host state and never synchronise (m_indptr stays on the device), so both may be captured
+ * The entry points keep no host state and never synchronise (m_indptr stays on the device), so all may be captured
  * into a graph; an empty problem returns 0 without a launch.
  *
  * Scale layouts.  Linear: [rows, nkb] bytes, nkb = k blocks per row.  Swizzled "128x4" (quantization.cuh:649-688):
@@ -800,6 +800,45 @@ typedef struct fi_group_gemm_mxfp4_params {
 } fi_group_gemm_mxfp4_params_t;
 
 FI_API int fi_group_gemm_mxfp8_mxfp4_nt_groupwise(const fi_group_gemm_mxfp4_params_t* params, fi_stream_t stream);
+
+/* MXFP4 quantiser (ref: fp4_quantize with sf_vec_size 32 and UE8M0 scales, flashinfer/fp4_quantization.py:525-587,
+ * quantization.cuh:427-499).  code = e2m1(x * 2^-e), sf = e + 127 per block of 32, where e is the smallest integer in
+ * [-127, 127] with 6 * 2^e >= amax (an all-zero block: e = -127, byte 0, codes 0).  The scaling is exact, nothing
+ * saturates, and the conversion rounds to nearest with ties to even.  One deliberate pin, as for MXFP8: the reference
+ * multiplies amax by an approximate reciprocal of 6, so at amax exactly 6 * 2^e its hardware may pick e + 1; here the
+ * compare is exact and such a block gets e.  The reference ignores its global scale with UE8M0 scales; there is none
+ * here.  The sign nibble of a value that rounds to zero is unspecified; NaN / Inf and magnitudes below 2^-126 are
+ * outside the contract.
+ * input: f16 / bf16 [num_groups * rows, k], k % 32 == 0, row stride in elements (a multiple of 8, base 16-byte
+ * aligned); group g owns rows [g * rows, (g + 1) * rows).  num_groups = 1 is the plain 2-D case.
+ * q: [num_groups * rows, k/2] bytes contiguous, element 2i in the low nibble of byte i (the b of the grouped GEMM).
+ * sf: linear [num_groups * rows, k/32], or swizzled: every group on its own, rows padded to 128 and blocks to 4,
+ * num_groups * ceil(rows/128)*128 * ceil(k/128)*4 bytes (the b_scale of the grouped GEMM when k % 128 == 0).
+ * EVERY byte of sf is written, padding as 0.  No host state, no synchronisation; an empty problem returns 0. */
+typedef struct fi_mxfp4_quantize_params {
+  const void* input;
+  void* q;
+  void* sf;
+  int64_t input_stride;
+  int64_t sf_bytes; /* size of the sf buffer */
+  int32_t num_groups, rows, k;
+  int32_t sf_layout; /* enum fi_mx_sf_layout */
+  int32_t dtype;     /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+} fi_mxfp4_quantize_params_t;
+
+FI_API int fi_mxfp4_quantize(const fi_mxfp4_quantize_params_t* params, fi_stream_t stream);
+
+/* Linear scale bytes [num_groups, rows, cols] (contiguous) -> the swizzled layout, every group on its own:
+ * num_groups * ceil(rows/128)*128 * ceil(cols/4)*4 bytes, EVERY one written, padding as 0 (ref: block_scale_interleave,
+ * flashinfer/fp4_quantization.py:590-619).  output is 4-byte aligned. */
+typedef struct fi_mx_sf_interleave_params {
+  const void* input;
+  void* output;
+  int64_t output_bytes; /* size of the output buffer */
+  int32_t num_groups, rows, cols;
+} fi_mx_sf_interleave_params_t;
+
+FI_API int fi_mx_sf_interleave(const fi_mx_sf_interleave_params_t* params, fi_stream_t stream);
 
 #ifdef __cplusplus
 }
