@@ -1,0 +1,573 @@
+// The mixture-of-experts layer around the MXFP4-weight grouped GEMM (gemm_mxfp4.hip): routing, the permutation into
+// the GEMM's row operand, the gated activation between the two GEMMs and the weighted sum of the expert outputs.
+// ref: trtllm_fp4_block_scale_moe, flashinfer/fused_moe/core.py:1819-1948; contracts in include/fi_mi355.h.
+// All of it is data movement and elementwise work: no MFMA here.
+//
+// route.     One wave per token.  Lane l holds logits l, l + 64, ... (up to 8, num_experts <= 512) in registers; each of
+//            the top_k rounds takes the lane's best untaken entry and reduces (value, index) over the wave with the
+//            order "larger value, then lower index", so ties resolve without another pass.
+// permute.   Four launches, no host round trip.  count: one wave per FI_MOE_SORT_BLOCK expanded indices builds the
+//            histogram of its block over the local experts (LDS adds: a count does not depend on their order).  scan: one
+//            workgroup turns the histograms into per-block offsets (a serial walk over the blocks per expert) and the
+//            expert totals into m_indptr.  place: the same wave ranks its indices 64 at a time -- the lanes of one
+//            expert are found by ballot, a lane's rank is the number of lower lanes with its expert -- on top of a
+//            running count in LDS that only this wave writes, which makes the order inside an expert the order of the
+//            expanded index.  gather: indexed by the rows of the scale tensor, padding included, as the quantiser is, so
+//            that every scale byte is written; a row copies its token's e4m3 bytes and moves the scale bytes of each
+//            128 k elements as one dword into the swizzled layout.
+// gated act. The quantiser's shape (mxfp8_quantize.hip) with the activation in front: a thread owns 8 output columns,
+//            the quad shares amax; the rule itself is mx_quant.h.
+// finalize.  A thread owns 8 columns of a token and walks its slots in order.
+// A row finds its group by a binary search over m_indptr, which every workgroup first copies to LDS.
+#include <math.h>
+
+#include "common.h"
+#include "mx_layout.h"
+#include "mx_quant.h"
+
+namespace fi {
+
+constexpr int kMoeThreads = 256;
+constexpr int kMoeSlots = FI_MOE_MAX_EXPERTS / 64;  // logits per lane
+
+// ---- route ----------------------------------------------------------------------------------------------------------
+struct MoeRouteArgs {
+  const void* logits;
+  int32_t* ids;
+  uint16_t* weights;
+  int32_t num_tokens, num_experts, top_k, method;
+};
+
+// (value, index) of the better of two candidates: the larger value, then the lower index
+__device__ __forceinline__ void moe_better(float& v, int& i, float ov, int oi) {
+  if (ov > v || (ov == v && oi < i)) {
+    v = ov;
+    i = oi;
+  }
+}
+
+template <int DT>
+__global__ void __launch_bounds__(kMoeThreads) moe_route_kernel(const MoeRouteArgs A) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * (kMoeThreads / 64) + (threadIdx.x >> 6);
+  if (t >= A.num_tokens) return;  // whole waves leave
+  const int E = A.num_experts;
+  float v[kMoeSlots];
+  uint32_t taken = 0;  // bit s: slot s is chosen already, or past the last expert
+#pragma unroll
+  for (int s = 0; s < kMoeSlots; ++s) {
+    const int e = lane + 64 * s;
+    float x = -INFINITY;
+    if (e < E) {
+      x = load_any_float(A.logits, (int64_t)t * E + e, DT);
+      if (!(x == x)) x = -INFINITY;
+    } else {
+      taken |= 1u << s;
+    }
+    v[s] = x;
+  }
+  float sel_v[FI_MOE_MAX_TOP_K];
+  int sel_i[FI_MOE_MAX_TOP_K];
+#pragma unroll
+  for (int r = 0; r < FI_MOE_MAX_TOP_K; ++r) {
+    sel_v[r] = -INFINITY;
+    sel_i[r] = 0;
+    if (r < A.top_k) {
+      float bv = -INFINITY;
+      int bi = 0x7fffffff;  // no candidate: loses against every expert, also one at -inf
+#pragma unroll
+      for (int s = 0; s < kMoeSlots; ++s)
+        if (!(taken >> s & 1)) moe_better(bv, bi, v[s], lane + 64 * s);
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        const float ov = __shfl_xor(bv, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        moe_better(bv, bi, ov, oi);
+      }
+      // top_k <= num_experts: an untaken expert exists, so bi is one and the same in every lane
+      if ((bi & 63) == lane) taken |= 1u << (bi >> 6);
+      sel_v[r] = bv;
+      sel_i[r] = bi;
+    }
+  }
+  // weights, every lane the same arithmetic; sel_v[0] is the row's maximum
+  const float m = sel_v[0];
+  float w[FI_MOE_MAX_TOP_K];
+  if (A.method == FI_MOE_ROUTING_TOPK) {
+#pragma unroll
+    for (int r = 0; r < FI_MOE_MAX_TOP_K; ++r) w[r] = sel_v[r];
+  } else {
+    float ex[FI_MOE_MAX_TOP_K], chosen = 0.f;
+#pragma unroll
+    for (int r = 0; r < FI_MOE_MAX_TOP_K; ++r) {
+      ex[r] = r < A.top_k ? expf(sel_v[r] - m) : 0.f;
+      chosen += ex[r];
+    }
+    if (A.method == FI_MOE_ROUTING_RENORMALIZE) {
+#pragma unroll
+      for (int r = 0; r < FI_MOE_MAX_TOP_K; ++r) w[r] = ex[r] / chosen;
+    } else {
+      float all = 0.f;
+#pragma unroll
+      for (int s = 0; s < kMoeSlots; ++s) all += lane + 64 * s < E ? expf(v[s] - m) : 0.f;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) all += __shfl_xor(all, off, 64);
+      float p[FI_MOE_MAX_TOP_K], psum = 0.f;
+#pragma unroll
+      for (int r = 0; r < FI_MOE_MAX_TOP_K; ++r) {
+        p[r] = ex[r] / all;
+        psum += p[r];
+      }
+#pragma unroll
+      for (int r = 0; r < FI_MOE_MAX_TOP_K; ++r) w[r] = A.method == FI_MOE_ROUTING_DEFAULT ? p[r] : p[r] / psum;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < FI_MOE_MAX_TOP_K; ++r) {
+    if (r < A.top_k && lane == r) {
+      A.ids[(int64_t)t * A.top_k + r] = sel_i[r];
+      A.weights[(int64_t)t * A.top_k + r] = f32_to_bf16_bits(w[r]);
+    }
+  }
+}
+
+// ---- permute --------------------------------------------------------------------------------------------------------
+struct MoePermuteArgs {
+  const int32_t* ids;
+  const uint8_t* x;
+  const uint8_t* x_sf;
+  int32_t* m_indptr;
+  int32_t* map;
+  uint8_t* x_out;
+  uint8_t* sf_out;
+  uint16_t* weights_out;
+  int32_t* hist;  // [num_blocks, G]: counts, then offsets of the block inside every expert
+  int32_t* p2e;   // [n] expanded index of a permuted row
+  int32_t n, top_k, hidden, nkb;
+  int32_t offset, G, packed;
+  int32_t num_blocks;
+  int32_t sf_rows;
+  int32_t tpr_log2;
+};
+
+// local expert of an entry of topk_ids, -1 when it is not in the window
+__device__ __forceinline__ int moe_local_expert(const MoePermuteArgs& A, int32_t id) {
+  const int e = (A.packed ? (int)((uint32_t)id & 0xffffu) : id) - A.offset;
+  return (e >= 0 && e < A.G) ? e : -1;
+}
+
+__global__ void __launch_bounds__(64) moe_count_kernel(const MoePermuteArgs A) {
+  __shared__ int32_t cnt[FI_MOE_MAX_EXPERTS];
+  const int lane = threadIdx.x;
+  for (int e = lane; e < A.G; e += 64) cnt[e] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * FI_MOE_SORT_BLOCK;
+  for (int step = 0; step < FI_MOE_SORT_BLOCK / 64; ++step) {
+    const int64_t i = base + step * 64 + lane;
+    const int le = i < A.n ? moe_local_expert(A, A.ids[i]) : -1;
+    if (le >= 0) atomicAdd(&cnt[le], 1);
+  }
+  __syncthreads();
+  for (int e = lane; e < A.G; e += 64) A.hist[(int64_t)blockIdx.x * A.G + e] = cnt[e];
+}
+
+__global__ void __launch_bounds__(FI_MOE_MAX_EXPERTS) moe_scan_kernel(const MoePermuteArgs A) {
+  __shared__ int32_t s[FI_MOE_MAX_EXPERTS];
+  const int e = threadIdx.x;
+  int total = 0;
+  if (e < A.G) {
+    for (int b = 0; b < A.num_blocks; ++b) {
+      const int64_t at = (int64_t)b * A.G + e;
+      const int c = A.hist[at];
+      A.hist[at] = total;
+      total += c;
+    }
+  }
+  s[e] = total;
+  __syncthreads();
+  for (int off = 1; off < FI_MOE_MAX_EXPERTS; off <<= 1) {
+    const int add = e >= off ? s[e - off] : 0;
+    __syncthreads();
+    s[e] += add;
+    __syncthreads();
+  }
+  if (e < A.G) A.m_indptr[e] = s[e] - total;
+  if (e == A.G - 1) A.m_indptr[A.G] = s[e];
+}
+
+__global__ void __launch_bounds__(64) moe_place_kernel(const MoePermuteArgs A) {
+  __shared__ int32_t run[FI_MOE_MAX_EXPERTS];  // next permuted row of every expert, for this block
+  const int lane = threadIdx.x;
+  for (int e = lane; e < A.G; e += 64) run[e] = A.m_indptr[e] + A.hist[(int64_t)blockIdx.x * A.G + e];
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * FI_MOE_SORT_BLOCK;
+  for (int step = 0; step < FI_MOE_SORT_BLOCK / 64; ++step) {
+    const int64_t i = base + step * 64 + lane;
+    const int32_t id = i < A.n ? A.ids[i] : -1;
+    const int le = i < A.n ? moe_local_expert(A, id) : -1;
+    int rank = 0, count = 0;
+    unsigned long long todo = __ballot(le >= 0);
+    while (todo) {  // one turn per expert present among the 64
+      const int e0 = __shfl(le, __ffsll((unsigned long long)todo) - 1, 64);
+      const unsigned long long same = __ballot(le == e0);
+      if (le == e0) {
+        rank = __popcll(same & ((1ull << lane) - 1));
+        count = __popcll(same);
+      }
+      todo &= ~same;
+    }
+    const int first = le >= 0 ? run[le] : 0;
+    __syncthreads();  // every lane has read before the last lane of an expert moves its count on
+    if (le >= 0 && rank == count - 1) run[le] = first + count;
+    __syncthreads();
+    if (i < A.n) {
+      const int p = le >= 0 ? first + rank : -1;
+      A.map[i] = p;
+      if (p >= 0 && p < A.n) A.p2e[p] = (int32_t)i;
+      if (A.weights_out) A.weights_out[i] = (uint16_t)((uint32_t)id >> 16);
+    }
+  }
+}
+
+// group of scale row s and the operand row it holds (-1: a padding row); indptr is the LDS copy of m_indptr
+__device__ __forceinline__ int moe_row_of_scale_row(const int32_t* indptr, int G, int64_t s, int cum_m, int& group) {
+  int lo = 0, hi = G;  // invariant: first scale row of lo <= s (< first scale row of hi)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (mx_sf_row_offset(indptr[mid], mid) <= s) lo = mid; else hi = mid;
+  }
+  group = lo;
+  const int begin = indptr[lo], end = indptr[lo + 1];
+  const int64_t r = s - mx_sf_row_offset(begin, lo);
+  return (begin >= 0 && r >= 0 && r < (int64_t)end - begin && begin + r < cum_m) ? (int)(begin + r) : -1;
+}
+
+__device__ __forceinline__ void moe_load_indptr(int32_t* dst, const int32_t* m_indptr, int G) {
+  for (int i = threadIdx.x; i <= G; i += kMoeThreads) dst[i] = m_indptr[i];
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(kMoeThreads) moe_gather_kernel(const MoePermuteArgs A) {
+  __shared__ int32_t indptr[FI_MOE_MAX_EXPERTS + 1];
+  moe_load_indptr(indptr, A.m_indptr, A.G);
+  const int tpr = 1 << A.tpr_log2;
+  const int t = threadIdx.x & (tpr - 1);
+  const int64_t s = (int64_t)blockIdx.x * (kMoeThreads >> A.tpr_log2) + (threadIdx.x >> A.tpr_log2);
+  if (s >= A.sf_rows) return;
+  int group;
+  const int p = moe_row_of_scale_row(indptr, A.G, s, A.n, group);
+  int token = -1;
+  if (p >= 0) {
+    const int i = A.p2e[p];
+    if (i >= 0 && i < A.n) token = i / A.top_k;
+  }
+  const int chunks = A.hidden / 16;  // 16 bytes each; 8 chunks are 128 k elements, one dword of scales
+  for (int c = t; c < chunks; c += tpr) {
+    if (token >= 0)
+      *(u32x4*)(A.x_out + (int64_t)p * A.hidden + c * 16) = *(const u32x4*)(A.x + (int64_t)token * A.hidden + c * 16);
+    if ((c & 7) == 0) {
+      const int kb = c >> 1;  // a multiple of 4
+      uint32_t w = 0;
+      if (token >= 0) w = *(const uint32_t*)(A.x_sf + (int64_t)token * A.nkb + kb);
+      *(uint32_t*)(A.sf_out + mx_sf_offset((int)s, kb, A.nkb)) = w;
+    }
+  }
+}
+
+// ---- gated activation -----------------------------------------------------------------------------------------------
+struct MoeActArgs {
+  const uint16_t* x;
+  const int32_t* m_indptr;
+  const float* bias;
+  const float* alpha;
+  const float* beta;
+  const float* limit;
+  uint8_t* q;
+  uint8_t* sf;
+  int32_t cum_m, inter, nkb, G, sf_rows, tpr_log2;
+};
+
+__global__ void __launch_bounds__(kMoeThreads) moe_gated_act_kernel(const MoeActArgs A) {
+  __shared__ int32_t indptr[FI_MOE_MAX_EXPERTS + 1];
+  moe_load_indptr(indptr, A.m_indptr, A.G);
+  const int tpr = 1 << A.tpr_log2;
+  const int t = threadIdx.x & (tpr - 1);
+  const int64_t s = (int64_t)blockIdx.x * (kMoeThreads >> A.tpr_log2) + (threadIdx.x >> A.tpr_log2);
+  if (s >= A.sf_rows) return;  // whole quads leave: tpr is a multiple of 4
+  int g;
+  const int src = moe_row_of_scale_row(indptr, A.G, s, A.cum_m, g);
+  const float alpha = A.alpha ? A.alpha[g] : 1.f;
+  const float beta = A.beta ? A.beta[g] : 0.f;
+  const float limit = A.limit ? A.limit[g] : INFINITY;
+  const int I = A.inter;
+  const uint16_t* const xr = A.x + (int64_t)max(src, 0) * 2 * I;
+  const float* const br = A.bias ? A.bias + (int64_t)g * 2 * I : nullptr;
+  for (int cc = t; cc < I / 8; cc += tpr) {  // I / 8 is a multiple of 16: the lanes of a quad stay together
+    const int col = cc * 8;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.f;
+    if (src >= 0) {
+      float x1[8], x2[8];
+      load_16bit<FI_DTYPE_BF16, 8>(xr + col, x1);
+      load_16bit<FI_DTYPE_BF16, 8>(xr + I + col, x2);
+      if (br) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const f32x4 b1 = *(const f32x4*)(br + col + 4 * h);
+          const f32x4 b2 = *(const f32x4*)(br + I + col + 4 * h);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            x1[4 * h + j] += b1[j];
+            x2[4 * h + j] += b2[j];
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float gt = fminf(x2[j], limit);
+        const float l = fminf(fmaxf(x1[j], -limit), limit) + beta;
+        v[j] = gt * (1.0f / (1.0f + expf(-alpha * gt))) * l;
+      }
+    }
+    const int e = mx_e4m3_exponent(mx_quad_amax(v));
+    if (src >= 0) *(u32x2*)(A.q + (int64_t)src * I + col) = mx_e4m3_pack8(v, e);
+    if ((cc & 3) == 0) A.sf[mx_sf_offset((int)s, cc >> 2, A.nkb)] = src >= 0 ? (uint8_t)(e + 127) : (uint8_t)0;
+  }
+}
+
+// ---- finalize -------------------------------------------------------------------------------------------------------
+struct MoeFinalizeArgs {
+  const uint16_t* y;
+  const uint16_t* weights;
+  const int32_t* map;
+  const float* bias;
+  const int32_t* m_indptr;
+  uint16_t* out;
+  int32_t num_tokens, top_k, hidden, G, rows, tpr_log2;
+};
+
+__global__ void __launch_bounds__(kMoeThreads) moe_finalize_kernel(const MoeFinalizeArgs A) {
+  __shared__ int32_t indptr[FI_MOE_MAX_EXPERTS + 1];
+  if (A.bias) moe_load_indptr(indptr, A.m_indptr, A.G);
+  const int tpr = 1 << A.tpr_log2;
+  const int t = threadIdx.x & (tpr - 1);
+  const int64_t token = (int64_t)blockIdx.x * (kMoeThreads >> A.tpr_log2) + (threadIdx.x >> A.tpr_log2);
+  if (token >= A.num_tokens) return;
+  int rows[FI_MOE_MAX_TOP_K], groups[FI_MOE_MAX_TOP_K];
+  float w[FI_MOE_MAX_TOP_K];
+#pragma unroll
+  for (int j = 0; j < FI_MOE_MAX_TOP_K; ++j) {
+    rows[j] = -1;
+    groups[j] = 0;
+    w[j] = 0.f;
+    if (j < A.top_k) {
+      const int p = A.map[token * A.top_k + j];
+      if (p >= 0 && p < A.rows) {
+        rows[j] = p;
+        w[j] = __builtin_bit_cast(float, (uint32_t)A.weights[token * A.top_k + j] << 16);
+        if (A.bias) {
+          int lo = 0, hi = A.G;  // the last group whose first row is <= p
+          while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (indptr[mid] <= p) lo = mid; else hi = mid;
+          }
+          groups[j] = lo;
+        }
+      }
+    }
+  }
+  for (int c = t; c < A.hidden / 8; c += tpr) {
+    const int col = c * 8;
+    float acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < FI_MOE_MAX_TOP_K; ++j) {
+      if (rows[j] >= 0) {
+        float yv[8];
+        load_16bit<FI_DTYPE_BF16, 8>(A.y + (int64_t)rows[j] * A.hidden + col, yv);
+        if (A.bias) {
+          const float* const b = A.bias + (int64_t)groups[j] * A.hidden + col;
+          const f32x4 b0 = *(const f32x4*)b, b1 = *(const f32x4*)(b + 4);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            yv[i] += b0[i];
+            yv[4 + i] += b1[i];
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = __builtin_fmaf(w[j], yv[i], acc[i]);
+      }
+    }
+    store_16bit<FI_DTYPE_BF16, 8>(A.out + token * A.hidden + col, acc);
+  }
+}
+
+// threads per row: a power of two from one quad to the workgroup, enough for the row's chunks when it can be
+static int moe_tpr_log2(int64_t chunks) {
+  int l = 2;
+  while ((1 << l) < kMoeThreads && (1ll << l) < chunks) ++l;
+  return l;
+}
+
+static bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p % a) == 0; }
+
+}  // namespace fi
+
+using namespace fi;
+
+extern "C" FI_API int fi_moe_route(const fi_moe_route_params_t* p, fi_stream_t stream) {
+  FI_REQUIRE(p, "moe_route: null params");
+  FI_REQUIRE(p->num_tokens >= 0 && p->num_experts >= 0 && p->top_k >= 0,
+             "moe_route: negative size (num_tokens %d, num_experts %d, top_k %d)", p->num_tokens, p->num_experts, p->top_k);
+  FI_REQUIRE(p->num_experts >= 1 && p->num_experts <= FI_MOE_MAX_EXPERTS, "moe_route: num_experts %d is not in [1, %d]",
+             p->num_experts, FI_MOE_MAX_EXPERTS);
+  FI_REQUIRE(p->top_k >= 1 && p->top_k <= FI_MOE_MAX_TOP_K && p->top_k <= p->num_experts,
+             "moe_route: top_k %d is not in [1, min(%d, num_experts %d)]", p->top_k, FI_MOE_MAX_TOP_K, p->num_experts);
+  FI_REQUIRE(p->method == FI_MOE_ROUTING_DEFAULT || p->method == FI_MOE_ROUTING_RENORMALIZE ||
+                 p->method == FI_MOE_ROUTING_RENORMALIZE_NAIVE || p->method == FI_MOE_ROUTING_TOPK,
+             "moe_route: routing method %d is not provided", p->method);
+  FI_REQUIRE(p->dtype == FI_DTYPE_F32 || p->dtype == FI_DTYPE_BF16, "moe_route: dtype %d is not f32 or bf16", p->dtype);
+  if (p->num_tokens == 0) return 0;
+  FI_REQUIRE(p->logits && p->topk_ids && p->topk_weights, "moe_route: null tensor");
+  MoeRouteArgs a{p->logits, p->topk_ids, p->topk_weights, p->num_tokens, p->num_experts, p->top_k, p->method};
+  const uint32_t grid = (uint32_t)ceil_div<int64_t>(p->num_tokens, kMoeThreads / 64);
+  if (p->dtype == FI_DTYPE_F32)
+    moe_route_kernel<FI_DTYPE_F32><<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
+  else
+    moe_route_kernel<FI_DTYPE_BF16><<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}
+
+extern "C" FI_API int fi_moe_permute_mxfp8(const fi_moe_permute_params_t* p, fi_stream_t stream) {
+  FI_REQUIRE(p, "moe_permute_mxfp8: null params");
+  FI_REQUIRE(p->num_tokens >= 0 && p->top_k >= 0 && p->hidden >= 0 && p->local_num_experts >= 0 && p->local_expert_offset >= 0,
+             "moe_permute_mxfp8: negative size (num_tokens %d, top_k %d, hidden %d, local_expert_offset %d, "
+             "local_num_experts %d)", p->num_tokens, p->top_k, p->hidden, p->local_expert_offset, p->local_num_experts);
+  FI_REQUIRE(p->local_num_experts >= 1 && p->local_num_experts <= FI_MOE_MAX_EXPERTS,
+             "moe_permute_mxfp8: local_num_experts %d is not in [1, %d]", p->local_num_experts, FI_MOE_MAX_EXPERTS);
+  FI_REQUIRE(p->top_k >= 1 && p->top_k <= FI_MOE_MAX_TOP_K, "moe_permute_mxfp8: top_k %d is not in [1, %d]", p->top_k,
+             FI_MOE_MAX_TOP_K);
+  FI_REQUIRE(p->hidden > 0 && p->hidden % 128 == 0, "moe_permute_mxfp8: hidden %d must be a positive multiple of 128",
+             p->hidden);
+  if (p->num_tokens == 0) return 0;
+  const int64_t n = (int64_t)p->num_tokens * p->top_k;
+  const int64_t G = p->local_num_experts;
+  const int64_t sf_rows = mx_sf_row_offset(n, G);
+  FI_REQUIRE(sf_rows < (1ll << 31), "moe_permute_mxfp8: too many rows");
+  FI_REQUIRE(p->topk_ids && p->x && p->x_sf && p->m_indptr && p->expanded_to_permuted && p->x_permuted && p->sf_permuted &&
+                 p->workspace, "moe_permute_mxfp8: null tensor");
+  FI_REQUIRE(aligned(p->x, 16) && aligned(p->x_permuted, 16) && aligned(p->x_sf, 4) && aligned(p->sf_permuted, 4),
+             "moe_permute_mxfp8: x and x_permuted must be 16-byte aligned, x_sf and sf_permuted 4-byte aligned");
+  const int64_t nkb = p->hidden / kMxBlock;
+  FI_REQUIRE(p->sf_bytes >= sf_rows * nkb, "moe_permute_mxfp8: sf_permuted holds %lld bytes, %lld needed",
+             (long long)p->sf_bytes, (long long)(sf_rows * nkb));
+  const int64_t num_blocks = ceil_div<int64_t>(n, FI_MOE_SORT_BLOCK);
+  const int64_t ws_need = (num_blocks * G + n) * 4;
+  FI_REQUIRE(p->workspace_bytes >= ws_need, "moe_permute_mxfp8: workspace holds %lld bytes, %lld needed",
+             (long long)p->workspace_bytes, (long long)ws_need);
+  MoePermuteArgs a{};
+  a.ids = p->topk_ids;
+  a.x = (const uint8_t*)p->x;
+  a.x_sf = (const uint8_t*)p->x_sf;
+  a.m_indptr = p->m_indptr;
+  a.map = p->expanded_to_permuted;
+  a.x_out = (uint8_t*)p->x_permuted;
+  a.sf_out = (uint8_t*)p->sf_permuted;
+  a.weights_out = p->packed ? p->unpacked_weights : nullptr;
+  a.hist = p->workspace;
+  a.p2e = p->workspace + num_blocks * G;
+  a.n = (int32_t)n;
+  a.top_k = p->top_k;
+  a.hidden = p->hidden;
+  a.nkb = (int32_t)nkb;
+  a.offset = p->local_expert_offset;
+  a.G = (int32_t)G;
+  a.packed = p->packed != 0;
+  a.num_blocks = (int32_t)num_blocks;
+  a.sf_rows = (int32_t)sf_rows;
+  a.tpr_log2 = moe_tpr_log2(p->hidden / 16);
+  hipStream_t st = (hipStream_t)stream;
+  moe_count_kernel<<<dim3((uint32_t)num_blocks), dim3(64), 0, st>>>(a);
+  moe_scan_kernel<<<dim3(1), dim3(FI_MOE_MAX_EXPERTS), 0, st>>>(a);
+  moe_place_kernel<<<dim3((uint32_t)num_blocks), dim3(64), 0, st>>>(a);
+  const uint32_t grid = (uint32_t)ceil_div<int64_t>(sf_rows, kMoeThreads >> a.tpr_log2);
+  moe_gather_kernel<<<dim3(grid), dim3(kMoeThreads), 0, st>>>(a);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}
+
+extern "C" FI_API int fi_moe_gated_act_mxfp8(const fi_moe_gated_act_params_t* p, fi_stream_t stream) {
+  FI_REQUIRE(p, "moe_gated_act_mxfp8: null params");
+  FI_REQUIRE(p->cum_m >= 0 && p->intermediate >= 0 && p->num_groups >= 0,
+             "moe_gated_act_mxfp8: negative size (cum_m %d, intermediate %d, num_groups %d)", p->cum_m, p->intermediate,
+             p->num_groups);
+  FI_REQUIRE(p->num_groups >= 1 && p->num_groups <= FI_MOE_MAX_EXPERTS, "moe_gated_act_mxfp8: num_groups %d is not in [1, %d]",
+             p->num_groups, FI_MOE_MAX_EXPERTS);
+  FI_REQUIRE(p->intermediate > 0 && p->intermediate % 128 == 0,
+             "moe_gated_act_mxfp8: intermediate %d must be a positive multiple of 128", p->intermediate);
+  if (p->cum_m == 0) return 0;
+  const int64_t sf_rows = mx_sf_row_offset(p->cum_m, p->num_groups);
+  FI_REQUIRE(sf_rows < (1ll << 31), "moe_gated_act_mxfp8: too many rows");
+  FI_REQUIRE(p->x && p->m_indptr && p->q && p->sf, "moe_gated_act_mxfp8: null tensor");
+  FI_REQUIRE(aligned(p->x, 16) && aligned(p->q, 8) && (!p->bias || aligned(p->bias, 16)),
+             "moe_gated_act_mxfp8: x and bias must be 16-byte aligned, q 8-byte aligned");
+  const int64_t nkb = p->intermediate / kMxBlock;
+  FI_REQUIRE(p->sf_bytes >= sf_rows * nkb, "moe_gated_act_mxfp8: sf holds %lld bytes, %lld needed", (long long)p->sf_bytes,
+             (long long)(sf_rows * nkb));
+  MoeActArgs a{};
+  a.x = (const uint16_t*)p->x;
+  a.m_indptr = p->m_indptr;
+  a.bias = p->bias;
+  a.alpha = p->alpha;
+  a.beta = p->beta;
+  a.limit = p->limit;
+  a.q = (uint8_t*)p->q;
+  a.sf = (uint8_t*)p->sf;
+  a.cum_m = p->cum_m;
+  a.inter = p->intermediate;
+  a.nkb = (int32_t)nkb;
+  a.G = p->num_groups;
+  a.sf_rows = (int32_t)sf_rows;
+  a.tpr_log2 = moe_tpr_log2(p->intermediate / 8);
+  const uint32_t grid = (uint32_t)ceil_div<int64_t>(sf_rows, kMoeThreads >> a.tpr_log2);
+  moe_gated_act_kernel<<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}
+
+extern "C" FI_API int fi_moe_finalize(const fi_moe_finalize_params_t* p, fi_stream_t stream) {
+  FI_REQUIRE(p, "moe_finalize: null params");
+  FI_REQUIRE(p->num_tokens >= 0 && p->top_k >= 0 && p->hidden >= 0 && p->num_groups >= 0 && p->rows >= 0,
+             "moe_finalize: negative size (num_tokens %d, top_k %d, hidden %d, num_groups %d, rows %d)", p->num_tokens,
+             p->top_k, p->hidden, p->num_groups, p->rows);
+  FI_REQUIRE(p->top_k >= 1 && p->top_k <= FI_MOE_MAX_TOP_K, "moe_finalize: top_k %d is not in [1, %d]", p->top_k,
+             FI_MOE_MAX_TOP_K);
+  FI_REQUIRE(p->hidden > 0 && p->hidden % 8 == 0, "moe_finalize: hidden %d must be a positive multiple of 8", p->hidden);
+  FI_REQUIRE(!p->bias || (p->num_groups >= 1 && p->num_groups <= FI_MOE_MAX_EXPERTS),
+             "moe_finalize: num_groups %d is not in [1, %d]", p->num_groups, FI_MOE_MAX_EXPERTS);
+  if (p->num_tokens == 0) return 0;
+  FI_REQUIRE(p->weights && p->expanded_to_permuted && p->out && (p->rows == 0 || p->y), "moe_finalize: null tensor");
+  FI_REQUIRE(!p->bias || p->m_indptr, "moe_finalize: null tensor (m_indptr is needed with a bias)");
+  FI_REQUIRE(aligned(p->y, 16) && aligned(p->out, 16) && aligned(p->bias, 16),
+             "moe_finalize: y, out and bias must be 16-byte aligned");
+  MoeFinalizeArgs a{};
+  a.y = (const uint16_t*)p->y;
+  a.weights = p->weights;
+  a.map = p->expanded_to_permuted;
+  a.bias = p->bias;
+  a.m_indptr = p->m_indptr;
+  a.out = (uint16_t*)p->out;
+  a.num_tokens = p->num_tokens;
+  a.top_k = p->top_k;
+  a.hidden = p->hidden;
+  a.G = p->num_groups;
+  a.rows = p->rows;
+  a.tpr_log2 = moe_tpr_log2(p->hidden / 8);
+  const uint32_t grid = (uint32_t)ceil_div<int64_t>(p->num_tokens, kMoeThreads >> a.tpr_log2);
+  moe_finalize_kernel<<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}

@@ -2,12 +2,12 @@
 // ref: cvt_warp_fp16_to_mxfp8, csrc/nv_internal/tensorrt_llm/kernels/quantization.cuh:586-647; Python
 // flashinfer/fp8_quantization.py:179-212.
 //
-// Rule.  Per block of 32: amax = max |x|; e = the smallest integer in [-127, 127] with 448 . 2^e >= amax (amax = 0:
-// e = -127); scale byte = e + 127; q = e4m3(x . 2^-e), round to nearest even.  The multiplication by a power of two
-// is exact and |x . 2^-e| <= 448, so the conversion never saturates.  e is read off the f32 bits of amax = f . 2^E,
-// 1 <= f < 2: 448 = 1.75 . 2^8, so e = E - 8 when f <= 1.75 (mantissa field <= 0x600000) and E - 7 otherwise -- an
-// integer compare, no log2.  (The reference multiplies by an approximate reciprocal of 448 and rounds the quotient's
-// exponent up; at amax exactly 448 . 2^e its hardware may give e + 1.  The compare here is exact: see fi_mi355.h.)
+// Rule (the device code is mx_quant.h, shared with the MoE layer's gated activation).  Per block of 32: amax = max |x|;
+// e = the smallest integer in [-127, 127] with 448 . 2^e >= amax (amax = 0: e = -127); scale byte = e + 127;
+// q = e4m3(x . 2^-e), round to nearest even.  The multiplication by a power of two is exact and |x . 2^-e| <= 448, so
+// the conversion never saturates.  (The reference multiplies by an approximate reciprocal of 448 and rounds the
+// quotient's exponent up; at amax exactly 448 . 2^e its hardware may give e + 1.  The compare here is exact: see
+// fi_mi355.h.)
 //
 // Shape.  One pass: a thread owns 8 consecutive elements (one 16-byte load, one 8-byte store), the 4 threads of a
 // block of 32 are the 4 lanes of a quad and share amax by two quad-permute moves.  The kernel is indexed by the rows
@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "mx_layout.h"
+#include "mx_quant.h"
 
 namespace fi {
 
@@ -75,28 +76,8 @@ __global__ void __launch_bounds__(kMxQuantThreads) mxfp8_quantize_kernel(const M
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = 0.f;
     if (src >= 0 && col < A.k) load_16bit<DT, 8>(xr + col, v);
-    float amax = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
-    amax = fmaxf(amax, lane_xor<1>(amax));
-    amax = fmaxf(amax, lane_xor<2>(amax));
-    const uint32_t bits = __builtin_bit_cast(uint32_t, amax);
-    int e = (int)(bits >> 23) - 127 - 8 + ((bits & 0x7fffffu) > 0x600000u ? 1 : 0);
-    e = min(max(e, -127), 127);
-    const float scale = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);  // 2^-e; e <= 120 for 16-bit inputs
-    if (src >= 0 && col < A.k_pad) {
-      uint32_t w[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        float y[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) y[j] = __builtin_amdgcn_fmed3f(v[4 * h + j] * scale, -448.f, 448.f);
-        int packed = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-        packed = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], packed, true);
-        w[h] = (uint32_t)packed;
-      }
-      *(u32x2*)(A.q + (int64_t)src * A.k_pad + col) = u32x2{w[0], w[1]};
-    }
+    const int e = mx_e4m3_exponent(mx_quad_amax(v));
+    if (src >= 0 && col < A.k_pad) *(u32x2*)(A.q + (int64_t)src * A.k_pad + col) = mx_e4m3_pack8(v, e);
     if (s >= 0 && (cc & 3) == 0) {
       const int kb = cc >> 2;
       const int64_t pos = A.swizzled ? mx_sf_offset((int)s, kb, A.nkb) : s * A.nkb + kb;

@@ -1,6 +1,6 @@
 """flashinfer -- MI355X (gfx950) native implementation of FlashInfer's paged-KV attention hot path.
 
-Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / sparse / gemm / fp8_quantization / fp4_quantization / sampling / norm / activation`` operator API
+Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / sparse / gemm / fused_moe / fp8_quantization / fp4_quantization / sampling / norm / activation`` operator API
 of FlashInfer v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-written HIP kernels behind the C ABI of
 ``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided.
 """
@@ -8,6 +8,7 @@ from . import _lib as _lib
 from . import activation as activation
 from . import fp4_quantization as fp4_quantization
 from . import fp8_quantization as fp8_quantization
+from . import fused_moe as fused_moe
 from . import mla as mla
 from . import norm as norm
 from . import sampling as sampling
@@ -48,6 +49,12 @@ from .fp4_quantization import mxfp4_quantize_grouped as mxfp4_quantize_grouped
 from .fp4_quantization import nvfp4_block_scale_interleave as nvfp4_block_scale_interleave
 from .fp8_quantization import mxfp8_dequantize_host as mxfp8_dequantize_host
 from .fp8_quantization import mxfp8_quantize as mxfp8_quantize
+from .fused_moe import GatedActType as GatedActType
+from .fused_moe import RoutingMethodType as RoutingMethodType
+from .fused_moe import trtllm_fp4_block_scale_moe as trtllm_fp4_block_scale_moe
+from .fused_moe import (
+    trtllm_fp4_block_scale_routed_moe as trtllm_fp4_block_scale_routed_moe,
+)
 from .gemm import gemm_fp8_nt_groupwise as gemm_fp8_nt_groupwise
 from .gemm import group_gemm_fp8_nt_groupwise as group_gemm_fp8_nt_groupwise
 from .mla import BatchMLAPagedAttentionWrapper as BatchMLAPagedAttentionWrapper

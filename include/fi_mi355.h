@@ -1,7 +1,8 @@
 /*
  * fi_mi355.h -- C ABI of libfi_mi355.so, the MI355X (gfx950) implementation of FlashInfer's
  * batch paged-KV attention hot path (decode / prefill / cascade merge / page append), the fp8
- * groupwise (grouped) GEMM, the sampling operators and the norm / gated-activation operators.
+ * groupwise (grouped) GEMM, the sampling operators, the norm / gated-activation operators, the MX quantisers with the
+ * MXFP4-weight grouped GEMM, and the MoE layer built on it.
  *
  * Every entry point replaces one TVM-FFI export of the reference (FlashInfer v0.3.1); the export it
  * stands in for is cited as `ref: file:line` (paths relative to the reference checkout).  The
@@ -839,6 +840,115 @@ typedef struct fi_mx_sf_interleave_params {
 } fi_mx_sf_interleave_params_t;
 
 FI_API int fi_mx_sf_interleave(const fi_mx_sf_interleave_params_t* params, fi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mixture-of-experts layer with MXFP8 activations and MXFP4 weights (csrc/moe.hip): the four stages around the two
+ * launches of fi_group_gemm_mxfp8_mxfp4_nt_groupwise.  ref: trtllm_fp4_block_scale_moe, flashinfer/fused_moe/core.py
+ * :1819-1948 (its MXFP8 x MXFP4 mode); routing methods core.py:62-76; the permutation is routing_reference with
+ * padding 1, tests/moe/test_trtllm_gen_fused_moe.py:1083-1142; the activation compute_with_experts,
+ * tests/moe/test_trtllm_cutlass_fused_moe.py:195-203.  The stages have no counterpart of their own in the reference,
+ * which runs the layer as one call.
+ *   route -> permute -> GEMM1 -> gated activation -> GEMM2 -> finalize
+ * No entry point keeps host state, reads a device value on the host or synchronises: all may be captured into a graph.
+ * Every buffer's size depends on shapes alone.  An empty problem (num_tokens == 0) returns 0 without a launch.
+ * Tensors are contiguous.  Expert e is local iff local_expert_offset <= e < local_expert_offset + local_num_experts;
+ * expanded index i = t * top_k + j is slot j of token t.
+ * ---------------------------------------------------------------------------------------------- */
+#define FI_MOE_MAX_EXPERTS 512
+#define FI_MOE_MAX_TOP_K 8
+#define FI_MOE_SORT_BLOCK 256 /* expanded indices ranked by one wave of the permutation (sizes its workspace) */
+
+/* the reference's RoutingMethodType values of the methods provided (core.py:62-76) */
+enum fi_moe_routing {
+  FI_MOE_ROUTING_DEFAULT = 0,           /* softmax over all experts -> top-k */
+  FI_MOE_ROUTING_RENORMALIZE = 1,       /* top-k -> softmax over the chosen logits */
+  FI_MOE_ROUTING_RENORMALIZE_NAIVE = 4, /* softmax -> top-k -> divide by the sum of the chosen */
+  FI_MOE_ROUTING_TOPK = 5               /* top-k, the weight is the logit itself */
+};
+
+/* Slot j of token t is the expert of the j-th largest logit; equal logits go to the lower expert index (softmax is
+ * monotone, so the methods that take the top-k of the probabilities choose the same experts).  Weights are computed
+ * in f32 and rounded once to bf16.  NaN logits count as -inf.  1 <= top_k <= min(8, num_experts), num_experts <= 512. */
+typedef struct fi_moe_route_params {
+  const void* logits;     /* [num_tokens, num_experts] f32 / bf16 */
+  int32_t* topk_ids;      /* out [num_tokens, top_k] */
+  uint16_t* topk_weights; /* out [num_tokens, top_k] bf16 */
+  int32_t num_tokens, num_experts, top_k;
+  int32_t method; /* enum fi_moe_routing */
+  int32_t dtype;  /* FI_DTYPE_F32 / FI_DTYPE_BF16 */
+} fi_moe_route_params_t;
+
+FI_API int fi_moe_route(const fi_moe_route_params_t* params, fi_stream_t stream);
+
+/* Sorts the expanded indices by local expert and gathers the MXFP8 rows into the grouped GEMM's row operand.
+ *   m_indptr[g] = number of slots routed to a local expert below local_expert_offset + g      (G = local_num_experts)
+ *   expanded_to_permuted[i] = m_indptr[g] + the number of i' < i routed to the same expert g; -1 for a non-local slot
+ *   x_permuted[p] = x[i / top_k] and its scale bytes at scale row sf_off(g) + p - m_indptr[g] of the grouped swizzled
+ *   layout (above), for p = expanded_to_permuted[i] >= 0
+ * so within an expert the rows ascend by expanded index and experts follow one another without padding rows.  The
+ * result is deterministic: counts per block of FI_MOE_SORT_BLOCK indices, a scan over the blocks, a stable rank inside
+ * the block; no atomic decides a placement.  EVERY byte of sf_permuted (sf_off(G) rows with num_tokens * top_k as cum_m)
+ * is written, padding as 0; rows of x_permuted at or past m_indptr[G] are not written.  Four launches.
+ * packed != 0: the low 16 bits of a topk_ids entry are the expert, the high 16 bits the bf16 weight (ref: topk_ids of
+ * trtllm_fp4_block_scale_routed_moe, core.py:1987-1990), copied to unpacked_weights when that is given.
+ * workspace: int32, at least (ceil(n / FI_MOE_SORT_BLOCK) * G + n) * 4 bytes with n = num_tokens * top_k.
+ * hidden % 128 == 0; x, x_permuted 16-byte aligned; x_sf, sf_permuted 4-byte aligned. */
+typedef struct fi_moe_permute_params {
+  const int32_t* topk_ids;        /* [num_tokens, top_k] */
+  const void* x;                  /* [num_tokens, hidden] e4m3 */
+  const void* x_sf;               /* [num_tokens, hidden / 32] E8M0 bytes, linear */
+  int32_t* m_indptr;              /* out [local_num_experts + 1] */
+  int32_t* expanded_to_permuted;  /* out [num_tokens * top_k] */
+  void* x_permuted;               /* out [num_tokens * top_k, hidden] */
+  void* sf_permuted;              /* out, grouped swizzled */
+  uint16_t* unpacked_weights;     /* optional out [num_tokens, top_k] bf16, packed ids only */
+  int32_t* workspace;
+  int64_t sf_bytes, workspace_bytes; /* sizes of sf_permuted and workspace */
+  int32_t num_tokens, top_k, hidden;
+  int32_t local_expert_offset, local_num_experts;
+  int32_t packed;
+} fi_moe_permute_params_t;
+
+FI_API int fi_moe_permute_mxfp8(const fi_moe_permute_params_t* params, fi_stream_t stream);
+
+/* Gated activation between the two GEMMs, quantised to MXFP8 for the second.  For row r of group g (m_indptr[g] <= r <
+ * m_indptr[g+1]) and column c < intermediate, with x1 = x[r, c] (the linear half) and x2 = x[r, intermediate + c] (the
+ * gate), all in f32:
+ *   gt = min(x2 + bias[g, intermediate + c], limit[g]);  l = clamp(x1 + bias[g, c], -limit[g], limit[g]) + beta[g]
+ *   act = gt * sigmoid(alpha[g] * gt) * l
+ * bias / alpha / beta / limit == NULL mean 0 / 1 / 0 / +inf.  q and sf follow the rule of fi_mxfp8_quantize (the same
+ * device code, csrc/mx_quant.h) in the grouped swizzled layout: EVERY byte of sf (sf_off(num_groups) rows with cum_m)
+ * is written, padding as 0; rows of q at or past m_indptr[num_groups] are not written.  intermediate % 128 == 0. */
+typedef struct fi_moe_gated_act_params {
+  const void* x;           /* [cum_m, 2 * intermediate] bf16 */
+  const int32_t* m_indptr; /* [num_groups + 1] device */
+  const float* bias;       /* optional [num_groups, 2 * intermediate] */
+  const float* alpha;      /* optional [num_groups] */
+  const float* beta;       /* optional [num_groups] */
+  const float* limit;      /* optional [num_groups] */
+  void* q;                 /* out [cum_m, intermediate] e4m3 */
+  void* sf;                /* out, grouped swizzled */
+  int64_t sf_bytes;        /* size of sf */
+  int32_t cum_m, intermediate, num_groups;
+} fi_moe_gated_act_params_t;
+
+FI_API int fi_moe_gated_act_mxfp8(const fi_moe_gated_act_params_t* params, fi_stream_t stream);
+
+/* out[t] = bf16(sum_j w[t, j] * (y[p(t, j)] + bias[g(t, j)])) over the slots with 0 <= p(t, j) =
+ * expanded_to_permuted[t * top_k + j] < rows, accumulated in f32 in the order of j; a token without such a slot gets
+ * zeros.  g is the group whose m_indptr range holds p; bias == NULL is 0 and then m_indptr may be NULL too.
+ * hidden % 8 == 0; y, out and bias 16-byte aligned. */
+typedef struct fi_moe_finalize_params {
+  const void* y;                       /* [rows, hidden] bf16 */
+  const uint16_t* weights;             /* [num_tokens, top_k] bf16 */
+  const int32_t* expanded_to_permuted; /* [num_tokens * top_k] */
+  const float* bias;                   /* optional [num_groups, hidden] */
+  const int32_t* m_indptr;             /* [num_groups + 1] device, needed with bias */
+  void* out;                           /* [num_tokens, hidden] bf16 */
+  int32_t num_tokens, top_k, hidden, num_groups, rows;
+} fi_moe_finalize_params_t;
+
+FI_API int fi_moe_finalize(const fi_moe_finalize_params_t* params, fi_stream_t stream);
 
 #ifdef __cplusplus
 }
