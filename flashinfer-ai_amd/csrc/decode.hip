@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "decode_kernel.h"
+#include "decode_plan.h"
 #include "merge_kernel.h"
 
 namespace fi {
@@ -190,6 +191,25 @@ static DecodeWork estimate_decode_work(const int32_t* indptr_h, int batch_size, 
   return {new_batch != (uint32_t)batch_size, pages_per_chunk, new_batch};
 }
 
+// The plan sizes the grid for the kernel a plain run() gets (no RoPE, plain logits, strides that fit).  A run()
+// that ends up on another kernel (RoPE, ALiBi, soft cap, wide strides) still works on this plan: the work list
+// holds (request, chunk) pairs only, and run() derives num_items = padded x kv heads x its own head_tiles.
+DecodeGridShape decode_grid_shape(int num_qo_heads, int num_kv_heads, int head_dim, int page_size, int q_dtype,
+                                  int kv_dtype, int max_grid_hint) {
+  const int head_tiles = choose_decode(num_qo_heads / num_kv_heads, q_dtype, kv_dtype, head_dim, page_size,
+                                       /*rope=*/false, /*plain_logits=*/true, /*strides_fit_31_bits=*/true)
+                             .head_tiles;
+  const uint32_t gdy = (uint32_t)(num_kv_heads * head_tiles);
+  // head tiles of one kv head stream the same rows (the partner wave's loads hit in L2), so a multi-tile
+  // launch is sized for twice the waves: measured 4.42 vs 3.73 TB/s at Hq/Hkv = 64/8 (r1)
+  const uint32_t max_grid =
+      max_grid_hint > 0 ? (uint32_t)max_grid_hint
+                        : (uint32_t)(fi_num_compute_units() * decode_waves_per_cu(kv_dtype, true) * (head_tiles > 1 ? 2 : 1));
+  return {gdy, max_grid};
+}
+
+bool decode_kernel_exists(int kv_dtype, int head_dim) { return find_launcher(kv_dtype, head_dim) != nullptr; }
+
 }  // namespace fi
 
 using namespace fi;
@@ -214,18 +234,8 @@ extern "C" FI_API int fi_batch_decode_plan(void* float_ws, size_t float_ws_bytes
   for (int i = 0; i < batch_size; ++i)
     FI_REQUIRE(indptr_h[i + 1] >= indptr_h[i], "batch_decode_plan: indptr must be non-decreasing");
 
-  // The plan sizes the grid for the kernel a plain run() gets (no RoPE, plain logits, strides that fit).  A run()
-  // that ends up on another kernel (RoPE, ALiBi, soft cap, wide strides) still works on this plan: the work list
-  // holds (request, chunk) pairs only, and run() derives num_items = padded x kv heads x its own head_tiles.
-  const int head_tiles = choose_decode(num_qo_heads / num_kv_heads, q_dtype, kv_dtype, head_dim, page_size,
-                                       /*rope=*/false, /*plain_logits=*/true, /*strides_fit_31_bits=*/true)
-                             .head_tiles;
-  const uint32_t gdy = (uint32_t)(num_kv_heads * head_tiles);
-  // head tiles of one kv head stream the same rows (the partner wave's loads hit in L2), so a multi-tile
-  // launch is sized for twice the waves: measured 4.42 vs 3.73 TB/s at Hq/Hkv = 64/8 (r1)
-  const uint32_t max_grid =
-      max_grid_hint > 0 ? (uint32_t)max_grid_hint
-                        : (uint32_t)(fi_num_compute_units() * decode_waves_per_cu(kv_dtype, true) * (head_tiles > 1 ? 2 : 1));
+  const auto [gdy, max_grid] =
+      decode_grid_shape(num_qo_heads, num_kv_heads, head_dim, page_size, q_dtype, kv_dtype, max_grid_hint);
 
   if (window_left < 0) window_left = -1;
   const auto [split_kv, pages_per_chunk, padded] =

@@ -1,8 +1,9 @@
-"""Decode attention operators: ``single_decode_with_kv_cache`` and
-``BatchDecodeWithPagedKVCacheWrapper`` (plan / run split).
+"""Decode attention operators: ``single_decode_with_kv_cache``,
+``BatchDecodeWithPagedKVCacheWrapper`` (plan / run split) and the plan-free
+``trtllm_batch_decode_with_kv_cache`` (the work list is planned on the device).
 
 Same names, arguments, defaults and error behaviour as the reference's ``flashinfer/decode.py``
-(single :389-578; wrapper :581-1410; CUDA-graph wrapper :1413-1480), with the JIT module layer
+(single :389-578; wrapper :581-1410; CUDA-graph wrapper :1413-1480; plan-free :2054-2071), with the JIT module layer
 replaced by the ahead-of-time C ABI of libfi_mi355.so.  The kernels are csrc/decode_kernel.h.
 """
 from __future__ import annotations
@@ -27,6 +28,7 @@ from .utils import (
     _resolve_logits_params,
     _unpack_paged_kv_cache,
     canonicalize_qkv_dtypes,
+    canonicalize_torch_dtype,
     check_shape_dtype_device,
     dense_kv_dims,
     paged_kv,
@@ -506,3 +508,160 @@ class CUDAGraphBatchDecodeWithPagedKVCacheWrapper(BatchDecodeWithPagedKVCacheWra
             paged_kv_indices_buffer=indices_buffer,
             paged_kv_last_page_len_buffer=last_page_len_buffer,
         )
+
+
+def _device_plan_regions(workspace_buffer: torch.Tensor, plan: "_lib.fi_batch_decode_plan_device_params_t"):
+    """Carve the int region (work list and CSR page table) and the float region (f32 partial states) a device plan
+    needs out of one workspace buffer, and write both into ``plan``.  ValueError, with the bytes needed, when the buffer
+    is too small."""
+    int_bytes, float_bytes = C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.lib().fi_batch_decode_plan_device_workspace(C.byref(plan), C.byref(int_bytes), C.byref(float_bytes)),
+               "trtllm_batch_decode_with_kv_cache")
+    base, have = workspace_buffer.data_ptr(), _lib.nbytes(workspace_buffer)
+    int_begin = -base % 16  # both regions 16-byte aligned, whatever the buffer's own alignment
+    float_begin = int_begin + (int_bytes.value + 15) // 16 * 16
+    need = float_begin + float_bytes.value
+    if need > have:
+        raise ValueError(f"workspace_buffer is too small: {have} bytes given, {need} bytes needed "
+                         f"({int_bytes.value} for the work list and page table, {float_bytes.value} for partial states)")
+    plan.int_ws, plan.int_ws_bytes = base + int_begin, int_bytes.value
+    plan.float_ws, plan.float_ws_bytes = base + float_begin, have - float_begin
+
+
+def trtllm_batch_decode_with_kv_cache(
+    query: torch.Tensor,
+    kv_cache: Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]],
+    workspace_buffer: torch.Tensor,
+    block_tables: torch.Tensor,
+    seq_lens: torch.Tensor,
+    max_seq_len: int,
+    bmm1_scale: float,
+    bmm2_scale: float,
+    window_left: int = -1,
+    out: Optional[torch.Tensor] = None,
+    out_dtype: Optional[Union[torch.dtype, str]] = None,
+    o_sf_scale: Optional[float] = None,
+    o_sf_vec_size: Optional[int] = None,
+    sinks: Optional[List[torch.Tensor]] = None,
+    enable_pdl: bool = None,
+    q_len_per_req: Optional[int] = 1,
+) -> torch.Tensor:
+    r"""Plan-free batch decode over a paged KV cache (ref: flashinfer/decode.py:2054-2071): a dense block table and
+    device-resident lengths instead of ``plan()``.  The split-KV work list is built by kernels on the current stream
+    (fi_batch_decode_plan_device), then the kernels of :class:`BatchDecodeWithPagedKVCacheWrapper` run on it.  There
+    is no host synchronisation and no allocation that depends on a length, so the whole call can be captured in a
+    graph; a replay plans again from what ``block_tables`` and ``seq_lens`` hold then.
+
+    query : ``[batch_size, num_qo_heads, head_dim]``, float16 or bfloat16.
+    kv_cache : one tensor ``[num_pages, 2, num_kv_heads, page_size, head_dim]`` (the HND layout), or a ``(k, v)`` tuple
+        of ``[num_pages, num_kv_heads, page_size, head_dim]`` tensors.
+    workspace_buffer : one buffer on the query's device; the work list, the page table and the f32 partial states are
+        carved out of it.  It need not be zeroed.  ValueError names the bytes needed when it is too small.
+    block_tables : int32 ``[batch_size, max_blocks]``; row ``b`` lists the pages of request ``b``.  Entries past a
+        request's ``ceil(seq_len / page_size)`` pages are never read.
+    seq_lens : int32 (or uint32) ``[batch_size]`` on the device.  A length beyond ``max_blocks * page_size`` is CLAMPED
+        to it (the host never sees the value, so it cannot be refused); a length of 0 gives a zero output row.
+    max_seq_len : checked against ``max_blocks * page_size``; otherwise unused.
+    bmm1_scale : the full scale of the logits (``sm_scale``).  bmm2_scale : multiplies the output.
+    window_left : sliding window, ``-1`` for none.  Chunks are cut over all pages; the kernel masks.
+    out : optional output tensor of the query's shape and dtype.  out_dtype : the query's dtype, if given.
+    sinks : optional float32 ``[num_qo_heads]`` attention-sink logits (or a one-element list holding them).
+    enable_pdl : accepted and ignored.
+
+    Not offered (NotImplementedError): ``q_len_per_req != 1``, an fp8 query, ``out_dtype="nvfp4"`` / an FP4Tensor
+    ``out`` / ``o_sf_scale`` / ``o_sf_vec_size``, and the ``[num_pages, 1, ...]`` cache with K and V shared.
+    """
+    if q_len_per_req is not None and q_len_per_req != 1:
+        raise NotImplementedError(f"trtllm_batch_decode_with_kv_cache: q_len_per_req={q_len_per_req} is not "
+                                  "supported (one query token per request)")
+    if query.dtype in (torch.float8_e4m3fn, torch.float8_e5m2):
+        raise NotImplementedError("trtllm_batch_decode_with_kv_cache: an fp8 query is not supported "
+                                  "(float16 / bfloat16)")
+    if out_dtype == "nvfp4" or o_sf_scale is not None or o_sf_vec_size is not None:
+        raise NotImplementedError("trtllm_batch_decode_with_kv_cache: out_dtype='nvfp4' (o_sf_scale, o_sf_vec_size) "
+                                  "is not supported")
+    if out is not None and not torch.is_tensor(out):
+        raise NotImplementedError(f"trtllm_batch_decode_with_kv_cache: out of type {type(out).__name__} "
+                                  "(FP4Tensor) is not supported")
+    if torch.is_tensor(kv_cache) and kv_cache.dim() == 5 and kv_cache.shape[1] == 1:
+        raise NotImplementedError("trtllm_batch_decode_with_kv_cache: the [num_pages, 1, ...] kv_cache with K and V "
+                                  "shared is not supported")
+    for name, t in (("query", query), ("workspace_buffer", workspace_buffer), ("block_tables", block_tables),
+                    ("seq_lens", seq_lens)):
+        _lib.require_gpu_tensor(t, name)
+    if torch.is_tensor(kv_cache):
+        if kv_cache.dim() != 5 or kv_cache.shape[1] != 2:
+            raise ValueError("kv_cache must be [num_pages, 2, num_kv_heads, page_size, head_dim] or a (k, v) tuple")
+    elif not (isinstance(kv_cache, tuple) and len(kv_cache) == 2 and all(t.dim() == 4 for t in kv_cache)):
+        raise ValueError("a kv_cache tuple holds k and v, each [num_pages, num_kv_heads, page_size, head_dim]")
+    k_cache, v_cache = _unpack_paged_kv_cache(kv_cache, "HND")
+    _lib.require_gpu_tensor(k_cache, "kv_cache")
+    _lib.require_gpu_tensor(v_cache, "kv_cache")
+    if query.dtype not in (torch.float16, torch.bfloat16) or query.dim() != 3 or query.stride(-1) != 1:
+        raise ValueError("query must be a float16 / bfloat16 [batch_size, num_qo_heads, head_dim] tensor, contiguous "
+                         "in head_dim")
+    batch_size, num_qo_heads, head_dim = query.shape
+    if block_tables.dtype != torch.int32 or block_tables.dim() != 2 or block_tables.shape[0] != batch_size \
+            or block_tables.shape[1] == 0 or block_tables.stride(1) != 1:
+        raise ValueError(f"block_tables must be int32 [{batch_size}, max_blocks] with contiguous rows")
+    if seq_lens.dtype == torch.uint32:
+        seq_lens = seq_lens.view(torch.int32)
+    if seq_lens.dtype != torch.int32 or seq_lens.shape != (batch_size,) or not seq_lens.is_contiguous():
+        raise ValueError(f"seq_lens must be a contiguous int32 / uint32 tensor of shape [{batch_size}]")
+    if not workspace_buffer.is_contiguous():
+        raise ValueError("workspace_buffer must be contiguous")
+    if out_dtype is not None and canonicalize_torch_dtype(out_dtype) != query.dtype:
+        raise ValueError(f"out_dtype {out_dtype} differs from the query's {query.dtype}")
+    if out is None:
+        out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
+    else:
+        check_shape_dtype_device(out, query.shape, query.dtype, query.device, "out")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+    if isinstance(sinks, (list, tuple)):
+        if len(sinks) != 1:
+            raise ValueError("sinks is one float32 [num_qo_heads] tensor, or a list holding that one tensor")
+        sinks = sinks[0]
+    if sinks is not None and (not torch.is_tensor(sinks) or sinks.dtype != torch.float32
+                              or sinks.shape != (num_qo_heads,) or not sinks.is_contiguous()
+                              or sinks.device != query.device):
+        raise ValueError(f"sinks must be a contiguous float32 tensor of shape [{num_qo_heads}] on {query.device}")
+
+    max_blocks = block_tables.shape[1]
+    # the cache view; its three page-table pointers are set below, once the planner has said where it writes them
+    kv, page_size, num_kv_heads, kv_head_dim = paged_kv(k_cache, v_cache, "HND", block_tables, None, None, batch_size)
+    if kv_head_dim != head_dim:
+        raise ValueError(f"head_dim of query ({head_dim}) and kv_cache ({kv_head_dim}) differ")
+    if max_seq_len > max_blocks * page_size:
+        raise ValueError(f"max_seq_len {max_seq_len} exceeds what block_tables can hold: {max_blocks} blocks of "
+                         f"{page_size} tokens")
+    if batch_size == 0:
+        return out
+
+    plan = _lib.fi_batch_decode_plan_device_params_t(
+        block_tables=block_tables.data_ptr(), seq_lens=seq_lens.data_ptr(), block_tables_stride=block_tables.stride(0),
+        batch_size=batch_size, max_blocks=max_blocks, page_size=page_size, num_qo_heads=num_qo_heads,
+        num_kv_heads=num_kv_heads, head_dim=head_dim, q_dtype=_lib.fi_dtype(query.dtype),
+        kv_dtype=_lib.fi_dtype(k_cache.dtype), max_grid_hint=0)
+    _device_plan_regions(workspace_buffer, plan)
+    plan_info = (C.c_int64 * _lib.FI_DECODE_PLAN_INFO_LEN)()
+    csr = (C.c_int64 * 3)()
+    params = _lib.fi_batch_decode_params_t(
+        q=query.data_ptr(), q_stride_n=query.stride(0), q_stride_h=query.stride(1), kv=kv, o=out.data_ptr(), lse=None,
+        alibi_slopes=None, q_rope_offset=None, num_qo_heads=num_qo_heads, q_dtype=plan.q_dtype,
+        pos_encoding_mode=PosEncodingMode.NONE.value, window_left=window_left,
+        **_resolve_logits_params(head_dim, bmm1_scale, None, None, None, None, None))
+    lib = _lib.lib()
+    with torch.cuda.device(query.device):
+        stream = _lib.current_stream(query.device)
+        _lib.check(lib.fi_batch_decode_plan_device(C.byref(plan), plan_info, csr, stream),
+                   "trtllm_batch_decode_with_kv_cache")
+        # the page table the planner's kernels write, in place of the one plan() would have been given
+        params.kv.indptr, params.kv.indices, params.kv.last_page_len = (plan.int_ws + off for off in csr)
+        _lib.check(lib.fi_batch_decode_run_sinks(plan.float_ws, plan.float_ws_bytes, plan.int_ws, plan.int_ws_bytes,
+                                                 plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, C.byref(params),
+                                                 _lib.ptr(sinks), stream),
+                   "trtllm_batch_decode_with_kv_cache")
+    if bmm2_scale != 1.0:
+        out *= bmm2_scale
+    return out

@@ -177,6 +177,56 @@ FI_API int fi_batch_decode_run_sinks(void* float_ws, size_t float_ws_bytes, void
                               const int64_t* plan_info, int32_t plan_info_len,
                               const fi_batch_decode_params_t* params, const float* sinks, fi_stream_t stream);
 
+/* Device-side planning: the plan of fi_batch_decode_plan(enable_cuda_graph = 1, window_left = -1), written by kernels
+ * on `stream` from lengths that stay on the device.  No host read-back, no copy, no synchronisation: the call may be
+ * captured in a graph together with the fi_batch_decode_run[_sinks] that follows it, and a replay plans again from
+ * whatever `block_tables` and `seq_lens` hold then.  (The reference's plan-free decode entry,
+ * trtllm_batch_decode_with_kv_cache, flashinfer/decode.py:2054-2071, takes the same two tensors.)
+ *
+ * The kernels also write the CSR page table run() addresses the cache through, into the int workspace at
+ * csr_offsets_out[0..2] (byte offsets of indptr[batch+1], indices[batch * max_blocks], last_page_len[batch]):
+ *   pages(b) = min(ceil(seq_lens[b] / page_size), max_blocks); indptr is their exclusive scan; indices holds the first
+ *   pages(b) entries of row b, compacted; last_page_len[b] = len - (pages(b) - 1) * page_size, 0 for pages(b) == 0.
+ * Row entries past pages(b) are never read.  A length beyond max_blocks * page_size (or below 0) is CLAMPED to that
+ * range: it cannot be refused, the host never sees it.
+ *
+ * plan_info_out holds host-computed entries only: magic, ENABLE_CUDA_GRAPH = 1, WINDOW_LEFT = -1, UNIFORM_CHUNKS = 0,
+ * the offsets, FI_DP_PADDED_BATCH_SIZE, and SPLIT_KV by the branch the host knows (batch * gdy >= max_grid: unsplit).
+ * The list capacity of a split plan is max(max_grid / gdy, batch), what the host planner pads a graph plan to.  The
+ * host grows its list beyond that when empty requests (one chunk each) make it longer; here the chunk search also
+ * requires the list to fit, so such a batch gets longer chunks than the host would cut.  Every other batch, and every
+ * batch without an empty request, gets the host's plan.
+ * FI_DP_KV_CHUNK_SIZE and FI_DP_NUM_WORK are 0 here: both values exist on the device only, as two int32 at
+ * FI_DP_KV_CHUNK_SIZE_PTR_OFFSET (tokens per chunk, which the decode kernels read through kv_chunk_size_ptr, then the
+ * number of valid work items).
+ * Errors (fi_last_error) before any launch: null tensors, batch_size <= 0, a workspace too small (the message states
+ * the bytes needed), an unsupported head_dim / dtype. */
+typedef struct fi_batch_decode_plan_device_params {
+  const int32_t* block_tables; /* [batch_size, max_blocks] device, rows block_tables_stride elements apart */
+  const int32_t* seq_lens;     /* [batch_size] device: kv tokens per request */
+  int64_t block_tables_stride;
+  void* int_ws; /* device: work list, then the CSR page table */
+  size_t int_ws_bytes;
+  void* float_ws; /* device: f32 partial states of a split plan (only sized here, run() writes it) */
+  size_t float_ws_bytes;
+  int32_t batch_size;
+  int32_t max_blocks;
+  int32_t page_size;
+  int32_t num_qo_heads;
+  int32_t num_kv_heads;
+  int32_t head_dim;
+  int32_t q_dtype;
+  int32_t kv_dtype;
+  int32_t max_grid_hint; /* <= 0: sized from the device, as fi_batch_decode_plan */
+} fi_batch_decode_plan_device_params_t;
+
+FI_API int fi_batch_decode_plan_device(const fi_batch_decode_plan_device_params_t* params, int64_t* plan_info_out,
+                                       int64_t* csr_offsets_out, fi_stream_t stream);
+/* The bytes fi_batch_decode_plan_device needs of the two workspaces for these params (the pointers and sizes in them
+ * are not read): for callers that carve both regions out of one buffer.  Host arithmetic only. */
+FI_API int fi_batch_decode_plan_device_workspace(const fi_batch_decode_plan_device_params_t* params,
+                                                 size_t* int_ws_bytes_out, size_t* float_ws_bytes_out);
+
 /* ------------------------------------------------------------------------------------------------
  * Single-request decode over a dense KV tensor.
  * ref: single_decode_with_kv_cache, csrc/single_decode.cu:33-104; decode.cuh:658-737.
