@@ -5,7 +5,8 @@
 //
 // route.     One wave per token.  Lane l holds logits l, l + 64, ... (up to 8, num_experts <= 512) in registers; each of
 //            the top_k rounds takes the lane's best untaken entry and reduces (value, index) over the wave with the
-//            order "larger value, then lower index", so ties resolve without another pass.
+//            order "larger value, then lower index", so ties resolve without another pass.  The sigmoid methods
+//            (DeepSeekV3, Llama4) are a kernel of their own on the same layout and rounds: see moe_route_sigmoid_kernel.
 // permute.   Four launches, no host round trip.  count: one wave per FI_MOE_SORT_BLOCK expanded indices builds the
 //            histogram of its block over the local experts (LDS adds: a count does not depend on their order).  scan: one
 //            workgroup turns the histograms into per-block offsets (a serial walk over the blocks per expert) and the
@@ -46,6 +47,28 @@ __device__ __forceinline__ void moe_better(float& v, int& i, float ov, int oi) {
   }
 }
 
+// the better of every lane's (value, index), afterwards in every lane
+__device__ __forceinline__ void moe_wave_best(float& v, int& i) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float ov = __shfl_xor(v, off, 64);
+    const int oi = __shfl_xor(i, off, 64);
+    moe_better(v, i, ov, oi);
+  }
+}
+
+// one top-k round: the wave's best entry whose slot bit in `taken` is clear; the lane that holds it sets the bit
+__device__ __forceinline__ void moe_take_best(const float (&v)[kMoeSlots], uint32_t& taken, int lane, float& bv, int& bi) {
+  bv = -INFINITY;
+  bi = 0x7fffffff;  // no candidate: loses against every expert, also one at -inf
+#pragma unroll
+  for (int s = 0; s < kMoeSlots; ++s)
+    if (!(taken >> s & 1)) moe_better(bv, bi, v[s], lane + 64 * s);
+  moe_wave_best(bv, bi);
+  // the callers' limits leave an untaken expert: bi is one, and the same in every lane
+  if ((bi & 63) == lane) taken |= 1u << (bi >> 6);
+}
+
 template <int DT>
 __global__ void __launch_bounds__(kMoeThreads) moe_route_kernel(const MoeRouteArgs A) {
   const int lane = threadIdx.x & 63;
@@ -72,20 +95,10 @@ __global__ void __launch_bounds__(kMoeThreads) moe_route_kernel(const MoeRouteAr
   for (int r = 0; r < FI_MOE_MAX_TOP_K; ++r) {
     sel_v[r] = -INFINITY;
     sel_i[r] = 0;
-    if (r < A.top_k) {
-      float bv = -INFINITY;
-      int bi = 0x7fffffff;  // no candidate: loses against every expert, also one at -inf
-#pragma unroll
-      for (int s = 0; s < kMoeSlots; ++s)
-        if (!(taken >> s & 1)) moe_better(bv, bi, v[s], lane + 64 * s);
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_xor(bv, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        moe_better(bv, bi, ov, oi);
-      }
-      // top_k <= num_experts: an untaken expert exists, so bi is one and the same in every lane
-      if ((bi & 63) == lane) taken |= 1u << (bi >> 6);
+    if (r < A.top_k) {  // top_k <= num_experts
+      float bv;
+      int bi;
+      moe_take_best(v, taken, lane, bv, bi);
       sel_v[r] = bv;
       sel_i[r] = bi;
     }
@@ -127,6 +140,130 @@ __global__ void __launch_bounds__(kMoeThreads) moe_route_kernel(const MoeRouteAr
     if (r < A.top_k && lane == r) {
       A.ids[(int64_t)t * A.top_k + r] = sel_i[r];
       A.weights[(int64_t)t * A.top_k + r] = f32_to_bf16_bits(w[r]);
+    }
+  }
+}
+
+// ---- route, the sigmoid methods -------------------------------------------------------------------------------------
+struct MoeRouteSigmoidArgs {
+  const void* logits;
+  const void* bias;
+  int32_t* ids;
+  uint16_t* weights;
+  int32_t num_tokens, num_experts, top_k, method;
+  int32_t n_group, topk_group, epg;  // n_group 0: no groups, every expert is a candidate
+  int32_t bias_dt;
+  float scale;
+};
+
+// (largest, second largest) of a set and another one's (o1, o2), merged
+__device__ __forceinline__ void moe_top2_merge(float& b1, float& b2, float o1, float o2) {
+  b2 = fmaxf(fminf(b1, o1), fmaxf(b2, o2));
+  b1 = fmaxf(b1, o1);
+}
+
+// The layout and the top_k rounds of moe_route_kernel on the key b = sigmoid(logit) + bias (DeepSeekV3) or the logit
+// itself (Llama4).  With groups three steps come first.  (1) Every group's score, the sum of its two largest keys, lands
+// in lane g: when a group is epg = 2^k <= 64 consecutive lanes of one slot by a width-epg xor-shuffle of (best,
+// second) pairs, otherwise through LDS, where lane g walks the keys of group g.  (2) topk_group rounds of the same
+// (value, lower index) reduction over the lanes' scores build the bit mask of the kept groups, the same in every lane.
+// (3) The experts of the other groups are marked taken, so no key, whatever its sign, lets one of them win a round.
+template <int DT>
+__global__ void __launch_bounds__(kMoeThreads) moe_route_sigmoid_kernel(const MoeRouteSigmoidArgs A) {
+  __shared__ float lds_key[kMoeThreads / 64][FI_MOE_MAX_EXPERTS];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int t = blockIdx.x * (kMoeThreads / 64) + wave;
+  const bool live = t < A.num_tokens;  // a wave past the last token loads and stores nothing, but stays for the barrier
+  const int E = A.num_experts;
+  const bool deepseek = A.method == FI_MOE_ROUTING_DEEPSEEK_V3;
+  float key[kMoeSlots], sig[kMoeSlots];
+  uint32_t taken = 0;  // bit s: slot s is chosen already, in a dropped group, or past the last expert
+#pragma unroll
+  for (int s = 0; s < kMoeSlots; ++s) {
+    const int e = lane + 64 * s;
+    key[s] = -INFINITY;
+    sig[s] = 0.f;
+    if (e >= E) taken |= 1u << s;
+    if (e < E && live) {
+      float x = load_any_float(A.logits, (int64_t)t * E + e, DT);
+      if (!(x == x)) x = -INFINITY;
+      sig[s] = 1.0f / (1.0f + expf(-x));
+      key[s] = x;
+      if (deepseek) {
+        key[s] = sig[s] + load_any_float(A.bias, e, A.bias_dt);
+        if (!(key[s] == key[s])) key[s] = -INFINITY;
+      }
+    }
+  }
+  if (A.n_group > 1) {
+    const int epg = A.epg, G = A.n_group;
+    float score = -INFINITY;  // lane g < G: the score of group g
+    if (epg <= 64 && (epg & (epg - 1)) == 0) {
+#pragma unroll
+      for (int s = 0; s < kMoeSlots; ++s) {
+        if (64 * s < E) {  // the same in every lane
+          float b1 = key[s], b2 = -INFINITY;
+          for (int off = 1; off < epg; off <<= 1) {
+            const float o1 = __shfl_xor(b1, off, 64);
+            const float o2 = __shfl_xor(b2, off, 64);
+            moe_top2_merge(b1, b2, o1, o2);
+          }
+          // group g begins at expert g * epg: lane (g * epg) & 63 of slot (g * epg) >> 6
+          const float got = __shfl(b1 + b2, (lane * epg) & 63, 64);
+          if (lane < G && (lane * epg) >> 6 == s) score = got;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < kMoeSlots; ++s)
+        if (lane + 64 * s < E) lds_key[wave][lane + 64 * s] = key[s];
+      __syncthreads();
+      if (lane < G) {
+        float b1 = -INFINITY, b2 = -INFINITY;
+        for (int i = 0; i < epg; ++i) moe_top2_merge(b1, b2, lds_key[wave][lane * epg + i], -INFINITY);
+        score = b1 + b2;
+      }
+    }
+    if (!(score == score)) score = -INFINITY;  // +inf and -inf keys in one group
+    bool out = lane >= G;  // this lane's group is kept already, or there is none
+    unsigned long long kept = 0;
+    for (int r = 0; r < A.topk_group; ++r) {  // topk_group <= n_group: a group is left in every round
+      float bv = out ? -INFINITY : score;
+      int bi = out ? 0x7fffffff : lane;
+      moe_wave_best(bv, bi);
+      if (bi == lane) out = true;
+      kept |= 1ull << (bi & 63);
+    }
+#pragma unroll
+    for (int s = 0; s < kMoeSlots; ++s) {
+      const int e = lane + 64 * s;
+      if (e < E && !(kept >> (e / epg) & 1)) taken |= 1u << s;
+    }
+  }
+  float sel_s[FI_MOE_MAX_TOP_K], chosen = 0.f;
+  int sel_i[FI_MOE_MAX_TOP_K];
+#pragma unroll
+  for (int r = 0; r < FI_MOE_MAX_TOP_K; ++r) {
+    sel_s[r] = 0.f;
+    sel_i[r] = 0;
+    if (r < A.top_k) {  // top_k <= the number of candidates
+      float bv;
+      moe_take_best(key, taken, lane, bv, sel_i[r]);
+      float mine = 0.f;
+#pragma unroll
+      for (int s = 0; s < kMoeSlots; ++s)
+        if (sel_i[r] >> 6 == s) mine = sig[s];
+      sel_s[r] = __shfl(mine, sel_i[r] & 63, 64);  // selection is by the key, the weight comes from the plain sigmoid
+      chosen += sel_s[r];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < FI_MOE_MAX_TOP_K; ++r) {
+    if (live && r < A.top_k && lane == r) {
+      const float w = deepseek ? sel_s[r] * A.scale / (chosen + 1e-20f) : sel_s[r];
+      A.ids[(int64_t)t * A.top_k + r] = sel_i[r];
+      A.weights[(int64_t)t * A.top_k + r] = f32_to_bf16_bits(w);
     }
   }
 }
@@ -437,6 +574,67 @@ extern "C" FI_API int fi_moe_route(const fi_moe_route_params_t* p, fi_stream_t s
     moe_route_kernel<FI_DTYPE_F32><<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
   else
     moe_route_kernel<FI_DTYPE_BF16><<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}
+
+extern "C" FI_API int fi_moe_route_sigmoid(const fi_moe_route_sigmoid_params_t* p, fi_stream_t stream) {
+  FI_REQUIRE(p, "moe_route_sigmoid: null params");
+  FI_REQUIRE(p->num_tokens >= 0 && p->num_experts >= 0 && p->top_k >= 0 && p->n_group >= 0 && p->topk_group >= 0,
+             "moe_route_sigmoid: negative size (num_tokens %d, num_experts %d, top_k %d, n_group %d, topk_group %d)",
+             p->num_tokens, p->num_experts, p->top_k, p->n_group, p->topk_group);
+  const bool deepseek = p->method == FI_MOE_ROUTING_DEEPSEEK_V3;
+  FI_REQUIRE(deepseek || p->method == FI_MOE_ROUTING_LLAMA4, "moe_route_sigmoid: routing method %d is not provided",
+             p->method);
+  FI_REQUIRE(p->num_experts >= 1 && p->num_experts <= FI_MOE_MAX_EXPERTS,
+             "moe_route_sigmoid: num_experts %d is not in [1, %d]", p->num_experts, FI_MOE_MAX_EXPERTS);
+  FI_REQUIRE(p->top_k >= 1 && p->top_k <= FI_MOE_MAX_TOP_K && p->top_k <= p->num_experts,
+             "moe_route_sigmoid: top_k %d is not in [1, min(%d, num_experts %d)]", p->top_k, FI_MOE_MAX_TOP_K,
+             p->num_experts);
+  FI_REQUIRE(p->dtype == FI_DTYPE_F32 || p->dtype == FI_DTYPE_BF16, "moe_route_sigmoid: dtype %d is not f32 or bf16",
+             p->dtype);
+  const bool groups = deepseek && p->n_group > 1;
+  int epg = 0;
+  if (!deepseek) {
+    FI_REQUIRE(p->top_k == 1, "moe_route_sigmoid: Llama4 routing takes top_k 1, not %d", p->top_k);
+  } else {
+    FI_REQUIRE(p->bias_dtype == FI_DTYPE_F32 || p->bias_dtype == FI_DTYPE_BF16,
+               "moe_route_sigmoid: bias_dtype %d is not f32 or bf16", p->bias_dtype);
+    if (groups) {
+      FI_REQUIRE(p->n_group <= 64, "moe_route_sigmoid: n_group %d is not in [0, 64]", p->n_group);
+      FI_REQUIRE(p->num_experts % p->n_group == 0, "moe_route_sigmoid: num_experts %d is not a multiple of n_group %d",
+                 p->num_experts, p->n_group);
+      epg = p->num_experts / p->n_group;
+      FI_REQUIRE(epg >= 2, "moe_route_sigmoid: num_experts %d / n_group %d leaves %d expert per group, 2 needed",
+                 p->num_experts, p->n_group, epg);
+      FI_REQUIRE(p->topk_group >= 1 && p->topk_group <= p->n_group, "moe_route_sigmoid: topk_group %d is not in [1, n_group %d]",
+                 p->topk_group, p->n_group);
+      FI_REQUIRE(p->top_k <= p->topk_group * epg, "moe_route_sigmoid: top_k %d exceeds the %d experts of topk_group %d groups",
+                 p->top_k, p->topk_group * epg, p->topk_group);
+    }
+  }
+  if (p->num_tokens == 0) return 0;
+  FI_REQUIRE(p->logits && p->topk_ids && p->topk_weights, "moe_route_sigmoid: null tensor");
+  FI_REQUIRE(!deepseek || p->bias, "moe_route_sigmoid: null tensor (DeepSeekV3 routing reads bias)");
+  MoeRouteSigmoidArgs a{};
+  a.logits = p->logits;
+  a.bias = p->bias;
+  a.ids = p->topk_ids;
+  a.weights = p->topk_weights;
+  a.num_tokens = p->num_tokens;
+  a.num_experts = p->num_experts;
+  a.top_k = p->top_k;
+  a.method = p->method;
+  a.n_group = groups ? p->n_group : 0;
+  a.topk_group = groups ? p->topk_group : 0;
+  a.epg = epg;
+  a.bias_dt = p->bias_dtype;
+  a.scale = p->routed_scaling_factor;
+  const uint32_t grid = (uint32_t)ceil_div<int64_t>(p->num_tokens, kMoeThreads / 64);
+  if (p->dtype == FI_DTYPE_F32)
+    moe_route_sigmoid_kernel<FI_DTYPE_F32><<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
+  else
+    moe_route_sigmoid_kernel<FI_DTYPE_BF16><<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
   FI_HIP_CALL(hipGetLastError());
   return 0;
 }

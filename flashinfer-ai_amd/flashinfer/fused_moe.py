@@ -13,8 +13,16 @@ What differs from the reference: weights are plain ``[E_local, 
 swizzled layout, as ``mxfp4_quantize_grouped`` returns them -- the trtllm-gen weight shuffle and gate / up row interleave
 are NVIDIA kernel layouts and are neither applied nor accepted; rows ``[0, I)`` of GEMM1's output are the linear half and
 rows ``[I, 2 I)`` the gate; GEMM1's output is rounded to bf16 before the activation.  Everything outside the mode above
-(bf16 or nvfp4 activations, DeepSeekV3 / Llama4 routing, a routing bias, expert groups, GeGlu, per-tensor output
-scales) raises NotImplementedError naming the argument, before any launch.
+(bf16 or nvfp4 activations, GeGlu, per-tensor output scales) raises NotImplementedError naming the argument, before
+any launch.
+
+Routing is every method of ``RoutingMethodType`` but ``Unspecified``.  ``DeepSeekV3`` (sigmoid scores, ``routing_bias``,
+``topk_group`` of ``n_group`` expert groups by their top-2 sums, ``routed_scaling_factor``; without groups Kimi-K2's shape)
+and ``Llama4`` (top-1, then sigmoid) run as one kernel of their own behind fi_moe_route_sigmoid; ``routing_bias``,
+``n_group``, ``topk_group`` and a ``routed_scaling_factor`` other than 1 belong to ``DeepSeekV3`` and are refused with any
+other method and in the routed call, where no routing runs.  An expert of a dropped group is never chosen, also
+where the reference's kernel and the routine its tests compare it with would let it win against negative biased scores
+(INTEGRATION.md).
 
 Nothing here reads a device value on the host or synchronises, and every buffer's size depends on shapes alone, so a
 call can be captured into a graph.
@@ -60,19 +68,17 @@ class GatedActType(IntEnum):
     GeGlu = 1
 
 
-_ROUTING_PROVIDED = (RoutingMethodType.Default, RoutingMethodType.Renormalize, RoutingMethodType.RenormalizeNaive,
-                     RoutingMethodType.TopK)
+_MAX_GROUPS = 64
 
 
-def _check_routing_method(routing_method_type: int) -> int:
-    try:
-        method = RoutingMethodType(int(routing_method_type))
-    except ValueError:
-        raise NotImplementedError(f"routing_method_type {routing_method_type} is not a routing method") from None
-    if method not in _ROUTING_PROVIDED:
-        raise NotImplementedError(
-            f"routing_method_type {method.name} is not provided: only Default, Renormalize, RenormalizeNaive and TopK")
-    return int(method)
+def _check_no_deepseek_arguments(routing_bias, n_group, topk_group, routed_scaling_factor) -> None:
+    """What only DeepSeekV3 routing takes, wherever that routing does not run."""
+    if routing_bias is not None:
+        raise NotImplementedError("routing_bias is not provided (it belongs to DeepSeekV3 routing): pass None")
+    if n_group not in (None, 0) or topk_group not in (None, 0):
+        raise NotImplementedError("n_group / topk_group (expert groups, DeepSeekV3 routing) are not provided: pass None")
+    if routed_scaling_factor is not None and routed_scaling_factor != 1.0:
+        raise NotImplementedError(f"routed_scaling_factor {routed_scaling_factor} is not provided: pass None or 1.0")
 
 
 def _check_top_k(top_k: int, num_experts: int) -> None:
@@ -80,6 +86,52 @@ def _check_top_k(top_k: int, num_experts: int) -> None:
         raise NotImplementedError(f"num_experts {num_experts} is not in [1, {_MAX_EXPERTS}]")
     if not 1 <= top_k <= min(_MAX_TOP_K, num_experts):
         raise NotImplementedError(f"top_k {top_k} is not in [1, min({_MAX_TOP_K}, num_experts = {num_experts})]")
+
+
+def _check_routing(routing_method_type: int, top_k: int, num_experts: int, routing_bias: Optional[torch.Tensor],
+                   n_group: Optional[int], topk_group: Optional[int],
+                   routed_scaling_factor: Optional[float]) -> Tuple[int, int, int, float]:
+    """The routing arguments of ``moe_route`` and the layer, without a tensor read: ``(method, n_group, topk_group,
+    routed_scaling_factor)`` as the C ABI takes them, ``n_group`` 0 for no groups."""
+    try:
+        method = RoutingMethodType(int(routing_method_type))
+    except ValueError:
+        raise NotImplementedError(f"routing_method_type {routing_method_type} is not a routing method") from None
+    if method == RoutingMethodType.Unspecified:
+        raise NotImplementedError("routing_method_type Unspecified is not provided: name the method")
+    if method == RoutingMethodType.DeepSeekV3 and routing_bias is None:
+        raise NotImplementedError("routing_method_type DeepSeekV3 needs routing_bias: the bias is part of the method "
+                                  "(pass zeros for none)")
+    if method == RoutingMethodType.Llama4 and top_k != 1:
+        raise NotImplementedError(f"routing_method_type Llama4 is top-1 routing: top_k {top_k} is not provided")
+    _check_top_k(top_k, num_experts)
+    if method != RoutingMethodType.DeepSeekV3:
+        _check_no_deepseek_arguments(routing_bias, n_group, topk_group, routed_scaling_factor)
+        return int(method), 0, 0, 1.0
+    E = num_experts
+    if routing_bias.dtype not in (torch.float32, torch.bfloat16) or tuple(routing_bias.shape) != (E,):
+        raise ValueError(f"routing_bias must be float32 or bfloat16 of shape ({E},), got {routing_bias.dtype} "
+                         f"{tuple(routing_bias.shape)}")
+    n_group, topk_group = int(n_group or 0), int(topk_group or 0)
+    if n_group < 0 or topk_group < 0:
+        raise ValueError(f"n_group {n_group} and topk_group {topk_group} must not be negative")
+    if n_group <= 1:
+        if topk_group > n_group:
+            raise ValueError(f"topk_group {topk_group} is given without expert groups (n_group {n_group})")
+        n_group = topk_group = 0
+    else:
+        if n_group > _MAX_GROUPS:
+            raise NotImplementedError(f"n_group {n_group} is not in [0, {_MAX_GROUPS}]")
+        if E % n_group != 0:
+            raise ValueError(f"num_experts {E} is not a multiple of n_group {n_group}")
+        epg = E // n_group
+        if epg < 2:
+            raise NotImplementedError(f"n_group {n_group} leaves {epg} expert per group: a group's score is the sum of two")
+        if not 1 <= topk_group <= n_group:
+            raise ValueError(f"topk_group {topk_group} is not in [1, n_group = {n_group}]")
+        if top_k > topk_group * epg:
+            raise ValueError(f"top_k {top_k} exceeds the {topk_group * epg} experts of topk_group {topk_group} groups of {epg}")
+    return int(method), n_group, topk_group, 1.0 if routed_scaling_factor is None else float(routed_scaling_factor)
 
 
 def _bytes(t: torch.Tensor) -> torch.Tensor:
@@ -92,34 +144,62 @@ def _aligned(t: torch.Tensor, alignment: int) -> torch.Tensor:
     return t if t.data_ptr() % alignment == 0 else t.clone()
 
 
-def moe_route(routing_logits: torch.Tensor, top_k: int,
-              routing_method_type: int = RoutingMethodType.Default) -> Tuple[torch.Tensor, torch.Tensor]:
+def moe_route(routing_logits: torch.Tensor, top_k: int, routing_method_type: int = RoutingMethodType.Default,
+              routing_bias: Optional[torch.Tensor] = None, n_group: Optional[int] = None,
+              topk_group: Optional[int] = None,
+              routed_scaling_factor: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Router logits -> expert ids and weights.  Not part of the reference, which routes inside its fused call.
 
     ``routing_logits`` is f32 or bf16 ``[T, E]`` with ``E <= 512`` and ``1 <= top_k <= min(8, E)``.  Returns ``(ids, weights)``:
-    int32 and bf16 ``[T, top_k]``.  Slot ``j`` of a token is the expert of its ``j``-th largest logit, ties to the lower
-    expert index.  The weights are computed in f32 and rounded once: ``Default`` softmax over all experts;
-    ``Renormalize`` softmax over the chosen logits; ``RenormalizeNaive`` the ``Default`` weights divided by their sum;
-    ``TopK`` the logits themselves.
+    int32 and bf16 ``[T, top_k]``.  The weights are computed in f32 and rounded once; a NaN logit counts as -inf.
+
+    ``Default``, ``Renormalize``, ``RenormalizeNaive``, ``TopK``: slot ``j`` of a token is the expert of its ``j``-th largest
+    logit, ties to the lower expert index.  ``Default`` softmax over all experts; ``Renormalize`` softmax over the chosen
+    logits; ``RenormalizeNaive`` the ``Default`` weights divided by their sum; ``TopK`` the logits themselves.  The four
+    trailing arguments belong to ``DeepSeekV3`` and are refused.
+
+    ``DeepSeekV3`` (``routing_bias`` f32 or bf16 ``[E]`` is required): ``s = sigmoid(logit)``, ``b = s + routing_bias``.  With
+    ``n_group > 1`` the experts ``[g * epg, (g + 1) * epg)``, ``epg = E / n_group``, are group ``g``; a group's score is the sum
+    of its two largest ``b`` and only the ``topk_group`` groups of the largest score (ties to the lower group) stay
+    candidates: ``E % n_group == 0``, ``epg >= 2``, ``n_group <= 64``, ``1 <= topk_group <= n_group``, ``top_k <= topk_group *
+    epg``.  With ``n_group`` ``None``, 0 or 1 every expert is a candidate.  Slot ``j`` is the candidate of the ``j``-th largest
+    ``b``, ties to the lower expert, and ``w[j] = s[id_j] * routed_scaling_factor / (sum_j s[id_j] + 1e-20)``;
+    ``routed_scaling_factor=None`` is 1.  An expert of a dropped group is never chosen, also when every kept ``b`` is
+    negative.
+
+    ``Llama4``: ``top_k == 1``; the expert of the largest logit, ties to the lower index, with weight ``sigmoid(logit)``.
     """
-    method = _check_routing_method(routing_method_type)
     if routing_logits.dim() != 2:
         raise ValueError(f"routing_logits must be 2D (T, E), got shape {tuple(routing_logits.shape)}")
     T, E = routing_logits.shape
-    _check_top_k(top_k, E)
+    method, n_group, topk_group, scale = _check_routing(routing_method_type, top_k, E, routing_bias, n_group, topk_group,
+                                                        routed_scaling_factor)
     if routing_logits.dtype not in (torch.float32, torch.bfloat16):
         raise NotImplementedError(f"routing_logits has dtype {routing_logits.dtype}: only float32 and bfloat16")
     _lib.require_gpu_tensor(routing_logits, "routing_logits")
+    if routing_bias is not None:
+        _lib.require_gpu_tensor(routing_bias, "routing_bias")
+        if routing_bias.device != routing_logits.device:
+            raise ValueError(f"routing_bias is on {routing_bias.device}, routing_logits on {routing_logits.device}")
     ids = torch.empty((T, top_k), dtype=torch.int32, device=routing_logits.device)
     weights = torch.empty((T, top_k), dtype=torch.bfloat16, device=routing_logits.device)
     if T == 0:
         return ids, weights
     logits = routing_logits.contiguous()
-    p = _lib.fi_moe_route_params_t(
-        logits=logits.data_ptr(), topk_ids=ids.data_ptr(), topk_weights=weights.data_ptr(), num_tokens=T, num_experts=E,
-        top_k=top_k, method=method, dtype=_lib.fi_dtype(logits.dtype))
     with torch.cuda.device(logits.device):
-        _lib.check(_lib.lib().fi_moe_route(C.byref(p), _lib.current_stream(logits.device)), "moe_route")
+        if method in (RoutingMethodType.DeepSeekV3, RoutingMethodType.Llama4):
+            bias = None if routing_bias is None else routing_bias.contiguous()
+            p = _lib.fi_moe_route_sigmoid_params_t(
+                logits=logits.data_ptr(), bias=_lib.ptr(bias), topk_ids=ids.data_ptr(), topk_weights=weights.data_ptr(),
+                num_tokens=T, num_experts=E, top_k=top_k, n_group=n_group, topk_group=topk_group,
+                routed_scaling_factor=scale, method=method, dtype=_lib.fi_dtype(logits.dtype),
+                bias_dtype=_lib.fi_dtype(torch.float32 if bias is None else bias.dtype))
+            _lib.check(_lib.lib().fi_moe_route_sigmoid(C.byref(p), _lib.current_stream(logits.device)), "moe_route_sigmoid")
+        else:
+            p = _lib.fi_moe_route_params_t(
+                logits=logits.data_ptr(), topk_ids=ids.data_ptr(), topk_weights=weights.data_ptr(), num_tokens=T,
+                num_experts=E, top_k=top_k, method=method, dtype=_lib.fi_dtype(logits.dtype))
+            _lib.check(_lib.lib().fi_moe_route(C.byref(p), _lib.current_stream(logits.device)), "moe_route")
     return ids, weights
 
 
@@ -375,19 +455,16 @@ def _moe(routing_logits, topk_ids, routing_bias, hidden_states, hidden_states_sc
          intermediate_size, local_expert_offset, local_num_experts, routed_scaling_factor, tile_tokens_dim,
          routing_method_type, do_finalize, enable_pdl, gated_act_type, output, tune_max_num_tokens) -> List[torch.Tensor]:
     # ---- what is not provided, before anything touches the device ----
-    if routing_bias is not None:
-        raise NotImplementedError("routing_bias is not provided (it belongs to DeepSeekV3 routing): pass None")
-    if n_group not in (None, 0) or topk_group not in (None, 0):
-        raise NotImplementedError("n_group / topk_group (expert groups, DeepSeekV3 routing) are not provided: pass None")
-    if routed_scaling_factor is not None and routed_scaling_factor != 1.0:
-        raise NotImplementedError(f"routed_scaling_factor {routed_scaling_factor} is not provided: pass None or 1.0")
+    if topk_ids is None:
+        _check_routing(routing_method_type, top_k, num_experts, routing_bias, n_group, topk_group, routed_scaling_factor)
+    else:  # no routing runs
+        _check_no_deepseek_arguments(routing_bias, n_group, topk_group, routed_scaling_factor)
     for name, t in (("output1_scale_scalar", output1_scale_scalar), ("output1_scale_gate_scalar", output1_scale_gate_scalar),
                     ("output2_scale_scalar", output2_scale_scalar)):
         if t is not None:
             raise NotImplementedError(f"{name} must be None: MX operands carry their own scales")
     if int(gated_act_type) != GatedActType.SwiGlu:
         raise NotImplementedError(f"gated_act_type {gated_act_type} is not provided: only SwiGlu (0)")
-    method = _check_routing_method(routing_method_type) if topk_ids is None else None
     _check_top_k(top_k, num_experts)
     _check_activations(hidden_states, hidden_states_scale)
     T, H = hidden_states.shape
@@ -418,7 +495,8 @@ def _moe(routing_logits, topk_ids, routing_bias, hidden_states, hidden_states_sc
         raise ValueError(f"topk_ids must be int32 of shape ({T}, {top_k}), got {topk_ids.dtype} {tuple(topk_ids.shape)}")
     if output is not None:
         _check_output(output, T, H)
-    tensors = [("routing_logits", routing_logits), ("topk_ids", topk_ids), ("hidden_states", hidden_states),
+    tensors = [("routing_logits", routing_logits), ("routing_bias", routing_bias), ("topk_ids", topk_ids),
+               ("hidden_states", hidden_states),
                ("hidden_states_scale", hidden_states_scale), ("gemm1_weights", gemm1_weights),
                ("gemm1_weights_scale", gemm1_weights_scale), ("gemm2_weights", gemm2_weights),
                ("gemm2_weights_scale", gemm2_weights_scale), ("output", output)]
@@ -435,7 +513,8 @@ def _moe(routing_logits, topk_ids, routing_bias, hidden_states, hidden_states_sc
 
     # ---- the layer ----
     if topk_ids is None:
-        ids, expert_weights = moe_route(routing_logits, top_k, method)
+        ids, expert_weights = moe_route(routing_logits, top_k, routing_method_type, routing_bias=routing_bias,
+                                        n_group=n_group, topk_group=topk_group, routed_scaling_factor=routed_scaling_factor)
         m_indptr, emap, x_perm, sf_perm = moe_permute_mxfp8(ids, hidden_states, hidden_states_scale, local_expert_offset, G)
     else:
         m_indptr, emap, x_perm, sf_perm, expert_weights = moe_permute_mxfp8(
@@ -494,9 +573,12 @@ def trtllm_fp4_block_scale_moe(
     gemm1_bias, gemm1_alpha, gemm1_beta, gemm1_clamp_limit : f32 ``[E_local, 2 I]`` / ``[E_local]`` or None (see
         ``moe_gated_act_mxfp8``).
     gemm2_weights, gemm2_weights_scale : uint8 ``[E_local, H, I / 2]`` and scales; gemm2_bias f32 ``[E_local, H]`` or None.
-    routing_method_type : Default, Renormalize, RenormalizeNaive or TopK.  gated_act_type : SwiGlu.
-    routing_bias, n_group, topk_group, output1_scale_scalar, output1_scale_gate_scalar, output2_scale_scalar : None;
-        routed_scaling_factor : None or 1.0.  tile_tokens_dim, tune_max_num_tokens, enable_pdl : validated, then ignored.
+    routing_method_type : any but Unspecified (see ``moe_route``).  gated_act_type : SwiGlu.
+    routing_bias, n_group, topk_group, routed_scaling_factor : with DeepSeekV3, ``routing_bias`` f32 / bf16
+        ``[num_experts]`` (required), ``topk_group`` of ``n_group`` expert groups (``n_group`` None, 0 or 1: none) and the
+        factor on the weights (None: 1); with any other method None, the factor None or 1.0.  Llama4 takes ``top_k`` 1.
+    output1_scale_scalar, output1_scale_gate_scalar, output2_scale_scalar : None.
+    tile_tokens_dim, tune_max_num_tokens, enable_pdl : validated, then ignored.
     output : optional contiguous bf16 ``[T, H]``.
 
     Returns ``[out]`` (bf16 ``[T, H]``) with ``do_finalize``, else ``[gemm2_output, expert_weights,
@@ -546,8 +628,8 @@ def trtllm_fp4_block_scale_routed_moe(
     """``trtllm_fp4_block_scale_moe`` on experts chosen by the caller (ref: flashinfer/fused_moe/core.py:1951-2082).
 
     topk_ids : int32 ``[T, top_k]``; the low 16 bits of an entry are the unsigned expert index, the high 16 bits the bit
-    pattern of the bf16 weight.  No routing kernel runs and ``routing_method_type`` is not used.  Everything else as
-    ``trtllm_fp4_block_scale_moe``.
+    pattern of the bf16 weight.  No routing kernel runs and ``routing_method_type`` is not used: ``routing_bias``, ``n_group``
+    and ``topk_group`` are None and ``routed_scaling_factor`` None or 1.0.  Everything else as ``trtllm_fp4_block_scale_moe``.
     """
     return _moe(None, topk_ids, routing_bias, hidden_states, hidden_states_scale, gemm1_weights, gemm1_weights_scale,
                 gemm1_bias, gemm1_alpha, gemm1_beta, gemm1_clamp_limit, gemm2_weights, gemm2_weights_scale, gemm2_bias,

@@ -908,10 +908,13 @@ FI_API int fi_mx_sf_interleave(const fi_mx_sf_interleave_params_t* params, fi_st
 #define FI_MOE_MAX_TOP_K 8
 #define FI_MOE_SORT_BLOCK 256 /* expanded indices ranked by one wave of the permutation (sizes its workspace) */
 
-/* the reference's RoutingMethodType values of the methods provided (core.py:62-76) */
+/* the reference's RoutingMethodType values of the methods provided (core.py:62-76): 0, 1, 4, 5 by fi_moe_route, 2 and 3
+ * by fi_moe_route_sigmoid */
 enum fi_moe_routing {
   FI_MOE_ROUTING_DEFAULT = 0,           /* softmax over all experts -> top-k */
   FI_MOE_ROUTING_RENORMALIZE = 1,       /* top-k -> softmax over the chosen logits */
+  FI_MOE_ROUTING_DEEPSEEK_V3 = 2,       /* sigmoid -> + bias -> top groups by their top-2 sum -> top-k of those groups */
+  FI_MOE_ROUTING_LLAMA4 = 3,            /* top-1 -> sigmoid */
   FI_MOE_ROUTING_RENORMALIZE_NAIVE = 4, /* softmax -> top-k -> divide by the sum of the chosen */
   FI_MOE_ROUTING_TOPK = 5               /* top-k, the weight is the logit itself */
 };
@@ -929,6 +932,34 @@ typedef struct fi_moe_route_params {
 } fi_moe_route_params_t;
 
 FI_API int fi_moe_route(const fi_moe_route_params_t* params, fi_stream_t stream);
+
+/* The two sigmoid routing methods (ref: csrc/trtllm_fused_moe_routing_deepseek.cu:45-210, noaux_tc_ref of
+ * tests/moe/test_trtllm_gen_fused_moe.py:1145-1183; csrc/trtllm_fused_moe_routing_llama4.cu).  All arithmetic is f32,
+ * weights are rounded once to bf16, a NaN logit counts as -inf.  With s[e] = sigmoid(logit[t, e]):
+ *   FI_MOE_ROUTING_DEEPSEEK_V3: b[e] = s[e] + bias[e].  With n_group > 1 the experts [g * epg, (g + 1) * epg), epg =
+ *     num_experts / n_group, are group g; a group's score is the sum of its two largest b, and the topk_group groups of
+ *     the largest score (equal scores: the lower group) are kept.  With n_group 0 or 1 every expert is a candidate and
+ *     topk_group is not read.  Slot j is the candidate of the j-th largest b (equal b: the lower expert), and
+ *       w[j] = s[id_j] * routed_scaling_factor / (sum_j s[id_j] + 1e-20f).
+ *     An expert of a dropped group is never chosen, whatever the signs of b.
+ *   FI_MOE_ROUTING_LLAMA4: top_k == 1; the id is the largest logit's (equal logits: the lower expert), w = s[id].
+ *     bias, n_group, topk_group and routed_scaling_factor are not read.
+ * num_experts <= 512, 1 <= top_k <= 8; with groups: num_experts % n_group == 0, epg >= 2, n_group <= 64,
+ * 1 <= topk_group <= n_group, top_k <= topk_group * epg; without: top_k <= num_experts.  One launch. */
+typedef struct fi_moe_route_sigmoid_params {
+  const void* logits;     /* [num_tokens, num_experts] f32 / bf16 */
+  const void* bias;       /* [num_experts] f32 / bf16; may be NULL for FI_MOE_ROUTING_LLAMA4 only */
+  int32_t* topk_ids;      /* out [num_tokens, top_k] */
+  uint16_t* topk_weights; /* out [num_tokens, top_k] bf16 */
+  int32_t num_tokens, num_experts, top_k;
+  int32_t n_group, topk_group;
+  float routed_scaling_factor;
+  int32_t method;     /* FI_MOE_ROUTING_DEEPSEEK_V3 / FI_MOE_ROUTING_LLAMA4 */
+  int32_t dtype;      /* of logits: FI_DTYPE_F32 / FI_DTYPE_BF16 */
+  int32_t bias_dtype; /* of bias: FI_DTYPE_F32 / FI_DTYPE_BF16 */
+} fi_moe_route_sigmoid_params_t;
+
+FI_API int fi_moe_route_sigmoid(const fi_moe_route_sigmoid_params_t* params, fi_stream_t stream);
 
 /* Sorts the expanded indices by local expert and gathers the MXFP8 rows into the grouped GEMM's row operand.
  *   m_indptr[g] = number of slots routed to a local expert below local_expert_offset + g      (G = local_num_experts)
