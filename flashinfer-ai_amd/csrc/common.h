@@ -63,6 +63,15 @@ inline T ceil_div(T a, T b) {
   return (a + b - 1) / b;
 }
 
+// A row team: the threads of a workgroup that share one row of a row-indexed kernel (mxfp8_quantize.hip; gather, gated
+// activation and finalize of moe.hip) -- a power of two of them from one quad to the workgroup, enough for the row's
+// chunks when it can be (this is its log2); more chunks take further passes.  row_team() below is the device side.
+inline int row_team_log2(int64_t chunks, int threads) {
+  int l = 2;
+  while ((1 << l) < threads && (1ll << l) < chunks) ++l;
+  return l;
+}
+
 // 16-byte aligned bump allocator over a caller-owned workspace; returns byte offsets.
 // ref: AlignedAllocator, include/flashinfer/allocator.h:32-59.
 struct OffsetAllocator {
@@ -116,6 +125,18 @@ using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
 
 __device__ __forceinline__ uint32_t fast_div(uint32_t n, const FastDiv& fd) {
   return (__umulhi(n, fd.m) + n) >> fd.l;
+}
+
+struct RowTeam {
+  int lane, size;  // this thread in its team; threads per team (row_team_log2)
+  int64_t row;
+  bool past_end;   // row >= rows.  Whole quads leave: the size is a multiple of 4
+};
+template <int THREADS>
+__device__ __forceinline__ RowTeam row_team(int size_log2, int32_t rows) {
+  const int size = 1 << size_log2;
+  const int64_t row = (int64_t)blockIdx.x * (THREADS >> size_log2) + (threadIdx.x >> size_log2);
+  return RowTeam{(int)(threadIdx.x & (size - 1)), size, row, row >= rows};
 }
 
 constexpr float kLog2e = 1.44269504088896340736f;

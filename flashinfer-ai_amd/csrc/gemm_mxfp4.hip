@@ -4,7 +4,7 @@
 // (include/flashinfer/gemm/group_gemm_mxfp4_groupwise_sm100.cuh, flashinfer/gemm.py:2814-2949).
 //   d[r, j] = sum_k a[r, k] 2^(sa[r, k/32] - 127) . e2m1(b[g, j, k]) 2^(sb[g, j, k/32] - 127)   for r in group g
 //   a (cum_m, k) e4m3 / e5m2, b (G, n, k/2) bytes (k = 2i in the low nibble of byte i), scales E8M0 bytes in the
-//   swizzled layout of mx_layout.h, f32 accumulation, one rounding to f16 / bf16.
+//   swizzled layout of mx_layout.h (offsets and sizes), f32 accumulation, one rounding to f16 / bf16.
 //
 // Structure.  v_mfma_scale_f32_16x16x128_f8f6f4 multiplies a [16][128] by a [128][16] operand and scales every run of 32
 // k elements of every row by its own E8M0 byte: the MX format itself, so the weight nibbles and both tensors' scale
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(kMxThreads) group_gemm_mxfp4_kernel(const MxGe
   // ---- per-lane sources; rows past the edge of n or of the group re-read the last valid row and are masked at the store
   const uint8_t* const b_tile = p.b + ((int64_t)g * N + n0) * (K >> 1);
   const uint8_t* const a_tile = p.a + (int64_t)m0 * K;
-  const uint8_t* const sb_base = p.b_scale + (int64_t)g * ((N + 127) / 128 * 128) * nkb;
+  const uint8_t* const sb_base = p.b_scale + (int64_t)g * mx_sf_rows(N, true) * nkb;
   const uint8_t* const sa_base = p.a_scale + mx_sf_row_offset(m_begin, g) * nkb;
   uint32_t w_off[2], sw_off[2], a_off[MB], sa_off[MB];
 #pragma unroll
@@ -209,10 +209,10 @@ extern "C" FI_API int fi_group_gemm_mxfp8_mxfp4_nt_groupwise(const fi_group_gemm
                  ((uintptr_t)p->a_scale % 4) == 0 && ((uintptr_t)p->b_scale % 4) == 0,
              "%s: a / b must be 16-byte, d 8-byte and the scales 4-byte aligned", who);
   const int64_t nkb = p->k / kMxBlock;
-  const int64_t a_need = mx_sf_row_offset(p->cum_m, p->num_groups) * nkb;
+  const int64_t a_need = mx_sf_rows_grouped(p->cum_m, p->num_groups) * nkb;
   FI_REQUIRE(p->a_scale_bytes >= a_need, "%s: a_scale holds %lld bytes, %lld needed ((cum_m + 127 G) / 128 * 128 rows)", who,
              (long long)p->a_scale_bytes, (long long)a_need);
-  const int64_t b_need = (int64_t)p->num_groups * ((p->n + 127) / 128 * 128) * nkb;
+  const int64_t b_need = (int64_t)p->num_groups * mx_sf_rows(p->n, true) * nkb;
   FI_REQUIRE(p->b_scale_bytes >= b_need, "%s: b_scale holds %lld bytes, %lld needed (n padded to 128 per group)", who,
              (long long)p->b_scale_bytes, (long long)b_need);
   // 32-bit offsets inside a tile and inside a scale tensor

@@ -19,7 +19,8 @@
 // gated act. The quantiser's shape (mxfp8_quantize.hip) with the activation in front: a thread owns 8 output columns,
 //            the quad shares amax; the rule itself is mx_quant.h.
 // finalize.  A thread owns 8 columns of a token and walks its slots in order.
-// A row finds its group by a binary search over m_indptr, which every workgroup first copies to LDS.
+// gather, gated act. and finalize give a row to a row team (common.h).  A scale row finds its group and operand row by
+// mx_row_of_scale_row (mx_layout.h) on m_indptr, which every workgroup first copies to LDS.
 #include <math.h>
 
 #include "common.h"
@@ -366,19 +367,6 @@ __global__ void __launch_bounds__(64) moe_place_kernel(const MoePermuteArgs A) {
   }
 }
 
-// group of scale row s and the operand row it holds (-1: a padding row); indptr is the LDS copy of m_indptr
-__device__ __forceinline__ int moe_row_of_scale_row(const int32_t* indptr, int G, int64_t s, int cum_m, int& group) {
-  int lo = 0, hi = G;  // invariant: first scale row of lo <= s (< first scale row of hi)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (mx_sf_row_offset(indptr[mid], mid) <= s) lo = mid; else hi = mid;
-  }
-  group = lo;
-  const int begin = indptr[lo], end = indptr[lo + 1];
-  const int64_t r = s - mx_sf_row_offset(begin, lo);
-  return (begin >= 0 && r >= 0 && r < (int64_t)end - begin && begin + r < cum_m) ? (int)(begin + r) : -1;
-}
-
 __device__ __forceinline__ void moe_load_indptr(int32_t* dst, const int32_t* m_indptr, int G) {
   for (int i = threadIdx.x; i <= G; i += kMoeThreads) dst[i] = m_indptr[i];
   __syncthreads();
@@ -387,26 +375,24 @@ __device__ __forceinline__ void moe_load_indptr(int32_t* dst, const int32_t* m_i
 __global__ void __launch_bounds__(kMoeThreads) moe_gather_kernel(const MoePermuteArgs A) {
   __shared__ int32_t indptr[FI_MOE_MAX_EXPERTS + 1];
   moe_load_indptr(indptr, A.m_indptr, A.G);
-  const int tpr = 1 << A.tpr_log2;
-  const int t = threadIdx.x & (tpr - 1);
-  const int64_t s = (int64_t)blockIdx.x * (kMoeThreads >> A.tpr_log2) + (threadIdx.x >> A.tpr_log2);
-  if (s >= A.sf_rows) return;
+  const RowTeam team = row_team<kMoeThreads>(A.tpr_log2, A.sf_rows);
+  if (team.past_end) return;
   int group;
-  const int p = moe_row_of_scale_row(indptr, A.G, s, A.n, group);
+  const int p = mx_row_of_scale_row(indptr, A.G, team.row, A.n, group);
   int token = -1;
   if (p >= 0) {
     const int i = A.p2e[p];
     if (i >= 0 && i < A.n) token = i / A.top_k;
   }
   const int chunks = A.hidden / 16;  // 16 bytes each; 8 chunks are 128 k elements, one dword of scales
-  for (int c = t; c < chunks; c += tpr) {
+  for (int c = team.lane; c < chunks; c += team.size) {
     if (token >= 0)
       *(u32x4*)(A.x_out + (int64_t)p * A.hidden + c * 16) = *(const u32x4*)(A.x + (int64_t)token * A.hidden + c * 16);
     if ((c & 7) == 0) {
       const int kb = c >> 1;  // a multiple of 4
       uint32_t w = 0;
       if (token >= 0) w = *(const uint32_t*)(A.x_sf + (int64_t)token * A.nkb + kb);
-      *(uint32_t*)(A.sf_out + mx_sf_offset((int)s, kb, A.nkb)) = w;
+      *(uint32_t*)(A.sf_out + mx_sf_offset((int)team.row, kb, A.nkb)) = w;
     }
   }
 }
@@ -427,19 +413,17 @@ struct MoeActArgs {
 __global__ void __launch_bounds__(kMoeThreads) moe_gated_act_kernel(const MoeActArgs A) {
   __shared__ int32_t indptr[FI_MOE_MAX_EXPERTS + 1];
   moe_load_indptr(indptr, A.m_indptr, A.G);
-  const int tpr = 1 << A.tpr_log2;
-  const int t = threadIdx.x & (tpr - 1);
-  const int64_t s = (int64_t)blockIdx.x * (kMoeThreads >> A.tpr_log2) + (threadIdx.x >> A.tpr_log2);
-  if (s >= A.sf_rows) return;  // whole quads leave: tpr is a multiple of 4
+  const RowTeam team = row_team<kMoeThreads>(A.tpr_log2, A.sf_rows);
+  if (team.past_end) return;
   int g;
-  const int src = moe_row_of_scale_row(indptr, A.G, s, A.cum_m, g);
+  const int src = mx_row_of_scale_row(indptr, A.G, team.row, A.cum_m, g);
   const float alpha = A.alpha ? A.alpha[g] : 1.f;
   const float beta = A.beta ? A.beta[g] : 0.f;
   const float limit = A.limit ? A.limit[g] : INFINITY;
   const int I = A.inter;
   const uint16_t* const xr = A.x + (int64_t)max(src, 0) * 2 * I;
   const float* const br = A.bias ? A.bias + (int64_t)g * 2 * I : nullptr;
-  for (int cc = t; cc < I / 8; cc += tpr) {  // I / 8 is a multiple of 16: the lanes of a quad stay together
+  for (int cc = team.lane; cc < I / 8; cc += team.size) {  // I / 8 is a multiple of 16: the lanes of a quad stay together
     const int col = cc * 8;
     float v[8];
 #pragma unroll
@@ -467,9 +451,9 @@ __global__ void __launch_bounds__(kMoeThreads) moe_gated_act_kernel(const MoeAct
         v[j] = gt * (1.0f / (1.0f + expf(-alpha * gt))) * l;
       }
     }
-    const int e = mx_e4m3_exponent(mx_quad_amax(v));
+    const int e = mx_e4m3_exponent(mx_quad_max(mx_amax8(v)));
     if (src >= 0) *(u32x2*)(A.q + (int64_t)src * I + col) = mx_e4m3_pack8(v, e);
-    if ((cc & 3) == 0) A.sf[mx_sf_offset((int)s, cc >> 2, A.nkb)] = src >= 0 ? (uint8_t)(e + 127) : (uint8_t)0;
+    if ((cc & 3) == 0) A.sf[mx_sf_offset((int)team.row, cc >> 2, A.nkb)] = src >= 0 ? (uint8_t)(e + 127) : (uint8_t)0;
   }
 }
 
@@ -487,10 +471,9 @@ struct MoeFinalizeArgs {
 __global__ void __launch_bounds__(kMoeThreads) moe_finalize_kernel(const MoeFinalizeArgs A) {
   __shared__ int32_t indptr[FI_MOE_MAX_EXPERTS + 1];
   if (A.bias) moe_load_indptr(indptr, A.m_indptr, A.G);
-  const int tpr = 1 << A.tpr_log2;
-  const int t = threadIdx.x & (tpr - 1);
-  const int64_t token = (int64_t)blockIdx.x * (kMoeThreads >> A.tpr_log2) + (threadIdx.x >> A.tpr_log2);
-  if (token >= A.num_tokens) return;
+  const RowTeam team = row_team<kMoeThreads>(A.tpr_log2, A.num_tokens);
+  if (team.past_end) return;
+  const int64_t token = team.row;
   int rows[FI_MOE_MAX_TOP_K], groups[FI_MOE_MAX_TOP_K];
   float w[FI_MOE_MAX_TOP_K];
 #pragma unroll
@@ -514,7 +497,7 @@ __global__ void __launch_bounds__(kMoeThreads) moe_finalize_kernel(const MoeFina
       }
     }
   }
-  for (int c = t; c < A.hidden / 8; c += tpr) {
+  for (int c = team.lane; c < A.hidden / 8; c += team.size) {
     const int col = c * 8;
     float acc[8];
 #pragma unroll
@@ -541,14 +524,16 @@ __global__ void __launch_bounds__(kMoeThreads) moe_finalize_kernel(const MoeFina
   }
 }
 
-// threads per row: a power of two from one quad to the workgroup, enough for the row's chunks when it can be
-static int moe_tpr_log2(int64_t chunks) {
-  int l = 2;
-  while ((1 << l) < kMoeThreads && (1ll << l) < chunks) ++l;
-  return l;
-}
-
 static bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p % a) == 0; }
+
+// the limits of both route entry points on num_experts and top_k
+static int moe_route_check(const char* who, int num_experts, int top_k) {
+  FI_REQUIRE(num_experts >= 1 && num_experts <= FI_MOE_MAX_EXPERTS, "%s: num_experts %d is not in [1, %d]", who, num_experts,
+             FI_MOE_MAX_EXPERTS);
+  FI_REQUIRE(top_k >= 1 && top_k <= FI_MOE_MAX_TOP_K && top_k <= num_experts,
+             "%s: top_k %d is not in [1, min(%d, num_experts %d)]", who, top_k, FI_MOE_MAX_TOP_K, num_experts);
+  return 0;
+}
 
 }  // namespace fi
 
@@ -558,10 +543,7 @@ extern "C" FI_API int fi_moe_route(const fi_moe_route_params_t* p, fi_stream_t s
   FI_REQUIRE(p, "moe_route: null params");
   FI_REQUIRE(p->num_tokens >= 0 && p->num_experts >= 0 && p->top_k >= 0,
              "moe_route: negative size (num_tokens %d, num_experts %d, top_k %d)", p->num_tokens, p->num_experts, p->top_k);
-  FI_REQUIRE(p->num_experts >= 1 && p->num_experts <= FI_MOE_MAX_EXPERTS, "moe_route: num_experts %d is not in [1, %d]",
-             p->num_experts, FI_MOE_MAX_EXPERTS);
-  FI_REQUIRE(p->top_k >= 1 && p->top_k <= FI_MOE_MAX_TOP_K && p->top_k <= p->num_experts,
-             "moe_route: top_k %d is not in [1, min(%d, num_experts %d)]", p->top_k, FI_MOE_MAX_TOP_K, p->num_experts);
+  if (const int rc = moe_route_check("moe_route", p->num_experts, p->top_k)) return rc;
   FI_REQUIRE(p->method == FI_MOE_ROUTING_DEFAULT || p->method == FI_MOE_ROUTING_RENORMALIZE ||
                  p->method == FI_MOE_ROUTING_RENORMALIZE_NAIVE || p->method == FI_MOE_ROUTING_TOPK,
              "moe_route: routing method %d is not provided", p->method);
@@ -586,11 +568,7 @@ extern "C" FI_API int fi_moe_route_sigmoid(const fi_moe_route_sigmoid_params_t* 
   const bool deepseek = p->method == FI_MOE_ROUTING_DEEPSEEK_V3;
   FI_REQUIRE(deepseek || p->method == FI_MOE_ROUTING_LLAMA4, "moe_route_sigmoid: routing method %d is not provided",
              p->method);
-  FI_REQUIRE(p->num_experts >= 1 && p->num_experts <= FI_MOE_MAX_EXPERTS,
-             "moe_route_sigmoid: num_experts %d is not in [1, %d]", p->num_experts, FI_MOE_MAX_EXPERTS);
-  FI_REQUIRE(p->top_k >= 1 && p->top_k <= FI_MOE_MAX_TOP_K && p->top_k <= p->num_experts,
-             "moe_route_sigmoid: top_k %d is not in [1, min(%d, num_experts %d)]", p->top_k, FI_MOE_MAX_TOP_K,
-             p->num_experts);
+  if (const int rc = moe_route_check("moe_route_sigmoid", p->num_experts, p->top_k)) return rc;
   FI_REQUIRE(p->dtype == FI_DTYPE_F32 || p->dtype == FI_DTYPE_BF16, "moe_route_sigmoid: dtype %d is not f32 or bf16",
              p->dtype);
   const bool groups = deepseek && p->n_group > 1;
@@ -653,7 +631,7 @@ extern "C" FI_API int fi_moe_permute_mxfp8(const fi_moe_permute_params_t* p, fi_
   if (p->num_tokens == 0) return 0;
   const int64_t n = (int64_t)p->num_tokens * p->top_k;
   const int64_t G = p->local_num_experts;
-  const int64_t sf_rows = mx_sf_row_offset(n, G);
+  const int64_t sf_rows = mx_sf_rows_grouped(n, G);
   FI_REQUIRE(sf_rows < (1ll << 31), "moe_permute_mxfp8: too many rows");
   FI_REQUIRE(p->topk_ids && p->x && p->x_sf && p->m_indptr && p->expanded_to_permuted && p->x_permuted && p->sf_permuted &&
                  p->workspace, "moe_permute_mxfp8: null tensor");
@@ -686,7 +664,7 @@ extern "C" FI_API int fi_moe_permute_mxfp8(const fi_moe_permute_params_t* p, fi_
   a.packed = p->packed != 0;
   a.num_blocks = (int32_t)num_blocks;
   a.sf_rows = (int32_t)sf_rows;
-  a.tpr_log2 = moe_tpr_log2(p->hidden / 16);
+  a.tpr_log2 = row_team_log2(p->hidden / 16, kMoeThreads);
   hipStream_t st = (hipStream_t)stream;
   moe_count_kernel<<<dim3((uint32_t)num_blocks), dim3(64), 0, st>>>(a);
   moe_scan_kernel<<<dim3(1), dim3(FI_MOE_MAX_EXPERTS), 0, st>>>(a);
@@ -707,7 +685,7 @@ extern "C" FI_API int fi_moe_gated_act_mxfp8(const fi_moe_gated_act_params_t* p,
   FI_REQUIRE(p->intermediate > 0 && p->intermediate % 128 == 0,
              "moe_gated_act_mxfp8: intermediate %d must be a positive multiple of 128", p->intermediate);
   if (p->cum_m == 0) return 0;
-  const int64_t sf_rows = mx_sf_row_offset(p->cum_m, p->num_groups);
+  const int64_t sf_rows = mx_sf_rows_grouped(p->cum_m, p->num_groups);
   FI_REQUIRE(sf_rows < (1ll << 31), "moe_gated_act_mxfp8: too many rows");
   FI_REQUIRE(p->x && p->m_indptr && p->q && p->sf, "moe_gated_act_mxfp8: null tensor");
   FI_REQUIRE(aligned(p->x, 16) && aligned(p->q, 8) && (!p->bias || aligned(p->bias, 16)),
@@ -729,7 +707,7 @@ extern "C" FI_API int fi_moe_gated_act_mxfp8(const fi_moe_gated_act_params_t* p,
   a.nkb = (int32_t)nkb;
   a.G = p->num_groups;
   a.sf_rows = (int32_t)sf_rows;
-  a.tpr_log2 = moe_tpr_log2(p->intermediate / 8);
+  a.tpr_log2 = row_team_log2(p->intermediate / 8, kMoeThreads);
   const uint32_t grid = (uint32_t)ceil_div<int64_t>(sf_rows, kMoeThreads >> a.tpr_log2);
   moe_gated_act_kernel<<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
   FI_HIP_CALL(hipGetLastError());
@@ -763,7 +741,7 @@ extern "C" FI_API int fi_moe_finalize(const fi_moe_finalize_params_t* p, fi_stre
   a.hidden = p->hidden;
   a.G = p->num_groups;
   a.rows = p->rows;
-  a.tpr_log2 = moe_tpr_log2(p->hidden / 8);
+  a.tpr_log2 = row_team_log2(p->hidden / 8, kMoeThreads);
   const uint32_t grid = (uint32_t)ceil_div<int64_t>(p->num_tokens, kMoeThreads >> a.tpr_log2);
   moe_finalize_kernel<<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
   FI_HIP_CALL(hipGetLastError());

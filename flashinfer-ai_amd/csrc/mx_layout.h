@@ -1,5 +1,6 @@
-// Where the E8M0 scale bytes of an MX operand live: the one place the quantiser (mxfp8_quantize.hip) and the MXFP4
-// grouped GEMM (gemm_mxfp4.hip) share.  One scale byte covers 32 consecutive k elements of one row.
+// Where the E8M0 scale bytes of an MX operand live and how many there are: the one place the quantisers
+// (mxfp8_quantize.hip, mxfp4_quantize.hip), the MXFP4 grouped GEMM (gemm_mxfp4.hip) and the MoE stages (moe.hip) share;
+// flashinfer/_mx.py is the Python side.  One scale byte covers 32 consecutive k elements of one row.
 //
 // Swizzled "128x4" layout (ref: get_sf_out_offset_128x4, csrc/nv_internal/tensorrt_llm/kernels/quantization.cuh:649-688):
 // rows pad to 128, k blocks to 4; a [128 rows][4 blocks] tile is 512 bytes, stored as [row % 32][(row % 128) / 32][kb % 4].
@@ -29,7 +30,28 @@ FI_MX_HD int64_t mx_sf_offset(int r, int kb, int nkb) {
   return ((int64_t)(r >> 7) * k_tiles + (kb >> 2)) * 512 + (r & 31) * 16 + ((r & 127) >> 5) * 4 + (kb & 3);
 }
 
-// first scale row of group g whose first operand row is m_begin; with (cum_m, G) the row count of the whole tensor
+// first scale row of group g whose first operand row is m_begin
 FI_MX_HD int64_t mx_sf_row_offset(int64_t m_begin, int64_t g) { return (m_begin + g * 127) / 128 * 128; }
+
+// rows and k blocks of a scale tensor as stored, padding included; the grouped layout ends where a group G would begin
+template <typename T>
+FI_MX_HD T mx_sf_rows(T m, bool swizzled) { return swizzled ? (m + 127) / 128 * 128 : m; }
+FI_MX_HD int64_t mx_sf_rows_grouped(int64_t cum_m, int64_t G) { return mx_sf_row_offset(cum_m, G); }
+template <typename T>
+FI_MX_HD T mx_sf_kblocks(T nkb, bool swizzled) { return swizzled ? (nkb + 3) / 4 * 4 : nkb; }
+
+// group of scale row s of the grouped layout and the operand row it holds (-1: a padding row, also one in front of the
+// first group or of a row at or past cum_m); m_indptr (G + 1 entries) is in global memory or a copy in LDS
+FI_MX_HD int mx_row_of_scale_row(const int32_t* m_indptr, int G, int64_t s, int cum_m, int& group) {
+  int lo = 0, hi = G;  // invariant: first scale row of lo <= s (< first scale row of hi)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (mx_sf_row_offset(m_indptr[mid], mid) <= s) lo = mid; else hi = mid;
+  }
+  group = lo;
+  const int begin = m_indptr[lo], end = m_indptr[lo + 1];
+  const int64_t r = s - mx_sf_row_offset(begin, lo);
+  return (begin >= 0 && r >= 0 && r < (int64_t)end - begin && begin + r < cum_m) ? (int)(begin + r) : -1;
+}
 
 }  // namespace fi

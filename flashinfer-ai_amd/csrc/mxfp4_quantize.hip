@@ -3,28 +3,24 @@
 // ref: cvt_warp_fp16_to_fp4<Type, 32, true>, csrc/nv_internal/tensorrt_llm/kernels/quantization.cuh:427-499;
 // block_scale_interleave_kernel, csrc/nv_internal/cpp/kernels/quantization.cu; Python flashinfer/fp4_quantization.py:525-830.
 //
-// Rule.  Per block of 32: amax = max |x|; e = the smallest integer in [-127, 127] with 6 . 2^e >= amax (amax = 0:
-// e = -127); scale byte = e + 127; code = e2m1(x . 2^-e), round to nearest, ties to even.  The multiplication by a
-// power of two is exact and |x . 2^-e| <= 6, so the conversion never saturates.  e is read off the f32 bits of
-// amax = f . 2^E, 1 <= f < 2: 6 = 1.5 . 2^2, so e = E - 2 when f <= 1.5 (mantissa field <= 0x400000) and E - 1
-// otherwise -- an integer compare, no log2.  (The reference multiplies by an approximate reciprocal of 6 and rounds
-// the quotient's exponent up; at amax exactly 6 . 2^e its hardware may give e + 1.  The compare here is exact: see
-// fi_mi355.h.  In this UE8M0 branch the reference does not use its global scale, and neither does this kernel.)
+// Rule: mx_quant.h, with 6 the largest e2m1 magnitude, the pinned difference from the reference included;
+// code = e2m1(x . 2^-e), round to nearest, ties to even.  (In this UE8M0 branch the reference does not use its global
+// scale, and neither does this kernel.)
 // Two codes share a byte, element 2i in the low nibble of byte i, bit 3 of a code is the sign.
 //
 // Conversion.  v_cvt_scalef32_pk_fp4_f32 on the values already multiplied by 2^-e, with the instruction's own scale
 // operand at 1.0: two f32 -> one byte of two codes.  tools/probe_cvt_fp4.hip records what the instruction does on
 // the card.
 //
-// Shape.  One pass, as mxfp8_quantize.hip: a thread owns 8 consecutive elements (one 16-byte load, one 4-byte
-// store), the 4 threads of a block of 32 are the 4 lanes of a quad and share amax by two quad-permute moves.  The
-// kernel is indexed by the (row, k block) pairs of the SCALE tensor, padding included in both, so that every byte of
-// the scale buffer is written (padding as 0) and the caller needs no memset.  The pairs are one flat range, a quad
-// per pair and kMx4Pairs pairs per quad.  (The MXFP8 kernel gives a row to a team of threads that loops over the
-// row's blocks; here no lane idles when the blocks of a row do not fill the team.)  Every group of `rows` input
-// rows has its own scale rows (swizzled: padded to 128 and swizzled on their own).
+// Shape.  One pass with the threads and quads of mx_quant.h (one 16-byte load, one 4-byte store per thread).  The
+// kernel is indexed by the (row, k block) pairs of the SCALE tensor, padding included in both (the sizes are
+// mx_layout.h's), so that every byte of the scale buffer is written (padding as 0) and the caller needs no memset.
+// The pairs are one flat range, a quad per pair and kMx4Pairs pairs per quad.  (The MXFP8 kernel gives a row to a
+// team of threads that loops over the row's blocks; here no lane idles when the blocks of a row do not fill the
+// team.)  Every group of `rows` input rows has its own scale rows (swizzled: padded to 128 and swizzled on their own).
 #include "common.h"
 #include "mx_layout.h"
+#include "mx_quant.h"
 
 namespace fi {
 
@@ -77,15 +73,9 @@ __global__ void __launch_bounds__(kMx4QuantThreads) mxfp4_quantize_kernel(const 
 #pragma unroll
   for (int u = 0; u < kMx4Pairs; ++u) {
     if (!live[u]) continue;
-    float amax = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[u][j]));
-    amax = in[u] ? amax : 0.f;
-    amax = fmaxf(amax, lane_xor<1>(amax));
-    amax = fmaxf(amax, lane_xor<2>(amax));
-    const uint32_t bits = __builtin_bit_cast(uint32_t, amax);
-    int e = (int)(bits >> 23) - 127 - 2 + ((bits & 0x7fffffu) > 0x400000u ? 1 : 0);
-    e = min(max(e, -127), 127);
+    float amax = mx_amax8(v[u]);
+    amax = in[u] ? amax : 0.f;  // a padding lane holds input bytes, not zeros
+    const int e = mx_e2m1_exponent(mx_quad_max(amax));
     const float scale = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);  // 2^-e; e <= 126 for 16-bit inputs
     if (in[u]) {
       uint32_t w = 0;
@@ -144,8 +134,8 @@ extern "C" FI_API int fi_mxfp4_quantize(const fi_mxfp4_quantize_params_t* p, fi_
              "mxfp4_quantize: unknown scale layout %d", p->sf_layout);
   const bool swizzled = p->sf_layout == FI_MX_SF_SWIZZLED_128X4;
   const int64_t nkb = p->k / kMxBlock;
-  const int64_t nkb_loop = swizzled ? ceil_div<int64_t>(nkb, 4) * 4 : nkb;
-  const int64_t sf_rows = swizzled ? ceil_div<int64_t>(p->rows, 128) * 128 : (int64_t)p->rows;
+  const int64_t nkb_loop = mx_sf_kblocks(nkb, swizzled);
+  const int64_t sf_rows = mx_sf_rows<int64_t>(p->rows, swizzled);
   const int64_t items = sf_rows * p->num_groups;
   if (items == 0 || nkb_loop == 0) return 0;
   FI_REQUIRE(items < (1ll << 31), "mxfp4_quantize: too many rows");
@@ -184,8 +174,8 @@ extern "C" FI_API int fi_mx_sf_interleave(const fi_mx_sf_interleave_params_t* p,
   FI_REQUIRE(p, "mx_sf_interleave: null params");
   FI_REQUIRE(p->num_groups >= 0 && p->rows >= 0 && p->cols >= 0,
              "mx_sf_interleave: negative size (num_groups %d, rows %d, cols %d)", p->num_groups, p->rows, p->cols);
-  const int64_t k_tiles = ceil_div<int64_t>(p->cols, 4);
-  const int64_t group_words = ceil_div<int64_t>(p->rows, 128) * 128 * k_tiles;
+  const int64_t k_tiles = mx_sf_kblocks<int64_t>(p->cols, true) / 4;
+  const int64_t group_words = mx_sf_rows<int64_t>(p->rows, true) * k_tiles;
   if (group_words == 0 || p->num_groups == 0) return 0;
   FI_REQUIRE(group_words < (1ll << 31), "mx_sf_interleave: tensor too large");
   const int64_t words = group_words * p->num_groups;

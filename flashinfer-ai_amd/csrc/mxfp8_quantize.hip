@@ -2,18 +2,13 @@
 // ref: cvt_warp_fp16_to_mxfp8, csrc/nv_internal/tensorrt_llm/kernels/quantization.cuh:586-647; Python
 // flashinfer/fp8_quantization.py:179-212.
 //
-// Rule (the device code is mx_quant.h, shared with the MoE layer's gated activation).  Per block of 32: amax = max |x|;
-// e = the smallest integer in [-127, 127] with 448 . 2^e >= amax (amax = 0: e = -127); scale byte = e + 127;
-// q = e4m3(x . 2^-e), round to nearest even.  The multiplication by a power of two is exact and |x . 2^-e| <= 448, so
-// the conversion never saturates.  (The reference multiplies by an approximate reciprocal of 448 and rounds the
-// quotient's exponent up; at amax exactly 448 . 2^e its hardware may give e + 1.  The compare here is exact: see
-// fi_mi355.h.)
+// Rule: mx_quant.h, with 448 the largest e4m3 magnitude, the pinned difference from the reference included.
 //
-// Shape.  One pass: a thread owns 8 consecutive elements (one 16-byte load, one 8-byte store), the 4 threads of a
-// block of 32 are the 4 lanes of a quad and share amax by two quad-permute moves.  The kernel is indexed by the rows
-// of the SCALE tensor, padding included, and by its k blocks, padding included, so that every byte of the scale
-// buffer is written (padding as 0) and the caller needs no memset.  In the grouped layout (mx_layout.h) a scale
-// row finds its group by a binary search over m_indptr on the device.
+// Shape.  One pass with the threads and quads of mx_quant.h (one 16-byte load, one 8-byte store per thread).  The kernel
+// is indexed by the rows of the SCALE tensor and by its k blocks, padding included in both (the sizes are
+// mx_layout.h's), so that every byte of the scale buffer is written (padding as 0) and the caller needs no memset; a
+// row belongs to a row team (common.h).  In the grouped layout a scale row finds its operand row by mx_row_of_scale_row
+// (mx_layout.h) on the m_indptr in global memory; the scale rows of no group, also in front of the first, are padding.
 #include <algorithm>
 
 #include "common.h"
@@ -37,15 +32,14 @@ struct MxQuantArgs {
   int32_t items;     // sf_rows, plus m for the grouped layout (rows outside every group still get their q)
   int32_t num_groups;
   int32_t swizzled;
-  int32_t tpr_log2;  // threads per row
+  int32_t tpr_log2;  // the row team (common.h)
 };
 
 template <int DT>
 __global__ void __launch_bounds__(kMxQuantThreads) mxfp8_quantize_kernel(const MxQuantArgs A) {
-  const int tpr = 1 << A.tpr_log2;
-  const int t = threadIdx.x & (tpr - 1);
-  const int64_t item = (int64_t)blockIdx.x * (kMxQuantThreads >> A.tpr_log2) + (threadIdx.x >> A.tpr_log2);
-  if (item >= A.items) return;  // whole quads leave: tpr is a multiple of 4
+  const RowTeam team = row_team<kMxQuantThreads>(A.tpr_log2, A.items);
+  if (team.past_end) return;
+  const int64_t item = team.row;
 
   int src = -1;     // input row, -1: a padding row of the scale tensor
   int64_t s = -1;   // scale row, -1: none (grouped layout, a row past m_indptr[G])
@@ -54,14 +48,8 @@ __global__ void __launch_bounds__(kMxQuantThreads) mxfp8_quantize_kernel(const M
     if (A.m_indptr == nullptr) {
       src = item < A.m ? (int)item : -1;
     } else {
-      int lo = 0, hi = A.num_groups;  // invariant: first scale row of lo <= s (< first scale row of hi)
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (mx_sf_row_offset(A.m_indptr[mid], mid) <= s) lo = mid; else hi = mid;
-      }
-      const int begin = A.m_indptr[lo], end = A.m_indptr[lo + 1];
-      const int64_t r = s - mx_sf_row_offset(begin, lo);
-      src = (begin >= 0 && r < (int64_t)end - begin && begin + r < A.m) ? (int)(begin + r) : -1;
+      int group;
+      src = mx_row_of_scale_row(A.m_indptr, A.num_groups, s, A.m, group);
     }
   } else {
     // rows of no group (below m_indptr[0], at or past m_indptr[G]) get their q here, without a scale row
@@ -70,13 +58,13 @@ __global__ void __launch_bounds__(kMxQuantThreads) mxfp8_quantize_kernel(const M
   }
 
   const uint16_t* const xr = A.x + (int64_t)max(src, 0) * A.x_stride;
-  for (int cc = t; cc < A.nkb_loop * 4; cc += tpr) {
+  for (int cc = team.lane; cc < A.nkb_loop * 4; cc += team.size) {
     const int col = cc * 8;
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = 0.f;
     if (src >= 0 && col < A.k) load_16bit<DT, 8>(xr + col, v);
-    const int e = mx_e4m3_exponent(mx_quad_amax(v));
+    const int e = mx_e4m3_exponent(mx_quad_max(mx_amax8(v)));
     if (src >= 0 && col < A.k_pad) *(u32x2*)(A.q + (int64_t)src * A.k_pad + col) = mx_e4m3_pack8(v, e);
     if (s >= 0 && (cc & 3) == 0) {
       const int kb = cc >> 2;
@@ -107,9 +95,8 @@ extern "C" FI_API int fi_mxfp8_quantize(const fi_mxfp8_quantize_params_t* p, fi_
   FI_REQUIRE(k_pad < (1ll << 30), "mxfp8_quantize: k too large");
   const bool swizzled = p->sf_layout == FI_MX_SF_SWIZZLED_128X4;
   const int64_t nkb = k_pad / kMxBlock;
-  const int64_t nkb_loop = swizzled ? ceil_div<int64_t>(nkb, 4) * 4 : nkb;
-  const int64_t sf_rows = grouped ? mx_sf_row_offset(p->m, p->num_groups)
-                                  : (swizzled ? ceil_div<int64_t>(p->m, 128) * 128 : (int64_t)p->m);
+  const int64_t nkb_loop = mx_sf_kblocks(nkb, swizzled);
+  const int64_t sf_rows = grouped ? mx_sf_rows_grouped(p->m, p->num_groups) : mx_sf_rows<int64_t>(p->m, swizzled);
   const int64_t items = sf_rows + (grouped ? p->m : 0);
   if (items == 0 || k_pad == 0) return 0;
   FI_REQUIRE(sf_rows < (1ll << 31) && items < (1ll << 31), "mxfp8_quantize: too many rows");
@@ -136,11 +123,8 @@ extern "C" FI_API int fi_mxfp8_quantize(const fi_mxfp8_quantize_params_t* p, fi_
   a.items = (int32_t)items;
   a.num_groups = p->num_groups;
   a.swizzled = swizzled;
-  // threads per row: a power of two from one quad to the workgroup, enough for the row's chunks when it can be
-  int tpr_log2 = 2;
-  while ((1 << tpr_log2) < kMxQuantThreads && (1ll << tpr_log2) < nkb_loop * 4) ++tpr_log2;
-  a.tpr_log2 = tpr_log2;
-  const int64_t rows_per_block = kMxQuantThreads >> tpr_log2;
+  a.tpr_log2 = row_team_log2(nkb_loop * 4, kMxQuantThreads);
+  const int64_t rows_per_block = kMxQuantThreads >> a.tpr_log2;
   const uint32_t grid = (uint32_t)ceil_div<int64_t>(items, rows_per_block);
   if (p->dtype == FI_DTYPE_F16)
     mxfp8_quantize_kernel<FI_DTYPE_F16><<<dim3(grid), dim3(kMxQuantThreads), 0, (hipStream_t)stream>>>(a);

@@ -23,9 +23,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .fp8_quantization import _ceil_to, _linear_scales
+from ._mx import BLOCK, linear_scales, sf_shape
 
-_BLOCK = 32
 _E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 
 
@@ -84,8 +83,9 @@ def fp4_quantize(
     k = input.shape[-1]
     assert k % sf_vec_size == 0
     m = input.numel() // k if k else 0
-    nkb = k // _BLOCK
-    sf_size = _ceil_to(m, 128) * _ceil_to(nkb, 4) if is_sf_swizzled_layout else m * nkb
+    nkb = k // BLOCK
+    sf_rows, sf_blocks = sf_shape(m, nkb, bool(is_sf_swizzled_layout))
+    sf_size = sf_rows * sf_blocks
     if nkb and sf_size % nkb != 0:
         raise ValueError(f"{sf_size} swizzled scale bytes do not reshape to (-1, {nkb}): use k % 128 == 0 or the linear layout")
     x_q = torch.empty((*input.shape[:-1], k // 2), dtype=torch.uint8, device=input.device)
@@ -118,7 +118,7 @@ def mxfp4_quantize_grouped(input: torch.Tensor) -> Tuple[torch.Tensor, torch.Ten
     if k % 128 != 0:
         raise ValueError(f"k = {k} must be a multiple of 128 for the grouped layout")
     b = torch.empty((G, n, k // 2), dtype=torch.uint8, device=input.device)
-    b_scale = torch.empty((G, _ceil_to(n, 128), k // _BLOCK), dtype=torch.uint8, device=input.device)
+    b_scale = torch.empty((G, *sf_shape(n, k // BLOCK)), dtype=torch.uint8, device=input.device)
     _quantize_into(input.reshape(G * n, k), b.view(G * n, k // 2), b_scale, G, True)
     return b, b_scale
 
@@ -134,7 +134,7 @@ def block_scale_interleave(unswizzled_sf: torch.Tensor) -> torch.Tensor:
     x = unswizzled_sf.contiguous()
     rows, cols = x.shape[-2:]
     groups = x.shape[0] if x.dim() == 3 else 1
-    out = torch.empty((groups * _ceil_to(rows, 128) * _ceil_to(cols, 4),), dtype=torch.uint8, device=x.device)
+    out = torch.empty((groups, *sf_shape(rows, cols)), dtype=torch.uint8, device=x.device).view(-1)
     p = _lib.fi_mx_sf_interleave_params_t(input=x.data_ptr(), output=out.data_ptr(), output_bytes=out.numel(),
                                           num_groups=groups, rows=rows, cols=cols)
     with torch.cuda.device(x.device):
@@ -157,7 +157,7 @@ def _dequantize(packed: torch.Tensor, sf: torch.Tensor) -> torch.Tensor:
     """codes ``[m, k / 2]`` times the scale bytes ``[m, k / 32]``, as float32 (every product is exact in float64)."""
     m, k = packed.shape[0], packed.shape[1] * 2
     scale = torch.exp2(sf.double() - 127.0).unsqueeze(-1)
-    return (_e2m1_to_float(packed).view(m, k // _BLOCK, _BLOCK) * scale).view(m, k).to(torch.float32)
+    return (_e2m1_to_float(packed).view(m, k // BLOCK, BLOCK) * scale).view(m, k).to(torch.float32)
 
 
 def e2m1_and_ufp8sf_scale_to_float(
@@ -178,10 +178,10 @@ def e2m1_and_ufp8sf_scale_to_float(
         raise RuntimeError("e2m1_and_ufp8sf_scale_to_float works on CPU tensors (move them with .cpu())")
     if e2m1_tensor.dtype != torch.uint8 or ufp8_scale_tensor.dtype != torch.uint8:
         raise ValueError("e2m1_tensor and ufp8_scale_tensor must be uint8")
-    if e2m1_tensor.dim() != 2 or e2m1_tensor.shape[1] % (_BLOCK // 2) != 0:
-        raise ValueError(f"e2m1_tensor must be 2D (m, k / 2) with k a multiple of {_BLOCK}, got shape {tuple(e2m1_tensor.shape)}")
-    m, nkb = e2m1_tensor.shape[0], e2m1_tensor.shape[1] * 2 // _BLOCK
-    return _dequantize(e2m1_tensor, _linear_scales(ufp8_scale_tensor, m, nkb, is_sf_swizzled_layout))
+    if e2m1_tensor.dim() != 2 or e2m1_tensor.shape[1] % (BLOCK // 2) != 0:
+        raise ValueError(f"e2m1_tensor must be 2D (m, k / 2) with k a multiple of {BLOCK}, got shape {tuple(e2m1_tensor.shape)}")
+    m, nkb = e2m1_tensor.shape[0], e2m1_tensor.shape[1] * 2 // BLOCK
+    return _dequantize(e2m1_tensor, linear_scales(ufp8_scale_tensor, m, nkb, is_sf_swizzled_layout))
 
 
 def mxfp4_dequantize(a_fp4: torch.Tensor, a_sf: torch.Tensor) -> torch.Tensor:
@@ -198,15 +198,15 @@ def mxfp4_dequantize_host(
 ) -> torch.Tensor:
     """``weight`` (uint8 ``[m, k / 2]``) times its linear scales (uint8 ``[m, k / 32]``), as float32; pure torch on CPU
     tensors (ref: fp4_quantization.py:805-830)."""
-    if group_size != _BLOCK:
-        raise NotImplementedError(f"group_size {group_size}: MXFP4 has blocks of {_BLOCK}")
+    if group_size != BLOCK:
+        raise NotImplementedError(f"group_size {group_size}: MXFP4 has blocks of {BLOCK}")
     if weight.is_cuda or scale.is_cuda:
         raise RuntimeError("mxfp4_dequantize_host works on CPU tensors (move them with .cpu())")
     if weight.dtype != torch.uint8 or scale.dtype != torch.uint8:
         raise ValueError("weight and scale must be uint8")
-    if weight.dim() != 2 or weight.shape[1] % (_BLOCK // 2) != 0:
-        raise ValueError(f"weight must be 2D (m, k / 2) with k a multiple of {_BLOCK}, got shape {tuple(weight.shape)}")
-    m, nkb = weight.shape[0], weight.shape[1] * 2 // _BLOCK
+    if weight.dim() != 2 or weight.shape[1] % (BLOCK // 2) != 0:
+        raise ValueError(f"weight must be 2D (m, k / 2) with k a multiple of {BLOCK}, got shape {tuple(weight.shape)}")
+    m, nkb = weight.shape[0], weight.shape[1] * 2 // BLOCK
     if scale.numel() != m * nkb:
         raise ValueError(f"scale holds {scale.numel()} bytes, {m * nkb} needed")
     return _dequantize(weight, scale.reshape(m, nkb))

@@ -16,37 +16,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-
-_BLOCK = 32
-
-
-def _ceil_to(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
-
-
-def _sf_offset(r: torch.Tensor, kb: torch.Tensor, nkb: int) -> torch.Tensor:
-    """Byte of (row, k block) in the swizzled "128x4" layout (include/fi_mi355.h, csrc/mx_layout.h)."""
-    return (r // 128) * ((nkb + 3) // 4) * 512 + (kb // 4) * 512 + (r % 32) * 16 + ((r % 128) // 32) * 4 + kb % 4
-
-
-def _linear_scales(scale_tensor: torch.Tensor, m: int, nkb: int, swizzled: bool) -> torch.Tensor:
-    """The ``[m, nkb]`` scale bytes of a CPU scale tensor in the linear or the swizzled layout (padding is not read)."""
-    flat = scale_tensor.reshape(-1)
-    need = _ceil_to(m, 128) * _ceil_to(nkb, 4) if swizzled else m * nkb
-    if flat.numel() < need:
-        raise ValueError(f"the scale tensor holds {flat.numel()} bytes, {need} needed")
-    if not swizzled:
-        return flat[: m * nkb].view(m, nkb)
-    r = torch.arange(m).view(-1, 1).expand(m, nkb)
-    kb = torch.arange(nkb).view(1, -1).expand(m, nkb)
-    return flat[_sf_offset(r, kb, nkb).reshape(-1)].view(m, nkb)
-
-
-def sf_row_offset(m_begin: int, group: int) -> int:
-    """First scale row of ``group`` whose rows start at ``m_begin`` in the grouped layout; ``sf_row_offset(cum_m, G)`` is
-    the row count of the whole scale tensor."""
-    return (m_begin + 127 * group) // 128 * 128
-
+from ._mx import BLOCK, ceil_to, linear_scales, sf_row_offset, sf_shape
 
 def _check_input(input: torch.Tensor, alignment: int) -> None:
     _lib.require_gpu_tensor(input, "input")
@@ -54,9 +24,9 @@ def _check_input(input: torch.Tensor, alignment: int) -> None:
         raise ValueError(f"input has dtype {input.dtype}, expected float16 or bfloat16")
     if input.dim() < 1:
         raise ValueError("input must have at least one dim")
-    assert input.shape[-1] % _BLOCK == 0
-    if alignment <= 0 or alignment % _BLOCK != 0:
-        raise ValueError(f"alignment {alignment} must be a positive multiple of {_BLOCK}")
+    assert input.shape[-1] % BLOCK == 0
+    if alignment <= 0 or alignment % BLOCK != 0:
+        raise ValueError(f"alignment {alignment} must be a positive multiple of {BLOCK}")
 
 
 def _quantize_into(x: torch.Tensor, q: torch.Tensor, sf: torch.Tensor, swizzled: bool, alignment: int,
@@ -89,11 +59,10 @@ def mxfp8_quantize(
     _check_input(input, alignment)
     k = input.shape[-1]
     m = input.numel() // k if k else 0
-    k_pad = _ceil_to(k, alignment)
-    nkb = k_pad // _BLOCK
+    k_pad = ceil_to(k, alignment)
+    nkb = k_pad // BLOCK
     x_q = torch.empty((*input.shape[:-1], k_pad), dtype=torch.float8_e4m3fn, device=input.device)
-    sf_size = _ceil_to(m, 128) * _ceil_to(nkb, 4) if is_sf_swizzled_layout else m * nkb
-    sf = torch.empty((sf_size,), dtype=torch.uint8, device=input.device)
+    sf = torch.empty(sf_shape(m, nkb, bool(is_sf_swizzled_layout)), dtype=torch.uint8, device=input.device).view(-1)
     _quantize_into(input.reshape(m, k), x_q.view(m, k_pad), sf, bool(is_sf_swizzled_layout), alignment)
     return x_q, sf
 
@@ -107,7 +76,7 @@ def mxfp8_quantize_grouped(input: torch.Tensor, m_indptr: torch.Tensor) -> Tuple
     ``((cum_m + 127 G) // 128 * 128, k // 32)`` in the grouped swizzled layout, padding as 0.
     Rows of no group (below ``m_indptr[0]``, at or past ``m_indptr[-1]``) are quantised too; they have no scale row.
     """
-    _check_input(input, _BLOCK)
+    _check_input(input, BLOCK)
     _lib.require_gpu_tensor(m_indptr, "m_indptr")
     if input.dim() != 2:
         raise ValueError(f"input must be 2D (cum_m, k), got shape {tuple(input.shape)}")
@@ -116,10 +85,9 @@ def mxfp8_quantize_grouped(input: torch.Tensor, m_indptr: torch.Tensor) -> Tuple
     if m_indptr.dtype != torch.int32 or m_indptr.dim() != 1 or m_indptr.shape[0] < 2:
         raise ValueError("m_indptr must be a 1D int32 tensor of G + 1 >= 2 entries")
     cum_m, k = input.shape
-    rows = sf_row_offset(cum_m, m_indptr.shape[0] - 1)
     x_q = torch.empty((cum_m, k), dtype=torch.float8_e4m3fn, device=input.device)
-    a_scale = torch.empty((rows, k // _BLOCK), dtype=torch.uint8, device=input.device)
-    _quantize_into(input, x_q, a_scale, True, _BLOCK, m_indptr.contiguous())
+    a_scale = torch.empty(sf_shape(cum_m, k // BLOCK, groups=m_indptr.shape[0] - 1), dtype=torch.uint8, device=input.device)
+    _quantize_into(input, x_q, a_scale, True, BLOCK, m_indptr.contiguous())
     return x_q, a_scale
 
 
@@ -132,14 +100,14 @@ def mxfp8_dequantize_host(
     CPU tensors (ref: fp8_quantization.py:215-239)."""
     if input.is_cuda or scale_tensor.is_cuda:
         raise RuntimeError("mxfp8_dequantize_host works on CPU tensors (move them with .cpu())")
-    if input.dim() != 2 or input.shape[1] % _BLOCK != 0:
-        raise ValueError(f"input must be 2D (m, k) with k a multiple of {_BLOCK}, got shape {tuple(input.shape)}")
+    if input.dim() != 2 or input.shape[1] % BLOCK != 0:
+        raise ValueError(f"input must be 2D (m, k) with k a multiple of {BLOCK}, got shape {tuple(input.shape)}")
     if scale_tensor.dtype != torch.uint8:
         raise ValueError(f"scale_tensor has dtype {scale_tensor.dtype}, expected uint8")
     if input.dtype == torch.uint8:
         input = input.view(torch.float8_e4m3fn)
     m, k = input.shape
-    nkb = k // _BLOCK
-    sf = _linear_scales(scale_tensor, m, nkb, is_sf_swizzled_layout)
+    nkb = k // BLOCK
+    sf = linear_scales(scale_tensor, m, nkb, is_sf_swizzled_layout)
     scale = torch.exp2(sf.double() - 127.0).unsqueeze(-1)
-    return (input.to(torch.float32).double().view(m, nkb, _BLOCK) * scale).view(m, k).to(torch.float32)
+    return (input.to(torch.float32).double().view(m, nkb, BLOCK) * scale).view(m, k).to(torch.float32)

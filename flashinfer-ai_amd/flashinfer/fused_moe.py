@@ -36,10 +36,9 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import _lib
-from .fp8_quantization import sf_row_offset
+from ._mx import BLOCK, contiguous_aligned, scale_bytes, sf_shape
 from .gemm import _group_gemm_mxfp4_into
 
-_BLOCK = 32
 _MAX_EXPERTS = 512
 _MAX_TOP_K = 8
 
@@ -134,16 +133,6 @@ def _check_routing(routing_method_type: int, top_k: int, num_experts: int, routi
     return int(method), n_group, topk_group, 1.0 if routed_scaling_factor is None else float(routed_scaling_factor)
 
 
-def _bytes(t: torch.Tensor) -> torch.Tensor:
-    """E8M0 scale bytes given as uint8 or float8_e4m3fn: either is read as bytes."""
-    return t if t.dtype == torch.uint8 else t.view(torch.uint8)
-
-
-def _aligned(t: torch.Tensor, alignment: int) -> torch.Tensor:
-    t = t.contiguous()
-    return t if t.data_ptr() % alignment == 0 else t.clone()
-
-
 def moe_route(routing_logits: torch.Tensor, top_k: int, routing_method_type: int = RoutingMethodType.Default,
               routing_bias: Optional[torch.Tensor] = None, n_group: Optional[int] = None,
               topk_group: Optional[int] = None,
@@ -221,8 +210,8 @@ def _check_activations(hidden_states: torch.Tensor, hidden_states_scale: Optiona
     T, H = hidden_states.shape
     if H == 0 or H % 128 != 0:
         raise NotImplementedError(f"hidden_states has hidden size {H}: it must be a multiple of 128 (pad it)")
-    if hidden_states_scale.numel() != T * (H // _BLOCK):
-        raise ValueError(f"hidden_states_scale holds {hidden_states_scale.numel()} bytes, {T * (H // _BLOCK)} needed "
+    if hidden_states_scale.numel() != T * (H // BLOCK):
+        raise ValueError(f"hidden_states_scale holds {hidden_states_scale.numel()} bytes, {T * (H // BLOCK)} needed "
                          "(linear layout, one byte per 32 elements)")
 
 
@@ -236,8 +225,8 @@ def _permute_into(topk_ids: torch.Tensor, hidden_states: torch.Tensor, hidden_st
     n, G, dev = T * top_k, local_num_experts, hidden_states.device
     blocks = -(-n // _lib.FI_MOE_SORT_BLOCK)
     workspace = torch.empty((blocks * G + n,), dtype=torch.int32, device=dev)
-    ids, x = topk_ids.contiguous(), _aligned(hidden_states, 16)
-    x_sf = _aligned(_bytes(hidden_states_scale), 4)
+    ids, x = topk_ids.contiguous(), contiguous_aligned(hidden_states, 16)
+    x_sf = contiguous_aligned(scale_bytes(hidden_states_scale), 4)
     p = _lib.fi_moe_permute_params_t(
         topk_ids=ids.data_ptr(), x=x.data_ptr(), x_sf=x_sf.data_ptr(), m_indptr=m_indptr.data_ptr(),
         expanded_to_permuted=emap.data_ptr(), x_permuted=x_permuted.data_ptr(), sf_permuted=sf_permuted.data_ptr(),
@@ -289,7 +278,7 @@ def moe_permute_mxfp8(
     m_indptr = torch.empty((G + 1,), dtype=torch.int32, device=dev)
     emap = torch.empty((n,), dtype=torch.int32, device=dev)
     x_permuted = torch.empty((n, H), dtype=torch.float8_e4m3fn, device=dev)
-    sf_permuted = torch.empty((sf_row_offset(n, G) if n else 0, H // _BLOCK), dtype=torch.uint8, device=dev)
+    sf_permuted = torch.empty(sf_shape(n, H // BLOCK, groups=G) if n else (0, H // BLOCK), dtype=torch.uint8, device=dev)
     weights = torch.empty((T, top_k), dtype=torch.bfloat16, device=dev) if packed else None
     if T == 0:
         m_indptr.zero_()
@@ -317,7 +306,7 @@ def _gated_act_into(gemm1_output: torch.Tensor, m_indptr: torch.Tensor, bias: Op
     rows of ``q`` at or past ``m_indptr[-1]`` are not."""
     cum_m, two_i = gemm1_output.shape
     dev = gemm1_output.device
-    x = _aligned(gemm1_output, 16)
+    x = contiguous_aligned(gemm1_output, 16)
     p = _lib.fi_moe_gated_act_params_t(
         x=x.data_ptr(), m_indptr=m_indptr.contiguous().data_ptr(), bias=_lib.ptr(bias), alpha=_lib.ptr(alpha),
         beta=_lib.ptr(beta), limit=_lib.ptr(limit), q=q.data_ptr(), sf=sf.data_ptr(), sf_bytes=sf.numel(), cum_m=cum_m,
@@ -359,7 +348,7 @@ def moe_gated_act_mxfp8(
     _lib.require_gpu_tensor(gemm1_output, "gemm1_output")
     _lib.require_gpu_tensor(m_indptr, "m_indptr")
     bias = _per_expert(gemm1_bias, "gemm1_bias", (G, two_i))
-    bias = None if bias is None else _aligned(bias, 16)
+    bias = None if bias is None else contiguous_aligned(bias, 16)
     alpha, beta, limit = (
         None if t is None else t.contiguous() for t in (
             _per_expert(gemm1_alpha, "gemm1_alpha", (G,)),
@@ -367,7 +356,7 @@ def moe_gated_act_mxfp8(
             _per_expert(gemm1_clamp_limit, "gemm1_clamp_limit", (G,))))
     dev = gemm1_output.device
     q = torch.empty((cum_m, I), dtype=torch.float8_e4m3fn, device=dev)
-    sf = torch.empty((sf_row_offset(cum_m, G) if cum_m else 0, I // _BLOCK), dtype=torch.uint8, device=dev)
+    sf = torch.empty(sf_shape(cum_m, I // BLOCK, groups=G) if cum_m else (0, I // BLOCK), dtype=torch.uint8, device=dev)
     if cum_m == 0:
         return q, sf
     _gated_act_into(gemm1_output, m_indptr, bias, alpha, beta, limit, q, sf)
@@ -408,7 +397,7 @@ def moe_finalize(
         G = m_indptr.shape[0] - 1
         _lib.require_gpu_tensor(m_indptr, "m_indptr")
     bias = _per_expert(gemm2_bias, "gemm2_bias", (G, H))
-    bias = None if bias is None else _aligned(bias, 16)
+    bias = None if bias is None else contiguous_aligned(bias, 16)
     for t, name in ((gemm2_output, "gemm2_output"), (expert_weights, "expert_weights"),
                     (expanded_idx_to_permuted_idx, "expanded_idx_to_permuted_idx")):
         _lib.require_gpu_tensor(t, name)
@@ -420,7 +409,7 @@ def moe_finalize(
         _lib.require_gpu_tensor(output, "output")
     if T == 0:
         return output
-    y = _aligned(gemm2_output, 16)
+    y = contiguous_aligned(gemm2_output, 16)
     p = _lib.fi_moe_finalize_params_t(
         y=y.data_ptr(), weights=expert_weights.contiguous().data_ptr(),
         expanded_to_permuted=expanded_idx_to_permuted_idx.contiguous().data_ptr(), bias=_lib.ptr(bias),
@@ -442,10 +431,10 @@ def _check_weights(name: str, w: torch.Tensor, sf: torch.Tensor, G: int, n: int,
         raise NotImplementedError(
             f"{name} must be uint8 of shape ({G}, {n}, {k // 2}) (plain MXFP4, two e2m1 codes per byte, not shuffled), got "
             f"{w.dtype} {tuple(w.shape)}")
-    n_pad = (n + 127) // 128 * 128
-    if sf.dtype != torch.uint8 or sf.numel() != G * n_pad * (k // _BLOCK):
+    n_pad, nkb = sf_shape(n, k // BLOCK)
+    if sf.dtype != torch.uint8 or sf.numel() != G * n_pad * nkb:
         raise NotImplementedError(
-            f"{name}_scale must be uint8 with {G * n_pad * (k // _BLOCK)} bytes in the grouped swizzled layout, as "
+            f"{name}_scale must be uint8 with {G * n_pad * nkb} bytes in the grouped swizzled layout, as "
             f"mxfp4_quantize_grouped returns it, got {sf.dtype} with {sf.numel()}")
 
 

@@ -2,7 +2,8 @@
 stage on the device's own previous-stage output and exact where exactness is possible, then the whole layer: bit-identical
 to its stages called by hand, and against the oracle at the reference's own bar for this mode.
 
-Shapes are the smallest at which each kernel can still go wrong: H = I = 128 (one k tile) unless two tiles matter."""
+Shapes are the smallest at which each kernel can still go wrong: H = I = 128 (one k tile) unless two tiles matter, and
+one size past the 256-thread row team (H = 4224, I = 2176, H = 2056) for its second pass."""
 import functools
 
 import pytest
@@ -77,10 +78,9 @@ PERMUTE_CASES = {
 }
 
 
-def _check_permute(ids, offset, G, packed_weights=None):
+def _check_permute(ids, offset, G, packed_weights=None, H=128):
     F = _fm()
     T, top_k = ids.shape
-    H = 128
     x_q, x_sf = _activations(T, H, seed=T)
     n = T * top_k
     dev_ids = ids if packed_weights is None else M.pack_topk_ids(ids, packed_weights)
@@ -120,6 +120,9 @@ def test_permute_is_exact(case):
     if case == "empty_expert":
         assert 3 not in ids.tolist()
     _check_permute(ids, offset, G)
+    if case in ("empty_expert", "one_expert_crosses_a_scale_tile"):
+        # 264 sixteen-byte chunks, more than the 256-thread row team: its second pass writes the scale dword at k block 128
+        _check_permute(ids, offset, G, H=4224)
 
 
 def test_permute_takes_packed_ids():
@@ -132,6 +135,8 @@ def test_permute_takes_packed_ids():
 
 # ---- gated activation ---------------------------------------------------------------------------------------------------
 ACT_SEGMENTS = {"ragged": (4, 132, 0, 260), "one_group": (130,), "small": (3, 0, 1, 2, 0, 5, 1, 1)}
+# I = 2176: 272 chunks of 8 columns, a partial second pass of the 256-thread row team
+ACT_CASES = [(s, I) for s in sorted(ACT_SEGMENTS) for I in (128, 256)] + [("ragged", 2176), ("small", 2176)]
 
 
 def _e4m3_step(v: torch.Tensor) -> torch.Tensor:
@@ -156,8 +161,7 @@ def _act_case(segments, I, with_params):
 
 
 @pytest.mark.parametrize("with_params", [False, True], ids=["plain", "bias_alpha_beta_limit"])
-@pytest.mark.parametrize("I", [128, 256])
-@pytest.mark.parametrize("segments", sorted(ACT_SEGMENTS))
+@pytest.mark.parametrize("segments,I", ACT_CASES)
 def test_gated_activation_against_the_oracle(segments, I, with_params):
     F = _fm()
     segs = ACT_SEGMENTS[segments]
@@ -343,6 +347,30 @@ def test_finalize_on_the_devices_own_outputs(T, offset, G, with_params):
     plain = F.moe_finalize(y2, w, emap)
     want0, mag0 = M.finalize_ref(y_cpu, w.cpu(), emap.cpu(), top_k)
     assert bool(((plain.cpu().double() - want0).abs() <= 2.0 ** -8 * mag0).all())
+
+
+@pytest.mark.parametrize("with_bias", [False, True], ids=["plain", "bias"])
+@pytest.mark.parametrize("H", [8, 2056])
+def test_finalize_on_made_up_inputs(H, with_bias):
+    """The row team at its ends: H = 8 is one chunk of 8 columns (a one-quad team with three idle lanes), H = 2056 is 257
+    chunks (one lane of the 256-thread team takes a second pass).  T = 5, top_k = 2, G = 3 with an empty group; token 3
+    has no local slot."""
+    F = _fm()
+    T, top_k = 5, 2
+    g = torch.Generator().manual_seed(H + int(with_bias))
+    emap = torch.tensor([0, 3, -1, 4, 1, -1, -1, -1, 5, 2], dtype=torch.int32)
+    m_indptr = torch.tensor([0, 3, 3, 6], dtype=torch.int32)
+    y = torch.randn(T * top_k, H, generator=g).to(torch.bfloat16)  # rows 6 .. 9 are past the local count: never read
+    w = torch.randn(T, top_k, generator=g).to(torch.bfloat16)
+    bias = torch.randn(3, H, generator=g) if with_bias else None
+    out = F.moe_finalize(y.to(DEV), w.to(DEV), emap.to(DEV), None if bias is None else bias.to(DEV),
+                         m_indptr.to(DEV) if with_bias else None)
+    torch.cuda.synchronize()
+    assert out.shape == (T, H) and out.dtype == torch.bfloat16
+    want, mag = M.finalize_ref(y, w, emap, top_k, bias, m_indptr if with_bias else None)
+    err = (out.cpu().double() - want).abs()
+    assert bool((err <= 2.0 ** -8 * mag).all()), (err - 2.0 ** -8 * mag).max().item()
+    assert mag[[0, 1, 2, 4]].all() and not out.cpu()[3].view(torch.int16).any()  # exact zeros, +0
 
 
 # ---- graph capture --------------------------------------------------------------------------------------------------------

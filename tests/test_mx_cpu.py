@@ -88,9 +88,9 @@ def test_swizzled_offsets():
     assert flat.numel() == 256 * 8 and torch.equal(R.unswizzle(flat, 200, 6), sf)
     assert int((flat == 7).sum()) >= 256 * 8 - 200 * 6
     # the package's own copy of the function (mxfp8_dequantize_host) is the same function
-    from flashinfer import fp8_quantization as Q
+    from flashinfer import _mx
 
-    assert torch.equal(Q._sf_offset(r, kb, 6), R.sf_offset(r, kb, 6))
+    assert torch.equal(_mx.sf_offset(r, kb, 6), R.sf_offset(r, kb, 6))
 
 
 def test_grouped_scale_row_offsets():
@@ -118,6 +118,26 @@ def test_grouped_scale_row_offsets():
         assert torch.equal(R.unswizzle(grouped.reshape(-1)[off[g] * 12:], m, 12), sf[begin:begin + m])
         begin += m
     assert int((grouped == 254).sum()) >= 896 * 12 - 396 * 12
+
+
+def test_scale_tensor_sizes():
+    """flashinfer._mx.sf_shape sizes every scale tensor the package allocates or checks: it gives the byte counts of
+    the oracle's swizzle and group_swizzle_a, padding in both dimensions included, and it is the one function the
+    modules that size a scale tensor call."""
+    from flashinfer import _mx, fp4_quantization, fp8_quantization, fused_moe
+
+    for rows, nkb in ((1, 1), (127, 4), (128, 5), (129, 6), (200, 6), (300, 129)):
+        sf = torch.zeros(rows, nkb, dtype=torch.uint8)
+        assert _mx.sf_shape(rows, nkb, False) == (rows, nkb)  # linear
+        swz = _mx.sf_shape(rows, nkb, True)  # swizzled
+        assert swz[0] * swz[1] == R.swizzle(sf).numel() and swz[0] % 128 == 0 and swz[1] % 4 == 0
+    for ms in (MS, (130,), (0, 0, 5), (3, 0, 1, 2, 0, 5, 1, 1)):  # grouped
+        grouped = R.group_swizzle_a(torch.zeros(sum(ms), 12, dtype=torch.uint8), ms)
+        assert _mx.sf_shape(sum(ms), 12, groups=len(ms)) == tuple(grouped.shape)
+        assert _mx.sf_shape(sum(ms), 12, groups=len(ms))[0] == _mx.sf_row_offset(sum(ms), len(ms))
+    for module in (fp8_quantization, fp4_quantization, fused_moe):
+        assert module.sf_shape is _mx.sf_shape
+    assert fp8_quantization.sf_row_offset is _mx.sf_row_offset  # the public name
 
 
 def test_e2m1_decoding():

@@ -218,38 +218,42 @@ def test_quantiser_3d_and_strided_input():
 def test_quantiser_grouped_layout(dtype):
     from flashinfer import fp8_quantization as Q
 
-    ms, k = GROUPED, 384
-    x = _quant_input(sum(ms) + 8, k, dtype, 11)  # 8 rows past m_indptr[G]: quantised, without scales
-    q, a_scale = Q.mxfp8_quantize_grouped(x.cuda(), indptr_of(ms).cuda())
-    rows = (sum(ms) + 8 + 127 * len(ms)) // 128 * 128
-    assert a_scale.shape == (rows, k // 32) and a_scale.dtype == torch.uint8 and q.shape == x.shape
-    q, a_scale = q.cpu(), a_scale.cpu()
-    want_q, want_sf = R.mxfp8_quantize_ref(x)
-    assert torch.equal(q.view(torch.uint8), want_q.view(torch.uint8))
-    want_scale = torch.zeros(rows, k // 32, dtype=torch.uint8)
-    grouped = R.group_swizzle_a(want_sf[:sum(ms)], ms)
-    want_scale[:grouped.shape[0]] = grouped
-    assert torch.equal(a_scale, want_scale)  # padding rows and the rows of no group are 0
+    ms = GROUPED
+    for k in (384, 2176):  # 2176: 272 chunks of 8, a partial second pass of the 256-thread row team
+        x = _quant_input(sum(ms) + 8, k, dtype, 11)  # 8 rows past m_indptr[G]: quantised, without scales
+        q, a_scale = Q.mxfp8_quantize_grouped(x.cuda(), indptr_of(ms).cuda())
+        rows = (sum(ms) + 8 + 127 * len(ms)) // 128 * 128
+        assert a_scale.shape == (rows, k // 32) and a_scale.dtype == torch.uint8 and q.shape == x.shape
+        q, a_scale = q.cpu(), a_scale.cpu()
+        want_q, want_sf = R.mxfp8_quantize_ref(x)
+        assert torch.equal(q.view(torch.uint8), want_q.view(torch.uint8))
+        want_scale = torch.zeros(rows, k // 32, dtype=torch.uint8)
+        grouped = R.group_swizzle_a(want_sf[:sum(ms)], ms)
+        want_scale[:grouped.shape[0]] = grouped
+        assert torch.equal(a_scale, want_scale)  # padding rows and the rows of no group are 0
 
 
 def test_quantiser_grouped_layout_rows_of_no_group():
     """m_indptr need not start at 0 or end at cum_m: rows below m_indptr[0] and at or past m_indptr[G] belong to no
-    group; they are quantised like every other row and have no scale row."""
+    group; they are quantised like every other row and have no scale row.  With m_indptr[0] >= 128 (the second input)
+    whole scale rows lie in front of the first group: they are padding."""
     from flashinfer import fp8_quantization as Q
 
-    k, indptr = 128, [8, 12, 144]
-    x = _quant_input(150, k, torch.bfloat16, 13)
-    q, a_scale = Q.mxfp8_quantize_grouped(x.cuda(), torch.tensor(indptr, dtype=torch.int32).cuda())
-    q, a_scale = q.cpu(), a_scale.cpu()
-    want_q, want_sf = R.mxfp8_quantize_ref(x)
-    assert torch.equal(q.view(torch.uint8), want_q.view(torch.uint8))
-    rows = (150 + 127 * 2) // 128 * 128
-    want_scale = torch.zeros(rows * 4, dtype=torch.uint8)
-    for g in range(2):
-        first = (indptr[g] + 127 * g) // 128 * 128
-        piece = R.swizzle(want_sf[indptr[g]:indptr[g + 1]])
-        want_scale[first * 4: first * 4 + piece.numel()] = piece
-    assert torch.equal(a_scale, want_scale.view(rows, 4))
+    k = 128
+    for m, indptr in ((150, [8, 12, 144]), (140, [130, 134])):
+        G = len(indptr) - 1
+        x = _quant_input(m, k, torch.bfloat16, 13)
+        q, a_scale = Q.mxfp8_quantize_grouped(x.cuda(), torch.tensor(indptr, dtype=torch.int32).cuda())
+        q, a_scale = q.cpu(), a_scale.cpu()
+        want_q, want_sf = R.mxfp8_quantize_ref(x)
+        assert torch.equal(q.view(torch.uint8), want_q.view(torch.uint8))
+        rows = (m + 127 * G) // 128 * 128
+        want_scale = torch.zeros(rows * 4, dtype=torch.uint8)
+        for g in range(G):
+            first = (indptr[g] + 127 * g) // 128 * 128
+            piece = R.swizzle(want_sf[indptr[g]:indptr[g + 1]])
+            want_scale[first * 4: first * 4 + piece.numel()] = piece
+        assert torch.equal(a_scale, want_scale.view(rows, 4)), indptr
 
 
 # ---- e. pipeline, f. graph capture --------------------------------------------------------------------------------------

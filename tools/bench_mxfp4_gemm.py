@@ -28,7 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "flashinfer-ai_amd"))
 import torch
 
 import flashinfer
-from flashinfer import fp8_quantization
+from flashinfer import _mx, fp8_quantization
 
 DEV = torch.device("cuda", 0)
 FP8_PEAK = 5.0e15
@@ -46,7 +46,7 @@ def swizzle_b_scale(sf):
     n_pad = ceil_to(n, 128)
     r = torch.arange(n, device=sf.device).view(-1, 1).expand(n, nkb)
     kb = torch.arange(nkb, device=sf.device).view(1, -1).expand(n, nkb)
-    off = fp8_quantization._sf_offset(r, kb, nkb).reshape(-1)
+    off = _mx.sf_offset(r, kb, nkb).reshape(-1)
     out = torch.zeros(G, n_pad * nkb, dtype=torch.uint8, device=sf.device)
     out[:, off] = sf.reshape(G, -1)
     return out.view(G, n_pad, nkb)
