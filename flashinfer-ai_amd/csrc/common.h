@@ -221,6 +221,83 @@ __device__ __forceinline__ float group_sum(float x) {
   return x;
 }
 
+// ---- scans and reductions over a wave and over a workgroup ----
+// Only exact operations reduce here: maxima, and sums of integers.  A float sum over lanes has its bits fixed by its
+// order and stays with its kernel (group_sum above, the ladders of merge.hip, moe.hip and norm.hip); the one float sum
+// here is the scan, whose order is part of its definition.
+struct RedMax {
+  static __device__ __forceinline__ float of(float a, float b) { return fmaxf(a, b); }
+  static __device__ __forceinline__ uint32_t of(uint32_t a, uint32_t b) { return max(a, b); }
+};
+struct RedSum {
+  static __device__ __forceinline__ uint32_t of(uint32_t a, uint32_t b) { return a + b; }
+  static __device__ __forceinline__ int of(int a, int b) { return a + b; }
+};
+
+// OP over the 64 lanes, the result in every lane
+template <class OP, typename T>
+__device__ __forceinline__ T wave_reduce(T v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = OP::of(v, __shfl_xor(v, d, 64));
+  return v;
+}
+
+// Inclusive sum over the 64 lanes in lane order, by doubling: six steps, step d adding the partial sum that ends d
+// lanes below.  The association is fixed, so a float scan gives the same bits in every run.
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan(T v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T o = __shfl_up(v, d, 64);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+// The two workgroup forms, for a one-dimensional workgroup of WAVES waves and WAVES words of LDS at `wave_tot`.
+// Both publish one word per wave, barrier, read all the words, barrier.  The contract:
+//   - every thread of the workgroup makes the call, in uniform control flow (it holds two __syncthreads());
+//   - nobody reads wave_tot after the last barrier in front of the call: the call overwrites it without waiting;
+//   - the first barrier puts every LDS write made before the call in front of every LDS access made after it, and
+//     every LDS read made before the call in front of every LDS write made after it, so a caller may initialise or
+//     reuse other LDS words around the call without a barrier of its own;
+//   - the second barrier ends the reads of wave_tot: the scratch is free when the call returns, for the next call
+//     or for anything else.
+
+// Inclusive sum in thread order: the wave scan, then the totals of the waves in front added in wave order
+// (((t0 + t1) + ...) + own scan).  `total`, the sum over the workgroup in the same order, goes to every thread.
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_incl_scan(T v, T* wave_tot, T& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  v = wave_incl_scan(v);
+  if (lane == 63) wave_tot[wave] = v;
+  __syncthreads();
+  T base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) {
+    const T x = wave_tot[w];
+    if (w < wave) base += x;
+    tot += x;
+  }
+  __syncthreads();
+  total = tot;
+  return base + v;
+}
+
+// OP over the workgroup, the result in every thread
+template <int WAVES, class OP, typename T>
+__device__ __forceinline__ T block_reduce(T v, T* wave_tot) {
+  v = wave_reduce<OP>(v);
+  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T r = wave_tot[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) r = OP::of(r, wave_tot[w]);
+  __syncthreads();
+  return r;
+}
+
 // ---- storage-type unpack: 16 bytes -> VEC floats ----
 template <int DT>
 struct KVTraits;

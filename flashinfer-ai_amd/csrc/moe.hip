@@ -310,7 +310,7 @@ __global__ void __launch_bounds__(64) moe_count_kernel(const MoePermuteArgs A) {
 }
 
 __global__ void __launch_bounds__(FI_MOE_MAX_EXPERTS) moe_scan_kernel(const MoePermuteArgs A) {
-  __shared__ int32_t s[FI_MOE_MAX_EXPERTS];
+  __shared__ int32_t wave_tot[FI_MOE_MAX_EXPERTS / 64];
   const int e = threadIdx.x;
   int total = 0;
   if (e < A.G) {
@@ -321,16 +321,10 @@ __global__ void __launch_bounds__(FI_MOE_MAX_EXPERTS) moe_scan_kernel(const MoeP
       total += c;
     }
   }
-  s[e] = total;
-  __syncthreads();
-  for (int off = 1; off < FI_MOE_MAX_EXPERTS; off <<= 1) {
-    const int add = e >= off ? s[e - off] : 0;
-    __syncthreads();
-    s[e] += add;
-    __syncthreads();
-  }
-  if (e < A.G) A.m_indptr[e] = s[e] - total;
-  if (e == A.G - 1) A.m_indptr[A.G] = s[e];
+  int rows;  // threads past G add 0
+  const int incl = block_incl_scan<FI_MOE_MAX_EXPERTS / 64>(total, wave_tot, rows);
+  if (e < A.G) A.m_indptr[e] = incl - total;
+  if (e == 0) A.m_indptr[A.G] = rows;
 }
 
 __global__ void __launch_bounds__(64) moe_place_kernel(const MoePermuteArgs A) {

@@ -16,7 +16,7 @@
 //                  that thread's wave reads its chunks again (1/1024 of the row, one chunk per lane), scans the
 //                  chunk sums and picks the entry.  Entries of weight 0 are never returned; when rounding leaves
 //                  the target unreached the last positive entry is.
-//   block_scan     wave scan by __shfl_up, then the 16 wave totals summed in index order.
+//   block_incl_scan  (common.h) a wave scan in lane order, then the 16 wave totals summed in index order.
 //
 // Streaming loops issue four 16-byte loads per thread ahead of their use (for_chunks) and the kernels are held to 64
 // registers, so two workgroups stay resident per CU.  The select-based kernels pay for that cap with a few registers
@@ -74,48 +74,6 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t offset, 
   uint32_t r[4];
   philox4x32_10(seed, offset, row, j >> 2, r);
   return (float)(r[j & 3] >> 8) * 5.9604644775390625e-08f;
-}
-
-// ---- block primitives (fixed order) ----
-template <typename T>
-__device__ __forceinline__ T wave_incl_scan(T v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-template <typename T>
-__device__ __forceinline__ T block_incl_scan(T v, T* wave_tot, T& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = wave_incl_scan(v);
-  if (lane == 63) wave_tot[wave] = v;
-  __syncthreads();
-  T base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kSampWaves; ++w) {
-    const T x = wave_tot[w];
-    if (w < wave) base += x;
-    tot += x;
-  }
-  __syncthreads();
-  total = tot;
-  return base + v;
-}
-
-__device__ __forceinline__ float block_max(float v, float* wave_tot) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float m = wave_tot[0];
-#pragma unroll
-  for (int w = 1; w < kSampWaves; ++w) m = fmaxf(m, wave_tot[w]);
-  __syncthreads();
-  return m;
 }
 
 // ---- row access: chunk c = elements 4c .. 4c+3; entries past the row read as `fill` ----
@@ -204,7 +162,7 @@ __device__ uint32_t radix_select(const Row& row, KW kw, u64 target, SampSmem& sm
     const int b0 = nb - 1 - 2 * (int)threadIdx.x, b1 = b0 - 1;
     const u64 h0 = b0 >= 0 ? sm.hist[b0] : 0, h1 = b1 >= 0 ? sm.hist[b1] : 0;
     u64 tot;
-    const u64 inc = block_incl_scan<u64>(h0 + h1, sm.utot, tot);
+    const u64 inc = block_incl_scan<kSampWaves, u64>(h0 + h1, sm.utot, tot);
     const u64 exc = above + inc - h0 - h1;
     if (h0 != 0 && exc + h0 >= target) atomicMax(&sm.sel_bin, b0);
     if (h1 != 0 && exc + h0 + h1 >= target) atomicMax(&sm.sel_bin, b1);
@@ -269,8 +227,8 @@ __device__ int sample_weighted(W4 w4, int nc, float u, SampSmem& sm) {
     sm.sampled = -1;
     sm.last_valid = -1;
   }
-  float total;
-  const float inc = block_incl_scan<float>(m, sm.ftot, total);  // its barriers order the initialisation above
+  float total;  // the scan's first barrier orders the initialisation above (its contract, common.h)
+  const float inc = block_incl_scan<kSampWaves, float>(m, sm.ftot, total);
   const float target = u * total;
   if (last >= 0) atomicMax(&sm.last_valid, last);
   if (inc > target) atomicMin(&sm.winner, (int)threadIdx.x);
@@ -333,7 +291,7 @@ __device__ void sample_row(const fi_sampling_params_t& P, int bx, SampSmem& sm) 
     for_chunks(row.nc, [&](int c) { return row.load(c, -INFINITY); }, [&](int c, f32x4 x) {
       mx = fmaxf(mx, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));  // fmaxf drops NaN
     });
-    mx = block_max(mx, sm.ftot);
+    mx = block_reduce<kSampWaves, RedMax>(mx, sm.ftot);
     id = sample_weighted(
         [&](int c) {
           f32x4 x = row.load(c, -INFINITY);
@@ -347,7 +305,7 @@ __device__ void sample_row(const fi_sampling_params_t& P, int bx, SampSmem& sm) 
     for_chunks(row.nc, [&](int c) { return row.load(c, 0.f); }, [&](int c, f32x4 x) {
       mx = fmaxf(mx, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
     });
-    mx = block_max(mx, sm.ftot);
+    mx = block_reduce<kSampWaves, RedMax>(mx, sm.ftot);
     const float min_p = P.top_p_arr ? P.top_p_arr[pi] : P.top_p_val;
     const float thr = fminf(min_p, 1.f) * mx;  // min_p > 1 would keep nothing: the maximum always stays
     id = sample_weighted(
@@ -410,9 +368,9 @@ __device__ void transform_row(const fi_row_transform_params_t& P, int bx, SampSm
         m = mn;
       }
     });
-    const float mx = block_max(m, sm.ftot);
+    const float mx = block_reduce<kSampWaves, RedMax>(m, sm.ftot);
     float total;
-    block_incl_scan<float>(m > -INFINITY ? s * fast_exp2((m - mx) * sc) : 0.f, sm.ftot, total);
+    block_incl_scan<kSampWaves, float>(m > -INFINITY ? s * fast_exp2((m - mx) * sc) : 0.f, sm.ftot, total);
     const float inv = 1.f / total;
     for_chunks(row.nc, [&](int c) { return row.load(c, -INFINITY); }, [&](int c, f32x4 x) {
 #pragma unroll
@@ -438,7 +396,7 @@ __device__ void transform_row(const fi_row_transform_params_t& P, int bx, SampSm
       for (int j = 0; j < 4; ++j) s += (x[j] > 0.f && prob_key(x[j]) >= thr) ? x[j] : 0.f;
     });
     float total;
-    block_incl_scan<float>(s, sm.ftot, total);
+    block_incl_scan<kSampWaves, float>(s, sm.ftot, total);
     const float inv = 1.f / total;
     for_chunks(row.nc, [&](int c) { return row.load(c, 0.f); }, [&](int c, f32x4 x) {
 #pragma unroll

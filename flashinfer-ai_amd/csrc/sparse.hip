@@ -12,29 +12,6 @@ namespace fi {
 constexpr int kSparseThreads = 256;
 constexpr int kSparseWaves = kSparseThreads / 64;
 
-// Inclusive prefix sum of one int per thread over the workgroup: a shuffle scan inside each wave, the wave totals
-// through `wave_total` (LDS, kSparseWaves entries).  `total` receives the workgroup's sum.  Every thread must call it.
-__device__ __forceinline__ int workgroup_inclusive_scan(int x, int* wave_total, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  __syncthreads();  // the previous call's readers are done with wave_total
-  if (lane == 63) wave_total[wave] = x;
-  __syncthreads();
-  int base = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kSparseWaves; ++w) {
-    const int t = wave_total[w];
-    if (w < wave) base += t;
-    total += t;
-  }
-  return x + base;
-}
-
 // one workgroup per (head, block row): pages its selected column blocks hold
 __global__ void __launch_bounds__(kSparseThreads)
     block_mask_row_pages_kernel(const uint8_t* __restrict__ mask, const int32_t* __restrict__ col_sz,
@@ -46,8 +23,7 @@ __global__ void __launch_bounds__(kSparseThreads)
   int pages = 0;
   for (int c = threadIdx.x; c < NB; c += kSparseThreads)
     if (m[c]) pages += (int)fast_div((uint32_t)cs[c], granule);
-  int total;
-  workgroup_inclusive_scan(pages, wave_total, total);
+  const int total = block_reduce<kSparseWaves, RedSum>(pages, wave_total);
   if (threadIdx.x == 0) row_pages[row] = total;
 }
 
@@ -59,7 +35,7 @@ __global__ void __launch_bounds__(kSparseThreads)
     block_mask_to_page_indices_kernel(const uint8_t* __restrict__ mask, const int32_t* __restrict__ col_sz,
                                       const int32_t* __restrict__ kv_indptr, int32_t* __restrict__ kv_indices, int MB,
                                       int NB, FastDiv granule, int64_t head_pages, int64_t capacity) {
-  __shared__ int wave_total[2][kSparseWaves];
+  __shared__ int wave_total[kSparseWaves];
   __shared__ int out_end[kSparseThreads];  // end of the block's pages among this pass's output positions
   __shared__ int page_of[kSparseThreads];  // page number = page_of[block] + output position
   const int row = blockIdx.x, h = row / MB;
@@ -74,8 +50,9 @@ __global__ void __launch_bounds__(kSparseThreads)
     const int pages = c < NB ? (int)fast_div((uint32_t)cs[c], granule) : 0;
     const int emitted = (c < NB && m[c]) ? pages : 0;
     int pass_pages, pass_emitted;
-    const int pages_incl = workgroup_inclusive_scan(pages, wave_total[0], pass_pages);
-    const int emitted_incl = workgroup_inclusive_scan(emitted, wave_total[1], pass_emitted);
+    // the scans' barriers also stand between the previous pass's reads of out_end / page_of and the writes below
+    const int pages_incl = block_incl_scan<kSparseWaves>(pages, wave_total, pass_pages);
+    const int emitted_incl = block_incl_scan<kSparseWaves>(emitted, wave_total, pass_emitted);
     out_end[threadIdx.x] = emitted_incl;
     page_of[threadIdx.x] = first_page + (pages_incl - pages) - (emitted_incl - emitted);
     __syncthreads();
@@ -87,7 +64,6 @@ __global__ void __launch_bounds__(kSparseThreads)
       }
       if (out >= 0 && out + p < out_limit) kv_indices[out + p] = page_of[lo] + p;
     }
-    __syncthreads();  // before the next pass rewrites out_end / page_of
     first_page += pass_pages;
     out += pass_emitted;
   }

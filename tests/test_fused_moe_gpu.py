@@ -75,6 +75,8 @@ PERMUTE_CASES = {
     "several_placement_blocks": (lambda: _routed_ids(300, 8, 4, 4), 0, 8),
     "local_window": (lambda: _routed_ids(67, 8, 2, 5), 2, 3),
     "512_experts": (lambda: _routed_ids(40, 512, 8, 6), 0, 512),
+    # wave boundaries of the scan over the experts inside the window, the last wave partly filled (8 of 64)
+    "local_window_of_200": (lambda: _routed_ids(40, 512, 8, 8), 100, 200),
 }
 
 
@@ -119,6 +121,10 @@ def test_permute_is_exact(case):
     ids = build()
     if case == "empty_expert":
         assert 3 not in ids.tolist()
+    if case == "local_window_of_200":
+        rows = torch.tensor(M.segments(M.permute_ref(ids, offset, G)[0]))
+        for part in rows.split(64):  # every 64-expert range of the window has an empty and a non-empty expert
+            assert bool((part == 0).any()) and bool((part > 0).any())
     _check_permute(ids, offset, G)
     if case in ("empty_expert", "one_expert_crosses_a_scale_tile"):
         # 264 sixteen-byte chunks, more than the 256-thread row team: its second pass writes the scale dword at k block 128
