@@ -12,11 +12,9 @@
 #include <algorithm>
 
 #include "decode_plan.h"
+#include "plan_device.h"
 
 namespace fi {
-
-constexpr int kPlanThreads = 256;
-constexpr int kPlanWaves = kPlanThreads / 64;
 
 struct DevicePlanParams {
   const int32_t* block_tables;
@@ -40,12 +38,12 @@ struct DevicePlanParams {
   int32_t row_blocks;   // fill kernel: workgroups per block-table row
 };
 
-// tokens of request b the plan covers: the length clamped to what its block-table row can hold
+// tokens and pages of request b that the plan covers (plan_device.h)
 __device__ __forceinline__ int32_t planned_len(const DevicePlanParams& p, int b) {
-  return min(max(p.seq_lens[b], 0), p.max_blocks * p.page_size);
+  return planned_kv_len(p.seq_lens, b, p.max_blocks, p.page_size);
 }
 __device__ __forceinline__ uint32_t pages_of(const DevicePlanParams& p, int b) {
-  return ((uint32_t)planned_len(p, b) + (uint32_t)p.page_size - 1) / (uint32_t)p.page_size;
+  return pages_holding(planned_len(p, b), p.page_size);
 }
 
 __global__ __launch_bounds__(kPlanThreads) void decode_plan_scan_kernel(const DevicePlanParams p) {
@@ -119,7 +117,7 @@ __global__ __launch_bounds__(kPlanThreads) void decode_plan_scan_kernel(const De
     if (valid) {
       p.indptr[b] = before_pages + ip - np;
       p.o_indptr[b] = before_chunks + ic - nc;
-      p.last_page_len[b] = np > 0 ? len - (np - 1) * p.page_size : 0;
+      p.last_page_len[b] = last_page_tokens(len, np, p.page_size);
     }
   }
   if (tid == 0) {
@@ -166,8 +164,7 @@ __global__ __launch_bounds__(kPlanThreads) void decode_plan_fill_kernel(const De
   const int blk = (int)blockIdx.x - p.list_blocks;
   const int b = blk / p.row_blocks;
   const int j = (blk - b * p.row_blocks) * kPlanThreads + tid;
-  const int32_t begin = p.indptr[b];
-  if (j < p.indptr[b + 1] - begin) p.indices[begin + j] = p.block_tables[(int64_t)b * p.block_tables_stride + j];
+  compact_page_id(p.block_tables, p.block_tables_stride, p.indptr, p.indices, b, j);
 }
 
 struct DevicePlanLayout {

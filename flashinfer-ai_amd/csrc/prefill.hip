@@ -8,6 +8,7 @@
 
 #include "merge_kernel.h"
 #include "prefill_kernel.h"
+#include "prefill_plan.h"
 #include "prefill_qkvo_kernel.h"
 
 namespace fi {
@@ -62,17 +63,9 @@ struct BatchShape {
   int64_t total_q_tiles, max_kv_len;
 };
 
-// keys a request's chunks are cut from.  Sliding window: a q tile only walks the keys from its first row's window
-// start on (the kernel skips the rest), so chunks are cut from that span (ref: effective_kv_len_arr,
-// scheduler.cuh:561-567)
-static int64_t kv_span(int64_t kv_len, int64_t qo_len, bool causal, int window_left) {
-  const int64_t span = std::max<int64_t>(kv_len, 1);
-  return window_left < 0 ? span : std::min<int64_t>(span, (int64_t)window_left + (causal ? kTileQ : qo_len) + kTileKV);
-}
+static_assert(kPlanTileQ == kTileQ && kPlanTileKV == kTileKV, "prefill_plan.h restates the kernels' tile sizes");
 
-// resident workgroups (2 per CU) over the kv heads each item is launched for
-// (ref: max_batch_size_if_split = max_grid_size / num_kv_heads, scheduler.cuh:718)
-static int64_t resident_items(int num_kv_heads) {
+int64_t resident_items(int num_kv_heads) {
   return std::max<int64_t>((int64_t)fi_num_compute_units() * 2 / num_kv_heads, 1);
 }
 

@@ -510,13 +510,14 @@ class CUDAGraphBatchDecodeWithPagedKVCacheWrapper(BatchDecodeWithPagedKVCacheWra
         )
 
 
-def _device_plan_regions(workspace_buffer: torch.Tensor, plan: "_lib.fi_batch_decode_plan_device_params_t"):
+def _device_plan_regions(workspace_buffer: torch.Tensor, plan, workspace_fn: str = "fi_batch_decode_plan_device_workspace",
+                         name: str = "trtllm_batch_decode_with_kv_cache"):
     """Carve the int region (work list and CSR page table) and the float region (f32 partial states) a device plan
-    needs out of one workspace buffer, and write both into ``plan``.  ValueError, with the bytes needed, when the buffer
-    is too small."""
+    needs out of one workspace buffer, and write both into ``plan`` (the params of fi_batch_decode_plan_device or of
+    fi_batch_prefill_plan_device; ``workspace_fn`` is the C entry that sizes them).  ValueError, with the bytes needed,
+    when the buffer is too small."""
     int_bytes, float_bytes = C.c_size_t(), C.c_size_t()
-    _lib.check(_lib.lib().fi_batch_decode_plan_device_workspace(C.byref(plan), C.byref(int_bytes), C.byref(float_bytes)),
-               "trtllm_batch_decode_with_kv_cache")
+    _lib.check(getattr(_lib.lib(), workspace_fn)(C.byref(plan), C.byref(int_bytes), C.byref(float_bytes)), name)
     base, have = workspace_buffer.data_ptr(), _lib.nbytes(workspace_buffer)
     int_begin = -base % 16  # both regions 16-byte aligned, whatever the buffer's own alignment
     float_begin = int_begin + (int_bytes.value + 15) // 16 * 16
@@ -526,6 +527,58 @@ def _device_plan_regions(workspace_buffer: torch.Tensor, plan: "_lib.fi_batch_de
                          f"({int_bytes.value} for the work list and page table, {float_bytes.value} for partial states)")
     plan.int_ws, plan.int_ws_bytes = base + int_begin, int_bytes.value
     plan.float_ws, plan.float_ws_bytes = base + float_begin, have - float_begin
+
+
+# ---- argument checks the two plan-free calls share (this one and prefill.trtllm_batch_context_with_kv_cache) ----
+
+def _refuse_fp4_out_and_shared_kv(name: str, kv_cache, out, out_dtype, o_sf_scale, o_sf_vec_size) -> None:
+    """NotImplementedError, by name, for the reference's FP4 output forms and its cache with K and V shared."""
+    if out_dtype == "nvfp4" or o_sf_scale is not None or o_sf_vec_size is not None:
+        raise NotImplementedError(f"{name}: out_dtype='nvfp4' (o_sf_scale, o_sf_vec_size) is not supported")
+    if out is not None and not torch.is_tensor(out):
+        raise NotImplementedError(f"{name}: out of type {type(out).__name__} (FP4Tensor) is not supported")
+    if torch.is_tensor(kv_cache) and kv_cache.dim() == 5 and kv_cache.shape[1] == 1:
+        raise NotImplementedError(f"{name}: the [num_pages, 1, ...] kv_cache with K and V shared is not supported")
+
+
+def _hnd_cache_views(kv_cache) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(k_cache, v_cache) of ``[num_pages, 2, num_kv_heads, page_size, head_dim]`` or of a ``(k, v)`` tuple, on a GPU."""
+    if torch.is_tensor(kv_cache):
+        if kv_cache.dim() != 5 or kv_cache.shape[1] != 2:
+            raise ValueError("kv_cache must be [num_pages, 2, num_kv_heads, page_size, head_dim] or a (k, v) tuple")
+    elif not (isinstance(kv_cache, tuple) and len(kv_cache) == 2 and all(t.dim() == 4 for t in kv_cache)):
+        raise ValueError("a kv_cache tuple holds k and v, each [num_pages, num_kv_heads, page_size, head_dim]")
+    k_cache, v_cache = _unpack_paged_kv_cache(kv_cache, "HND")
+    _lib.require_gpu_tensor(k_cache, "kv_cache")
+    _lib.require_gpu_tensor(v_cache, "kv_cache")
+    return k_cache, v_cache
+
+
+def _check_block_tables_and_lens(block_tables, seq_lens, workspace_buffer, batch_size: int) -> torch.Tensor:
+    """The dense block table, the device-resident lengths (returned as int32) and the workspace of a plan-free call."""
+    if block_tables.dtype != torch.int32 or block_tables.dim() != 2 or block_tables.shape[0] != batch_size \
+            or block_tables.shape[1] == 0 or block_tables.stride(1) != 1:
+        raise ValueError(f"block_tables must be int32 [{batch_size}, max_blocks] with contiguous rows")
+    if seq_lens.dtype == torch.uint32:
+        seq_lens = seq_lens.view(torch.int32)
+    if seq_lens.dtype != torch.int32 or seq_lens.shape != (batch_size,) or not seq_lens.is_contiguous():
+        raise ValueError(f"seq_lens must be a contiguous int32 / uint32 tensor of shape [{batch_size}]")
+    if not workspace_buffer.is_contiguous():
+        raise ValueError("workspace_buffer must be contiguous")
+    return seq_lens
+
+
+def _one_sinks_tensor(sinks, num_qo_heads: int, device) -> Optional[torch.Tensor]:
+    """``sinks`` as one float32 ``[num_qo_heads]`` tensor: given so, or as a one-element list."""
+    if isinstance(sinks, (list, tuple)):
+        if len(sinks) != 1:
+            raise ValueError("sinks is one float32 [num_qo_heads] tensor, or a list holding that one tensor")
+        sinks = sinks[0]
+    if sinks is not None and (not torch.is_tensor(sinks) or sinks.dtype != torch.float32
+                              or sinks.shape != (num_qo_heads,) or not sinks.is_contiguous()
+                              or sinks.device != device):
+        raise ValueError(f"sinks must be a contiguous float32 tensor of shape [{num_qo_heads}] on {device}")
+    return sinks
 
 
 def trtllm_batch_decode_with_kv_cache(
@@ -577,39 +630,17 @@ def trtllm_batch_decode_with_kv_cache(
     if query.dtype in (torch.float8_e4m3fn, torch.float8_e5m2):
         raise NotImplementedError("trtllm_batch_decode_with_kv_cache: an fp8 query is not supported "
                                   "(float16 / bfloat16)")
-    if out_dtype == "nvfp4" or o_sf_scale is not None or o_sf_vec_size is not None:
-        raise NotImplementedError("trtllm_batch_decode_with_kv_cache: out_dtype='nvfp4' (o_sf_scale, o_sf_vec_size) "
-                                  "is not supported")
-    if out is not None and not torch.is_tensor(out):
-        raise NotImplementedError(f"trtllm_batch_decode_with_kv_cache: out of type {type(out).__name__} "
-                                  "(FP4Tensor) is not supported")
-    if torch.is_tensor(kv_cache) and kv_cache.dim() == 5 and kv_cache.shape[1] == 1:
-        raise NotImplementedError("trtllm_batch_decode_with_kv_cache: the [num_pages, 1, ...] kv_cache with K and V "
-                                  "shared is not supported")
+    _refuse_fp4_out_and_shared_kv("trtllm_batch_decode_with_kv_cache", kv_cache, out, out_dtype, o_sf_scale,
+                                  o_sf_vec_size)
     for name, t in (("query", query), ("workspace_buffer", workspace_buffer), ("block_tables", block_tables),
                     ("seq_lens", seq_lens)):
         _lib.require_gpu_tensor(t, name)
-    if torch.is_tensor(kv_cache):
-        if kv_cache.dim() != 5 or kv_cache.shape[1] != 2:
-            raise ValueError("kv_cache must be [num_pages, 2, num_kv_heads, page_size, head_dim] or a (k, v) tuple")
-    elif not (isinstance(kv_cache, tuple) and len(kv_cache) == 2 and all(t.dim() == 4 for t in kv_cache)):
-        raise ValueError("a kv_cache tuple holds k and v, each [num_pages, num_kv_heads, page_size, head_dim]")
-    k_cache, v_cache = _unpack_paged_kv_cache(kv_cache, "HND")
-    _lib.require_gpu_tensor(k_cache, "kv_cache")
-    _lib.require_gpu_tensor(v_cache, "kv_cache")
+    k_cache, v_cache = _hnd_cache_views(kv_cache)
     if query.dtype not in (torch.float16, torch.bfloat16) or query.dim() != 3 or query.stride(-1) != 1:
         raise ValueError("query must be a float16 / bfloat16 [batch_size, num_qo_heads, head_dim] tensor, contiguous "
                          "in head_dim")
     batch_size, num_qo_heads, head_dim = query.shape
-    if block_tables.dtype != torch.int32 or block_tables.dim() != 2 or block_tables.shape[0] != batch_size \
-            or block_tables.shape[1] == 0 or block_tables.stride(1) != 1:
-        raise ValueError(f"block_tables must be int32 [{batch_size}, max_blocks] with contiguous rows")
-    if seq_lens.dtype == torch.uint32:
-        seq_lens = seq_lens.view(torch.int32)
-    if seq_lens.dtype != torch.int32 or seq_lens.shape != (batch_size,) or not seq_lens.is_contiguous():
-        raise ValueError(f"seq_lens must be a contiguous int32 / uint32 tensor of shape [{batch_size}]")
-    if not workspace_buffer.is_contiguous():
-        raise ValueError("workspace_buffer must be contiguous")
+    seq_lens = _check_block_tables_and_lens(block_tables, seq_lens, workspace_buffer, batch_size)
     if out_dtype is not None and canonicalize_torch_dtype(out_dtype) != query.dtype:
         raise ValueError(f"out_dtype {out_dtype} differs from the query's {query.dtype}")
     if out is None:
@@ -618,14 +649,7 @@ def trtllm_batch_decode_with_kv_cache(
         check_shape_dtype_device(out, query.shape, query.dtype, query.device, "out")
         if not out.is_contiguous():
             raise ValueError("out must be contiguous")
-    if isinstance(sinks, (list, tuple)):
-        if len(sinks) != 1:
-            raise ValueError("sinks is one float32 [num_qo_heads] tensor, or a list holding that one tensor")
-        sinks = sinks[0]
-    if sinks is not None and (not torch.is_tensor(sinks) or sinks.dtype != torch.float32
-                              or sinks.shape != (num_qo_heads,) or not sinks.is_contiguous()
-                              or sinks.device != query.device):
-        raise ValueError(f"sinks must be a contiguous float32 tensor of shape [{num_qo_heads}] on {query.device}")
+    sinks = _one_sinks_tensor(sinks, num_qo_heads, query.device)
 
     max_blocks = block_tables.shape[1]
     # the cache view; its three page-table pointers are set below, once the planner has said where it writes them

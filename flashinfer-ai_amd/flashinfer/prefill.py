@@ -16,6 +16,13 @@ import torch
 
 from . import _lib
 from ._wrapper import BatchAttentionWrapper
+from .decode import (
+    _check_block_tables_and_lens,
+    _device_plan_regions,
+    _hnd_cache_views,
+    _one_sinks_tensor,
+    _refuse_fp4_out_and_shared_kv,
+)
 from .page import get_seq_lens
 from .quantization import packbits, segment_packbits
 from .utils import (
@@ -827,3 +834,143 @@ class BatchPrefillWithRaggedKVCacheWrapper(BatchAttentionWrapper):
 
     def end_forward(self) -> None:
         pass
+
+
+def trtllm_batch_context_with_kv_cache(
+    query: torch.Tensor,
+    kv_cache: Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]],
+    workspace_buffer: torch.Tensor,
+    block_tables: torch.Tensor,
+    seq_lens: torch.Tensor,
+    max_q_len: int,
+    max_kv_len: int,
+    bmm1_scale: float,
+    bmm2_scale: float,
+    batch_size: int,
+    cum_seq_lens_q: torch.Tensor,
+    cum_seq_lens_kv: torch.Tensor,
+    window_left: int = -1,
+    out: Optional[torch.Tensor] = None,
+    out_dtype: Optional[Union[torch.dtype, str]] = None,
+    o_sf_scale: Optional[float] = None,
+    o_sf_vec_size: Optional[int] = None,
+    enable_pdl: Optional[bool] = None,
+    sinks: Optional[List[torch.Tensor]] = None,
+) -> torch.Tensor:
+    r"""Plan-free causal prefill / chunked prefill / mixed step over a paged KV cache (ref: flashinfer/prefill.py
+    :3314-3334): a dense block table, device-resident kv lengths and query offsets instead of ``plan()``.  The work list,
+    the page table and the query offsets the kernels read are written by kernels on the current stream
+    (fi_batch_prefill_plan_device), then the kernels of :class:`BatchPrefillWithPagedKVCacheWrapper` run on them: two
+    planner launches, the prefill launch, and the merge when the plan splits the kv axis.  There is no host
+    synchronisation and nothing is allocated by a length, so the whole call can be captured in a graph; a replay plans
+    again from what ``block_tables``, ``seq_lens`` and ``cum_seq_lens_q`` hold then.
+
+    query : ``[num_tokens, num_qo_heads, head_dim]``, float16 or bfloat16 (rows may be strided), or float8_e4m3fn with
+        an e4m3 cache; then ``out`` or ``out_dtype`` must name float16 or bfloat16.
+    kv_cache : one tensor ``[num_pages, 2, num_kv_heads, page_size, head_dim]`` (the HND layout), or a ``(k, v)`` tuple
+        of ``[num_pages, num_kv_heads, page_size, head_dim]`` tensors; the query's dtype, or fp8 under a 16-bit query.
+    workspace_buffer : one buffer on the query's device; the work list, the page table and the f32 partial states are
+        carved out of it.  It need not be zeroed.  ValueError names the bytes needed when it is too small.
+    block_tables : int32 ``[batch_size, max_blocks]``; row ``b`` lists the pages of request ``b``.
+    seq_lens : int32 (or uint32) ``[batch_size]`` on the device: kv tokens per request, the new ones included.  A
+        length beyond ``max_blocks * page_size`` is CLAMPED to it, a negative one to 0 (the host never sees the values).
+    max_q_len : unused.  max_kv_len : checked against ``max_blocks * page_size``; otherwise unused.
+    bmm1_scale : the full scale of the logits (``sm_scale``).  bmm2_scale : multiplies the output.
+    batch_size : must equal ``block_tables.shape[0]``.
+    cum_seq_lens_q : int32 ``[batch_size + 1]`` on the device: request ``b`` owns the query rows
+        ``cum_seq_lens_q[b]:cum_seq_lens_q[b + 1]``, which sit at the END of its ``seq_lens[b]`` kv tokens (causal).
+        The kernels read a copy clamped to ``[0, num_tokens]`` and made non-decreasing.  Rows of ``out`` from
+        ``cum_seq_lens_q[batch_size]`` on are left untouched.
+    cum_seq_lens_kv : accepted and not read.
+    window_left : sliding window, ``-1`` for none.
+    out : optional output ``[num_tokens, num_qo_heads, head_dim]``.  out_dtype : its dtype (a 16-bit query's own).
+    sinks : optional float32 ``[num_qo_heads]`` attention-sink logits (or a one-element list holding them); float16 /
+        bfloat16 queries only.
+    enable_pdl : accepted and ignored.
+
+    Not offered (NotImplementedError): ``out_dtype="nvfp4"`` / an FP4Tensor ``out`` / ``o_sf_scale`` /
+    ``o_sf_vec_size``, an fp8 output, the ``[num_pages, 1, ...]`` cache with K and V shared, and an e5m2 query.
+    """
+    name = "trtllm_batch_context_with_kv_cache"
+    if query.dtype == torch.float8_e5m2:
+        raise NotImplementedError(f"{name}: an e5m2 query is not supported (float16 / bfloat16 / float8_e4m3fn)")
+    _refuse_fp4_out_and_shared_kv(name, kv_cache, out, out_dtype, o_sf_scale, o_sf_vec_size)
+    o_dtype = out.dtype if out is not None else None if out_dtype is None else canonicalize_torch_dtype(out_dtype)
+    if o_dtype in (torch.float8_e4m3fn, torch.float8_e5m2):
+        raise NotImplementedError(f"{name}: an fp8 output is not supported (float16 / bfloat16)")
+    for arg, t in (("query", query), ("workspace_buffer", workspace_buffer), ("block_tables", block_tables),
+                   ("seq_lens", seq_lens), ("cum_seq_lens_q", cum_seq_lens_q)):
+        _lib.require_gpu_tensor(t, arg)
+    k_cache, v_cache = _hnd_cache_views(kv_cache)
+    fp8_query = query.dtype == torch.float8_e4m3fn
+    if query.dtype not in (torch.float16, torch.bfloat16, torch.float8_e4m3fn) or query.dim() != 3 \
+            or query.stride(-1) != 1:
+        raise ValueError("query must be a float16 / bfloat16 / float8_e4m3fn [num_tokens, num_qo_heads, head_dim] "
+                         "tensor, contiguous in head_dim")
+    num_tokens, num_qo_heads, head_dim = query.shape
+    if batch_size != block_tables.shape[0]:
+        raise ValueError(f"batch_size {batch_size} differs from block_tables.shape[0] = {block_tables.shape[0]}")
+    seq_lens = _check_block_tables_and_lens(block_tables, seq_lens, workspace_buffer, batch_size)
+    if cum_seq_lens_q.dtype != torch.int32 or cum_seq_lens_q.shape != (batch_size + 1,) \
+            or not cum_seq_lens_q.is_contiguous():
+        raise ValueError(f"cum_seq_lens_q must be a contiguous int32 tensor of shape [{batch_size + 1}]")
+    if fp8_query:
+        if o_dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("an fp8 query needs out or out_dtype to name float16 or bfloat16")
+        if k_cache.dtype != torch.float8_e4m3fn:
+            raise ValueError(f"an fp8 e4m3 query needs an e4m3 kv_cache, got {k_cache.dtype}")
+    elif o_dtype is None:
+        o_dtype = query.dtype
+    elif o_dtype != query.dtype:
+        raise ValueError(f"the output dtype {o_dtype} differs from the query's {query.dtype}")
+    if out_dtype is not None and canonicalize_torch_dtype(out_dtype) != o_dtype:
+        raise ValueError(f"out_dtype {out_dtype} differs from out's {o_dtype}")
+    if out is None:
+        out = torch.empty(query.shape, dtype=o_dtype, device=query.device)
+    else:
+        check_shape_dtype_device(out, query.shape, o_dtype, query.device, "out")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+    sinks = _one_sinks_tensor(sinks, num_qo_heads, query.device)
+    if sinks is not None and fp8_query:
+        raise ValueError("sinks need a float16 / bfloat16 query")
+
+    max_blocks = block_tables.shape[1]
+    # the cache view; its three page-table pointers are set below, once the planner has said where it writes them
+    kv, page_size, num_kv_heads, kv_head_dim = paged_kv(k_cache, v_cache, "HND", block_tables, None, None, batch_size)
+    if kv_head_dim != head_dim:
+        raise ValueError(f"head_dim of query ({head_dim}) and kv_cache ({kv_head_dim}) differ")
+    if max_kv_len > max_blocks * page_size:
+        raise ValueError(f"max_kv_len {max_kv_len} exceeds what block_tables can hold: {max_blocks} blocks of "
+                         f"{page_size} tokens")
+    if batch_size == 0 or num_tokens == 0:
+        return out
+
+    plan = _lib.fi_batch_prefill_plan_device_params_t(
+        block_tables=block_tables.data_ptr(), seq_lens=seq_lens.data_ptr(), cum_seq_lens_q=cum_seq_lens_q.data_ptr(),
+        block_tables_stride=block_tables.stride(0), batch_size=batch_size, max_blocks=max_blocks, page_size=page_size,
+        total_num_rows=num_tokens, num_qo_heads=num_qo_heads, num_kv_heads=num_kv_heads, head_dim=head_dim,
+        q_dtype=_lib.fi_dtype(query.dtype), kv_dtype=_lib.fi_dtype(k_cache.dtype), window_left=window_left,
+        max_items_hint=0)
+    _device_plan_regions(workspace_buffer, plan, "fi_batch_prefill_plan_device_workspace", name)
+    plan_info = (C.c_int64 * _lib.FI_PREFILL_PLAN_INFO_LEN)()
+    csr = (C.c_int64 * 4)()
+    # bmm2_scale rides on the kernels' per-kv-head V scale, so rows no request owns stay untouched
+    scale_v = None if bmm2_scale == 1.0 else torch.full((num_kv_heads,), float(bmm2_scale), dtype=torch.float32,
+                                                        device=query.device)
+    params = _lib.fi_batch_prefill_params_t(
+        q=query.data_ptr(), q_stride_n=query.stride(0), q_stride_h=query.stride(1), kv=kv, o=out.data_ptr(),
+        scale_v=_lib.ptr(scale_v), num_qo_heads=num_qo_heads, q_dtype=plan.q_dtype, o_dtype=_lib.fi_dtype(o_dtype),
+        mask_mode=MaskMode.CAUSAL.value, pos_encoding_mode=PosEncodingMode.NONE.value, window_left=window_left,
+        **_resolve_logits_params(head_dim, bmm1_scale, None, None, None, None, None))
+    lib = _lib.lib()
+    with torch.cuda.device(query.device):
+        stream = _lib.current_stream(query.device)
+        _lib.check(lib.fi_batch_prefill_plan_device(C.byref(plan), plan_info, csr, stream), name)
+        # the page table and the clamped query offsets the planner's kernels write, in place of what plan() is given
+        params.kv.indptr, params.kv.indices, params.kv.last_page_len, params.qo_indptr = (
+            plan.int_ws + off for off in csr)
+        _lib.check(lib.fi_batch_prefill_paged_run_sinks(plan.float_ws, plan.float_ws_bytes, plan.int_ws,
+                                                        plan.int_ws_bytes, plan_info, _lib.FI_PREFILL_PLAN_INFO_LEN,
+                                                        C.byref(params), _lib.ptr(sinks), stream), name)
+    return out

@@ -375,6 +375,69 @@ FI_API int fi_batch_prefill_paged_run_sinks(void* float_ws, size_t float_ws_byte
                                      const fi_batch_prefill_params_t* params, const float* sinks,
                                      fi_stream_t stream);
 
+/* Device-side planning of a causal paged prefill: the plan of fi_batch_prefill_plan(enable_cuda_graph = 1, causal = 1)
+ * written by kernels on `stream` from lengths that stay on the device, for the fi_batch_prefill_paged_run[_sinks] that
+ * follows.  No host read-back, no copy, no synchronisation: both calls may be captured in one graph, and a replay plans
+ * again from whatever `block_tables`, `seq_lens` and `cum_seq_lens_q` hold then.  (The reference's plan-free prefill
+ * entry, trtllm_batch_context_with_kv_cache, flashinfer/prefill.py:3314-3334, takes the same tensors.)
+ *
+ * The rule is the host's graph-mode rule: 128-row q tiles over qo_len x group packed rows; span = max(kv_len, 1),
+ * narrowed under a sliding window to window_left + 128 + 64; the chunk is 64 x the smallest n in
+ * [2, ceil(max span / 64)] with sum(q_tiles x ceil(span / 64 n)) <= max_items, the range's upper end when none fits.
+ * The work list is in request order (the host sorts requests by cost and interleaves wide and narrow items): per
+ * request the q tiles from the last one down, per q tile the chunks upwards.
+ *
+ * The host knows one branch.  With T0 = ceil(total_num_rows x group / 128):
+ *   T0 > max_items   no chunk size can fit, so the plan is unsplit: FI_PP_SPLIT_KV = 0, the kernels write the output
+ *                    themselves, no merge is launched and the float workspace is not used (0 bytes).  List capacity
+ *                    T0 + batch - 1.  (The host's graph plan routes such a batch through f32 partial states.)
+ *   T0 <= max_items  FI_PP_SPLIT_KV = 1, merged with skip_empty as a host graph plan.  List capacity
+ *                    max(max_items, T0 + batch - 1); partial states for max_items x (ceil(128 / group) + 1) entries.
+ *
+ * Device values are not trusted; every store is bounded by a host-known capacity:
+ *   kv tokens of request b = clamp(seq_lens[b], 0, max_blocks x page_size), pages(b) = ceil(tokens / page_size);
+ *   the kernels write their own qo_indptr[batch + 1] into the int workspace, qo_indptr[b] = max over j <= b of
+ *   clamp(cum_seq_lens_q[j], 0, total_num_rows), and run() must be given THAT copy (params.qo_indptr), not the caller's.
+ * csr_offsets_out[0..3]: byte offsets in the int workspace of the CSR indptr[batch + 1], indices[batch x max_blocks],
+ * last_page_len[batch] (as fi_batch_decode_plan_device writes them) and of that qo_indptr.
+ *
+ * plan_info_out holds host-computed entries only: FI_PREFILL_PLAN_MAGIC, ENABLE_CUDA_GRAPH = 1, SPLIT_KV by the branch,
+ * PADDED_BATCH_SIZE = the list capacity, TOTAL_NUM_ROWS = total_num_rows, the offsets.  FI_PP_KV_CHUNK_SIZE and
+ * FI_PP_NUM_WORK are 0: both exist on the device only, as two int32 at FI_PP_KV_CHUNK_SIZE_PTR_OFFSET (tokens per
+ * chunk, which the prefill kernels read through kv_chunk_size_ptr, then the number of real work items); entries of the
+ * list past that number hold request -1.  merge_indptr has total_num_rows + 1 entries in both branches; rows past
+ * qo_indptr[batch] get empty ranges, so the merge leaves them alone.
+ * Errors (fi_last_error) before any launch: null tensors, batch_size <= 0, a workspace too small (the message states
+ * the bytes needed), an unsupported head_dim / dtype pair. */
+typedef struct fi_batch_prefill_plan_device_params {
+  const int32_t* block_tables;   /* [batch_size, max_blocks] device, rows block_tables_stride elements apart */
+  const int32_t* seq_lens;       /* [batch_size] device: kv tokens per request */
+  const int32_t* cum_seq_lens_q; /* [batch_size + 1] device: first query row of each request, then their end */
+  int64_t block_tables_stride;
+  void* int_ws; /* device: work list, merge_indptr, qo_indptr, scans, then the CSR page table */
+  size_t int_ws_bytes;
+  void* float_ws; /* device: f32 partial states of a split plan (only sized here, run() writes it) */
+  size_t float_ws_bytes;
+  int32_t batch_size;
+  int32_t max_blocks;
+  int32_t page_size;
+  int32_t total_num_rows; /* rows of q and of the output */
+  int32_t num_qo_heads;
+  int32_t num_kv_heads;
+  int32_t head_dim;
+  int32_t q_dtype;  /* f16 / bf16 / fp8_e4m3 */
+  int32_t kv_dtype; /* the q dtype, or fp8 under a 16-bit q */
+  int32_t window_left;    /* < 0: none */
+  int32_t max_items_hint; /* <= 0: 2 workgroups per CU over the kv heads, as fi_batch_prefill_plan */
+} fi_batch_prefill_plan_device_params_t;
+
+FI_API int fi_batch_prefill_plan_device(const fi_batch_prefill_plan_device_params_t* params, int64_t* plan_info_out,
+                                        int64_t* csr_offsets_out, fi_stream_t stream);
+/* The bytes fi_batch_prefill_plan_device needs of the two workspaces for these params (the pointers and sizes in them
+ * are not read).  Host arithmetic only. */
+FI_API int fi_batch_prefill_plan_device_workspace(const fi_batch_prefill_plan_device_params_t* params,
+                                                  size_t* int_ws_bytes_out, size_t* float_ws_bytes_out);
+
 /* Single-request prefill over dense K/V.  ref: csrc/single_prefill.cu, flashinfer/prefill.py:960-1194. */
 typedef struct fi_single_prefill_params {
   const void* q; /* [qo_len, num_qo_heads, head_dim] */
