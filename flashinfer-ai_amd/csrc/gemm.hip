@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
   };
   // scales: a per lane (its m column), b per workgroup n tile
   auto a_scale_at = [&](int kb, int m) -> float {
-    const int mi = p.a_gran_m == 1 ? m : m / p.a_gran_m;
+    const int mi = a_scale_row(p.a_gran_m, m_begin, m);
     const int m_cnt = p.a_gran_m == 1 ? p.m_total : (p.m_total + p.a_gran_m - 1) / p.a_gran_m;
     return p.scale_k_major ? p.a_scale[(int64_t)mi * kblocks + kb] : p.a_scale[(int64_t)kb * m_cnt + mi];
   };
@@ -412,7 +412,7 @@ __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const
     const float* a_sc_dma;
     {
       const int m = min(m0 + 64 * wm + lane, m_end - 1);
-      const int mi = p.a_gran_m == 1 ? m : m / p.a_gran_m;
+      const int mi = a_scale_row(p.a_gran_m, m_begin, m);
       a_sc_dma = p.scale_k_major ? p.a_scale + (int64_t)mi * kblocks : p.a_scale + mi;
     }
     auto dma = [&](int kb, int stage) {

@@ -232,7 +232,7 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
     uint32_t a_sc_voff;
     {
       const int m = min(m0 + 64 * wm + lane, m_end - 1);
-      const int mi = p.a_gran_m == 1 ? m : m / p.a_gran_m;
+      const int mi = a_scale_row(p.a_gran_m, m_begin, m);
       a_sc_voff = (uint32_t)(p.scale_k_major ? mi * kblocks : mi) * 4u;
     }
     // oob = 0x80000000 pushes every lane's offset past the descriptor's range: the pieces are then written as zeros

@@ -70,6 +70,14 @@ __device__ __forceinline__ bool find_group_tile(const int32_t* m_indptr, int num
 
 using i32x8g = __attribute__((ext_vector_type(8))) int;
 
+// Row of a_scale for row m of a, m_begin being the first row of m's group (0 without groups).  gran_m == 128: a
+// group's scale rows start at m_begin / 128 and block the group's rows from its first one, as the reference offsets
+// the scale pointer per group (group_gemm_fp8_groupwise_sm100.cuh:52-69, sf_m_offset) -- never past the global row's
+// block, so a_scale's ceil(m_total / 128) rows cover it.
+__device__ __forceinline__ int a_scale_row(int gran_m, int m_begin, int m) {
+  return gran_m == 1 ? m : m_begin / gran_m + (m - m_begin) / gran_m;
+}
+
 // The power-of-two verdict of a call: kPow2Words words, one per workgroup of the check kernel (non-zero = that
 // workgroup saw a scale that is not a positive normal power of two).  No word is ever reset: every call's check
 // kernel rewrites all of its slot's words, so there is no memset node in front of it.

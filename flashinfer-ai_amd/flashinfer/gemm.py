@@ -38,9 +38,10 @@ def gemm_fp8_nt_groupwise(
     r"""``out = (a * a_scale) @ (b * b_scale)^T`` with fp8 inputs and groupwise scales.
 
     a : ``(m, k)`` fp8 row-major; b : ``(n, k)`` fp8.
-    a_scale : ``(m // gm, k // 128)`` if ``scale_major_mode == "K"`` else ``(k // 128, m // gm)``.
+    a_scale : ``(ceil(m / gm), k // 128)`` if ``scale_major_mode == "K"`` else ``(k // 128, ceil(m / gm))``: row
+        ``r`` of ``a`` uses scale row ``r // gm``.
     b_scale : ``(n // 128, k // 128)`` if ``"K"`` else ``(k // 128, n // 128)``.
-    scale_granularity_mnk : ``(1, 128, 128)`` or ``(128, 128, 128)``.
+    scale_granularity_mnk : ``(gm, 128, 128)`` with ``gm`` 1 or 128.
     out / out_dtype : ``(m, n)`` bf16 (default) or fp16.
     """
     for t, name in ((a, "a"), (b, "b"), (a_scale, "a_scale"), (b_scale, "b_scale")):
@@ -98,8 +99,13 @@ def group_gemm_fp8_nt_groupwise(
     are multiplied with ``b[g]^T``.
 
     a : ``(cum_m, k)`` fp8; b : ``(batch_size, n, k)`` fp8.
-    a_scale : ``(cum_m, k // 128)`` if ``"K"`` else ``(k // 128, cum_m)`` (float32).
+    a_scale : float32, ``(ceil(cum_m / gm), k // 128)`` if ``"K"`` else ``(k // 128, ceil(cum_m / gm))``: ``cum_m``
+        scale rows with ``gm == 1``, ``ceil(cum_m / 128)`` with ``gm == 128``.  Group ``g``'s rows use the scale rows
+        from ``m_indptr[g] // gm`` on, blocked from the group's first row: row ``r`` of the group uses scale row
+        ``m_indptr[g] // gm + r // gm`` (the reference offsets the scale pointer per group by ``sf_m_offset``,
+        include/flashinfer/gemm/group_gemm_fp8_groupwise_sm100.cuh:52-69).
     b_scale : ``(batch_size, n // 128, k // 128)`` if ``"K"`` else ``(batch_size, k // 128, n // 128)``.
+    scale_granularity_mnk : ``(gm, 128, 128)`` with ``gm`` 1 or 128.
     m_indptr : ``(batch_size + 1,)`` int32, each entry a multiple of 4.
     out : ``(cum_m, n)`` bf16 (default) / fp16.
     """

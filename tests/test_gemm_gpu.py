@@ -10,7 +10,11 @@ switches are set through _lib.set_option before the test and returned to the env
   FI_GEMM_WS_MIN_TILES=0 FI_GEMM_DMA_TM=256 / 128 -> every shape takes the persistent LDS-DMA kernel with
                                        256 x 128 / 128 x 256 tiles
   ... FI_GEMM_HW_SCALES=0 -> the 256 x 256 kernel without its hardware-scale path (power-of-two scales, which the
-                                       reference's quantiser produces, otherwise ride the MFMA's E8M0 block scales)"""
+                                       reference's quantiser produces, otherwise ride the MFMA's E8M0 block scales)
+
+e5m2 operands and 128-row a_scale blocks (scale_granularity_mnk = (128, 128, 128)) are checked against an fp64 product
+of the same fp8 bytes (_fp64_reference; the a_scale row of each row of a is _a_scale_rows), with scales from a formula
+that gives neighbouring blocks different values, so that an off-by-one block index cannot pass."""
 import math
 
 import pytest
@@ -178,6 +182,206 @@ def test_gemm_errors():
         flashinfer.gemm_fp8_nt_groupwise(a, b, s, s, scale_major_mode="MN")
     with pytest.raises(ValueError):
         flashinfer.gemm_fp8_nt_groupwise(a, a, s, s, scale_major_mode="MN", out_dtype=torch.float32)
+    # only 1 or 128 rows of a and 128 x 128 blocks of b per scale: anything else is refused with the granularity in
+    # the message, before any kernel is launched (the output keeps what it held)
+    b = torch.zeros(16, 128, device=DEV).to(torch.float8_e4m3fn)
+    sb = torch.ones(1, 1, device=DEV)
+    m_indptr = torch.tensor([0, 8], dtype=torch.int32, device=DEV)
+    for gran in [(64, 128, 128), (1, 64, 128)]:
+        message = r"scale granularity \(%d,%d,%d\)" % gran
+        out = torch.full((8, 16), 7.0, device=DEV, dtype=torch.bfloat16)
+        with pytest.raises(RuntimeError, match=message):
+            flashinfer.gemm_fp8_nt_groupwise(a, b, s, sb, scale_major_mode="MN", scale_granularity_mnk=gran, out=out)
+        with pytest.raises(RuntimeError, match=message):
+            flashinfer.group_gemm_fp8_nt_groupwise(a, b[None], s, sb[None], m_indptr, scale_granularity_mnk=gran,
+                                                   out=out)
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all())
+
+
+E4M3, E5M2 = torch.float8_e4m3fn, torch.float8_e5m2
+FORMAT_PAIRS = [(E4M3, E4M3), (E4M3, E5M2), (E5M2, E4M3), (E5M2, E5M2)]
+_FMT_ID = {E4M3: "e4m3", E5M2: "e5m2"}.get
+
+
+def _a_scale_rows(gm, m_indptr):
+    """The a_scale row of every row of a (m_indptr = [0, m] for the ungrouped GEMM).  gm == 1: the row itself.
+    gm == 128: the group's scale rows start at m_indptr[g] // 128 and block the group's rows from its first one
+    (the reference: include/flashinfer/gemm/group_gemm_fp8_groupwise_sm100.cuh:52-69, sf_m_offset)."""
+    m_indptr = m_indptr.long()
+    rows = torch.arange(int(m_indptr[-1]))
+    begin = torch.repeat_interleave(m_indptr[:-1], m_indptr[1:] - m_indptr[:-1])
+    return rows if gm == 1 else begin // gm + (rows - begin) // gm
+
+
+def _formula_scales(ms, n, k, gm):
+    """Scales whose neighbouring blocks (along m, n, k and the group) always differ, all powers of two:
+    a_scale (k // 128, rows), b_scale (G, k // 128, ceil(n / 128)), both in the "MN" layout."""
+    kb = torch.arange(k // 128)
+    rows = -(-sum(ms) // gm)
+    sa = torch.pow(2.0, ((3 * torch.arange(rows)[None, :] + kb[:, None]) % 5 - 2).float())
+    nb = torch.arange(-(-n // 128))
+    g = torch.arange(len(ms))
+    sb = torch.pow(2.0, ((2 * nb[None, None, :] + kb[None, :, None] + g[:, None, None]) % 3 - 1).float())
+    return sa, sb
+
+
+def _small_integers(shape, fmt):
+    """Integers in -3..3 as fp8; both formats hold them exactly."""
+    x = torch.randint(-3, 4, shape).float()
+    x8 = x.to(fmt)
+    assert torch.equal(x8.float(), x)
+    return x8
+
+
+def _fp64_reference(a8, b8, sa, sb, m_indptr, gm):
+    """(a . sa) (b[g] . sb[g])^T per group and per 128-wide k block in fp64, from the fp8 bytes the kernel gets.
+    a8 (cum_m, k), b8 (G, n, k); sa (k // 128, a-scale rows) and sb (G, k // 128, ceil(n / 128)) in the "MN" layout."""
+    cum, k = a8.shape
+    n = b8.shape[1]
+    a, b = a8.float().double(), b8.float().double()
+    a_rows = _a_scale_rows(gm, m_indptr)
+    ref = torch.zeros(cum, n, dtype=torch.float64)
+    for gi in range(b8.shape[0]):
+        lo, hi = int(m_indptr[gi]), int(m_indptr[gi + 1])
+        for kb in range(k // 128):
+            part = a[lo:hi, kb * 128:(kb + 1) * 128] @ b[gi, :, kb * 128:(kb + 1) * 128].T
+            ref[lo:hi] += part * sa[kb, a_rows[lo:hi], None].double() * sb[gi, kb].double().repeat_interleave(128)[:n][None]
+    return ref
+
+
+def _run_gemm(a8, b8, sa, sb, m_indptr, gm, mode, out_dtype, grouped):
+    """The kernel's result on the CPU as f32; sa / sb come in the "MN" layout and go out in `mode`'s."""
+    import flashinfer
+
+    if mode == "K":
+        sa, sb = sa.t(), sb.transpose(1, 2)
+    sa, sb = sa.contiguous().to(DEV), sb.contiguous().to(DEV)
+    if grouped:
+        out = flashinfer.group_gemm_fp8_nt_groupwise(a8.to(DEV), b8.to(DEV), sa, sb, m_indptr.to(DEV),
+                                                     scale_granularity_mnk=(gm, 128, 128), scale_major_mode=mode,
+                                                     out_dtype=out_dtype)
+    else:
+        out = flashinfer.gemm_fp8_nt_groupwise(a8.to(DEV), b8[0].to(DEV), sa, sb[0], scale_major_mode=mode,
+                                               scale_granularity_mnk=(gm, 128, 128), out_dtype=out_dtype)
+    assert out.dtype == out_dtype
+    return out.float().cpu()
+
+
+def _exact_formula_scales(ms, n, k, gm, mode, grouped, fmts=(E4M3, E4M3), last_a_scale=None):
+    """Small-integer operands and formula scales: the f16 result must be exact."""
+    torch.manual_seed(7)
+    a8 = _small_integers((sum(ms), k), fmts[0])
+    b8 = _small_integers((len(ms), n, k), fmts[1])
+    sa, sb = _formula_scales(ms, n, k, gm)
+    if last_a_scale is not None:
+        sa[-1, -1] = last_a_scale  # the last element in memory order of either layout
+    m_indptr = indptr_of(ms)
+    ref = _fp64_reference(a8, b8, sa, sb, m_indptr, gm)
+    assert ref.abs().max() < 60000
+    out = _run_gemm(a8, b8, sa, sb, m_indptr, gm, mode, torch.float16, grouped)
+    torch.testing.assert_close(out, ref.float().half().float(), atol=0, rtol=0)
+
+
+def _decode_fp8_codes(exp_bits, man_bits, bias):
+    """Value of each of the 256 codes of a sign | exponent | mantissa byte in fp64, from the format's definition
+    (no infinities or NaNs: the caller masks those codes)."""
+    code = torch.arange(256)
+    sign = 1.0 - 2.0 * (code >> 7).double()
+    e = (code >> man_bits) & ((1 << exp_bits) - 1)
+    f = (code & ((1 << man_bits) - 1)).double() / (1 << man_bits)
+    normal = torch.pow(2.0, (e - bias).double()) * (1.0 + f)
+    subnormal = 2.0 ** (1 - bias) * f
+    return sign * torch.where(e == 0, subnormal, normal)
+
+
+@pytest.mark.parametrize("scale", [1.0, 0.75])
+@pytest.mark.parametrize("out_dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("side", ["a", "b"])
+@pytest.mark.parametrize("fmt", [E4M3, E5M2], ids=_FMT_ID)
+def test_gemm_fp8_format_decode_tables(fmt, side, out_dtype, scale):
+    """Every finite code of an fp8 format -- both signs, the subnormals (e5m2 from 2^-16, e4m3 from 2^-9), the largest
+    values -- times a 128 x 128 identity in e4m3: the output is the code's value times the scale, bit for bit (scale 1
+    can ride the MFMA's hardware scales, 0.75 takes the fold).  An operand decoded in the other format, on either side
+    of the MFMA, cannot pass."""
+    codes = torch.arange(256, dtype=torch.uint8)
+    finite = torch.isfinite(codes.view(fmt).float())
+    assert int((~finite).sum()) == (2 if fmt == E4M3 else 8)
+    codes = torch.where(finite, codes, torch.zeros_like(codes))
+    value = torch.where(finite, _decode_fp8_codes(4, 3, 7) if fmt == E4M3 else _decode_fp8_codes(5, 2, 15),
+                        torch.zeros(256, dtype=torch.float64))
+    assert torch.equal(codes.view(fmt).float().double(), value)  # torch's table is the format's definition
+    x = torch.zeros(256, 128, dtype=torch.uint8)
+    x[torch.arange(256), torch.arange(256) % 128] = codes
+    x8 = x.view(fmt)
+    expected = x8.float().double() * scale  # (256, 128): row r holds code r at column r % 128
+    assert torch.equal(expected.float().to(out_dtype).double(), expected)  # exactly representable in the output type
+    eye = torch.eye(128).to(E4M3)
+    if side == "a":
+        a8, b8 = x8, eye[None]
+        sa, sb = torch.full((1, 256), scale), torch.ones(1, 1, 1)
+    else:
+        a8, b8 = eye, x8[None]
+        sa, sb = torch.ones(1, 128), torch.full((1, 1, 2), scale)
+        expected = expected.t()
+    out = _run_gemm(a8, b8, sa, sb, None, 1, "MN", out_dtype, grouped=False)
+    torch.testing.assert_close(out, expected.float(), atol=0, rtol=0)
+
+
+@pytest.mark.parametrize("mode", ["MN", "K"])
+@pytest.mark.parametrize("a_fmt,b_fmt", FORMAT_PAIRS, ids=_FMT_ID)
+def test_group_gemm_fp8_format_pairs_exact(a_fmt, b_fmt, mode):
+    """e4m3 / e5m2 on either side, grouped (an empty group, ragged tiles).  Of the integers -3..3 only +-2 has the same
+    byte in both formats (+-1 and +-3 read in the other format are 0.5 / 1.5 or 4 / 2.5), so an operand decoded in the
+    wrong format cannot give the exact result."""
+    _exact_formula_scales([132, 0, 260, 4], 136, 256, 1, mode, grouped=True, fmts=(a_fmt, b_fmt))
+
+
+@pytest.mark.parametrize("mode", ["MN", "K"])
+@pytest.mark.parametrize("a_fmt,b_fmt", FORMAT_PAIRS[1:], ids=_FMT_ID)
+def test_group_gemm_fp8_format_pairs_random(a_fmt, b_fmt, mode):
+    """Random normals cast to e5m2 on one side or both (subnormal codes included), against the fp64 product of the same
+    bytes: input quantisation is not part of the comparison, so the bar is the file's, whatever the format."""
+    torch.manual_seed(11)
+    ms, n, k = [260, 4, 512], 512, 512
+    g, cum = len(ms), sum(ms)
+    a8 = torch.randn(cum, k).to(a_fmt)
+    b8 = (torch.randn(g, n, k) / math.sqrt(k)).to(b_fmt)
+    sa = torch.pow(2.0, torch.randint(-3, 4, (k // 128, cum)).float())
+    sb = torch.pow(2.0, torch.randint(-3, 4, (g, k // 128, n // 128)).float())
+    m_indptr = indptr_of(ms)
+    ref = _fp64_reference(a8, b8, sa, sb, m_indptr, 1)
+    out = _run_gemm(a8, b8, sa, sb, m_indptr, 1, mode, torch.bfloat16, grouped=True)
+    torch.testing.assert_close(out, ref.float(), atol=1e-2, rtol=1e-2)
+
+
+@pytest.mark.parametrize("mode", ["MN", "K"])
+@pytest.mark.parametrize("m,last_a_scale", [(128, None), (384, None), (300, None), (384, 0.75)])
+def test_gemm_fp8_a_scale_blocks_of_128_rows_exact(m, last_a_scale, mode):
+    """scale_granularity_mnk = (128, 128, 128): a_scale has ceil(m / 128) rows (m = 300: three, the last block ragged).
+    With the LAST a_scale element in memory set to 0.75 the whole call must take the fold: the power-of-two check has
+    to scan exactly ceil(m / 128) * k / 128 a scales."""
+    _exact_formula_scales([m], 136, 384, 128, mode, grouped=False, last_a_scale=last_a_scale)
+
+
+@pytest.mark.parametrize("mode", ["MN", "K"])
+def test_group_gemm_fp8_a_scale_blocks_of_128_rows_aligned_exact(mode):
+    """Every group starts at a multiple of 128: a group's scale rows are the ones of its global rows."""
+    ms = [128, 0, 384, 256]
+    m_indptr = indptr_of(ms)
+    assert torch.equal(_a_scale_rows(128, m_indptr), torch.arange(sum(ms)) // 128)
+    _exact_formula_scales(ms, 264, 256, 128, mode, grouped=True)
+
+
+@pytest.mark.parametrize("mode", ["MN", "K"])
+def test_group_gemm_fp8_a_scale_blocks_of_128_rows_unaligned_exact(mode):
+    """Groups that start between two multiples of 128: group g's rows are blocked from the GROUP's first row, its scale
+    rows start at m_indptr[g] // 128 (see _a_scale_rows) -- not at the global row's block, which is a different scale
+    row for some of these rows."""
+    ms = [132, 260, 4, 384]
+    m_indptr = indptr_of(ms)
+    assert int((_a_scale_rows(128, m_indptr) != torch.arange(sum(ms)) // 128).sum()) == 44
+    _exact_formula_scales(ms, 264, 256, 128, mode, grouped=True)
 
 
 @pytest.mark.parametrize("ms,n,k", [([1300, 4, 0, 2300, 520], 400, 256), ([2500], 136, 256), ([128] * 37, 264, 256),
