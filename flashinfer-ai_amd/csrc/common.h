@@ -37,6 +37,7 @@ enum Option {
   OPT_GEMM_BIG_MIN_TILES,
   OPT_GEMM_BIG_FOLD_MIN_TILES,
   OPT_GEMM_HW_SCALES,
+  OPT_MM_FP4_KERNEL,
   OPT_COUNT
 };
 // The switch's value; none when neither fi_set_option nor the environment gave it one.  One atomic load: a call

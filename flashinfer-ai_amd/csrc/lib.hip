@@ -26,7 +26,8 @@ const char* last_error() { return g_err; }
 // ---- the switch table: one entry per Option and in its order, named as its environment variable ----
 static const char* const kOptionNames[OPT_COUNT] = {
     "FI_NUM_CUS",           "FI_DECODE_MFMA16",      "FI_GEMM_WS_MIN_TILES",       "FI_GEMM_DMA_TM",
-    "FI_GEMM_BIG",          "FI_GEMM_BIG_MIN_TILES", "FI_GEMM_BIG_FOLD_MIN_TILES", "FI_GEMM_HW_SCALES"};
+    "FI_GEMM_BIG",          "FI_GEMM_BIG_MIN_TILES", "FI_GEMM_BIG_FOLD_MIN_TILES", "FI_GEMM_HW_SCALES",
+    "FI_MM_FP4_KERNEL"};
 constexpr int64_t kUnset = INT64_MIN;     // no int: an entry holds an int or this
 static int64_t g_env[OPT_COUNT];          // what the environment gave, written at load only
 static std::atomic<int64_t> g_option[OPT_COUNT];

@@ -2,7 +2,8 @@
 
 Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / sparse / gemm / fused_moe / fp8_quantization / fp4_quantization / sampling / norm / activation`` operator API
 of FlashInfer v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-written HIP kernels behind the C ABI of
-``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided.
+``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided; of the fp4 matmuls that is
+``mm_fp4`` in its MXFP4 mode (``use_nvfp4=False, block_size=32``), not nvfp4.
 """
 from . import _lib as _lib
 from . import activation as activation
@@ -57,6 +58,7 @@ from .fused_moe import (
 )
 from .gemm import gemm_fp8_nt_groupwise as gemm_fp8_nt_groupwise
 from .gemm import group_gemm_fp8_nt_groupwise as group_gemm_fp8_nt_groupwise
+from .gemm import mm_fp4 as mm_fp4
 from .mla import BatchMLAPagedAttentionWrapper as BatchMLAPagedAttentionWrapper
 from .norm import fused_add_rmsnorm as fused_add_rmsnorm
 from .norm import gemma_fused_add_rmsnorm as gemma_fused_add_rmsnorm

@@ -1,9 +1,10 @@
-"""fp8 groupwise-scaled GEMM operators (``gemm_fp8_nt_groupwise``, ``group_gemm_fp8_nt_groupwise``) and the grouped
-GEMM with MXFP8 activations and MXFP4 weights (``group_gemm_mxfp8_mxfp4_nt_groupwise``).
+"""fp8 groupwise-scaled GEMM operators (``gemm_fp8_nt_groupwise``, ``group_gemm_fp8_nt_groupwise``), the grouped
+GEMM with MXFP8 activations and MXFP4 weights (``group_gemm_mxfp8_mxfp4_nt_groupwise``) and the dense MXFP4 x MXFP4
+matmul (``mm_fp4`` in its ``use_nvfp4=False`` mode).
 
-API of the reference's ``flashinfer/gemm.py`` (:2321-2484, :2657-2811, :2814-2949); the kernels are csrc/gemm.hip
-(MFMA fp8, two-level accumulation per 128-wide K block) and csrc/gemm_mxfp4.hip (block-scaled MFMA, the E8M0 scale
-bytes ride the instruction's scale operands).  NVIDIA-only knobs (``mma_sm``, ``backend``, tile shapes, ``swap_ab``)
+API of the reference's ``flashinfer/gemm.py`` (:2321-2484, :2657-2811, :2814-2949, :2012-2160); the kernels are
+csrc/gemm.hip (MFMA fp8, two-level accumulation per 128-wide K block), csrc/gemm_mxfp4.hip and csrc/mm_fp4.hip
+(block-scaled MFMA, the E8M0 scale bytes ride the instruction's scale operands).  NVIDIA-only knobs (``mma_sm``, ``backend``, tile shapes, ``swap_ab``)
 are accepted and ignored.
 """
 from __future__ import annotations
@@ -240,3 +241,117 @@ def group_gemm_mxfp8_mxfp4_nt_groupwise(
 
 # the reference keeps the old name (gemm.py:2948-2949)
 group_gemm_mxfp4_nt_groupwise = group_gemm_mxfp8_mxfp4_nt_groupwise
+
+_FP4_BYTES = tuple(t for t in (torch.uint8, getattr(torch, "float4_e2m1fn_x2", None)) if t is not None)
+_SF_BYTES = (torch.float8_e4m3fn, torch.uint8)
+
+
+def _scale_bytes(t: torch.Tensor, name: str, transposed_ok: bool) -> torch.Tensor:
+    """The storage of a swizzled scale tensor as flat uint8, without a copy."""
+    if transposed_ok and t.ndim == 2 and t.stride(0) == 1 and t.T.is_contiguous():
+        t = t.T  # the reference's sf.T: the storage is read in order
+    elif transposed_ok and t.ndim != 1 or not t.is_contiguous():
+        form = "the transposed view sf.T of mxfp4_quantize's scales (2-D, stride(0) == 1) or a flat tensor of its bytes" \
+            if transposed_ok else "contiguous"
+        raise ValueError(f"{name} must be {form}, got shape {tuple(t.shape)} with strides {t.stride()}")
+    return t.view(torch.uint8).reshape(-1)
+
+
+def mm_fp4(
+    a: torch.Tensor,
+    b: torch.Tensor,
+    a_descale: torch.Tensor,
+    b_descale: torch.Tensor,
+    alpha: Optional[torch.Tensor] = None,
+    out_dtype: torch.dtype = torch.bfloat16,
+    out: Optional[torch.Tensor] = None,
+    block_size: int = 16,
+    use_8x4_sf_layout: bool = False,
+    backend: Literal["cudnn", "trtllm", "cutlass"] = "cudnn",
+    use_nvfp4: bool = True,
+) -> torch.Tensor:
+    r"""``out = alpha * dequant(a) @ dequant(b)`` with both operands MXFP4 (ref: flashinfer/gemm.py:2012-2160), f32
+    accumulation, ``alpha`` multiplied in f32, one rounding to ``out_dtype``.  The kernels are csrc/mm_fp4.hip (block-scaled
+    fp4 x fp4 MFMA; weight streaming for few rows, 128 x 128 LDS tiles for many).
+
+    Only ``use_nvfp4=False, block_size=32, use_8x4_sf_layout=False`` runs.  The defaults select nvfp4 (16-element blocks,
+    e4m3 scales, a global scale), which is not provided, so a bare call raises NotImplementedError; so does the 8x4 layout.
+
+    a : ``(m, k / 2)`` uint8 (or float4_e2m1fn_x2) row-major: what ``mxfp4_quantize(x)`` returns.
+    b : ``(k / 2, n)`` COLUMN-major: ``w_q.T`` of the ``(n, k / 2)`` tensor ``mxfp4_quantize(w)`` returns.  There is no silent
+        copy of a weight matrix: a ``b`` whose ``.T`` is not contiguous raises ValueError.
+    a_descale : the swizzled "128x4" bytes of the ``(m, k / 32)`` scales, uint8 or float8_e4m3fn read as bytes, contiguous, in
+        any shape with at least ``ceil(m / 128) * 128 * k / 32`` bytes.
+    b_descale : the same for ``(n, k / 32)``, as the transposed view ``sf.T`` of what ``mxfp4_quantize(w)`` returns (2-D with
+        ``stride(0) == 1``) or as a 1-D tensor of the bytes.
+    alpha : None or a float32 tensor of one element on the device; the kernel reads it, the host never does.
+    out_dtype / out : bf16 or f16; ``out``, if given, is contiguous ``(m, n)`` of ``out_dtype`` and is returned.
+    backend : the reference's names, accepted and ignored.
+    ``k % 128 == 0`` and ``n % 8 == 0``; any ``m >= 0``.  No host read of a device value, no synchronisation: the call can be
+    captured into a graph.
+    """
+    if a.ndim != 2 or b.ndim != 2:
+        raise ValueError(f"mm_fp4 accepts 2d tensors, got {a.shape} and {b.shape}")
+    if a.shape[1] != b.shape[0]:
+        raise ValueError(f"K dimension mismatch in mm_fp4. got a.shape[1] = {a.shape[1]}, b.shape[0] = {b.shape[0]}")
+    if a.dtype not in _FP4_BYTES or b.dtype not in _FP4_BYTES:
+        raise ValueError(f"a and b must have float4_e2m1fn_x2 packed into uint8. Got {a.dtype} and {b.dtype}.")
+    if a_descale.dtype not in _SF_BYTES or b_descale.dtype not in _SF_BYTES:
+        raise ValueError(f"a_descale and b_descale must have float8_e4m3fnx2 packed into uint8. "
+                         f"Got {a_descale.dtype} and {b_descale.dtype}.")
+    if alpha is not None and alpha.dtype != torch.float:
+        raise ValueError(f"alpha must be a float tensor, got {alpha.dtype}")
+    if alpha is not None and alpha.numel() != 1:
+        raise ValueError(f"alpha must be a scalar, got {alpha.numel()}")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"Unsupported output dtype: {out_dtype}. "
+                         f"Only torch.bfloat16 and torch.float16 are supported for FP4 GEMM operations.")
+    if use_nvfp4 and block_size != 16:
+        raise ValueError("nvfp4 only supports block_size = 16.")
+    if not use_nvfp4 and block_size != 32:
+        raise ValueError("mxfp4 supports block_size = 32.")
+    if backend not in ("cudnn", "trtllm", "cutlass"):
+        raise ValueError(f"Invalid backend {backend!r}: expected 'cudnn', 'trtllm' or 'cutlass'")
+    if use_nvfp4:
+        raise NotImplementedError(
+            "nvfp4 (block_size 16, e4m3 scales, a global scale) is not provided: only MXFP4, use_nvfp4=False with "
+            "block_size=32, runs on this hardware")
+    if use_8x4_sf_layout:
+        raise NotImplementedError("the 8x4 layout of the scales is not provided: only 128x4")
+
+    m, n, k = a.shape[0], b.shape[1], a.shape[1] * 2
+    if k == 0 or k % 128 != 0:
+        raise NotImplementedError(f"k = {k} (a.shape[1] * 2) must be a positive multiple of 128: pad a and b with zero codes")
+    if n % 8 != 0:
+        raise NotImplementedError(f"n = {n} (b.shape[1]) must be a multiple of 8: pad b with rows of zero codes")
+    if not a.is_contiguous():
+        raise ValueError(f"a must be row-major contiguous, got strides {a.stride()}")
+    if not b.T.is_contiguous():
+        raise ValueError(f"b must be column-major (k / 2, n): pass w_q.T of the (n, k / 2) quantised weight; got strides "
+                         f"{b.stride()} and there is no silent copy of a weight matrix")
+    sa = _scale_bytes(a_descale, "a_descale", False)
+    sb = _scale_bytes(b_descale, "b_descale", True)
+    if out is not None:
+        if tuple(out.shape) != (m, n):
+            raise ValueError(f"Output shape mismatch. Expected {(m, n)}, got {tuple(out.shape)}.")
+        if out.dtype != out_dtype:
+            raise ValueError(f"Output dtype mismatch. Expected {out_dtype}, got {out.dtype}.")
+        if out.device != a.device:
+            raise ValueError(f"Output device mismatch. Expected {a.device}, got {out.device}.")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+    tensors = [(a, "a"), (b, "b"), (a_descale, "a_descale"), (b_descale, "b_descale")]
+    for t, name in tensors + ([(alpha, "alpha")] if alpha is not None else []):
+        _lib.require_gpu_tensor(t, name)
+    if out is None:
+        out = torch.empty((m, n), device=a.device, dtype=out_dtype)
+    if m == 0 or n == 0:
+        return out
+    p = _lib.fi_mm_mxfp4_params_t(
+        a=a.data_ptr(), b=b.data_ptr(), a_scale=sa.data_ptr(), b_scale=sb.data_ptr(), alpha=_lib.ptr(alpha),
+        d=out.data_ptr(), a_scale_bytes=sa.numel(), b_scale_bytes=sb.numel(), m=m, n=n, k=k,
+        d_dtype=_lib.fi_dtype(out_dtype))
+    fi_mm_mxfp4 = _lib.lib().fi_mm_mxfp4
+    with torch.cuda.device(a.device):
+        _lib.check(fi_mm_mxfp4(C.byref(p), _lib.current_stream(a.device)), "mm_fp4")
+    return out

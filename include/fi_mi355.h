@@ -915,6 +915,31 @@ typedef struct fi_group_gemm_mxfp4_params {
 
 FI_API int fi_group_gemm_mxfp8_mxfp4_nt_groupwise(const fi_group_gemm_mxfp4_params_t* params, fi_stream_t stream);
 
+/* Dense MXFP4 x MXFP4 matmul (csrc/mm_fp4.hip; ref: mm_fp4 with use_nvfp4=False, block_size=32, flashinfer/gemm.py
+ * :2012-2160):  d[r, j] = alpha * sum_k e2m1(a[r, k]) 2^(sa[r, k/32] - 127) * e2m1(b[j, k]) 2^(sb[j, k/32] - 127),
+ * f32 accumulation, alpha multiplied in f32, one round-to-nearest to the output dtype.
+ *   a: (m, k/2) bytes, b: (n, k/2) bytes, both contiguous, element k = 2i in the low nibble of byte i;
+ *   a_scale / b_scale: swizzled "128x4" E8M0 bytes of (m, k/32) resp. (n, k/32): at least ceil(m/128)*128 * k/32 resp.
+ *   ceil(n/128)*128 * k/32 bytes;  alpha: one float on the DEVICE or NULL (= 1), read by the kernel;
+ *   d: (m, n) f16 / bf16 contiguous.  n % 8 == 0, k % 128 == 0, k > 0.
+ * a and b 16-byte, d 8-byte, scales and alpha 4-byte aligned.  Padding bytes of the scale tensors never reach d.  Scale
+ * byte 255 (the E8M0 NaN) is unspecified.  Two kernels (few rows: weight streaming with k split over a workgroup's waves;
+ * many rows: 128 x 128 LDS tiles), chosen by m or by the switch FI_MM_FP4_KERNEL; the result never depends on
+ * scheduling.  No workspace, no host state, no synchronisation; m == 0 or n == 0 returns 0 without a launch. */
+typedef struct fi_mm_mxfp4_params {
+  const void* a;
+  const void* b;
+  const void* a_scale;
+  const void* b_scale;
+  const float* alpha; /* optional, device */
+  void* d;
+  int64_t a_scale_bytes, b_scale_bytes; /* sizes of the scale buffers, checked on the host */
+  int32_t m, n, k;
+  int32_t d_dtype; /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+} fi_mm_mxfp4_params_t;
+
+FI_API int fi_mm_mxfp4(const fi_mm_mxfp4_params_t* params, fi_stream_t stream);
+
 /* MXFP4 quantiser (ref: fp4_quantize with sf_vec_size 32 and UE8M0 scales, flashinfer/fp4_quantization.py:525-587,
  * quantization.cuh:427-499).  code = e2m1(x * 2^-e), sf = e + 127 per block of 32, where e is the smallest integer in
  * [-127, 127] with 6 * 2^e >= amax (an all-zero block: e = -127, byte 0, codes 0).  The scaling is exact, nothing
