@@ -185,8 +185,11 @@ __global__ void __launch_bounds__(kMergeThreads) merge_2_kernel(const Merge2Para
   if (p.mask && !p.mask[row]) return;
   const float sa = p.s_a[item], sb = p.s_b[item];
   const float mx = fmaxf(sa, sb);
-  const float wa = fast_exp2(sa - mx), wb = fast_exp2(sb - mx);
-  const float inv = 1.0f / (wa + wb);
+  // both states empty in the callers' encoding (s = -inf): -inf - -inf is NaN, so the weights are set, not computed;
+  // the result is (0, -inf).  Every other input takes the arithmetic below unchanged (merge_kernel.h, "empty states").
+  const bool none = mx == -INFINITY;
+  const float wa = none ? 0.f : fast_exp2(sa - mx), wb = none ? 0.f : fast_exp2(sb - mx);
+  const float inv = none ? 0.f : 1.0f / (wa + wb);
   const float a_scale = wa * inv, b_scale = wb * inv;
   const int D = p.head_dim;
   const int64_t base = item * D;
@@ -195,7 +198,7 @@ __global__ void __launch_bounds__(kMergeThreads) merge_2_kernel(const Merge2Para
     float vb = load_any_float(p.v_b, base + i, p.dtype);
     store_any_float(p.v_out, base + i, a_scale * va + b_scale * vb, p.dtype);
   }
-  if (lane == 0 && p.s_out) p.s_out[item] = fast_log2(wa + wb) + mx;
+  if (lane == 0 && p.s_out) p.s_out[item] = none ? -INFINITY : fast_log2(wa + wb) + mx;
 }
 
 

@@ -3,6 +3,18 @@
 // segment.  Operator (ref: include/flashinfer/attention/cascade.cuh:44-71, state.cuh:52-63):
 //   (v, s) (+) (v', s'):  m = max(s, s');  w = 2^(s-m), w' = 2^(s'-m)
 //   v <- (w v + w' v') / (w + w'),  s <- m + log2(w + w')
+//
+// Empty states.  A state that saw no key comes in two encodings, both with v = 0:
+//   * s = FI_NEG_INF (-5e4): what every attention kernel here writes for a chunk, row or request without a key -- the
+//     partial states of split-KV decode (decode_kernel.h, decode_mfma_kernel.h, decode_mfma16_kernel.h), prefill
+//     (prefill_kernel.h, prefill_fp8_kernel.h, prefill_qkvo_kernel.h) and MLA (mla.hip), and their final (o, lse):
+//     l = 0 there, so inv = 0, v = acc * 0 = 0 and s = FI_NEG_INF.  An empty (row, chunk) slot that a merge
+//     reads is written like any other; stale workspace bytes are never a state (tests/test_unowned_memory_gpu.py runs
+//     every split path on a workspace of NaN bytes).
+//   * s = -inf: what the reference's callers pass for a level that holds nothing.
+// Both carry weight 2^(s - m) = 0 next to a live state.  merge_n_* turns a row of nothing but empty states into
+// (0, FI_NEG_INF); merge_2 keeps the encoding it was given: (0, -inf) for two -inf states, (0, FI_NEG_INF + 1) for two
+// FI_NEG_INF states -- either merges with a live state to that live state.
 #pragma once
 #include "common.h"
 

@@ -113,3 +113,32 @@ def planned_prefill_wrapper(ws_bytes, layout, qo_indptr, indptr, indices, last, 
     w = flashinfer.BatchPrefillWithPagedKVCacheWrapper(torch.zeros(ws_bytes, dtype=torch.uint8, device=DEV), layout)
     w.plan(qo_indptr.to(DEV), indptr.to(DEV), indices.to(DEV), last.to(DEV), *plan_args, **plan_kw)
     return w
+
+
+def owned_slots(kv_lens, indptr, indices, page_size, num_pages):
+    """bool [num_pages, page_size]: true where some request holds a token (request b's token t sits in entry
+    t % page_size of page indices[indptr[b] + t // page_size]).  Entries of indices past indptr[-1] own nothing."""
+    owned = torch.zeros(num_pages, page_size, dtype=torch.bool)
+    for b, n in enumerate(kv_lens):
+        t = torch.arange(int(n))
+        owned[indices[int(indptr[b]) + t // page_size].long(), t % page_size] = True
+    return owned
+
+
+def poison_unowned(cache, layout, owned):
+    """A copy of a paged cache ([pages, 2, ...] or a (k, v) tuple of [pages, ...]) whose unowned slots hold 0xFF bytes
+    in K and in V: a NaN in f16, bf16, f32, e4m3fn and e5m2.  Written through a uint8 view, owned slots untouched."""
+    if isinstance(cache, tuple):
+        return tuple(poison_unowned(c.unsqueeze(1), layout, owned).squeeze(1) for c in cache)
+    out = cache.clone()
+    raw = out.view(torch.uint8)  # [pages, kv, page, H, D * itemsize] (NHD) or [pages, kv, H, page, D * itemsize] (HND)
+    if layout == "HND":
+        raw = raw.transpose(2, 3)
+    raw.transpose(1, 2)[~owned] = 0xFF  # [pages, page, kv, H, bytes]
+    return out
+
+
+def poison_(t):
+    """Every byte of t becomes 0xFF, in place (workspaces, padding rows); returns t."""
+    t.view(torch.uint8).fill_(0xFF)
+    return t

@@ -3,7 +3,9 @@ dense scatter, and a pin of the seeded draw order every GPU test's inputs depend
 import pytest
 import torch
 
-from attn_inputs import indptr_of, make_paged, page_table, scatter_to_pages
+from attn_inputs import (indptr_of, make_paged, owned_slots, page_table, poison_, poison_unowned,
+                         scatter_to_pages)
+from oracle import attention_ref as R
 
 
 def test_indptr_of():
@@ -73,6 +75,78 @@ def test_scatter_to_pages_round_trip(layout):
     used = torch.zeros(num_pages, dtype=torch.bool)
     used[indices.long()] = True
     assert not nhd[~used].any()  # spare pages stay zero
+
+
+@pytest.mark.parametrize("page", [1, 5, 16])
+def test_owned_slots_marks_exactly_the_tokens(page):
+    kv_lens = [0, 1, page, page + 1, 3 * page + 2]
+    indptr, indices, last, num_pages = page_table(kv_lens, page, torch.Generator().manual_seed(4), extra_pages=3)
+    # surplus entries (graph padding) behind indptr[-1] own nothing, whichever page they name
+    padded = torch.cat([indices, indices[:2]])
+    owned = owned_slots(kv_lens, indptr, padded, page, num_pages)
+    assert owned.shape == (num_pages, page) and owned.dtype == torch.bool
+    want = torch.zeros(num_pages * page, dtype=torch.bool)
+    for b, n in enumerate(kv_lens):  # token by token, the definition
+        for t in range(n):
+            slot = int(indices[int(indptr[b]) + t // page]) * page + t % page
+            assert not want[slot]  # no slot is held twice
+            want[slot] = True
+    assert torch.equal(owned.flatten(), want) and int(owned.sum()) == sum(kv_lens)
+    used = torch.zeros(num_pages, dtype=torch.bool)
+    used[indices.long()] = True
+    assert int((~used).sum()) == 3 and not owned[~used].any()  # the spare pages are wholly unowned
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16, torch.float32, torch.float8_e4m3fn,
+                                   torch.float8_e5m2])
+@pytest.mark.parametrize("layout", ["NHD", "HND"])
+def test_poison_unowned_is_nan_on_the_complement_and_leaves_the_tokens(dtype, layout):
+    page, hkv, d = 5, 2, 8
+    kv_lens = [0, 1, page, page + 1]
+    cache, indptr, indices, last = make_paged(len(kv_lens), kv_lens, page, hkv, d, dtype, layout, seed=6)
+    owned = owned_slots(kv_lens, indptr, indices, page, cache.shape[0])
+    before = cache.clone()
+    bad = poison_unowned(cache, layout, owned)
+    assert torch.equal(cache.view(torch.uint8), before.view(torch.uint8))  # a copy: the argument is left alone
+    assert bad.dtype == dtype and bad.shape == cache.shape
+    nhd = lambda c: c if layout == "NHD" else c.transpose(2, 3)  # [pages, 2, page, H, D]
+    slots = lambda c: nhd(c).transpose(1, 2)  # [pages, page, 2, H, D]
+    assert torch.equal(slots(bad.view(torch.uint8))[owned], slots(cache.view(torch.uint8))[owned])
+    assert (slots(bad.view(torch.uint8))[~owned] == 0xFF).all()
+    assert slots(bad.float())[~owned].isnan().all() and not slots(bad.float())[owned].isnan().any()
+    k, v = poison_unowned((cache[:, 0], cache[:, 1]), layout, owned)  # the tuple form
+    assert torch.equal(k.view(torch.uint8), bad[:, 0].view(torch.uint8))
+    assert torch.equal(v.view(torch.uint8), bad[:, 1].view(torch.uint8))
+    t = torch.zeros(3, 4, dtype=dtype)
+    assert poison_(t) is t and t.float().isnan().all()
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16, torch.float8_e4m3fn, torch.float8_e5m2])
+@pytest.mark.parametrize("layout", ["NHD", "HND"])
+@pytest.mark.parametrize("page", [5, 16])
+def test_the_oracle_never_reads_an_unowned_slot(page, layout, dtype):
+    """batch_decode_ref and batch_prefill_ref slice [:kv_len], they do not mask: (o, lse) for the poisoned cache are
+    bit-identical to those for the clean one, and finite.  This is what lets the GPU tests hold a kernel that ran on
+    the poisoned cache to the oracle of the clean one."""
+    hq, hkv, d = 4, 2, 16
+    kv_lens = [1, page + 1, 2 * page + 1, 130, page, 0]
+    qo_lens = [1, 3, 2 * page + 1, 2, 1, 2]
+    cache, indptr, indices, last = make_paged(len(kv_lens), kv_lens, page, hkv, d, dtype, layout, seed=3)
+    g = torch.Generator().manual_seed(4)
+    owned = owned_slots(kv_lens, indptr, indices, page, cache.shape[0])
+    bad = poison_unowned(cache, layout, owned)
+    assert bad.float().isnan().any()
+    q = torch.randn(len(kv_lens), hq, d, generator=g)
+    clean = R.batch_decode_ref(q, cache.float(), layout, indptr, indices, last)
+    dirty = R.batch_decode_ref(q, bad.float(), layout, indptr, indices, last)
+    for a, b in zip(clean, dirty):
+        assert torch.equal(a, b) and torch.isfinite(b).all()
+    qp = torch.randn(sum(qo_lens), hq, d, generator=g)
+    for causal in (False, True):
+        clean = R.batch_prefill_ref(qp, indptr_of(qo_lens), cache.float(), layout, indptr, indices, last, causal=causal)
+        dirty = R.batch_prefill_ref(qp, indptr_of(qo_lens), bad.float(), layout, indptr, indices, last, causal=causal)
+        for a, b in zip(clean, dirty):
+            assert torch.equal(a, b) and not b.isnan().any()
 
 
 def test_make_paged_draw_order_is_pinned():

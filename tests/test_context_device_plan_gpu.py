@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from attn_inputs import indptr_of, make_paged, page_table, ptol, scatter_to_pages
+from attn_inputs import indptr_of, make_paged, page_table, poison_, ptol, scatter_to_pages
 from flashinfer import _lib
 from oracle import attention_ref as R
 from oracle.plan_ref import prefill_plan_ref
@@ -212,16 +212,15 @@ def _table_of(indptr, indices, max_blocks, fill, stride=None):
 
 @functools.lru_cache(maxsize=None)
 def _problem(qo, kv, ps, dtype, hq=HQ, hkv=HKV, d=D, kv_dtype=None, window=-1, extra_rows=0, seed=7):
-    """An HND cache, a dense block table whose entries past a request's pages point at a valid page full of large
-    finite values (which changes the result if it is read), the CSR table of the same pages for the oracle, and the
+    """An HND cache, a dense block table whose entries past a request's pages point at a valid page of 0xFF bytes (NaN
+    in f16, bf16 and e4m3fn: read even under a probability of zero, it turns the result into NaN), the CSR table of the
+    same pages for the oracle, and the
     oracle's output, computed once per problem and left unchanged."""
     kv_dtype = kv_dtype or dtype
     B, max_blocks = len(kv), -(-max(kv) // ps) + 2
     cache, indptr, indices, last = make_paged(B, list(kv), ps, hkv, d, kv_dtype, "HND", seed=seed)
     poison = min(set(range(cache.shape[0])) - set(indices.tolist()))
-    cache = cache.float()  # exact, and back
-    cache[poison] = 3.0e4 if kv_dtype in (torch.float16, torch.bfloat16) else 400.0
-    cache = cache.to(kv_dtype)
+    poison_(cache[poison])
     rows = sum(qo)
     q = torch.randn(rows + extra_rows, hq, d, generator=torch.Generator().manual_seed(seed + 1)).to(dtype)
     qo_indptr = indptr_of(qo)

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from attn_inputs import indptr_of, make_paged, page_table, tol
+from attn_inputs import indptr_of, make_paged, page_table, poison_, tol
 from flashinfer import _lib
 from oracle import attention_ref as R
 from oracle.plan_ref import decode_plan_ref
@@ -152,11 +152,12 @@ def _table_of(indptr, indices, max_blocks, fill):
 @functools.lru_cache(maxsize=None)
 def _problem(dtype):
     """Lens (a), Hq/Hkv/D = 32/8/128, page 16, an HND cache; block-table entries past a request's pages point at a
-    valid page full of large finite values, which changes the result if it is read.  The oracle output is shared."""
+    valid page of 0xFF bytes (NaN in f16 and bf16), which turns the result into NaN if it is read, even under a
+    probability of zero.  The oracle output is shared."""
     ps, max_blocks = 16, 256
     cache, indptr, indices, last = make_paged(len(LENS_A), LENS_A, ps, HKV, D, dtype, "HND", seed=7)
     poison = min(set(range(cache.shape[0])) - set(indices.tolist()))
-    cache[poison] = 3.0e4
+    poison_(cache[poison])
     q = torch.randn(len(LENS_A), HQ, D, generator=torch.Generator().manual_seed(8)).to(dtype)
     o_ref, _ = R.batch_decode_ref(q.float(), cache.float(), "HND", indptr, indices, last)
     return dict(q=q.to(DEV), cache=cache.to(DEV), indptr=indptr, indices=indices, last=last, o_ref=o_ref.float(),

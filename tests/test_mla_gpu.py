@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import flashinfer
-from attn_inputs import indptr_of, page_table, tol
+from attn_inputs import indptr_of, owned_slots, page_table, tol
 from oracle.attention_ref import attention_ref
 
 pytestmark = pytest.mark.gpu
@@ -19,23 +19,23 @@ DEV = "cuda:0"
 CKV, KPE = 512, 64
 
 
-def make_case(kv_lens, qo_lens, H, page_size, dtype, seed=0, nan_fill=False):
+def make_case(kv_lens, qo_lens, H, page_size, dtype, seed=0, nan_fill=False, spare_pages=0):
+    """nan_fill: every slot of ckv and kpe that no request owns -- the tail of each last page and the spare_pages
+    pages no request references -- holds 0xFF bytes, a NaN in f16 and bf16."""
     g = torch.Generator().manual_seed(seed)
-    B = len(kv_lens)
     pages = [-(-l // page_size) for l in kv_lens]
     kv_indptr = indptr_of(pages)
     total_pages = int(kv_indptr[-1])
-    kv_indices = torch.randperm(max(total_pages, 1), generator=g)[:total_pages].to(torch.int32)
+    num_pages = max(total_pages, 1) + spare_pages
+    kv_indices = torch.randperm(num_pages, generator=g)[:total_pages].to(torch.int32)
     qo_indptr = indptr_of(qo_lens)
     nnz = int(qo_indptr[-1])
-    ckv = (torch.randn(max(total_pages, 1), page_size, CKV, generator=g) * 0.5).to(dtype)
-    kpe = (torch.randn(max(total_pages, 1), page_size, KPE, generator=g) * 0.5).to(dtype)
+    ckv = (torch.randn(num_pages, page_size, CKV, generator=g) * 0.5).to(dtype)
+    kpe = (torch.randn(num_pages, page_size, KPE, generator=g) * 0.5).to(dtype)
     if nan_fill:
-        for b in range(B):
-            if pages[b] and kv_lens[b] % page_size:
-                last = int(kv_indices[kv_indptr[b + 1] - 1])
-                ckv[last, kv_lens[b] % page_size:] = float("nan")
-                kpe[last, kv_lens[b] % page_size:] = float("nan")
+        owned = owned_slots(kv_lens, kv_indptr, kv_indices, page_size, num_pages)
+        ckv.view(torch.int16)[~owned] = -1
+        kpe.view(torch.int16)[~owned] = -1
     q_nope = torch.randn(nnz, H, CKV, generator=g).to(dtype)
     q_pe = torch.randn(nnz, H, KPE, generator=g).to(dtype)
     return dict(kv_lens=kv_lens, qo_lens=qo_lens, H=H, page_size=page_size, dtype=dtype, qo_indptr=qo_indptr,
@@ -127,12 +127,23 @@ def test_mla_empty_requests():
     check(c, o, lse, False, SM)
 
 
-@pytest.mark.parametrize("ps", [16, 64])
-def test_mla_nan_past_kv_len(ps):
-    c = make_case([17, 2743, 70], [1, 2, 1], 16, ps, torch.float16, seed=6, nan_fill=True)
-    _, o, lse = plan_run(c, False, SM)
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("ps", [16, 64, 5, 1])
+def test_mla_nan_past_kv_len(ps, causal, dtype):
+    """NaN behind every request's last token and in three pages no request references (page 5: a tail on a page that
+    is no power of two; page 1: no tails, free pages only): finite, the oracle's result, and bit for bit the result on
+    the same cache without the NaN."""
+    args = ([17, 2743, 70], [1, 2, 1], 16, ps, dtype)
+    c = make_case(*args, seed=6, nan_fill=True, spare_pages=3)
+    assert c["ckv"].isnan().sum() >= 3 * ps * CKV and c["kpe"].isnan().sum() >= 3 * ps * KPE
+    _, o, lse = plan_run(c, causal, SM)
     assert torch.isfinite(o).all() and torch.isfinite(lse).all()
-    check(c, o, lse, False, SM)
+    check(c, o, lse, causal, SM)
+    clean = make_case(*args, seed=6, spare_pages=3)  # the same draws
+    assert not clean["ckv"].isnan().any() and torch.equal(clean["q_nope"], c["q_nope"])
+    _, o_clean, lse_clean = plan_run(clean, causal, SM)
+    assert torch.equal(o.view(torch.int16), o_clean.view(torch.int16)) and torch.equal(lse, lse_clean)
 
 
 def test_mla_strided_views():

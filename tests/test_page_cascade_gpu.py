@@ -153,14 +153,11 @@ def test_shared_prefix_decode_wrapper_and_sharded_path_world1():
     assert v_x.shape == (batch, 1, hq, d) and torch.equal(v_x[:, 0], o)
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_three_level_cascade_random_shapes_match_flat_attention(seed):
-    """MultiLevelCascadeAttentionWrapper with 3 levels (global prefix -> group prefix -> unique suffix with
-    several query rows per request, causal on the last level only; ref: flashinfer/cascade.py:228-555):
-    the merged result must equal flat causal attention over [global | group | unique]."""
+def three_level_problem(seed):
+    """The random three-level problem of a seed: (cache, q, plan_args, plan_kw, check).  plan_args / plan_kw are those
+    of MultiLevelCascadeAttentionWrapper.plan, tensors on the CPU; check(o) holds the wrapper's output to flat causal
+    attention over [global | group | unique], read from `cache`."""
     import random
-
-    import flashinfer
 
     rng = random.Random(seed)
     hkv = rng.choice([1, 2, 4])
@@ -211,28 +208,44 @@ def test_three_level_cascade_random_shapes_match_flat_attention(seed):
     kv_indices = [glob_idx, torch.cat(grp_idx), torch.cat(unq_idx)]
     last = [torch.tensor([ps], dtype=torch.int32), torch.full((n_groups,), ps, dtype=torch.int32),
             torch.tensor([(u - 1) % ps + 1 for u in uniq_lens], dtype=torch.int32)]
-    ws = torch.zeros(64 << 20, dtype=torch.uint8, device=DEV)
-    w = flashinfer.MultiLevelCascadeAttentionWrapper(3, ws, "NHD")
-    w.plan([x.to(DEV) for x in qo_indptr], [x.to(DEV) for x in kv_indptr], [x.to(DEV) for x in kv_indices],
-           [x.to(DEV) for x in last], hq, hkv, d, ps, causal=True, q_data_type=dtype)
-    o = w.run(q.to(DEV), cache.to(DEV))
 
     def rows(idx, n_tokens):
         kv = cache[idx.long()].float()
         return kv[:, 0].reshape(-1, hkv, d)[:n_tokens], kv[:, 1].reshape(-1, hkv, d)[:n_tokens]
 
-    kg, vg = rows(glob_idx, global_len)
-    r = 0
-    for gi, n in enumerate(reqs_per_group):
-        kgr, vgr = rows(grp_idx[gi], group_lens[gi])
-        for _ in range(n):
-            ku, vu = rows(unq_idx[r], uniq_lens[r])
-            k_all, v_all = torch.cat([kg, kgr, ku]), torch.cat([vg, vgr, vu])
-            qr = q[qo_cum[r]: qo_cum[r + 1]].float()
-            o_ref, _ = R.attention_ref(qr, k_all, v_all, causal=True)
-            t = dict(rtol=2.0 ** -6, atol=4e-3) if dtype == torch.bfloat16 else dict(rtol=2e-3, atol=2e-3)
-            torch.testing.assert_close(o[qo_cum[r]: qo_cum[r + 1]].float().cpu(), o_ref.float(), **t)
-            r += 1
+    def check(o):
+        kg, vg = rows(glob_idx, global_len)
+        r = 0
+        for gi, n in enumerate(reqs_per_group):
+            kgr, vgr = rows(grp_idx[gi], group_lens[gi])
+            for _ in range(n):
+                ku, vu = rows(unq_idx[r], uniq_lens[r])
+                k_all, v_all = torch.cat([kg, kgr, ku]), torch.cat([vg, vgr, vu])
+                qr = q[qo_cum[r]: qo_cum[r + 1]].float()
+                o_ref, _ = R.attention_ref(qr, k_all, v_all, causal=True)
+                t = dict(rtol=2.0 ** -6, atol=4e-3) if dtype == torch.bfloat16 else dict(rtol=2e-3, atol=2e-3)
+                torch.testing.assert_close(o[qo_cum[r]: qo_cum[r + 1]].float().cpu(), o_ref.float(), **t)
+                r += 1
+
+    return cache, q, (qo_indptr, kv_indptr, kv_indices, last, hq, hkv, d, ps), dict(causal=True, q_data_type=dtype), check
+
+
+def plan_cascade(w, plan_args, plan_kw):
+    tensors, rest = plan_args[:4], plan_args[4:]
+    w.plan(*([x.to(DEV) for x in level] for level in tensors), *rest, **plan_kw)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_three_level_cascade_random_shapes_match_flat_attention(seed):
+    """MultiLevelCascadeAttentionWrapper with 3 levels (global prefix -> group prefix -> unique suffix with
+    several query rows per request, causal on the last level only; ref: flashinfer/cascade.py:228-555):
+    the merged result must equal flat causal attention over [global | group | unique]."""
+    import flashinfer
+
+    cache, q, plan_args, plan_kw, check = three_level_problem(seed)
+    w = flashinfer.MultiLevelCascadeAttentionWrapper(3, torch.zeros(64 << 20, dtype=torch.uint8, device=DEV), "NHD")
+    plan_cascade(w, plan_args, plan_kw)
+    check(w.run(q.to(DEV), cache.to(DEV)))
 
 
 def test_batch_prefill_shared_prefix_wrapper():
