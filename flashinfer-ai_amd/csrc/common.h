@@ -299,6 +299,27 @@ __device__ __forceinline__ T block_reduce(T v, T* wave_tot) {
   return r;
 }
 
+// ---- LDS-DMA and its hand-counted wait (gemm.hip, gemm_big.hip, mm_fp4.hip, prefill_fp8_kernel.h) ----
+// global -> LDS without a register: every lane fetches 16 (or 4) bytes from its own `src`, the wave writes them
+// linearly from `lds_dst` on (lane i -> byte 16 i resp. 4 i).  The builtin wants the size as a literal.
+__device__ __forceinline__ void lds_dma16(const void* src, void* lds_dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
+}
+__device__ __forceinline__ void lds_dma4(const void* src, void* lds_dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
+}
+
+// Wait until at most VMCNT of this wave's memory instructions (the DMA pieces still allowed in flight) and none of
+// its LDS accesses are outstanding, then the workgroup barrier -- `__syncthreads()` would drain vmcnt.  ONE asm
+// statement: the s_barrier builtin is no memory fence for the compiler, which may hoist the next LDS reads between a
+// separate wait and the barrier (seen in prefill_fp8_kernel.h).
+template <int VMCNT>
+__device__ __forceinline__ void wait_vmcnt_barrier() {
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VMCNT) : "memory");
+}
+
 // ---- storage-type unpack: 16 bytes -> VEC floats ----
 template <int DT>
 struct KVTraits;

@@ -37,31 +37,15 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
   const int lq = lane & 31, lh = lane >> 5;
 
   // ---- tile assignment: XCD-contiguous logical id ----
-  const int total = p.num_m_tiles_bound * p.n_tiles;
-  int logical;
-  {
-    const int b = blockIdx.x;
-    const int xcd = b & 7, slot = b >> 3;
-    const int qn = total >> 3, rn = total & 7;
-    logical = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + slot;
-  }
+  const int logical = xcd_share(p.num_m_tiles_bound * p.n_tiles, blockIdx.x & 7).start + (blockIdx.x >> 3);
   // Banded order inside the XCD's range: kBandM m tiles x all n tiles per band, m fastest.  The ~64
   // workgroups an XCD runs at a time then cover an 8 x 8 block of output tiles (16 operand tiles in L2 for
   // 64 products) instead of one m row (65 operand tiles): at C4 the B matrix of a group is streamed 4x
   // instead of 32x.
   constexpr int kBandM = 8;
-  const int band_tiles = kBandM * p.n_tiles;
-  const int band = logical / band_tiles;
-  const int in_band = logical - band * band_tiles;
-  const int band_m = min(kBandM, p.num_m_tiles_bound - band * kBandM);
-  const int nt = in_band / band_m;
-  const int mt_global = band * kBandM + (in_band - nt * band_m);
-  int g = 0, m_begin = 0, m_end = p.m_total, mt = mt_global;
-  if (p.m_indptr) {
-    if (!find_group_tile<kBM>(p.m_indptr, p.num_groups, mt_global, lane, g, m_begin, m_end, mt)) return;
-  } else if (mt_global * kBM >= p.m_total) {
-    return;
-  }
+  int mt_global, nt, g, m_begin, m_end, mt;
+  band_tile_of<kBandM>(logical, p.num_m_tiles_bound, p.n_tiles, mt_global, nt);
+  if (!group_of_tile<kBM>(p, mt_global, lane, /*cached=*/false, GroupRows{}, g, m_begin, m_end, mt)) return;
   const int m0 = m_begin + mt * kBM;
   const int n0 = nt * kBN;
   const int K = p.k, N = p.n;
@@ -70,7 +54,6 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
 
   // ---- staging geometry: 4 passes of 32 rows x 8 chunks ----
   const int st_row = tid >> 3, st_ch = tid & 7;
-  auto lds_off = [](int row, int ch) { return row * kBK + ((ch ^ ((row >> 1) & 7)) << 4); };
   // global loads run one k block ahead of the MFMAs, through registers; the k block past the end re-loads
   // the last one (no branch around a load)
   struct StageRegs {
@@ -99,11 +82,12 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
       const int row = ps * 32 + st_row;
-      *(u32x4*)(&smem[buf][0][lds_off(row, st_ch)]) = r.a[ps];
-      *(u32x4*)(&smem[buf][1][lds_off(row, st_ch)]) = r.b[ps];
+      *(u32x4*)(&smem[buf][0][image_off(row, st_ch)]) = r.a[ps];
+      *(u32x4*)(&smem[buf][1][image_off(row, st_ch)]) = r.b[ps];
     }
   };
   // scales: a per lane (its m column), b per workgroup n tile
+  // (not through ScaleGeom: with its offset + kb * stride form, or only its m_cnt, the k loop comes out different)
   auto a_scale_at = [&](int kb, int m) -> float {
     const int mi = a_scale_row(p.a_gran_m, m_begin, m);
     const int m_cnt = p.a_gran_m == 1 ? p.m_total : (p.m_total + p.a_gran_m - 1) / p.a_gran_m;
@@ -155,11 +139,9 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-      for (int mb = 0; mb < 2; ++mb) {
-        const u32x4 lo = *(const u32x4*)(&smem[buf][0][lds_off(64 * wm + 32 * mb + lq, 4 * kk + 2 * lh)]);
-        const u32x4 hi = *(const u32x4*)(&smem[buf][0][lds_off(64 * wm + 32 * mb + lq, 4 * kk + 2 * lh + 1)]);
-        fa[kk][mb] = i32x8g{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-      }
+      for (int mb = 0; mb < 2; ++mb)
+        fa[kk][mb] = fp8_frag(&smem[buf][0][image_off(64 * wm + 32 * mb + lq, 4 * kk + 2 * lh)],
+                              &smem[buf][0][image_off(64 * wm + 32 * mb + lq, 4 * kk + 2 * lh + 1)]);
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
       f32x16g part[2];
@@ -169,13 +151,10 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
         for (int r = 0; r < 16; ++r) part[mb][r] = 0.f;
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
-        const u32x4 lo = *(const u32x4*)(&smem[buf][1][lds_off(64 * wn + 32 * nb + lq, 4 * kk + 2 * lh)]);
-        const u32x4 hi = *(const u32x4*)(&smem[buf][1][lds_off(64 * wn + 32 * nb + lq, 4 * kk + 2 * lh + 1)]);
-        const i32x8g fb = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        const i32x8g fb = fp8_frag(&smem[buf][1][image_off(64 * wn + 32 * nb + lq, 4 * kk + 2 * lh)],
+                                   &smem[buf][1][image_off(64 * wn + 32 * nb + lq, 4 * kk + 2 * lh + 1)]);
 #pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-          part[mb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-              fb, fa[kk][mb], part[mb], MA_E5M2 ? 1 : 0, MB_E5M2 ? 1 : 0, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
+        for (int mb = 0; mb < 2; ++mb) part[mb] = mfma_fp8<MA_E5M2, MB_E5M2>(fb, fa[kk][mb], part[mb]);
       }
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb) {
@@ -208,16 +187,9 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-          uint32_t w[2];
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const uint32_t lo = f32_to_16bit(acc[nb][mb][4 * r4 + 2 * e], p.out_dtype);
-            const uint32_t hi = f32_to_16bit(acc[nb][mb][4 * r4 + 2 * e + 1], p.out_dtype);
-            w[e] = lo | (hi << 16);
-          }
-          *(u32x2*)(scratch + (32 * mb + lq) * kOutStride + (32 * nb + 8 * r4 + 4 * lh) * 2) = u32x2{w[0], w[1]};
-        }
+        for (int r4 = 0; r4 < 4; ++r4)
+          *(u32x2*)(scratch + (32 * mb + lq) * kOutStride + (32 * nb + 8 * r4 + 4 * lh) * 2) =
+              pack4_16bit(acc[nb][mb], 4 * r4, p.out_dtype);
     const bool d_aligned16 = (((uintptr_t)p.d) & 15) == 0;
 #pragma unroll
     for (int i2 = 0; i2 < 8; ++i2) {
@@ -227,13 +199,7 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
       const int m = m0 + 64 * wm + r;
       const int n = n0 + 64 * wn + 8 * c;
       if (m >= m_end || n >= N) continue;  // n is a multiple of 8 and so is N
-      uint16_t* dst = (uint16_t*)p.d + (int64_t)m * N + n;
-      if (d_aligned16) {
-        *(u32x4*)dst = v;
-      } else {
-        *(u32x2*)dst = u32x2{v[0], v[1]};
-        *(u32x2*)(dst + 4) = u32x2{v[2], v[3]};
-      }
+      store_row_piece((uint16_t*)p.d + (int64_t)m * N + n, v, d_aligned16);
     }
   }
 }
@@ -244,8 +210,7 @@ __global__ void __launch_bounds__(kGemmThreads, 2) group_gemm_fp8_kernel(const G
 // directly (`global_load_lds_dwordx4`, 1 KiB per wave instruction), two k blocks ahead through a ring of three 52 KB
 // LDS stages (156 of the 160 KB): no staging registers, no VGPR -> LDS store transfer.  Synchronisation is by hand:
 // every wave waits `vmcnt(8)` (its own pieces of the NEXT block landed, the 8 DMA instructions of the block after it
-// still in flight) and then a raw `s_barrier` -- `__syncthreads()` would drain vmcnt.  (r1's register-staged form of
-// this kernel was removed in r3: the DMA form replaced it as the default in r1 and nothing selected it.)
+// still in flight) and then a raw `s_barrier` -- `__syncthreads()` would drain vmcnt.
 constexpr int kWsThreads = 512;
 constexpr int kWsBM = 256;
 
@@ -270,49 +235,25 @@ __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const
   const int lq = lane & 31, lh = lane >> 5;
   const int K = p.k, N = p.n;
   const int kblocks = K / kBK;
-  auto lds_off = [](int row, int ch) { return row * kBK + ((ch ^ ((row >> 1) & 7)) << 4); };
-  const int m_cnt = p.a_gran_m == 1 ? p.m_total : (p.m_total + p.a_gran_m - 1) / p.a_gran_m;
-  const int a_sc_stride = p.scale_k_major ? 1 : m_cnt;
-  const int n_sblocks = (N + 127) / 128;
-  const int b_sc_stride = p.scale_k_major ? 1 : n_sblocks;
+  const ScaleGeom sg = scale_geom(p);
   // LDS read addresses: every fragment address is one per-lane base XOR a literal (the k half flips chunk
   // bit 2, the second 16 bytes chunk bit 0) plus a literal; the bases pass through an empty asm in the loop
   // so that the derived addresses are recomputed there instead of living in 16 registers
-  uint32_t a_rd_base = (uint32_t)lds_off(64 * wm + lq, 2 * lh);
-  uint32_t b_rd_base = (uint32_t)(kBOff + lds_off(64 * wn + lq, 2 * lh));
+  uint32_t a_rd_base = (uint32_t)image_off(64 * wm + lq, 2 * lh);
+  uint32_t b_rd_base = (uint32_t)(kBOff + image_off(64 * wn + lq, 2 * lh));
 
   // ---- persistent workgroup: the XCD-contiguous tile range of this XCD, strided by its workgroups ----
   const int n_tiles = (N + TN - 1) / TN;
-  const int total = p.num_m_tiles_bound * n_tiles;
-  int logical, logical_end;
-  const int logical_step = gridDim.x >> 3;
-  {
-    const int b = blockIdx.x;
-    const int xcd = b & 7, slot = b >> 3;
-    const int qn = total >> 3, rn = total & 7;
-    const int start = xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn;
-    logical = start + slot;
-    logical_end = start + qn + (xcd < rn ? 1 : 0);
-  }
+  const TileShare share = xcd_share(p.num_m_tiles_bound * n_tiles, blockIdx.x & 7);
+  int logical = share.start + (blockIdx.x >> 3);
+  const int logical_end = share.start + share.count, logical_step = gridDim.x >> 3;
 
   // Up to 64 groups: lane i keeps group i's row range and first tile for the whole kernel, so the per-tile
   // (group, m tile) search is a ballot + three readlanes instead of loads (a round trip per tile, with
   // nothing else in flight to hide it).  More groups: the looping search per tile.
   const bool groups_cached = p.m_indptr != nullptr && p.num_groups <= 64;
-  int gc_lo = 0, gc_hi = 0, gc_start = 0;
-  if (groups_cached) {
-    const bool in = lane < p.num_groups;
-    gc_lo = in ? p.m_indptr[lane] : 0;
-    gc_hi = in ? p.m_indptr[lane + 1] : 0;
-    const int tiles = (gc_hi - gc_lo + TM - 1) / TM;
-    int incl = tiles;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += v;
-    }
-    gc_start = incl - tiles;
-  }
+  GroupRows gc{0, 0, 0};
+  if (groups_cached) gc = lane_group_rows<TM>(p.m_indptr, p.num_groups, lane);
 
   f32x16g acc[2][2];  // [n block][m block]
   int out_m0 = 0, out_n0 = 0, out_m_end = 0;  // tile whose accumulators are waiting to be stored
@@ -330,16 +271,9 @@ __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-          uint32_t w[2];
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const uint32_t lo = f32_to_16bit(acc[nb][mb][4 * r4 + 2 * e], p.out_dtype);
-            const uint32_t hi = f32_to_16bit(acc[nb][mb][4 * r4 + 2 * e + 1], p.out_dtype);
-            w[e] = lo | (hi << 16);
-          }
-          *(u32x2*)(scratch + (32 * mb + lq) * kOutStride + (8 * r4 + 4 * lh) * 2) = u32x2{w[0], w[1]};
-        }
+        for (int r4 = 0; r4 < 4; ++r4)
+          *(u32x2*)(scratch + (32 * mb + lq) * kOutStride + (8 * r4 + 4 * lh) * 2) =
+              pack4_16bit(acc[nb][mb], 4 * r4, p.out_dtype);
 #pragma unroll
       for (int i2 = 0; i2 < 4; ++i2) {
         const int idx = lane + 64 * i2;
@@ -348,45 +282,16 @@ __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const
         const int m = out_m0 + 64 * wm + r;
         const int n = out_n0 + 64 * wn + 32 * nb + 8 * c;
         if (m >= out_m_end || n >= N) continue;  // n is a multiple of 8 and so is N
-        uint16_t* dst = (uint16_t*)p.d + (int64_t)m * N + n;
-        if (d_aligned16) {
-          *(u32x4*)dst = v;
-        } else {
-          *(u32x2*)dst = u32x2{v[0], v[1]};
-          *(u32x2*)(dst + 4) = u32x2{v[2], v[3]};
-        }
+        store_row_piece((uint16_t*)p.d + (int64_t)m * N + n, v, d_aligned16);
       }
     }
   };
 
   for (; logical < logical_end; logical += logical_step) {
     constexpr int kBandM = 1024 / TM;  // 1024 rows x all n per band, as in the 128 x 128 kernel
-    const int band_tiles = kBandM * n_tiles;
-    const int band = logical / band_tiles;
-    const int in_band = logical - band * band_tiles;
-    const int band_m = min(kBandM, p.num_m_tiles_bound - band * kBandM);
-    const int nt = in_band / band_m;
-    const int mt_global = band * kBandM + (in_band - nt * band_m);
-    int g = 0, m_begin = 0, m_end = p.m_total, mt = mt_global;
-    bool found = true;
-    if (p.m_indptr) {
-      if (groups_cached) {
-        const int tiles = (gc_hi - gc_lo + TM - 1) / TM;
-        const uint64_t hit = __ballot(mt_global >= gc_start && mt_global < gc_start + tiles);
-        found = hit != 0;
-        if (found) {
-          g = __builtin_ctzll(hit);
-          m_begin = __builtin_amdgcn_readlane(gc_lo, g);
-          m_end = __builtin_amdgcn_readlane(gc_hi, g);
-          mt = mt_global - __builtin_amdgcn_readlane(gc_start, g);
-        }
-      } else {
-        found = find_group_tile<TM>(p.m_indptr, p.num_groups, mt_global, lane, g, m_begin, m_end, mt);
-      }
-    } else if (mt_global * TM >= p.m_total) {
-      found = false;
-    }
-    if (!found) continue;  // the grid bound counts one partial tile per group; uniform per workgroup
+    int mt_global, nt, g, m_begin, m_end, mt;
+    band_tile_of<kBandM>(logical, p.num_m_tiles_bound, n_tiles, mt_global, nt);
+    if (!group_of_tile<TM>(p, mt_global, lane, groups_cached, gc, g, m_begin, m_end, mt)) continue;
     const int m0 = m_begin + mt * TM;
     const int n0 = nt * TN;
     const uint8_t* Bg = p.b + (int64_t)g * N * K;
@@ -401,36 +306,27 @@ __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const
 #pragma unroll
     for (int j2 = 0; j2 < 6; ++j2) {
       const int row = 8 * (6 * wave + j2) + (lane >> 3);
-      const int ch = (lane & 7) ^ ((row >> 1) & 7);
+      const int ch = image_chunk(row, lane & 7);
       const int r = row < TM ? min(m0 + row, m_end - 1) - m0 : min(n0 + row - TM, N - 1) - n0;
       d_off[j2] = (uint32_t)r * (uint32_t)K + ch * 16;
     }
     // scale sources for the DMA: one A-scale pointer per lane (row 64 wm + lane of the tile), B scale uniform
-    const int nsb = min((n0 + 64 * wn) / 128, n_sblocks - 1);  // this wave's 128-wide scale block of B
-    const float* const b_sc = p.scale_k_major ? p.b_scale + ((int64_t)g * n_sblocks + nsb) * kblocks
-                                              : p.b_scale + (int64_t)g * kblocks * n_sblocks + nsb;
-    const float* a_sc_dma;
-    {
-      const int m = min(m0 + 64 * wm + lane, m_end - 1);
-      const int mi = a_scale_row(p.a_gran_m, m_begin, m);
-      a_sc_dma = p.scale_k_major ? p.a_scale + (int64_t)mi * kblocks : p.a_scale + mi;
-    }
+    const int nsb = min((n0 + 64 * wn) / 128, sg.n_sblocks - 1);  // this wave's 128-wide scale block of B
+    const float* const b_sc = p.b_scale + sg.b_block(g, nsb);
+    const float* const a_sc_dma =
+        p.a_scale + sg.a_row(a_scale_row(p.a_gran_m, m_begin, min(m0 + 64 * wm + lane, m_end - 1)));
     auto dma = [&](int kb, int stage) {
       const uint32_t koff = (uint32_t)(kb * kBK);
 #pragma unroll
       for (int j2 = 0; j2 < 6; ++j2) {
         const int q = 6 * wave + j2;
-        const uint8_t* src_p = (q < TM / 8 ? a_tile : b_tile) + (d_off[j2] + koff);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_p,
-                                         (__attribute__((address_space(3))) void*)(&smem[stage][q * 1024]), 16, 0, 0);
+        lds_dma16((q < TM / 8 ? a_tile : b_tile) + (d_off[j2] + koff), &smem[stage][q * 1024]);
       }
       // the block's scales travel the same way (4 bytes per lane): lane L's A scale is the one of row
       // 64 wm + L of the tile, the B scale is fetched by every lane.  They are then ordinary LDS reads; an
       // ordinary global load in flight beside the DMA would cost a vmcnt(0) at its first use.
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_sc_dma + (int64_t)kb * a_sc_stride),
-                                       (__attribute__((address_space(3))) void*)(&smem[stage][kScOff + wave * 512]), 4, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_sc + (int64_t)kb * b_sc_stride),
-                                       (__attribute__((address_space(3))) void*)(&smem[stage][kScOff + wave * 512 + 256]), 4, 0, 0);
+      lds_dma4(a_sc_dma + (int64_t)kb * sg.a_stride, &smem[stage][kScOff + wave * 512]);
+      lds_dma4(b_sc + (int64_t)kb * sg.b_stride, &smem[stage][kScOff + wave * 512 + 256]);
     };
     // the next tile's first two blocks go out BEFORE the finished tile is converted and stored (stages 0
     // and 1; the store's scratch is stage 2): with one workgroup per CU nothing else would cover the round trip
@@ -450,11 +346,9 @@ __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const
         for (int r = 0; r < 16; ++r) acc[i2][j2][r] = 0.f;
     // D(0) landed.  The output stores are younger than both blocks and vmcnt retires in order, so with
     // stores in the queue the only count that is sure to cover D(0) is 0.
-    // wait + barrier as ONE asm statement: the s_barrier builtin is no memory fence for the compiler, which may
-    // hoist the next LDS reads between a separate wait and the barrier (seen in prefill_fp8_kernel.h)
     // (also: every wave is done with the stage 2 scratch before step 0's DMA)
-    if (kblocks > 1 && !stored) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (kblocks > 1 && !stored) wait_vmcnt_barrier<8>();
+    else wait_vmcnt_barrier<0>();
     f32x16g p_carry;  // block (1, 1) of the previous k step, folded at the start of the next one
 #pragma unroll
     for (int r = 0; r < 16; ++r) p_carry[r] = 0.f;
@@ -470,22 +364,6 @@ __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const
       const uint8_t* const stage = &smem[buf][0];
       // One 32 x 32 block at a time, cut into sched_barrier regions: left alone the scheduler hoists every
       // LDS read and all four partial products to the top and spills ~30 registers.
-      auto frag = [&](uint32_t base, int kk, int blk) {
-        const u32x4 lo = *(const u32x4*)(stage + ((base ^ (kk << 6)) + blk * 32 * kBK));
-        const u32x4 hi = *(const u32x4*)(stage + ((base ^ (kk << 6) ^ 16) + blk * 32 * kBK));
-        return i32x8g{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-      };
-      auto mfma0 = [&](const i32x8g& b, const i32x8g& a) {
-        f32x16g z;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) z[r] = 0.f;
-        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b, a, z, MA_E5M2 ? 1 : 0, MB_E5M2 ? 1 : 0, 0,
-                                                               0x7F7F7F7F, 0, 0x7F7F7F7F);
-      };
-      auto mfma1 = [&](const i32x8g& b, const i32x8g& a, const f32x16g& c) {
-        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b, a, c, MA_E5M2 ? 1 : 0, MB_E5M2 ? 1 : 0, 0,
-                                                               0x7F7F7F7F, 0, 0x7F7F7F7F);
-      };
       auto fold = [&](int nb, int mb, const f32x16g& part, float s) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nb][mb][r] += s * part[r];
@@ -497,43 +375,43 @@ __global__ void __launch_bounds__(kWsThreads, 1) group_gemm_fp8_dma_kernel(const
       // the first one runs, and neither can anything behind it in this wave.  So the previous block's fold
       // sits BETWEEN the two, in the shadow of the first.
       // region 0: fragment reads, the fold carried over from the previous k step hides their latency
-      fa0[0] = frag(a_rd_base, 0, 0);
-      fb0[0] = frag(b_rd_base, 0, 0);
-      fa0[1] = frag(a_rd_base, 1, 0);
-      fb0[1] = frag(b_rd_base, 1, 0);
-      fa1[0] = frag(a_rd_base, 0, 1);
-      fa1[1] = frag(a_rd_base, 1, 1);
+      fa0[0] = fp8_frag(stage, a_rd_base, 0, 0);
+      fb0[0] = fp8_frag(stage, b_rd_base, 0, 0);
+      fa0[1] = fp8_frag(stage, a_rd_base, 1, 0);
+      fb0[1] = fp8_frag(stage, b_rd_base, 1, 0);
+      fa1[0] = fp8_frag(stage, a_rd_base, 0, 1);
+      fa1[1] = fp8_frag(stage, a_rd_base, 1, 1);
       fold(1, 1, p_carry, s_carry);
       __builtin_amdgcn_sched_barrier(0);
-      f32x16g p00 = mfma0(fb0[0], fa0[0]);
+      f32x16g p00 = mfma_fp8_zero<MA_E5M2, MB_E5M2>(fb0[0], fa0[0]);
       __builtin_amdgcn_sched_barrier(0);
-      fb1[0] = frag(b_rd_base, 0, 1);
-      fb1[1] = frag(b_rd_base, 1, 1);
+      fb1[0] = fp8_frag(stage, b_rd_base, 0, 1);
+      fb1[1] = fp8_frag(stage, b_rd_base, 1, 1);
       __builtin_amdgcn_sched_barrier(0);
-      p00 = mfma1(fb0[1], fa0[1], p00);
+      p00 = mfma_fp8<MA_E5M2, MB_E5M2>(fb0[1], fa0[1], p00);
       // region 1
-      f32x16g p01 = mfma0(fb0[0], fa1[0]);
+      f32x16g p01 = mfma_fp8_zero<MA_E5M2, MB_E5M2>(fb0[0], fa1[0]);
       __builtin_amdgcn_sched_barrier(0);
       fold(0, 0, p00, s0);
       __builtin_amdgcn_sched_barrier(0);
-      p01 = mfma1(fb0[1], fa1[1], p01);
+      p01 = mfma_fp8<MA_E5M2, MB_E5M2>(fb0[1], fa1[1], p01);
       // region 2
-      f32x16g p10 = mfma0(fb1[0], fa0[0]);
+      f32x16g p10 = mfma_fp8_zero<MA_E5M2, MB_E5M2>(fb1[0], fa0[0]);
       __builtin_amdgcn_sched_barrier(0);
       fold(0, 1, p01, s1);
       __builtin_amdgcn_sched_barrier(0);
-      p10 = mfma1(fb1[1], fa0[1], p10);
+      p10 = mfma_fp8<MA_E5M2, MB_E5M2>(fb1[1], fa0[1], p10);
       // region 3
-      f32x16g p11 = mfma0(fb1[0], fa1[0]);
+      f32x16g p11 = mfma_fp8_zero<MA_E5M2, MB_E5M2>(fb1[0], fa1[0]);
       __builtin_amdgcn_sched_barrier(0);
       fold(1, 0, p10, s0);
       __builtin_amdgcn_sched_barrier(0);
-      p11 = mfma1(fb1[1], fa1[1], p11);
+      p11 = mfma_fp8<MA_E5M2, MB_E5M2>(fb1[1], fa1[1], p11);
       p_carry = p11;
       s_carry = s1;
       // D(kb + 1) must have landed (all waves' pieces: barrier); the 8 pieces of D(kb + 2) stay in flight
-      if (kb + 2 < kblocks) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if (kb + 2 < kblocks) wait_vmcnt_barrier<8>();
+      else wait_vmcnt_barrier<0>();
       __builtin_amdgcn_sched_barrier(0);  // no mixing of two k steps either
     };
     {

@@ -71,13 +71,9 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
   const int lq = lane & 31, lh = lane >> 5;
   const int K = p.k, N = p.n;
   const int kblocks = K / kBK;
-  auto lds_off = [](int row, int ch) { return row * kBK + ((ch ^ ((row >> 1) & 7)) << 4); };
-  const int m_cnt = p.a_gran_m == 1 ? p.m_total : (p.m_total + p.a_gran_m - 1) / p.a_gran_m;
-  const int a_sc_stride = p.scale_k_major ? 1 : m_cnt;
-  const int n_sblocks = (N + 127) / 128;
-  const int b_sc_stride = p.scale_k_major ? 1 : n_sblocks;
-  uint32_t a_rd_base = (uint32_t)lds_off(64 * wm + lq, 2 * lh);
-  uint32_t b_rd_base = (uint32_t)(kBOff + lds_off(128 * wn + lq, 2 * lh));
+  const ScaleGeom sg = scale_geom(p);
+  uint32_t a_rd_base = (uint32_t)image_off(64 * wm + lq, 2 * lh);
+  uint32_t b_rd_base = (uint32_t)(kBOff + image_off(128 * wn + lq, 2 * lh));
 
   // ---- persistent workgroup: the tiles of this XCD, strided by its workgroups ----
   // Tiles are ordered in bands of kBandM m tiles x all n tiles (m fastest inside a band, see gemm.hip).  The bands are
@@ -94,33 +90,15 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
   const int n_inter = (p.num_m_tiles_bound / (8 * kBandM)) * band_tiles;  // per XCD
   const int logical_step = gridDim.x >> 3;
   const int xcd_id = blockIdx.x & 7;
-  int logical = blockIdx.x >> 3, logical_end, rem_base;
-  {
-    const int rem_total = total - 8 * n_inter;
-    const int qn = rem_total >> 3, rn = rem_total & 7;
-    rem_base = 8 * n_inter + (xcd_id < rn ? xcd_id * (qn + 1) : rn * (qn + 1) + (xcd_id - rn) * qn);
-    logical_end = n_inter + qn + (xcd_id < rn ? 1 : 0);
-  }
+  const TileShare rem = xcd_share(total - 8 * n_inter, xcd_id);
+  const int rem_base = 8 * n_inter + rem.start, logical_end = n_inter + rem.count;
+  int logical = blockIdx.x >> 3;
 
   // up to 64 groups: group i's row range and first tile live in LDS (a register copy per lane would stay
   // live across the k loop), read back by lane i at every tile border -- no global round trip per tile
   const bool groups_cached = p.m_indptr != nullptr && p.num_groups <= 64;
-  int32_t* const group_tab = (int32_t*)&smem[kGroupTab];  // [3][64]: lo, hi, first tile
-  if (groups_cached && wave == 0) {
-    const bool in = lane < p.num_groups;
-    const int lo = in ? p.m_indptr[lane] : 0;
-    const int hi = in ? p.m_indptr[lane + 1] : 0;
-    const int tiles = (hi - lo + kBigTM - 1) / kBigTM;
-    int incl = tiles;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int v = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += v;
-    }
-    group_tab[lane] = lo;
-    group_tab[64 + lane] = hi;
-    group_tab[128 + lane] = incl - tiles;
-  }
+  GroupRows* const group_tab = (GroupRows*)&smem[kGroupTab];  // [64]
+  if (groups_cached && wave == 0) group_tab[lane] = lane_group_rows<kBigTM>(p.m_indptr, p.num_groups, lane);
   __syncthreads();
 
   f32x16g acc[4][2];  // [n block][m block]; register r of a block: n = 8 (r / 4) + 4 lh + r % 4, m = lq
@@ -139,32 +117,19 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-          for (int r4 = 0; r4 < 4; ++r4) {
-            uint32_t w[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-              const uint32_t lo = f32_to_16bit(acc[2 * h + nbl][mb][4 * r4 + 2 * e], p.out_dtype);
-              const uint32_t hi = f32_to_16bit(acc[2 * h + nbl][mb][4 * r4 + 2 * e + 1], p.out_dtype);
-              w[e] = lo | (hi << 16);
-            }
-            const int row = 32 * mb + lq;
-            *(u32x2*)(scratch + lds_off(row, 4 * nbl + r4) + 8 * lh) = u32x2{w[0], w[1]};
-          }
+          for (int r4 = 0; r4 < 4; ++r4)
+            *(u32x2*)(scratch + image_off(32 * mb + lq, 4 * nbl + r4) + 8 * lh) =
+                pack4_16bit(acc[2 * h + nbl][mb], 4 * r4, p.out_dtype);
 #pragma unroll
       for (int i2 = 0; i2 < 8; ++i2) {
         const int idx = lane + 64 * i2;
         const int r = idx >> 3, c = idx & 7;
-        const u32x4 v = *(const u32x4*)(scratch + lds_off(r, c));
+        const u32x4 v = *(const u32x4*)(scratch + image_off(r, c));
         const int m = out_m0 + 64 * wm + r;
         const int n = out_n0 + 128 * wn + 64 * h + 8 * c;
         if (m >= out_m_end || n >= N) continue;  // n is a multiple of 8 and so is N
-        uint16_t* dst = (uint16_t*)p.d + (int64_t)m * N + n;
-        if (d_aligned16) {
-          __builtin_nontemporal_store(v, (u32x4*)dst);  // 128 KB per tile that nobody reads again stay out of the L2's way
-        } else {
-          *(u32x2*)dst = u32x2{v[0], v[1]};
-          *(u32x2*)(dst + 4) = u32x2{v[2], v[3]};
-        }
+        // non-temporal: 128 KB per tile that nobody reads again stay out of the L2's way
+        store_row_piece</*NT=*/true>((uint16_t*)p.d + (int64_t)m * N + n, v, d_aligned16);
       }
     }
   };
@@ -180,30 +145,9 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
       band = gl / band_tiles;
       in_band = gl - band * band_tiles;
     }
-    const int band_m = min(kBandM, p.num_m_tiles_bound - band * kBandM);
-    const int nt = in_band / band_m;
-    const int mt_global = band * kBandM + (in_band - nt * band_m);
-    int g = 0, m_begin = 0, m_end = p.m_total, mt = mt_global;
-    bool found = true;
-    if (p.m_indptr) {
-      if (groups_cached) {
-        const int gc_lo = group_tab[lane], gc_hi = group_tab[64 + lane], gc_start = group_tab[128 + lane];
-        const int tiles = (gc_hi - gc_lo + kBigTM - 1) / kBigTM;
-        const uint64_t hit = __ballot(mt_global >= gc_start && mt_global < gc_start + tiles);
-        found = hit != 0;
-        if (found) {
-          g = __builtin_ctzll(hit);
-          m_begin = __builtin_amdgcn_readlane(gc_lo, g);
-          m_end = __builtin_amdgcn_readlane(gc_hi, g);
-          mt = mt_global - __builtin_amdgcn_readlane(gc_start, g);
-        }
-      } else {
-        found = find_group_tile<kBigTM>(p.m_indptr, p.num_groups, mt_global, lane, g, m_begin, m_end, mt);
-      }
-    } else if (mt_global * kBigTM >= p.m_total) {
-      found = false;
-    }
-    if (!found) continue;  // the grid bound counts one partial tile per group; uniform per workgroup
+    int mt_global, nt, g, m_begin, m_end, mt;
+    band_tile<kBandM>(band, in_band, p.num_m_tiles_bound, mt_global, nt);
+    if (!group_of_tile<kBigTM>(p, mt_global, lane, groups_cached, group_tab[lane], g, m_begin, m_end, mt)) continue;
     const int m0 = m_begin + mt * kBigTM;
     const int n0 = nt * kBigTN;
     const uint8_t* Bg = p.b + (int64_t)g * N * K;
@@ -220,21 +164,15 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
     const uint8_t* const src_tile = wave < 4 ? p.a + (int64_t)m0 * K : Bg + (int64_t)n0 * K;
     const auto src_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)src_tile, 0, __builtin_amdgcn_readfirstlane(rows_valid * K), 0x00020000);
-    const uint32_t v_par0 = (uint32_t)(64 * (wave & 3) + (lane >> 3)) * (uint32_t)K + (((lane & 7) ^ (lane >> 4)) << 4);
+    const uint32_t v_par0 = (uint32_t)(64 * (wave & 3) + (lane >> 3)) * (uint32_t)K + (image_chunk(lane >> 3, lane & 7) << 4);
     // the block's scales travel the same way (4 bytes per lane; see gemm.hip): lane L fetches the A scale of
     // row 64 wm + L of the tile, every lane the B scale of this wave's 128-wide block
-    const int nsb = min((n0 + 128 * wn) / 128, n_sblocks - 1);
-    const auto b_sc_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.scale_k_major ? p.b_scale + ((int64_t)g * n_sblocks + nsb) * kblocks
-                                : p.b_scale + (int64_t)g * kblocks * n_sblocks + nsb),
-        0, 0x7fffffff, 0x00020000);
+    const int nsb = min((n0 + 128 * wn) / 128, sg.n_sblocks - 1);
+    const auto b_sc_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(p.b_scale + sg.b_block(g, nsb)), 0, 0x7fffffff, 0x00020000);
     const auto a_sc_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.a_scale, 0, 0x7fffffff, 0x00020000);
-    uint32_t a_sc_voff;
-    {
-      const int m = min(m0 + 64 * wm + lane, m_end - 1);
-      const int mi = a_scale_row(p.a_gran_m, m_begin, m);
-      a_sc_voff = (uint32_t)(p.scale_k_major ? mi * kblocks : mi) * 4u;
-    }
+    const uint32_t a_sc_voff =
+        (uint32_t)sg.a_row(a_scale_row(p.a_gran_m, m_begin, min(m0 + 64 * wm + lane, m_end - 1))) * 4u;
     // oob = 0x80000000 pushes every lane's offset past the descriptor's range: the pieces are then written as zeros
     // without a memory access (see k_step)
     auto dma_pieces = [&](int kb, int stage, auto first_c, auto count_c, uint32_t oob = 0) {
@@ -253,10 +191,10 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
     auto dma_scales = [&](int kb, int stage, uint32_t oob = 0) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           a_sc_rsrc, (__attribute__((address_space(3))) void*)(&smem[stage * kBigStage + kBigScOff + wave * 512]), 4,
-          a_sc_voff + oob, kb * a_sc_stride * 4, 0, 0);
+          a_sc_voff + oob, kb * sg.a_stride * 4, 0, 0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           b_sc_rsrc, (__attribute__((address_space(3))) void*)(&smem[stage * kBigStage + kBigScOff + wave * 512 + 256]),
-          4, oob, kb * b_sc_stride * 4, 0, 0);
+          4, oob, kb * sg.b_stride * 4, 0, 0);
     };
     auto dma = [&](int kb, int stage, uint32_t oob = 0) {
       dma_pieces(kb, stage, std::integral_constant<int, 0>{}, std::integral_constant<int, 8>{}, oob);
@@ -278,7 +216,7 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
         for (int r = 0; r < 16; ++r) acc[i2][j2][r] = 0.f;
     // block 0 landed (the output stores are younger and vmcnt retires in order: 0 is the only safe count);
     // every wave is done with its stage 1 scratch
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    wait_vmcnt_barrier<0>();
     // Hardware-scale path: the last two MFMAs of a step (n block 3, second k half) are held back and issued BEHIND
     // the barrier, in front of the next step's first MFMA -- the matrix pipe has work while the new step's DMA
     // instructions issue and its first fragment reads are in flight.  Their operands (the A fragments' second k
@@ -311,22 +249,6 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
       if constexpr (!HWS) dma_next();
       asm volatile("" : "+v"(a_rd_base), "+v"(b_rd_base));
       const uint8_t* const stage = &smem[buf * kBigStage];
-      auto frag = [&](uint32_t base, int kk, int blk) {
-        const u32x4 lo = *(const u32x4*)(stage + ((base ^ (kk << 6)) + blk * 32 * kBK));
-        const u32x4 hi = *(const u32x4*)(stage + ((base ^ (kk << 6) ^ 16) + blk * 32 * kBK));
-        return i32x8g{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-      };
-      auto mfma0 = [&](const i32x8g& b, const i32x8g& a) {
-        f32x16g z;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) z[r] = 0.f;
-        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b, a, z, MA_E5M2 ? 1 : 0, MB_E5M2 ? 1 : 0, 0,
-                                                               0x7F7F7F7F, 0, 0x7F7F7F7F);
-      };
-      auto mfma1 = [&](const i32x8g& b, const i32x8g& a, const f32x16g& c) {
-        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b, a, c, MA_E5M2 ? 1 : 0, MB_E5M2 ? 1 : 0, 0,
-                                                               0x7F7F7F7F, 0, 0x7F7F7F7F);
-      };
       auto fold = [&](int nb, int mb, const f32x16g& part, float s) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nb][mb][r] += s * part[r];
@@ -337,32 +259,29 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
       // region 0: fragment reads first, the block's scales behind them (first needed at the first fold); the
       // fold carried over from the previous k step runs while the reads are in flight (carrying both blocks of
       // the last n block spilled inside the loop)
-      fa[0][0] = frag(a_rd_base, 0, 0);
-      fb[0][0] = frag(b_rd_base, 0, 0);
-      fa[0][1] = frag(a_rd_base, 1, 0);
-      fb[0][1] = frag(b_rd_base, 1, 0);
-      fa[1][0] = frag(a_rd_base, 0, 1);
-      fa[1][1] = frag(a_rd_base, 1, 1);
+      fa[0][0] = fp8_frag(stage, a_rd_base, 0, 0);
+      fb[0][0] = fp8_frag(stage, b_rd_base, 0, 0);
+      fa[0][1] = fp8_frag(stage, a_rd_base, 1, 0);
+      fb[0][1] = fp8_frag(stage, b_rd_base, 1, 0);
+      fa[1][0] = fp8_frag(stage, a_rd_base, 0, 1);
+      fa[1][1] = fp8_frag(stage, a_rd_base, 1, 1);
       const float* const sc = (const float*)(&smem[buf * kBigStage + kBigScOff + wave * 512]);
       const float sa[2] = {sc[lq], sc[32 + lq]};
       const float sb = sc[64 + lane];
       if constexpr (HWS) {
-        hfa[0][0] = frag(a_rd_base, 0, 0);
-        hfb[0][0] = frag(b_rd_base, 0, 0);
-        hfa[1][0] = frag(a_rd_base, 0, 1);
-        auto mfma_c = [&](const i32x8g& b, const i32x8g& a, const f32x16g& c, int eb, int ea) {
-          return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b, a, c, MA_E5M2 ? 1 : 0, MB_E5M2 ? 1 : 0, 0, eb, 0, ea);
-        };
+        hfa[0][0] = fp8_frag(stage, a_rd_base, 0, 0);
+        hfb[0][0] = fp8_frag(stage, b_rd_base, 0, 0);
+        hfa[1][0] = fp8_frag(stage, a_rd_base, 0, 1);
         __builtin_amdgcn_sched_barrier(0);
         // the previous step's held-back pair
-        acc[3][0] = mfma_c(hfb[1][1], hfa[0][1], acc[3][0], he_b, he_a0);
-        acc[3][1] = mfma_c(hfb[1][1], hfa[1][1], acc[3][1], he_b, he_a1);
+        acc[3][0] = mfma_fp8<MA_E5M2, MB_E5M2>(hfb[1][1], hfa[0][1], acc[3][0], he_b, he_a0);
+        acc[3][1] = mfma_fp8<MA_E5M2, MB_E5M2>(hfb[1][1], hfa[1][1], acc[3][1], he_b, he_a1);
         __builtin_amdgcn_sched_barrier(0);
         dma_next();
         __builtin_amdgcn_sched_barrier(0);
-        hfa[0][1] = frag(a_rd_base, 1, 0);
-        hfb[0][1] = frag(b_rd_base, 1, 0);
-        hfa[1][1] = frag(a_rd_base, 1, 1);
+        hfa[0][1] = fp8_frag(stage, a_rd_base, 1, 0);
+        hfb[0][1] = fp8_frag(stage, b_rd_base, 1, 0);
+        hfa[1][1] = fp8_frag(stage, a_rd_base, 1, 1);
         he_b = (int)(__builtin_bit_cast(uint32_t, sb) >> 23);
         he_a0 = (int)(__builtin_bit_cast(uint32_t, sa[0]) >> 23);
         he_a1 = (int)(__builtin_bit_cast(uint32_t, sa[1]) >> 23);
@@ -370,19 +289,19 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
           const int cur = nb & 1;
-          acc[nb][0] = mfma_c(hfb[cur][0], hfa[0][0], acc[nb][0], he_b, he_a0);
+          acc[nb][0] = mfma_fp8<MA_E5M2, MB_E5M2>(hfb[cur][0], hfa[0][0], acc[nb][0], he_b, he_a0);
           if (nb < 3) {
-            hfb[cur ^ 1][0] = frag(b_rd_base, 0, nb + 1);
-            hfb[cur ^ 1][1] = frag(b_rd_base, 1, nb + 1);
+            hfb[cur ^ 1][0] = fp8_frag(stage, b_rd_base, 0, nb + 1);
+            hfb[cur ^ 1][1] = fp8_frag(stage, b_rd_base, 1, nb + 1);
           }
-          acc[nb][1] = mfma_c(hfb[cur][0], hfa[1][0], acc[nb][1], he_b, he_a1);
+          acc[nb][1] = mfma_fp8<MA_E5M2, MB_E5M2>(hfb[cur][0], hfa[1][0], acc[nb][1], he_b, he_a1);
           if (nb < 3) {
-            acc[nb][0] = mfma_c(hfb[cur][1], hfa[0][1], acc[nb][0], he_b, he_a0);
-            acc[nb][1] = mfma_c(hfb[cur][1], hfa[1][1], acc[nb][1], he_b, he_a1);
+            acc[nb][0] = mfma_fp8<MA_E5M2, MB_E5M2>(hfb[cur][1], hfa[0][1], acc[nb][0], he_b, he_a0);
+            acc[nb][1] = mfma_fp8<MA_E5M2, MB_E5M2>(hfb[cur][1], hfa[1][1], acc[nb][1], he_b, he_a1);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        wait_vmcnt_barrier<0>();
         __builtin_amdgcn_sched_barrier(0);
         return;
       }
@@ -395,25 +314,25 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb) {
         const int cur = nb & 1;
-        f32x16g p0 = mfma0(fb[cur][0], fa[0][0]);
+        f32x16g p0 = mfma_fp8_zero<MA_E5M2, MB_E5M2>(fb[cur][0], fa[0][0]);
         __builtin_amdgcn_sched_barrier(0);
         if (nb < 3) {
-          fb[cur ^ 1][0] = frag(b_rd_base, 0, nb + 1);
-          fb[cur ^ 1][1] = frag(b_rd_base, 1, nb + 1);
+          fb[cur ^ 1][0] = fp8_frag(stage, b_rd_base, 0, nb + 1);
+          fb[cur ^ 1][1] = fp8_frag(stage, b_rd_base, 1, nb + 1);
         }
         if (nb > 0) fold(nb - 1, 1, p1, s1);
         __builtin_amdgcn_sched_barrier(0);
-        p0 = mfma1(fb[cur][1], fa[0][1], p0);
-        p1 = mfma0(fb[cur][0], fa[1][0]);
+        p0 = mfma_fp8<MA_E5M2, MB_E5M2>(fb[cur][1], fa[0][1], p0);
+        p1 = mfma_fp8_zero<MA_E5M2, MB_E5M2>(fb[cur][0], fa[1][0]);
         __builtin_amdgcn_sched_barrier(0);
         fold(nb, 0, p0, s0);
         __builtin_amdgcn_sched_barrier(0);
-        p1 = mfma1(fb[cur][1], fa[1][1], p1);
+        p1 = mfma_fp8<MA_E5M2, MB_E5M2>(fb[cur][1], fa[1][1], p1);
       }
       p_carry = p1;
       s_carry = s1;
       // block kb + 1 landed (every wave's pieces: barrier), nobody still reads this stage
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      wait_vmcnt_barrier<0>();
       __builtin_amdgcn_sched_barrier(0);
     };
     {
@@ -428,10 +347,8 @@ __global__ void __launch_bounds__(kBigThreads, 1) group_gemm_fp8_big_kernel(cons
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[3][1][r] += s_carry * p_carry[r];
     } else {
-      acc[3][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hfb[1][1], hfa[0][1], acc[3][0], MA_E5M2 ? 1 : 0,
-                                                                  MB_E5M2 ? 1 : 0, 0, he_b, 0, he_a0);
-      acc[3][1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(hfb[1][1], hfa[1][1], acc[3][1], MA_E5M2 ? 1 : 0,
-                                                                  MB_E5M2 ? 1 : 0, 0, he_b, 0, he_a1);
+      acc[3][0] = mfma_fp8<MA_E5M2, MB_E5M2>(hfb[1][1], hfa[0][1], acc[3][0], he_b, he_a0);
+      acc[3][1] = mfma_fp8<MA_E5M2, MB_E5M2>(hfb[1][1], hfa[1][1], acc[3][1], he_b, he_a1);
     }
   }
   if (have_out) store_tile();
@@ -461,10 +378,9 @@ uint32_t* pow2_flag_slot(hipStream_t stream) {
 }
 
 void launch_pow2_check(const GemmParams& p, hipStream_t stream) {
-  const int kblocks = p.k / kBK;
-  const int64_t m_cnt = p.a_gran_m == 1 ? p.m_total : (p.m_total + p.a_gran_m - 1) / p.a_gran_m;
-  const int64_t na = m_cnt * kblocks;
-  const int64_t nb = (int64_t)(p.m_indptr ? p.num_groups : 1) * kblocks * ((p.n + 127) / 128);
+  const ScaleGeom sg = scale_geom(p);
+  const int64_t na = (int64_t)sg.m_cnt * sg.kblocks;
+  const int64_t nb = (int64_t)(p.m_indptr ? p.num_groups : 1) * sg.kblocks * sg.n_sblocks;
   scales_pow2_check_kernel<<<dim3(kPow2Words), dim3(256), 0, stream>>>((const uint32_t*)p.a_scale, na,
                                                                        (const uint32_t*)p.b_scale, nb,
                                                                        (uint32_t*)p.pow2_flag);

@@ -27,13 +27,7 @@
 //                         resp. (column c, k block q), k block q = k 32 q .. 32 q + 31 -- for the fp4 operand the
 //                         block the lane holds, for the fp8 operand NOT the elements the lane holds
 //   result                register i of lane l is (row 4 q + i, column c)
-#include <stdlib.h>
-#include <string.h>
-
-#include <type_traits>
-
-#include "gemm_common.h"
-#include "mx_layout.h"
+#include "gemm_mx.h"
 
 namespace fi {
 
@@ -124,18 +118,16 @@ __global__ void __launch_bounds__(kMxThreads) group_gemm_mxfp4_kernel(const MxGe
     int ew[2];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
-      fw[nb] = i32x8g{(int)r.w[nb][0], (int)r.w[nb][1], (int)r.w[nb][2], (int)r.w[nb][3], 0, 0, 0, 0};
-      ew[nb] = (int)((r.sw[nb] >> (8 * q)) & 0xffu);  // this lane's k block of the dword
+      fw[nb] = mx_fp4_frag(r.w[nb]);
+      ew[nb] = mx_scale_byte(r.sw[nb], q);
     }
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
       const i32x8g fa = {(int)r.a[mb][0][0], (int)r.a[mb][0][1], (int)r.a[mb][0][2], (int)r.a[mb][0][3],
                          (int)r.a[mb][1][0], (int)r.a[mb][1][1], (int)r.a[mb][1][2], (int)r.a[mb][1][3]};
-      const int ea = (int)((r.sa[mb] >> (8 * q)) & 0xffu);
+      const int ea = mx_scale_byte(r.sa[mb], q);
 #pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-        acc[nb][mb] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[nb], fa, acc[nb][mb], /*cbsz fp4*/ 4,
-                                                                        A_E5M2 ? 1 : 0, 0, ew[nb], 0, ea);
+      for (int nb = 0; nb < 2; ++nb) acc[nb][mb] = mx_mfma<A_E5M2 ? 1 : 0>(fw[nb], ew[nb], fa, ea, acc[nb][mb]);
     }
   };
 
@@ -151,23 +143,12 @@ __global__ void __launch_bounds__(kMxThreads) group_gemm_mxfp4_kernel(const MxGe
   }
   if (ks < ksteps) compute(r0);
 
-  // ---- store: a lane holds 4 consecutive n of one token: 8 bytes.  n and N are multiples of 4 resp. 8, so a piece is
-  // inside n or outside it as a whole.
+  // ---- store: a lane holds 4 consecutive n of one token
 #pragma unroll
-  for (int mb = 0; mb < MB; ++mb) {
-    const int m = m0 + 16 * mb + c;
-    if (m >= m_end) continue;
+  for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-      const int n = n0 + 16 * nb + 4 * q;
-      if (n >= N) continue;
-      const uint32_t lo = (uint32_t)f32_to_16bit(acc[nb][mb][0], p.out_dtype) |
-                          ((uint32_t)f32_to_16bit(acc[nb][mb][1], p.out_dtype) << 16);
-      const uint32_t hi = (uint32_t)f32_to_16bit(acc[nb][mb][2], p.out_dtype) |
-                          ((uint32_t)f32_to_16bit(acc[nb][mb][3], p.out_dtype) << 16);
-      *(u32x2*)((uint16_t*)p.d + (int64_t)m * N + n) = u32x2{lo, hi};
-    }
-  }
+    for (int nb = 0; nb < 2; ++nb)
+      mx_store_piece(p.d, p.out_dtype, m0 + 16 * mb + c, m_end, n0 + 16 * nb + 4 * q, N, acc[nb][mb], 1.0f);
 }
 
 template <bool A_E5M2>
@@ -175,17 +156,13 @@ static void launch_mxfp4(const MxGemmParams& p_in, hipStream_t stream) {
   MxGemmParams p = p_in;
   p.n_tiles = ceil_div(p.n, kMxTileN);
   // token tile by the mean rows per group (the groups' sizes live on the device): a tile the mean group fills
-  const int64_t mean = ceil_div<int64_t>(p.cum_m, p.num_groups);
-  auto go = [&](auto mb_c) {
+  with_mx_token_blocks(ceil_div<int64_t>(p.cum_m, p.num_groups), [&](auto mb_c) {
     constexpr int MB = decltype(mb_c)::value;
     // every group adds at most one partial tile on top of cum_m / TM
     p.num_m_tiles_bound = p.cum_m / (16 * MB) + p.num_groups;
     group_gemm_mxfp4_kernel<A_E5M2, MB>
         <<<dim3((uint32_t)p.num_m_tiles_bound * (uint32_t)p.n_tiles), dim3(kMxThreads), 0, stream>>>(p);
-  };
-  if (mean <= 16) go(std::integral_constant<int, 1>{});
-  else if (mean <= 32) go(std::integral_constant<int, 2>{});
-  else go(std::integral_constant<int, 4>{});
+  });
 }
 
 }  // namespace fi
@@ -201,24 +178,15 @@ extern "C" FI_API int fi_group_gemm_mxfp8_mxfp4_nt_groupwise(const fi_group_gemm
   FI_REQUIRE(p->a && p->b && p->a_scale && p->b_scale && p->d && p->m_indptr, "%s: null tensor", who);
   FI_REQUIRE(p->a_dtype == FI_DTYPE_FP8_E4M3 || p->a_dtype == FI_DTYPE_FP8_E5M2, "%s: a dtype %d is not fp8 (e4m3 / e5m2)",
              who, p->a_dtype);
-  FI_REQUIRE(p->d_dtype == FI_DTYPE_F16 || p->d_dtype == FI_DTYPE_BF16, "%s: output dtype %d is not f16 / bf16", who,
-             p->d_dtype);
-  FI_REQUIRE(p->n % 8 == 0, "%s: n %d must be a multiple of 8", who, p->n);
-  FI_REQUIRE(p->k > 0 && p->k % 128 == 0, "%s: k %d must be a positive multiple of 128", who, p->k);
-  FI_REQUIRE(((uintptr_t)p->a % 16) == 0 && ((uintptr_t)p->b % 16) == 0 && ((uintptr_t)p->d % 8) == 0 &&
-                 ((uintptr_t)p->a_scale % 4) == 0 && ((uintptr_t)p->b_scale % 4) == 0,
-             "%s: a / b must be 16-byte, d 8-byte and the scales 4-byte aligned", who);
+  const bool aligned = ((uintptr_t)p->a % 16) == 0 && ((uintptr_t)p->b % 16) == 0 && ((uintptr_t)p->d % 8) == 0 &&
+                       ((uintptr_t)p->a_scale % 4) == 0 && ((uintptr_t)p->b_scale % 4) == 0;
   const int64_t nkb = p->k / kMxBlock;
-  const int64_t a_need = mx_sf_rows_grouped(p->cum_m, p->num_groups) * nkb;
-  FI_REQUIRE(p->a_scale_bytes >= a_need, "%s: a_scale holds %lld bytes, %lld needed ((cum_m + 127 G) / 128 * 128 rows)", who,
-             (long long)p->a_scale_bytes, (long long)a_need);
-  const int64_t b_need = (int64_t)p->num_groups * mx_sf_rows(p->n, true) * nkb;
-  FI_REQUIRE(p->b_scale_bytes >= b_need, "%s: b_scale holds %lld bytes, %lld needed (n padded to 128 per group)", who,
-             (long long)p->b_scale_bytes, (long long)b_need);
-  // 32-bit offsets inside a tile and inside a scale tensor
-  FI_REQUIRE(a_need < (1ll << 31) && b_need / p->num_groups < (1ll << 31) && (int64_t)p->k * 128 < (1ll << 31),
-             "%s: problem too large for 32-bit tile offsets", who);
-  FI_REQUIRE((int64_t)(p->cum_m / 16 + p->num_groups) * ceil_div(p->n, kMxTileN) < (1ll << 31), "%s: too many tiles", who);
+  if (const int e = mx_check_common(
+          who, p->d_dtype, p->n, p->k, aligned, "d 8-byte and the scales 4-byte", p->a_scale_bytes,
+          mx_sf_rows_grouped(p->cum_m, p->num_groups) * nkb, "(cum_m + 127 G) / 128 * 128 rows", p->b_scale_bytes,
+          (int64_t)p->num_groups * mx_sf_rows(p->n, true) * nkb, p->num_groups, "n padded to 128 per group",
+          (int64_t)(p->cum_m / 16 + p->num_groups) * ceil_div(p->n, kMxTileN)))
+    return e;
   MxGemmParams g{};
   g.a = (const uint8_t*)p->a;
   g.b = (const uint8_t*)p->b;

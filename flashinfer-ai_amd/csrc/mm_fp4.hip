@@ -38,8 +38,7 @@
 //   scales                byte 0 of the scale register (op_sel 0) of lane l is the byte of (row c, k block q) resp.
 //                         (column c, k block q): for both operands the block the lane holds
 //   result                register i of lane l is (row 4 q + i, column c)
-#include "gemm_common.h"
-#include "mx_layout.h"
+#include "gemm_mx.h"
 
 namespace fi {
 
@@ -58,25 +57,13 @@ struct MmFp4Params {
 // one block-scaled MFMA: 16 weight rows (w, scale dword sw) x 16 tokens (x, scale dword sx) over 128 k; q picks the
 // lane's k block out of the row's dword of four scales
 __device__ __forceinline__ f32x4 mfma_fp4(const u32x4& w, uint32_t sw, const u32x4& x, uint32_t sx, int q, const f32x4& acc) {
-  const i32x8g fw = {(int)w[0], (int)w[1], (int)w[2], (int)w[3], 0, 0, 0, 0};
-  const i32x8g fx = {(int)x[0], (int)x[1], (int)x[2], (int)x[3], 0, 0, 0, 0};
-  const int ew = (int)((sw >> (8 * q)) & 0xffu), ex = (int)((sx >> (8 * q)) & 0xffu);
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fx, acc, /*cbsz fp4*/ 4, /*blgp fp4*/ 4, 0, ew, 0, ex);
+  return mx_mfma</*blgp fp4*/ 4>(mx_fp4_frag(w), mx_scale_byte(sw, q), mx_fp4_frag(x), mx_scale_byte(sx, q), acc);
 }
 
 // alpha as a wave-uniform value, fetched (and waited for) where the kernel starts: left to the epilogue the load makes
 // every store wait for the one before it
 __device__ __forceinline__ float load_alpha(const MmFp4Params& p) {
   return p.alpha ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, *p.alpha))) : 1.0f;
-}
-
-// a lane's 4 consecutive n of token row m: 8 bytes.  n and N are multiples of 4 resp. 8, so a piece is inside n or
-// outside it as a whole.
-__device__ __forceinline__ void store_piece(const MmFp4Params& p, int m, int n, const f32x4& v, float alpha) {
-  if (m >= p.m || n >= p.n) return;
-  const uint32_t lo = (uint32_t)f32_to_16bit(v[0] * alpha, p.out_dtype) | ((uint32_t)f32_to_16bit(v[1] * alpha, p.out_dtype) << 16);
-  const uint32_t hi = (uint32_t)f32_to_16bit(v[2] * alpha, p.out_dtype) | ((uint32_t)f32_to_16bit(v[3] * alpha, p.out_dtype) << 16);
-  *(u32x2*)((uint16_t*)p.d + (int64_t)m * p.n + n) = u32x2{lo, hi};
 }
 
 // ---- streaming kernel ------------------------------------------------------------------------------------------------
@@ -199,7 +186,8 @@ __global__ void __launch_bounds__(kFp4Threads) mm_fp4_stream_kernel(const MmFp4P
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) store_piece(p, m0 + 16 * mb + c, n0 + 16 * nb + 4 * q, acc[nb][mb], alpha);
+    for (int nb = 0; nb < 2; ++nb)
+      mx_store_piece(p.d, p.out_dtype, m0 + 16 * mb + c, M, n0 + 16 * nb + 4 * q, N, acc[nb][mb], alpha);
 }
 
 // ---- tiled kernel ----------------------------------------------------------------------------------------------------
@@ -210,9 +198,7 @@ constexpr int kOpBytes = kTile * kRowBytes;  // 16 KB per operand per stage
 constexpr int kScOff = 2 * kOpBytes;         // [tokens step 0 | tokens step 1 | weights step 0 | weights step 1] x 512 B
 constexpr int kStageBytes = kScOff + 2 * kStageSteps * 512;
 constexpr int kBandM = 8;                    // token tiles per band of the tile order
-
-// byte of (row, 16-byte chunk ch of the stage's 8) in an operand's LDS image
-__device__ __forceinline__ int fp4_lds_off(int row, int ch) { return row * kRowBytes + ((ch ^ ((row >> 1) & 7)) << 4); }
+static_assert(kRowBytes == 128, "the operand images are image_off()'s: 8 chunks of 16 bytes per row");
 
 __global__ void __launch_bounds__(kFp4Threads) mm_fp4_tile_kernel(const MmFp4Params p) {
   // one array: [stage][tokens 16 KB | weights 16 KB | scales 2 KB]
@@ -228,12 +214,8 @@ __global__ void __launch_bounds__(kFp4Threads) mm_fp4_tile_kernel(const MmFp4Par
 
   // tile order: bands of kBandM token tiles x all weight tiles, token tiles fastest inside a band, so the workgroups
   // in flight together share few rows of both operands
-  const int band_tiles = kBandM * p.n_tiles;
-  const int band = blockIdx.x / band_tiles;
-  const int in_band = blockIdx.x - band * band_tiles;
-  const int band_m = min(kBandM, p.m_tiles - band * kBandM);
-  const int nt = in_band / band_m;
-  const int mt = band * kBandM + (in_band - nt * band_m);
+  int mt, nt;
+  band_tile_of<kBandM>(blockIdx.x, p.m_tiles, p.n_tiles, mt, nt);
   const int m0 = mt * kTile, n0 = nt * kTile;
 
   // DMA geometry: a piece = one wave instruction = 8 rows x 128 bytes = 1 KiB of the stage image, written linearly
@@ -249,7 +231,7 @@ __global__ void __launch_bounds__(kFp4Threads) mm_fp4_tile_kernel(const MmFp4Par
     const int row = 8 * (8 * (wave & 1) + j) + (lane >> 3);
     const int r = tokens ? min(m0 + row, M - 1) - m0 : min(n0 + row, N - 1) - n0;
     row_off[j] = (uint32_t)r * (uint32_t)(K >> 1);
-    ch_off[j] = (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
+    ch_off[j] = (uint32_t)(image_chunk(row, lane & 7) << 4);
   }
   // the scale blocks travel the same way, 4 bytes per lane: wave w & 1 brings the 512 bytes of the stage's step w & 1
   const uint8_t* const sc_tile = tokens ? p.a_scale + (int64_t)mt * ksteps * 512 : p.b_scale + (int64_t)nt * ksteps * 512;
@@ -257,14 +239,11 @@ __global__ void __launch_bounds__(kFp4Threads) mm_fp4_tile_kernel(const MmFp4Par
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const uint32_t off = row_off[j] + min((uint32_t)s * kRowBytes + ch_off[j], last_chunk);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(op_tile + off),
-                                       (__attribute__((address_space(3))) void*)(&smem[stage][(8 * wave + j) * 1024]), 16, 0, 0);
+      lds_dma16(op_tile + off, &smem[stage][(8 * wave + j) * 1024]);
     }
     const uint8_t* const sc = sc_tile + (int64_t)min(kStageSteps * s + (wave & 1), ksteps - 1) * 512 + lane * 4;
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sc + j * 256),
-                                       (__attribute__((address_space(3))) void*)(&smem[stage][kScOff + wave * 512 + j * 256]), 4, 0, 0);
+    for (int j = 0; j < 2; ++j) lds_dma4(sc + j * 256, &smem[stage][kScOff + wave * 512 + j * 256]);
   };
 
   // fragment and scale addresses of the stage's first k step; the second is chunk + 4 (address ^ 64), scales + 512
@@ -272,8 +251,8 @@ __global__ void __launch_bounds__(kFp4Threads) mm_fp4_tile_kernel(const MmFp4Par
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int xr = 64 * wm + 16 * i + c, wr = 64 * wn + 16 * i + c;
-    x_rd[i] = (uint32_t)fp4_lds_off(xr, q);
-    w_rd[i] = (uint32_t)(kOpBytes + fp4_lds_off(wr, q));
+    x_rd[i] = (uint32_t)image_off(xr, q);
+    w_rd[i] = (uint32_t)(kOpBytes + image_off(wr, q));
     sx_rd[i] = (uint32_t)(kScOff + (xr & 31) * 16 + (xr >> 5) * 4);
     sw_rd[i] = (uint32_t)(kScOff + kStageSteps * 512 + (wr & 31) * 16 + (wr >> 5) * 4);
   }
@@ -303,9 +282,8 @@ __global__ void __launch_bounds__(kFp4Threads) mm_fp4_tile_kernel(const MmFp4Par
 
   dma(0, 0);
   for (int s = 0; s < nstages; ++s) {
-    // stage s landed, for every wave's pieces (barrier); every wave is also done reading the other buffer (stage s - 1).
-    // wait + barrier as ONE asm statement: the barrier alone is no memory fence for the compiler
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    // stage s landed, for every wave's pieces (barrier); every wave is also done reading the other buffer (stage s - 1)
+    wait_vmcnt_barrier<0>();
     if (s + 1 < nstages) dma(s + 1, (s + 1) & 1);
     const uint8_t* const stage = &smem[s & 1][0];
     compute(stage, 0);
@@ -316,7 +294,7 @@ __global__ void __launch_bounds__(kFp4Threads) mm_fp4_tile_kernel(const MmFp4Par
   for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb)
-      store_piece(p, m0 + 64 * wm + 16 * mb + c, n0 + 64 * wn + 16 * nb + 4 * q, acc[nb][mb], alpha);
+      mx_store_piece(p.d, p.out_dtype, m0 + 64 * wm + 16 * mb + c, M, n0 + 64 * wn + 16 * nb + 4 * q, N, acc[nb][mb], alpha);
 }
 
 // The choice between the kernels (DESIGN.md 3.15 has the sweep).  The streaming kernel's time is the weights' streaming
@@ -339,7 +317,7 @@ static void launch_mm_fp4(MmFp4Params p, bool stream_kernel, int cus, hipStream_
     mm_fp4_tile_kernel<<<dim3((uint32_t)p.m_tiles * (uint32_t)p.n_tiles), dim3(kFp4Threads), 0, stream>>>(p);
     return;
   }
-  auto go = [&](auto mb_c) {
+  with_mx_token_blocks(p.m, [&](auto mb_c) {
     constexpr int MB = decltype(mb_c)::value;
     p.m_tiles = ceil_div(p.m, 16 * MB);
     // k is split over the waves while 128-row workgroups would leave compute units without one
@@ -350,10 +328,7 @@ static void launch_mm_fp4(MmFp4Params p, bool stream_kernel, int cus, hipStream_
       p.n_tiles = ceil_div(p.n, kStreamWaves * kStreamRows);
       mm_fp4_stream_kernel<MB, false><<<dim3((uint32_t)p.m_tiles * (uint32_t)p.n_tiles), dim3(kFp4Threads), 0, stream>>>(p);
     }
-  };
-  if (p.m <= 16) go(std::integral_constant<int, 1>{});
-  else if (p.m <= 32) go(std::integral_constant<int, 2>{});
-  else go(std::integral_constant<int, 4>{});
+  });
 }
 
 }  // namespace fi
@@ -366,23 +341,14 @@ extern "C" FI_API int fi_mm_mxfp4(const fi_mm_mxfp4_params_t* p, fi_stream_t str
   FI_REQUIRE(p->m >= 0 && p->n >= 0 && p->k >= 0, "%s: negative size (m %d, n %d, k %d)", who, p->m, p->n, p->k);
   if (p->m == 0 || p->n == 0) return 0;
   FI_REQUIRE(p->a && p->b && p->a_scale && p->b_scale && p->d, "%s: null tensor", who);
-  FI_REQUIRE(p->d_dtype == FI_DTYPE_F16 || p->d_dtype == FI_DTYPE_BF16, "%s: output dtype %d is not f16 / bf16", who,
-             p->d_dtype);
-  FI_REQUIRE(p->n % 8 == 0, "%s: n %d must be a multiple of 8", who, p->n);
-  FI_REQUIRE(p->k > 0 && p->k % 128 == 0, "%s: k %d must be a positive multiple of 128", who, p->k);
-  FI_REQUIRE(((uintptr_t)p->a % 16) == 0 && ((uintptr_t)p->b % 16) == 0 && ((uintptr_t)p->d % 8) == 0 &&
-                 ((uintptr_t)p->a_scale % 4) == 0 && ((uintptr_t)p->b_scale % 4) == 0 && ((uintptr_t)p->alpha % 4) == 0,
-             "%s: a / b must be 16-byte, d 8-byte, the scales and alpha 4-byte aligned", who);
+  const bool aligned = ((uintptr_t)p->a % 16) == 0 && ((uintptr_t)p->b % 16) == 0 && ((uintptr_t)p->d % 8) == 0 &&
+                       ((uintptr_t)p->a_scale % 4) == 0 && ((uintptr_t)p->b_scale % 4) == 0 && ((uintptr_t)p->alpha % 4) == 0;
   const int64_t nkb = p->k / kMxBlock;
-  const int64_t a_need = mx_sf_rows<int64_t>(p->m, true) * nkb, b_need = mx_sf_rows<int64_t>(p->n, true) * nkb;
-  FI_REQUIRE(p->a_scale_bytes >= a_need, "%s: a_scale holds %lld bytes, %lld needed (m padded to 128)", who,
-             (long long)p->a_scale_bytes, (long long)a_need);
-  FI_REQUIRE(p->b_scale_bytes >= b_need, "%s: b_scale holds %lld bytes, %lld needed (n padded to 128)", who,
-             (long long)p->b_scale_bytes, (long long)b_need);
-  // 32-bit offsets inside a tile and inside a scale tensor
-  FI_REQUIRE(a_need < (1ll << 31) && b_need < (1ll << 31) && (int64_t)p->k * 128 < (1ll << 31),
-             "%s: problem too large for 32-bit tile offsets", who);
-  FI_REQUIRE((int64_t)ceil_div(p->m, 16) * ceil_div(p->n, kStreamRows) < (1ll << 31), "%s: too many tiles", who);
+  if (const int e = mx_check_common(who, p->d_dtype, p->n, p->k, aligned, "d 8-byte, the scales and alpha 4-byte",
+                                    p->a_scale_bytes, mx_sf_rows<int64_t>(p->m, true) * nkb, "m padded to 128",
+                                    p->b_scale_bytes, mx_sf_rows<int64_t>(p->n, true) * nkb, 1, "n padded to 128",
+                                    (int64_t)ceil_div(p->m, 16) * ceil_div(p->n, kStreamRows)))
+    return e;
   MmFp4Params g{};
   g.a = (const uint8_t*)p->a;
   g.b = (const uint8_t*)p->b;

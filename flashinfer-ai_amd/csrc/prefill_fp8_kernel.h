@@ -95,9 +95,6 @@ __device__ __forceinline__ i32x2 lds_tr8(int addr) {
   return w;
 }
 
-typedef __attribute__((address_space(3))) void f8_lds_void;
-typedef const __attribute__((address_space(1))) void f8_gbl_void;
-
 // UNI: GQA group size 1, 2 or 4 -- every wave then holds rows of ONE query head (wave w: head w % G, 32 consecutive
 // tokens), so the logit scale c = sm_scale * scale_q[head] * scale_k[kv head] * log2 e is wave-uniform and sits in a
 // scalar register: exp2's argument fma(s, c, -m) then reads two vector registers instead of three (a vector
@@ -332,10 +329,10 @@ __global__ void __launch_bounds__(kPrefillThreads, D == 256 ? 1 : 2) batch_prefi
       char* const vdst = kdst + kF8VOff;
 #pragma unroll
       for (int j = 0; j < PASSES; ++j)
-        __builtin_amdgcn_global_load_lds((f8_gbl_void*)(k_thr + f.o[j]), (f8_lds_void*)(kdst + j * 4096), 16, 0, 0);
+        lds_dma16(k_thr + f.o[j], kdst + j * 4096);
 #pragma unroll
       for (int j = 0; j < PASSES; ++j)
-        __builtin_amdgcn_global_load_lds((f8_gbl_void*)(v_thr + f.o[j]), (f8_lds_void*)(vdst + j * 4096), 16, 0, 0);
+        lds_dma16(v_thr + f.o[j], vdst + j * 4096);
     };
     auto dma_tile = [&](int slot, int stage) {
       DmaOffs f;
