@@ -18,38 +18,17 @@
 
 #include "common.h"
 #include "merge_kernel.h"
+#include "mla_plan.h"
 
 namespace fi {
 
-constexpr int kMlaCkv = 512, kMlaKpe = 64, kMlaQK = kMlaCkv + kMlaKpe;
 constexpr int kMlaThreads = 256;
-constexpr int kMlaRows = 16;                      // packed rows per work item
-constexpr int kMlaTileKV = 64;                    // tokens per LDS tile
 constexpr int kMlaLdsRow = kMlaQK + 8;            // 16-bit elements per staged token (16 B pad against conflicts)
 constexpr int kMlaChunksPerToken = kMlaQK * 2 / 16;  // 72 16-byte chunks: 64 ckv + 8 kpe
 constexpr int kMlaLoadsPerThread = kMlaTileKV * kMlaChunksPerToken / kMlaThreads;  // 18
-// resident workgroups per CU the planner fills: the kernel takes 256 arch + 165 accumulator registers per lane
-// (-Rpass-analysis=kernel-resource-usage), one wave per SIMD, so one 4-wave workgroup per CU
-constexpr int kMlaWgPerCu = 1;
-constexpr int kMlaMinChunk = 256;                 // smallest kv chunk a split cuts (tokens)
-constexpr int kMlaHeaderBytes = 64;               // int workspace: header, then merge indptr, then items
 static_assert(kMlaTileKV * kMlaChunksPerToken % kMlaThreads == 0, "loads must tile the threads");
 
-// int workspace header (int32 slots)
-enum { kMlaHdrMagic = 0, kMlaHdrNumWork = 1, kMlaHdrItemsOff = 2, kMlaHdrSplit = 3 };
-constexpr int32_t kMlaWsMagic = 0x4d4c4131;  // "MLA1"
-
-// one work item (int32 x 8)
-struct MlaItem {
-  int32_t qo_start;   // first query token of the request (qo_indptr[b])
-  int32_t row0;       // first packed row of the tile, within the request
-  int32_t qo_len;
-  int32_t kv_start, kv_end;  // the chunk [kv_start, kv_end)
-  int32_t kv_len;
-  int32_t page_base;  // kv_indptr[b]
-  int32_t chunk;      // chunk index within the request; -1: the request is not split (write o / lse directly)
-};
-static_assert(sizeof(MlaItem) == 32, "MlaItem layout");
+// the sizes a plan is cut for, the int workspace header and MlaItem: mla_plan.h
 
 struct MlaParams {
   const void* q_nope;
@@ -273,15 +252,6 @@ __global__ void __launch_bounds__(kMlaThreads) mla_paged_kernel(const MlaParams 
   }
 }
 
-// ---- planner ----
-
-// Partial-state layout in the float workspace, fixed by its size alone so that a captured run() keeps valid
-// pointers across re-plans: lse entries first, then the 512-wide f32 rows.
-static int64_t mla_max_entries(size_t float_ws_bytes) {
-  return (int64_t)(float_ws_bytes / (sizeof(float) * (kMlaCkv + 1))) / 4 * 4;
-}
-static int64_t mla_v_offset(size_t float_ws_bytes) { return mla_max_entries(float_ws_bytes) * (int64_t)sizeof(float); }
-
 }  // namespace fi
 
 using namespace fi;
@@ -351,8 +321,7 @@ extern "C" FI_API int fi_batch_mla_plan(const fi_batch_mla_plan_params_t* a, int
   // int workspace: header | merge indptr [total_rows + 1] | items (per request and chunk, the row tiles that
   // read it are adjacent so that they run together and the later reads hit L2)
   const int64_t num_work = items_at(chunk);
-  const int64_t indptr_bytes = (total_rows + 1) * 4;
-  const int64_t items_off = ceil_div<int64_t>(kMlaHeaderBytes + indptr_bytes, 32) * 32;
+  const int64_t items_off = mla_items_offset(total_rows);
   const int64_t used = items_off + num_work * (int64_t)sizeof(MlaItem);
   FI_REQUIRE((int64_t)a->int_ws_bytes >= used,
              "batch_mla_plan: int workspace too small (%zu bytes, need %lld)", a->int_ws_bytes, (long long)used);

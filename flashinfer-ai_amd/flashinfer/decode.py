@@ -1,10 +1,12 @@
 """Decode attention operators: ``single_decode_with_kv_cache``,
 ``BatchDecodeWithPagedKVCacheWrapper`` (plan / run split) and the plan-free
-``trtllm_batch_decode_with_kv_cache`` (the work list is planned on the device).
+``trtllm_batch_decode_with_kv_cache`` and ``trtllm_batch_decode_with_kv_cache_mla`` (the work list is planned on the
+device).
 
 Same names, arguments, defaults and error behaviour as the reference's ``flashinfer/decode.py``
-(single :389-578; wrapper :581-1410; CUDA-graph wrapper :1413-1480; plan-free :2054-2071), with the JIT module layer
-replaced by the ahead-of-time C ABI of libfi_mi355.so.  The kernels are csrc/decode_kernel.h.
+(single :389-578; wrapper :581-1410; CUDA-graph wrapper :1413-1480; plan-free :2054-2071, MLA :2298-2315), with the JIT
+module layer replaced by the ahead-of-time C ABI of libfi_mi355.so.  The kernels are csrc/decode_kernel.h and, for MLA,
+csrc/mla.hip.
 """
 from __future__ import annotations
 
@@ -513,8 +515,8 @@ class CUDAGraphBatchDecodeWithPagedKVCacheWrapper(BatchDecodeWithPagedKVCacheWra
 def _device_plan_regions(workspace_buffer: torch.Tensor, plan, workspace_fn: str = "fi_batch_decode_plan_device_workspace",
                          name: str = "trtllm_batch_decode_with_kv_cache"):
     """Carve the int region (work list and CSR page table) and the float region (f32 partial states) a device plan
-    needs out of one workspace buffer, and write both into ``plan`` (the params of fi_batch_decode_plan_device or of
-    fi_batch_prefill_plan_device; ``workspace_fn`` is the C entry that sizes them).  ValueError, with the bytes needed,
+    needs out of one workspace buffer, and write both into ``plan`` (the params of fi_batch_decode_plan_device, of
+    fi_batch_prefill_plan_device or of fi_batch_mla_plan_device; ``workspace_fn`` is the C entry that sizes them).  ValueError, with the bytes needed,
     when the buffer is too small."""
     int_bytes, float_bytes = C.c_size_t(), C.c_size_t()
     _lib.check(getattr(_lib.lib(), workspace_fn)(C.byref(plan), C.byref(int_bytes), C.byref(float_bytes)), name)
@@ -686,6 +688,154 @@ def trtllm_batch_decode_with_kv_cache(
                                                  plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, C.byref(params),
                                                  _lib.ptr(sinks), stream),
                    "trtllm_batch_decode_with_kv_cache")
+    if bmm2_scale != 1.0:
+        out *= bmm2_scale
+    return out
+
+
+def _mla_query_rows(query: torch.Tensor) -> int:
+    """The element stride between consecutive query tokens of ``[batch, q_len, num_heads, 576]`` flattened to
+    ``[batch * q_len, num_heads, 576]`` without a copy; ValueError when the tensor cannot be read that way."""
+    batch_size, q_len = query.shape[:2]
+    if query.stride(-1) != 1:
+        raise ValueError("query must be contiguous in its last dimension")
+    if q_len > 1 and batch_size > 1 and query.stride(0) != q_len * query.stride(1):
+        raise ValueError("query must flatten to [batch_size * q_len_per_request, num_heads, 576] without a copy: "
+                         f"stride(0) = {query.stride(0)} is not q_len_per_request x stride(1) = "
+                         f"{q_len} x {query.stride(1)}")
+    stride_n = query.stride(1) if q_len > 1 else query.stride(0)
+    if stride_n % 8 or query.stride(2) % 8 or query.data_ptr() % 16:
+        raise ValueError("query: strides must be multiples of 8 elements and the base 16-byte aligned")
+    return stride_n
+
+
+def trtllm_batch_decode_with_kv_cache_mla(
+    query: torch.Tensor,
+    kv_cache: torch.Tensor,
+    workspace_buffer: torch.Tensor,
+    qk_nope_head_dim: int,
+    kv_lora_rank: int,
+    qk_rope_head_dim: int,
+    block_tables: torch.Tensor,
+    seq_lens: torch.Tensor,
+    max_seq_len: int,
+    out: Optional[torch.Tensor] = None,
+    bmm1_scale: Optional[float] = 1.0,
+    bmm2_scale: Optional[float] = 1.0,
+    bmm1_scale_log2_tensor: Optional[torch.Tensor] = None,
+    bmm2_scale_tensor: Optional[torch.Tensor] = None,
+    sinks: Optional[List[torch.Tensor]] = None,
+    enable_pdl: bool = None,
+) -> torch.Tensor:
+    r"""Plan-free MLA decode over a paged cache (ref: flashinfer/decode.py:2298-2315): a dense block table and
+    device-resident lengths instead of ``BatchMLAPagedAttentionWrapper.plan()``.  The work list is built by kernels on
+    the current stream (fi_batch_mla_plan_device), then the kernel of
+    :class:`flashinfer.mla.BatchMLAPagedAttentionWrapper` runs on it.  There is no host synchronisation and no
+    allocation that depends on a length, so the whole call can be captured in a graph; a replay plans again from what
+    ``block_tables`` and ``seq_lens`` hold then.
+
+    query : ``[batch_size, q_len_per_request, num_heads, 576]`` (``q_nope | q_pe``), float16 or bfloat16, contiguous in
+        the last dimension and flattenable to ``[batch_size * q_len_per_request, num_heads, 576]`` without a copy;
+        strides multiples of 8 elements, the base 16-byte aligned.  ``q_len_per_request > 1`` (MTP, speculative
+        verify) is causal within the request: row ``i`` sees keys ``<= seq_len - q_len_per_request + i``, and a row
+        that sees no key gives zeros.
+    kv_cache : ``[num_pages, 1, page_size, 576]`` or ``[num_pages, page_size, 576]`` (``ckv | kpe``), of the query's
+        dtype.  Any page size is taken: the reference's 32 / 64 restriction and its ``block_num % (128 / block_size)``
+        rule are tile constraints of its kernels and are not enforced here.
+    workspace_buffer : one buffer on the query's device; the work list and the f32 partial states are carved out of
+        it.  It need not be zeroed.  ValueError names the bytes needed when it is too small; whatever it holds beyond
+        that goes to partial states, and a small buffer only makes the planner cut longer chunks.
+    qk_nope_head_dim, kv_lora_rank, qk_rope_head_dim : 128, 512, 64; anything else is a ValueError.
+    block_tables : int32 ``[batch_size, max_blocks]``; row ``b`` lists the pages of request ``b``.  Entries past a
+        request's ``ceil(seq_len / page_size)`` pages are never read.
+    seq_lens : int32 (or uint32) ``[batch_size]`` on the device.  A length beyond ``max_blocks * page_size`` is CLAMPED
+        to it (the host never sees the value, so it cannot be refused); a length of 0 gives zero output rows.
+    max_seq_len : checked against ``max_blocks * page_size``; otherwise unused.
+    out : optional ``[batch_size, q_len_per_request, num_heads, 512]``, or ``[batch_size, num_heads, 512]`` when
+        ``q_len_per_request == 1``, contiguous, of the query's dtype; allocated in the first form when not given.
+    bmm1_scale : the full scale of the logits.  bmm2_scale : multiplies the output.
+    enable_pdl : accepted and ignored.
+
+    Not offered (NotImplementedError): an fp8 query or cache, ``bmm1_scale_log2_tensor`` / ``bmm2_scale_tensor``, and
+    ``sinks``.
+    """
+    name = "trtllm_batch_decode_with_kv_cache_mla"
+    fp8 = (torch.float8_e4m3fn, torch.float8_e5m2)
+    if query.dtype in fp8 or kv_cache.dtype in fp8:
+        raise NotImplementedError(f"{name}: an fp8 query or kv_cache is not supported (float16 / bfloat16)")
+    if bmm1_scale_log2_tensor is not None or bmm2_scale_tensor is not None:
+        raise NotImplementedError(f"{name}: bmm1_scale_log2_tensor / bmm2_scale_tensor are not supported "
+                                  "(pass bmm1_scale / bmm2_scale as floats)")
+    if sinks is not None:
+        raise NotImplementedError(f"{name}: sinks are not supported")
+    if (qk_nope_head_dim, kv_lora_rank, qk_rope_head_dim) != (128, 512, 64):
+        raise ValueError(f"{name}: qk_nope_head_dim / kv_lora_rank / qk_rope_head_dim must be 128 / 512 / 64, got "
+                         f"{qk_nope_head_dim} / {kv_lora_rank} / {qk_rope_head_dim}")
+    for what, t in (("query", query), ("kv_cache", kv_cache), ("workspace_buffer", workspace_buffer),
+                    ("block_tables", block_tables), ("seq_lens", seq_lens)):
+        _lib.require_gpu_tensor(t, what)
+    head_dim = kv_lora_rank + qk_rope_head_dim
+    if query.dtype not in (torch.float16, torch.bfloat16) or query.dim() != 4 or query.shape[-1] != head_dim:
+        raise ValueError(f"query must be a float16 / bfloat16 [batch_size, q_len_per_request, num_heads, {head_dim}] "
+                         "tensor")
+    batch_size, q_len, num_heads, _ = query.shape
+    if q_len == 0 or num_heads == 0:
+        raise ValueError("query must hold at least one token per request and one head")
+    q_stride_n = _mla_query_rows(query)
+    if kv_cache.dim() == 4 and kv_cache.shape[1] == 1:
+        kv_cache = kv_cache.squeeze(1)
+    if kv_cache.dim() != 3 or kv_cache.shape[-1] != head_dim or kv_cache.dtype != query.dtype \
+            or kv_cache.stride(-1) != 1:
+        raise ValueError(f"kv_cache must be [num_pages, 1, page_size, {head_dim}] or [num_pages, page_size, {head_dim}]"
+                         f", of the query's dtype {query.dtype} and contiguous in the last dimension")
+    if kv_cache.stride(0) % 8 or kv_cache.stride(1) % 8 or kv_cache.data_ptr() % 16:
+        raise ValueError("kv_cache: strides must be multiples of 8 elements and the base 16-byte aligned")
+    page_size = kv_cache.shape[1]
+    seq_lens = _check_block_tables_and_lens(block_tables, seq_lens, workspace_buffer, batch_size)
+    max_blocks = block_tables.shape[1]
+    if max_seq_len > max_blocks * page_size:
+        raise ValueError(f"max_seq_len {max_seq_len} exceeds what block_tables can hold: {max_blocks} blocks of "
+                         f"{page_size} tokens")
+    if batch_size * block_tables.stride(0) >= 1 << 31:
+        raise ValueError("batch_size x block_tables.stride(0) must be below 2^31")
+    out_shape = (batch_size, q_len, num_heads, kv_lora_rank)
+    if out is None:
+        out = torch.empty(out_shape, dtype=query.dtype, device=query.device)
+    else:
+        if q_len == 1 and out.dim() == 3:
+            out_shape = (batch_size, num_heads, kv_lora_rank)
+        check_shape_dtype_device(out, out_shape, query.dtype, query.device, "out")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+    if batch_size == 0:
+        return out
+
+    dtype = _lib.fi_dtype(query.dtype)
+    plan = _lib.fi_batch_mla_plan_device_params_t(
+        block_tables=block_tables.data_ptr(), seq_lens=seq_lens.data_ptr(), block_tables_stride=block_tables.stride(0),
+        batch_size=batch_size, max_blocks=max_blocks, page_size=page_size, num_heads=num_heads,
+        q_len_per_request=q_len, head_dim_ckv=kv_lora_rank, head_dim_kpe=qk_rope_head_dim, q_dtype=dtype,
+        kv_dtype=dtype, max_items_hint=0)
+    _device_plan_regions(workspace_buffer, plan, "fi_batch_mla_plan_device_workspace", name)
+    plan_info = (C.c_int64 * _lib.FI_MLA_PLAN_INFO_LEN)()
+    item = query.element_size()
+    # q_nope / q_pe and ckv / kpe are views of the two 576-wide tensors
+    params = _lib.fi_batch_mla_params_t(
+        q_nope=query.data_ptr(), q_nope_stride_n=q_stride_n, q_nope_stride_h=query.stride(2),
+        q_pe=query.data_ptr() + kv_lora_rank * item, q_pe_stride_n=q_stride_n, q_pe_stride_h=query.stride(2),
+        ckv=kv_cache.data_ptr(), ckv_stride_page=kv_cache.stride(0), ckv_stride_n=kv_cache.stride(1),
+        kpe=kv_cache.data_ptr() + kv_lora_rank * item, kpe_stride_page=kv_cache.stride(0),
+        kpe_stride_n=kv_cache.stride(1),
+        # no CSR page table: the planner's items address the block table's rows
+        kv_indices=block_tables.data_ptr(), o=out.data_ptr(), lse=None,
+        float_ws=plan.float_ws, float_ws_bytes=plan.float_ws_bytes, int_ws=plan.int_ws, int_ws_bytes=plan.int_ws_bytes,
+        num_rows=batch_size * q_len * num_heads, num_heads=num_heads, page_size=page_size, dtype=dtype, causal=1,
+        sm_scale=float(bmm1_scale))
+    lib = _lib.lib()
+    with torch.cuda.device(query.device):
+        stream = _lib.current_stream(query.device)
+        _lib.check(lib.fi_batch_mla_plan_device(C.byref(plan), plan_info, stream), name)
+        _lib.check(lib.fi_batch_mla_run(plan_info, _lib.FI_MLA_PLAN_INFO_LEN, C.byref(params), stream), name)
     if bmm2_scale != 1.0:
         out *= bmm2_scale
     return out

@@ -665,6 +665,55 @@ typedef struct fi_batch_mla_params {
 FI_API int fi_batch_mla_run(const int64_t* plan_info, int32_t plan_info_len, const fi_batch_mla_params_t* params,
                             fi_stream_t stream);
 
+/* Device-side planning: the int workspace of fi_batch_mla_plan(enable_cuda_graph = 1), written by kernels on `stream`
+ * for qo_len = q_len_per_request in every request and kv_len = clamp(seq_lens[b], 0, max_blocks x page_size), from
+ * lengths that stay on the device.  No host read-back, no copy, no synchronisation: the call may be captured in a graph
+ * together with the fi_batch_mla_run that follows it, and a replay plans again from whatever `seq_lens` holds then.
+ * (The reference's plan-free MLA entry, trtllm_batch_decode_with_kv_cache_mla, flashinfer/decode.py:2298-2315, takes
+ * the same two tensors.)
+ *
+ * The header, the merge indptr [total_rows + 1] and the item list (request, then chunk, then row tile) are the host
+ * planner's, by the host planner's chunk rule, with one field apart: there is no CSR page table, an item's page_base
+ * is b x block_tables_stride, and run() is given kv_indices = block_tables.  Entries of a row past the request's
+ * ceil(kv_len / page_size) pages are never read.  The list has the host-known capacity
+ * max(max_items, batch x ceil(q_len_per_request x num_heads / 16)); items past the header's count are not written.
+ * Behind the list the two kernels keep two scans of batch + 1 int32 each.
+ *
+ * plan_info_out holds host-known entries only: FI_MLA_PLAN_MAGIC, GRID = max_items, ENABLE_CUDA_GRAPH = 1 (run() always
+ * merges), TOTAL_ROWS = batch x q_len_per_request x num_heads, NUM_HEADS, BATCH_SIZE, PAGE_SIZE, DTYPE, V_OFFSET,
+ * INT_BYTES_USED (the list at its capacity, and the scans), the two offsets.  Decided on the device, and 0 here:
+ * FI_MLA_NUM_WORK and FI_MLA_SPLIT_KV (header slots 1 and 3 of the int workspace), FI_MLA_KV_CHUNK_SIZE (in the items
+ * only) and FI_MLA_NUM_ENTRIES (merge_indptr[total_rows]; never more than the float workspace holds).
+ * Errors (fi_last_error) before any launch: null tensors, bad sizes, a workspace too small (the message states the bytes
+ * needed), head dims other than 512 / 64, dtypes other than f16 / bf16 or differing. */
+typedef struct fi_batch_mla_plan_device_params {
+  const int32_t* block_tables; /* [batch_size, max_blocks] device, rows block_tables_stride elements apart */
+  const int32_t* seq_lens;     /* [batch_size] device: kv tokens per request */
+  int64_t block_tables_stride;
+  void* int_ws; /* device: header, merge indptr, items, scans */
+  size_t int_ws_bytes;
+  void* float_ws; /* device: f32 partial states (only sized here, run() writes it); chunks grow until they fit */
+  size_t float_ws_bytes;
+  int32_t batch_size;
+  int32_t max_blocks;
+  int32_t page_size;
+  int32_t num_heads;
+  int32_t q_len_per_request; /* query tokens of every request; causal masks align them to the end of the keys */
+  int32_t head_dim_ckv;
+  int32_t head_dim_kpe;
+  int32_t q_dtype;
+  int32_t kv_dtype;
+  int32_t max_items_hint; /* <= 0: one workgroup per CU (fi_num_compute_units), as fi_batch_mla_plan */
+} fi_batch_mla_plan_device_params_t;
+
+FI_API int fi_batch_mla_plan_device(const fi_batch_mla_plan_device_params_t* params, int64_t* plan_info_out,
+                                    fi_stream_t stream);
+/* The bytes fi_batch_mla_plan_device needs of the int workspace for these params (the pointers and sizes in them are not
+ * read), and the least it needs of the float workspace: 0, a plan that cannot split is still correct.  Whatever more
+ * the caller gives as float workspace lets the planner cut shorter chunks.  Host arithmetic only. */
+FI_API int fi_batch_mla_plan_device_workspace(const fi_batch_mla_plan_device_params_t* params,
+                                              size_t* int_ws_bytes_out, size_t* float_ws_bytes_out);
+
 /* Append: row i of append_ckv [nnz, 512] / append_kpe [nnz, 64] goes to page
  * kv_indices[kv_indptr[batch_indices[i]] + positions[i] / page_size], entry positions[i] % page_size. */
 typedef struct fi_append_paged_mla_kv_params {
