@@ -243,6 +243,15 @@ __device__ __forceinline__ T wave_reduce(T v) {
   return v;
 }
 
+// OP over groups of N consecutive lanes (N a power of two, groups aligned), the result in every lane of the group; the
+// lanes of a group make the call together
+template <int N, class OP, typename T>
+__device__ __forceinline__ T group_reduce(T v) {
+#pragma unroll
+  for (int d = N / 2; d >= 1; d >>= 1) v = OP::of(v, __shfl_xor(v, d, 64));
+  return v;
+}
+
 // Inclusive sum over the 64 lanes in lane order, by doubling: six steps, step d adding the partial sum that ends d
 // lanes below.  The association is fixed, so a float scan gives the same bits in every run.
 template <typename T>

@@ -1,0 +1,50 @@
+// The fp8 block-scale quantisation rule (DeepSeek's "1 x 128" activations) as device code: what the gated activation of
+// the fp8 block-scale MoE layer (moe.hip) and the quantiser fi_fp8_quantize_1x128 (fp8_block_quantize.hip) share, so that
+// both produce the same f32 scale and the same e4m3 bytes for the same f32 values.  The sibling of mx_quant.h, whose
+// scales are powers of two per 32 elements; here a scale is any positive normal f32 per 128 elements.
+//
+// Per row and block of 128 columns: amax = max |x|; s = max(amax / 448, 2^-126); q = e4m3(clamp(x / s, -448, 448)),
+// round to nearest even.  amax / 448 is the reference kernel's rule (csrc/trtllm_fused_moe_dev_kernel.cu:141-152).  The
+// floor keeps s a normal f32 and turns an all-zero block into q = 0 instead of 0 / 0.  Both divisions are IEEE
+// divisions (the library is built without fast-math), so s is the correctly rounded quotient; x / s may then land one ulp
+// above 448, and byte 0x7F is NaN in e4m3fn: hence the clamp.
+// A thread owns 8 consecutive elements; the 16 threads of a block are 16 consecutive, 16-aligned lanes (one DPP row).
+#pragma once
+#include "common.h"
+#include "mx_quant.h"  // mx_amax8
+
+#if defined(__HIPCC__)
+namespace fi {
+
+constexpr int kFp8Block = 128;          // columns per scale
+constexpr int kFp8BlockLanes = 128 / 8;  // lanes per block, 8 columns each
+
+// the block's scale from its amax: the largest of the 16 lanes' own maxima (every lane of the block calls it)
+__device__ __forceinline__ float fp8_block_scale(float lane_amax) {
+  return fmaxf(group_reduce<kFp8BlockLanes, RedMax>(lane_amax) / 448.0f, 0x1p-126f);
+}
+
+// 8 values divided by the block's scale as 8 e4m3 bytes
+__device__ __forceinline__ u32x2 fp8_block_pack8(const float* v, float s) {
+  uint32_t w[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    float y[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y[j] = __builtin_amdgcn_fmed3f(v[4 * h + j] / s, -448.f, 448.f);
+    int packed = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+    packed = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], packed, true);
+    w[h] = (uint32_t)packed;
+  }
+  return u32x2{w[0], w[1]};
+}
+
+// The whole rule for a lane's 8 values of a block (amax of 128 -> s -> pack): returns s, the bytes go to `q`.
+__device__ __forceinline__ float fp8_block_quantize8(const float* v, u32x2& q) {
+  const float s = fp8_block_scale(mx_amax8(v));
+  q = fp8_block_pack8(v, s);
+  return s;
+}
+
+}  // namespace fi
+#endif  // __HIPCC__

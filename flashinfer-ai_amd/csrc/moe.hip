@@ -21,9 +21,15 @@
 // finalize.  A thread owns 8 columns of a token and walks its slots in order.
 // gather, gated act. and finalize give a row to a row team (common.h).  A scale row finds its group and operand row by
 // mx_row_of_scale_row (mx_layout.h) on m_indptr, which every workgroup first copies to LDS.
+//
+// The fp8 block-scale layer (trtllm_fp8_block_scale_moe, core.py:1742-1816) around fi_group_gemm_fp8_nt_groupwise shares
+// route, the three sorting launches of permute and finalize.  Its gather and its gated activation are kernels of their
+// own further down: the scales are one f32 per 128 columns in a plain row-major tensor indexed by the permuted row, so a
+// row needs no scale-row lookup and no m_indptr in LDS, only m_indptr[G] to tell whether it is live.
 #include <math.h>
 
 #include "common.h"
+#include "fp8_block_quant.h"
 #include "mx_layout.h"
 #include "mx_quant.h"
 
@@ -391,6 +397,41 @@ __global__ void __launch_bounds__(kMoeThreads) moe_gather_kernel(const MoePermut
   }
 }
 
+// The gather of the fp8 block-scale layer: a row per permuted row, rows past the local count included.  A live row
+// copies its token's e4m3 bytes; the lane that copies the first 16 bytes of a 128-column block also moves the block's
+// f32 scale, read through both strides of the caller's tensor, into the row-major [n, nkb] operand of the GEMM.  A row at
+// or past m_indptr[G] gets the scale 1.0f and no bytes.
+struct MoeGatherFp8Args {
+  const uint8_t* x;
+  const float* x_scale;
+  const int32_t* m_indptr;
+  const int32_t* p2e;
+  uint8_t* x_out;
+  float* scale_out;
+  int64_t stride_kb, stride_t;
+  int32_t n, top_k, hidden, nkb, G, tpr_log2;
+};
+
+__global__ void __launch_bounds__(kMoeThreads) moe_gather_fp8_block_kernel(const MoeGatherFp8Args A) {
+  const RowTeam team = row_team<kMoeThreads>(A.tpr_log2, A.n);
+  if (team.past_end) return;
+  const int64_t p = team.row;
+  int token = -1;
+  if (p < A.m_indptr[A.G]) {
+    const int i = A.p2e[p];
+    if (i >= 0 && i < A.n) token = i / A.top_k;
+  }
+  const int chunks = A.hidden / 16;  // 16 bytes each; 8 chunks are 128 k elements, one scale
+  for (int c = team.lane; c < chunks; c += team.size) {
+    if (token >= 0)
+      *(u32x4*)(A.x_out + p * A.hidden + c * 16) = *(const u32x4*)(A.x + (int64_t)token * A.hidden + c * 16);
+    if ((c & 7) == 0) {
+      const int kb = c >> 3;
+      A.scale_out[p * A.nkb + kb] = token >= 0 ? A.x_scale[kb * A.stride_kb + token * A.stride_t] : 1.0f;
+    }
+  }
+}
+
 // ---- gated activation -----------------------------------------------------------------------------------------------
 struct MoeActArgs {
   const uint16_t* x;
@@ -448,6 +489,41 @@ __global__ void __launch_bounds__(kMoeThreads) moe_gated_act_kernel(const MoeAct
     const int e = mx_e4m3_exponent(mx_quad_max(mx_amax8(v)));
     if (src >= 0) *(u32x2*)(A.q + (int64_t)src * I + col) = mx_e4m3_pack8(v, e);
     if ((cc & 3) == 0) A.sf[mx_sf_offset((int)team.row, cc >> 2, A.nkb)] = src >= 0 ? (uint8_t)(e + 127) : (uint8_t)0;
+  }
+}
+
+// The gated activation of the fp8 block-scale layer: plain SwiGLU, then the block rule of fp8_block_quant.h.  A row per
+// row of x; a thread owns 8 output columns and the 16 lanes of a 128-column block share amax.  The team is at least 16
+// lanes and I / 8 a multiple of 16, so the lanes of a block take every turn of the loop together.
+struct MoeActFp8Args {
+  const uint16_t* x;
+  const int32_t* m_indptr;
+  uint8_t* q;
+  float* scale;
+  int32_t cum_m, inter, nkb, G, tpr_log2;
+};
+
+__global__ void __launch_bounds__(kMoeThreads) moe_gated_act_fp8_block_kernel(const MoeActFp8Args A) {
+  const RowTeam team = row_team<kMoeThreads>(A.tpr_log2, A.cum_m);
+  if (team.past_end) return;
+  const int64_t row = team.row;
+  const bool live = row < A.m_indptr[A.G];  // the same in every lane of the team
+  const int I = A.inter;
+  const uint16_t* const xr = A.x + row * 2 * I;
+  for (int cc = team.lane; cc < I / 8; cc += team.size) {
+    const int col = cc * 8;
+    float s = 1.0f;
+    if (live) {
+      float x1[8], x2[8], v[8];
+      load_16bit<FI_DTYPE_BF16, 8>(xr + col, x1);
+      load_16bit<FI_DTYPE_BF16, 8>(xr + I + col, x2);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = x2[j] * (1.0f / (1.0f + expf(-x2[j]))) * x1[j];
+      u32x2 q;
+      s = fp8_block_quantize8(v, q);
+      *(u32x2*)(A.q + row * I + col) = q;
+    }
+    if ((cc & (kFp8BlockLanes - 1)) == 0) A.scale[row * A.nkb + cc / kFp8BlockLanes] = s;
   }
 }
 
@@ -527,6 +603,47 @@ static int moe_route_check(const char* who, int num_experts, int top_k) {
   FI_REQUIRE(top_k >= 1 && top_k <= FI_MOE_MAX_TOP_K && top_k <= num_experts,
              "%s: top_k %d is not in [1, min(%d, num_experts %d)]", who, top_k, FI_MOE_MAX_TOP_K, num_experts);
   return 0;
+}
+
+// the limits of both permute entry points
+static int moe_permute_check(const char* who, int num_tokens, int top_k, int hidden, int offset, int G) {
+  FI_REQUIRE(num_tokens >= 0 && top_k >= 0 && hidden >= 0 && G >= 0 && offset >= 0,
+             "%s: negative size (num_tokens %d, top_k %d, hidden %d, local_expert_offset %d, local_num_experts %d)", who,
+             num_tokens, top_k, hidden, offset, G);
+  FI_REQUIRE(G >= 1 && G <= FI_MOE_MAX_EXPERTS, "%s: local_num_experts %d is not in [1, %d]", who, G, FI_MOE_MAX_EXPERTS);
+  FI_REQUIRE(top_k >= 1 && top_k <= FI_MOE_MAX_TOP_K, "%s: top_k %d is not in [1, %d]", who, top_k, FI_MOE_MAX_TOP_K);
+  FI_REQUIRE(hidden > 0 && hidden % 128 == 0, "%s: hidden %d must be a positive multiple of 128", who, hidden);
+  return 0;
+}
+
+// What the sort of both permute entry points (count, scan, place) reads, after the check of its workspace: block
+// histograms, then the inverse map a.p2e, which the entry point's gather reads.  The gather's own fields stay as they are.
+static int moe_sort_args(const char* who, MoePermuteArgs& a, const int32_t* ids, int32_t* m_indptr, int32_t* map,
+                         uint16_t* weights_out, int32_t* workspace, int64_t workspace_bytes, int64_t n, int top_k, int offset,
+                         int64_t G, bool packed) {
+  const int64_t num_blocks = ceil_div<int64_t>(n, FI_MOE_SORT_BLOCK);
+  const int64_t ws_need = (num_blocks * G + n) * 4;
+  FI_REQUIRE(workspace_bytes >= ws_need, "%s: workspace holds %lld bytes, %lld needed", who, (long long)workspace_bytes,
+             (long long)ws_need);
+  a.ids = ids;
+  a.m_indptr = m_indptr;
+  a.map = map;
+  a.weights_out = packed ? weights_out : nullptr;
+  a.hist = workspace;
+  a.p2e = workspace + num_blocks * G;
+  a.n = (int32_t)n;
+  a.top_k = top_k;
+  a.offset = offset;
+  a.G = (int32_t)G;
+  a.packed = packed;
+  a.num_blocks = (int32_t)num_blocks;
+  return 0;
+}
+
+static void moe_sort_launch(const MoePermuteArgs& a, hipStream_t st) {
+  moe_count_kernel<<<dim3((uint32_t)a.num_blocks), dim3(64), 0, st>>>(a);
+  moe_scan_kernel<<<dim3(1), dim3(FI_MOE_MAX_EXPERTS), 0, st>>>(a);
+  moe_place_kernel<<<dim3((uint32_t)a.num_blocks), dim3(64), 0, st>>>(a);
 }
 
 }  // namespace fi
@@ -613,15 +730,9 @@ extern "C" FI_API int fi_moe_route_sigmoid(const fi_moe_route_sigmoid_params_t* 
 
 extern "C" FI_API int fi_moe_permute_mxfp8(const fi_moe_permute_params_t* p, fi_stream_t stream) {
   FI_REQUIRE(p, "moe_permute_mxfp8: null params");
-  FI_REQUIRE(p->num_tokens >= 0 && p->top_k >= 0 && p->hidden >= 0 && p->local_num_experts >= 0 && p->local_expert_offset >= 0,
-             "moe_permute_mxfp8: negative size (num_tokens %d, top_k %d, hidden %d, local_expert_offset %d, "
-             "local_num_experts %d)", p->num_tokens, p->top_k, p->hidden, p->local_expert_offset, p->local_num_experts);
-  FI_REQUIRE(p->local_num_experts >= 1 && p->local_num_experts <= FI_MOE_MAX_EXPERTS,
-             "moe_permute_mxfp8: local_num_experts %d is not in [1, %d]", p->local_num_experts, FI_MOE_MAX_EXPERTS);
-  FI_REQUIRE(p->top_k >= 1 && p->top_k <= FI_MOE_MAX_TOP_K, "moe_permute_mxfp8: top_k %d is not in [1, %d]", p->top_k,
-             FI_MOE_MAX_TOP_K);
-  FI_REQUIRE(p->hidden > 0 && p->hidden % 128 == 0, "moe_permute_mxfp8: hidden %d must be a positive multiple of 128",
-             p->hidden);
+  if (const int rc = moe_permute_check("moe_permute_mxfp8", p->num_tokens, p->top_k, p->hidden, p->local_expert_offset,
+                                       p->local_num_experts))
+    return rc;
   if (p->num_tokens == 0) return 0;
   const int64_t n = (int64_t)p->num_tokens * p->top_k;
   const int64_t G = p->local_num_experts;
@@ -634,35 +745,21 @@ extern "C" FI_API int fi_moe_permute_mxfp8(const fi_moe_permute_params_t* p, fi_
   const int64_t nkb = p->hidden / kMxBlock;
   FI_REQUIRE(p->sf_bytes >= sf_rows * nkb, "moe_permute_mxfp8: sf_permuted holds %lld bytes, %lld needed",
              (long long)p->sf_bytes, (long long)(sf_rows * nkb));
-  const int64_t num_blocks = ceil_div<int64_t>(n, FI_MOE_SORT_BLOCK);
-  const int64_t ws_need = (num_blocks * G + n) * 4;
-  FI_REQUIRE(p->workspace_bytes >= ws_need, "moe_permute_mxfp8: workspace holds %lld bytes, %lld needed",
-             (long long)p->workspace_bytes, (long long)ws_need);
   MoePermuteArgs a{};
-  a.ids = p->topk_ids;
+  if (const int rc = moe_sort_args("moe_permute_mxfp8", a, p->topk_ids, p->m_indptr, p->expanded_to_permuted,
+                                   p->unpacked_weights, p->workspace, p->workspace_bytes, n, p->top_k, p->local_expert_offset,
+                                   G, p->packed != 0))
+    return rc;
   a.x = (const uint8_t*)p->x;
   a.x_sf = (const uint8_t*)p->x_sf;
-  a.m_indptr = p->m_indptr;
-  a.map = p->expanded_to_permuted;
   a.x_out = (uint8_t*)p->x_permuted;
   a.sf_out = (uint8_t*)p->sf_permuted;
-  a.weights_out = p->packed ? p->unpacked_weights : nullptr;
-  a.hist = p->workspace;
-  a.p2e = p->workspace + num_blocks * G;
-  a.n = (int32_t)n;
-  a.top_k = p->top_k;
   a.hidden = p->hidden;
   a.nkb = (int32_t)nkb;
-  a.offset = p->local_expert_offset;
-  a.G = (int32_t)G;
-  a.packed = p->packed != 0;
-  a.num_blocks = (int32_t)num_blocks;
   a.sf_rows = (int32_t)sf_rows;
   a.tpr_log2 = row_team_log2(p->hidden / 16, kMoeThreads);
   hipStream_t st = (hipStream_t)stream;
-  moe_count_kernel<<<dim3((uint32_t)num_blocks), dim3(64), 0, st>>>(a);
-  moe_scan_kernel<<<dim3(1), dim3(FI_MOE_MAX_EXPERTS), 0, st>>>(a);
-  moe_place_kernel<<<dim3((uint32_t)num_blocks), dim3(64), 0, st>>>(a);
+  moe_sort_launch(a, st);
   const uint32_t grid = (uint32_t)ceil_div<int64_t>(sf_rows, kMoeThreads >> a.tpr_log2);
   moe_gather_kernel<<<dim3(grid), dim3(kMoeThreads), 0, st>>>(a);
   FI_HIP_CALL(hipGetLastError());
@@ -704,6 +801,79 @@ extern "C" FI_API int fi_moe_gated_act_mxfp8(const fi_moe_gated_act_params_t* p,
   a.tpr_log2 = row_team_log2(p->intermediate / 8, kMoeThreads);
   const uint32_t grid = (uint32_t)ceil_div<int64_t>(sf_rows, kMoeThreads >> a.tpr_log2);
   moe_gated_act_kernel<<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}
+
+extern "C" FI_API int fi_moe_permute_fp8_block(const fi_moe_permute_fp8_block_params_t* p, fi_stream_t stream) {
+  FI_REQUIRE(p, "moe_permute_fp8_block: null params");
+  if (const int rc = moe_permute_check("moe_permute_fp8_block", p->num_tokens, p->top_k, p->hidden, p->local_expert_offset,
+                                       p->local_num_experts))
+    return rc;
+  FI_REQUIRE(p->scale_stride_kb >= 0 && p->scale_stride_t >= 0,
+             "moe_permute_fp8_block: negative stride of x_scale (%lld, %lld)", (long long)p->scale_stride_kb,
+             (long long)p->scale_stride_t);
+  if (p->num_tokens == 0) return 0;
+  const int64_t n = (int64_t)p->num_tokens * p->top_k;
+  const int64_t G = p->local_num_experts;
+  FI_REQUIRE(n < (1ll << 31), "moe_permute_fp8_block: too many rows");
+  FI_REQUIRE(p->topk_ids && p->x && p->x_scale && p->m_indptr && p->expanded_to_permuted && p->x_permuted &&
+                 p->scale_permuted && p->workspace, "moe_permute_fp8_block: null tensor");
+  FI_REQUIRE(aligned(p->x, 16) && aligned(p->x_permuted, 16) && aligned(p->x_scale, 4) && aligned(p->scale_permuted, 4),
+             "moe_permute_fp8_block: x and x_permuted must be 16-byte aligned, x_scale and scale_permuted 4-byte aligned");
+  MoePermuteArgs a{};
+  if (const int rc = moe_sort_args("moe_permute_fp8_block", a, p->topk_ids, p->m_indptr, p->expanded_to_permuted,
+                                   p->unpacked_weights, p->workspace, p->workspace_bytes, n, p->top_k, p->local_expert_offset,
+                                   G, p->packed != 0))
+    return rc;
+  MoeGatherFp8Args g{};
+  g.x = (const uint8_t*)p->x;
+  g.x_scale = p->x_scale;
+  g.m_indptr = p->m_indptr;
+  g.p2e = a.p2e;
+  g.x_out = (uint8_t*)p->x_permuted;
+  g.scale_out = p->scale_permuted;
+  g.stride_kb = p->scale_stride_kb;
+  g.stride_t = p->scale_stride_t;
+  g.n = (int32_t)n;
+  g.top_k = p->top_k;
+  g.hidden = p->hidden;
+  g.nkb = p->hidden / kFp8Block;
+  g.G = (int32_t)G;
+  g.tpr_log2 = row_team_log2(p->hidden / 16, kMoeThreads);
+  hipStream_t st = (hipStream_t)stream;
+  moe_sort_launch(a, st);
+  const uint32_t grid = (uint32_t)ceil_div<int64_t>(n, kMoeThreads >> g.tpr_log2);
+  moe_gather_fp8_block_kernel<<<dim3(grid), dim3(kMoeThreads), 0, st>>>(g);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}
+
+extern "C" FI_API int fi_moe_gated_act_fp8_block(const fi_moe_gated_act_fp8_block_params_t* p, fi_stream_t stream) {
+  FI_REQUIRE(p, "moe_gated_act_fp8_block: null params");
+  FI_REQUIRE(p->cum_m >= 0 && p->intermediate >= 0 && p->num_groups >= 0,
+             "moe_gated_act_fp8_block: negative size (cum_m %d, intermediate %d, num_groups %d)", p->cum_m, p->intermediate,
+             p->num_groups);
+  FI_REQUIRE(p->num_groups >= 1 && p->num_groups <= FI_MOE_MAX_EXPERTS,
+             "moe_gated_act_fp8_block: num_groups %d is not in [1, %d]", p->num_groups, FI_MOE_MAX_EXPERTS);
+  FI_REQUIRE(p->intermediate > 0 && p->intermediate % kFp8Block == 0,
+             "moe_gated_act_fp8_block: intermediate %d must be a positive multiple of 128", p->intermediate);
+  if (p->cum_m == 0) return 0;
+  FI_REQUIRE(p->x && p->m_indptr && p->q && p->scale, "moe_gated_act_fp8_block: null tensor");
+  FI_REQUIRE(aligned(p->x, 16) && aligned(p->q, 8) && aligned(p->scale, 4),
+             "moe_gated_act_fp8_block: x must be 16-byte aligned, q 8-byte aligned, scale 4-byte aligned");
+  MoeActFp8Args a{};
+  a.x = (const uint16_t*)p->x;
+  a.m_indptr = p->m_indptr;
+  a.q = (uint8_t*)p->q;
+  a.scale = p->scale;
+  a.cum_m = p->cum_m;
+  a.inter = p->intermediate;
+  a.nkb = p->intermediate / kFp8Block;
+  a.G = p->num_groups;
+  a.tpr_log2 = row_team_log2(p->intermediate / 8, kMoeThreads);  // intermediate / 8 >= 16: a team holds whole blocks
+  const uint32_t grid = (uint32_t)ceil_div<int64_t>(p->cum_m, kMoeThreads >> a.tpr_log2);
+  moe_gated_act_fp8_block_kernel<<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
   FI_HIP_CALL(hipGetLastError());
   return 0;
 }

@@ -1,6 +1,8 @@
 """MXFP8 quantisation: ``mxfp8_quantize`` and ``mxfp8_dequantize_host`` of the reference's flashinfer/fp8_quantization.py
 (:179-239), and ``mxfp8_quantize_grouped``, this project's own extension that writes the scales where the grouped
 MXFP4 GEMM reads them.  The kernel is csrc/mxfp8_quantize.hip behind fi_mxfp8_quantize (include/fi_mi355.h).
+``fp8_quantize_1x128``, also this project's own, makes DeepSeek's fp8 block-scale activations (one f32 scale per row and
+128 columns) for ``trtllm_fp8_block_scale_moe``; its kernel is csrc/fp8_block_quantize.hip.
 
 An MXFP8 tensor is e4m3 values plus one E8M0 byte (value ``2^(byte - 127)``) per 32 consecutive elements of a row.
 The scale of a block is the smallest power of two ``2^e`` with ``448 * 2^e >= amax``; the compare is exact (the
@@ -16,7 +18,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._mx import BLOCK, ceil_to, linear_scales, sf_row_offset, sf_shape
+from ._mx import BLOCK, ceil_to, contiguous_aligned, linear_scales, sf_row_offset, sf_shape
 
 def _check_input(input: torch.Tensor, alignment: int) -> None:
     _lib.require_gpu_tensor(input, "input")
@@ -89,6 +91,38 @@ def mxfp8_quantize_grouped(input: torch.Tensor, m_indptr: torch.Tensor) -> Tuple
     a_scale = torch.empty(sf_shape(cum_m, k // BLOCK, groups=m_indptr.shape[0] - 1), dtype=torch.uint8, device=input.device)
     _quantize_into(input, x_q, a_scale, True, BLOCK, m_indptr.contiguous())
     return x_q, a_scale
+
+
+def fp8_quantize_1x128(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Quantise activations to DeepSeek's fp8 block-scale format, the ``hidden_states`` / ``hidden_states_scale`` of
+    ``trtllm_fp8_block_scale_moe``.  Not part of the reference, whose callers quantise in their own code.
+
+    ``x`` is f16 / bf16 ``(T, H)`` with ``H % 128 == 0``.  Returns ``(q, scale)``: float8_e4m3fn ``(T, H)`` and float32
+    ``(H // 128, T)`` contiguous.  Per row and block of 128 columns, in f32: ``s = max(amax / 448, 2^-126)`` and
+    ``q = e4m3(clamp(x / s, -448, 448))`` rounded to nearest even; ``scale[kb, t] = s``.  ``amax / 448`` is the rule of the
+    reference's kernel (csrc/trtllm_fused_moe_dev_kernel.cu:141-152); an all-zero block gets ``s = 2^-126`` and ``q = 0``.
+    The gated activation of the layer quantises with the same device function (csrc/fp8_block_quant.h).
+    """
+    _lib.require_gpu_tensor(x, "x")
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"x has dtype {x.dtype}, expected float16 or bfloat16")
+    if x.dim() != 2:
+        raise ValueError(f"x must be 2D (T, H), got shape {tuple(x.shape)}")
+    T, H = x.shape
+    if H % 128 != 0:
+        raise ValueError(f"H = {H} must be a multiple of 128")
+    q = torch.empty((T, H), dtype=torch.float8_e4m3fn, device=x.device)
+    scale = torch.empty((H // 128, T), dtype=torch.float32, device=x.device)
+    if T == 0 or H == 0:
+        return q, scale
+    if x.stride(1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
+        x = contiguous_aligned(x, 16)
+    p = _lib.fi_fp8_quantize_1x128_params_t(
+        input=x.data_ptr(), q=q.data_ptr(), scale=scale.data_ptr(), input_stride=x.stride(0) if T > 1 else H, m=T, k=H,
+        dtype=_lib.fi_dtype(x.dtype))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().fi_fp8_quantize_1x128(C.byref(p), _lib.current_stream(x.device)), "fp8_quantize_1x128")
+    return q, scale
 
 
 def mxfp8_dequantize_host(

@@ -24,6 +24,10 @@ other method and in the routed call, where no routing runs.  An expert of a drop
 where the reference's kernel and the routine its tests compare it with would let it win against negative biased scores
 (INTEGRATION.md).
 
+``moe_permute_fp8_block`` and ``moe_gated_act_fp8_block`` (plain SwiGLU) are the same two stages on DeepSeek's fp8 block-scale
+format, f32 scales per token and 128 columns instead of E8M0 bytes: with ``moe_route`` and ``moe_finalize`` they are the
+steps of ``flashinfer.fused_moe_fp8.trtllm_fp8_block_scale_moe``, which lives in a module of its own.
+
 Nothing here reads a device value on the host or synchronises, and every buffer's size depends on shapes alone, so a
 call can be captured into a graph.
 """
@@ -625,3 +629,141 @@ def trtllm_fp4_block_scale_routed_moe(
                 output1_scale_scalar, output1_scale_gate_scalar, output2_scale_scalar, num_experts, top_k, n_group,
                 topk_group, intermediate_size, local_expert_offset, local_num_experts, routed_scaling_factor,
                 tile_tokens_dim, routing_method_type, do_finalize, enable_pdl, gated_act_type, output, tune_max_num_tokens)
+
+
+# ---- the fp8 block-scale layer (DeepSeek-V3 / R1 checkpoints) -----------------------------------------------------------
+_FP8_BLOCK = 128
+
+
+def _check_fp8_block_activations(hidden_states: torch.Tensor, hidden_states_scale: torch.Tensor) -> None:
+    if hidden_states.dtype != torch.float8_e4m3fn:
+        raise NotImplementedError(
+            f"hidden_states has dtype {hidden_states.dtype}: only float8_e4m3fn with float32 hidden_states_scale "
+            "(flashinfer.fp8_quantization.fp8_quantize_1x128 makes both)")
+    if hidden_states.dim() != 2:
+        raise ValueError(f"hidden_states must be 2D (T, H), got shape {tuple(hidden_states.shape)}")
+    T, H = hidden_states.shape
+    if H == 0 or H % _FP8_BLOCK != 0:
+        raise NotImplementedError(f"hidden_states has hidden size {H}: it must be a multiple of 128 (pad it)")
+    if hidden_states_scale is None or hidden_states_scale.dtype != torch.float32:
+        raise NotImplementedError("hidden_states_scale must be a float32 tensor: one scale per token and 128 columns")
+    if tuple(hidden_states_scale.shape) != (H // _FP8_BLOCK, T):
+        raise ValueError(f"hidden_states_scale must have shape ({H // _FP8_BLOCK}, {T}) = (H / 128, T) with any strides, got "
+                         f"{tuple(hidden_states_scale.shape)}")
+
+
+def _permute_fp8_block_into(topk_ids: torch.Tensor, hidden_states: torch.Tensor, hidden_states_scale: torch.Tensor,
+                            local_expert_offset: int, local_num_experts: int, packed: bool, m_indptr: torch.Tensor,
+                            emap: torch.Tensor, x_permuted: torch.Tensor, scale_permuted: torch.Tensor,
+                            weights: Optional[torch.Tensor]) -> None:
+    """fi_moe_permute_fp8_block on checked tensors (T > 0) into pre-allocated outputs; every word of ``scale_permuted`` is
+    written.  ``hidden_states_scale`` goes in by its strides: it is not copied."""
+    T, top_k = topk_ids.shape
+    n, G, dev = T * top_k, local_num_experts, hidden_states.device
+    blocks = -(-n // _lib.FI_MOE_SORT_BLOCK)
+    workspace = torch.empty((blocks * G + n,), dtype=torch.int32, device=dev)
+    ids, x = topk_ids.contiguous(), contiguous_aligned(hidden_states, 16)
+    p = _lib.fi_moe_permute_fp8_block_params_t(
+        topk_ids=ids.data_ptr(), x=x.data_ptr(), x_scale=hidden_states_scale.data_ptr(), m_indptr=m_indptr.data_ptr(),
+        expanded_to_permuted=emap.data_ptr(), x_permuted=x_permuted.data_ptr(), scale_permuted=scale_permuted.data_ptr(),
+        unpacked_weights=_lib.ptr(weights), workspace=workspace.data_ptr(),
+        scale_stride_kb=hidden_states_scale.stride(0), scale_stride_t=hidden_states_scale.stride(1),
+        workspace_bytes=_lib.nbytes(workspace), num_tokens=T, top_k=top_k, hidden=hidden_states.shape[1],
+        local_expert_offset=local_expert_offset, local_num_experts=G, packed=int(bool(packed)))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fi_moe_permute_fp8_block(C.byref(p), _lib.current_stream(dev)), "moe_permute_fp8_block")
+
+
+def moe_permute_fp8_block(
+    topk_ids: torch.Tensor,
+    hidden_states: torch.Tensor,
+    hidden_states_scale: torch.Tensor,
+    local_expert_offset: int,
+    local_num_experts: int,
+    packed: bool = False,
+) -> Tuple[torch.Tensor, ...]:
+    """``moe_permute_mxfp8`` for fp8 block-scale activations: the row operand of GEMM1 of ``trtllm_fp8_block_scale_moe``.
+    Not part of the reference.
+
+    ``topk_ids`` as there.  ``hidden_states`` float8_e4m3fn ``[T, H]`` and ``hidden_states_scale`` float32 ``[H / 128, T]``
+    with any strides (contiguous, or the ``.t()`` view of a ``[T, H / 128]`` tensor): it is read through them, not copied.
+    Returns ``(m_indptr, expanded_idx_to_permuted_idx, x_permuted, scale_permuted)`` and with ``packed`` the bf16 weights:
+
+    * ``m_indptr`` and ``expanded_idx_to_permuted_idx``: what ``moe_permute_mxfp8`` returns for the same ids;
+    * ``x_permuted`` float8_e4m3fn ``[T * top_k, H]``; rows at or past ``m_indptr[-1]`` are unwritten;
+    * ``scale_permuted`` float32 ``[T * top_k, H / 128]`` row-major, the ``a_scale`` of ``group_gemm_fp8_nt_groupwise`` in
+      its ``"K"`` mode; rows at or past ``m_indptr[-1]`` are 1.0.
+    """
+    if topk_ids.dtype != torch.int32 or topk_ids.dim() != 2:
+        raise ValueError("topk_ids must be a 2D int32 tensor (T, top_k)")
+    _check_fp8_block_activations(hidden_states, hidden_states_scale)
+    T, top_k = topk_ids.shape
+    H = hidden_states.shape[1]
+    if hidden_states.shape[0] != T:
+        raise ValueError(f"topk_ids has {T} rows, hidden_states {hidden_states.shape[0]}")
+    if not 1 <= top_k <= _MAX_TOP_K:
+        raise NotImplementedError(f"top_k {top_k} is not in [1, {_MAX_TOP_K}]")
+    if not 1 <= local_num_experts <= _MAX_EXPERTS or local_expert_offset < 0:
+        raise NotImplementedError(
+            f"local_num_experts {local_num_experts} is not in [1, {_MAX_EXPERTS}] or local_expert_offset {local_expert_offset} < 0")
+    for t, name in ((topk_ids, "topk_ids"), (hidden_states, "hidden_states"), (hidden_states_scale, "hidden_states_scale")):
+        _lib.require_gpu_tensor(t, name)
+    dev = hidden_states.device
+    n, G = T * top_k, local_num_experts
+    m_indptr = torch.empty((G + 1,), dtype=torch.int32, device=dev)
+    emap = torch.empty((n,), dtype=torch.int32, device=dev)
+    x_permuted = torch.empty((n, H), dtype=torch.float8_e4m3fn, device=dev)
+    scale_permuted = torch.empty((n, H // _FP8_BLOCK), dtype=torch.float32, device=dev)
+    weights = torch.empty((T, top_k), dtype=torch.bfloat16, device=dev) if packed else None
+    if T == 0:
+        m_indptr.zero_()
+    else:
+        _permute_fp8_block_into(topk_ids, hidden_states, hidden_states_scale, local_expert_offset, G, packed, m_indptr,
+                                emap, x_permuted, scale_permuted, weights)
+    if packed:
+        return m_indptr, emap, x_permuted, scale_permuted, weights
+    return m_indptr, emap, x_permuted, scale_permuted
+
+
+def _gated_act_fp8_block_into(gemm1_output: torch.Tensor, m_indptr: torch.Tensor, q: torch.Tensor,
+                              scale: torch.Tensor) -> None:
+    """fi_moe_gated_act_fp8_block on checked tensors (cum_m > 0) into pre-allocated outputs; every word of ``scale`` is
+    written, rows of ``q`` at or past ``m_indptr[-1]`` are not."""
+    cum_m, two_i = gemm1_output.shape
+    dev = gemm1_output.device
+    x = contiguous_aligned(gemm1_output, 16)
+    p = _lib.fi_moe_gated_act_fp8_block_params_t(
+        x=x.data_ptr(), m_indptr=m_indptr.contiguous().data_ptr(), q=q.data_ptr(), scale=scale.data_ptr(), cum_m=cum_m,
+        intermediate=two_i // 2, num_groups=m_indptr.shape[0] - 1)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fi_moe_gated_act_fp8_block(C.byref(p), _lib.current_stream(dev)), "moe_gated_act_fp8_block")
+
+
+def moe_gated_act_fp8_block(gemm1_output: torch.Tensor, m_indptr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """SwiGLU between the two GEMMs of ``trtllm_fp8_block_scale_moe``, quantised to fp8 with one f32 scale per row and 128
+    columns for the second.  Not part of the reference.
+
+    ``gemm1_output`` is bf16 ``[cum_m, 2 I]`` with ``I % 128 == 0``: columns ``[0, I)`` the linear half ``x1``, ``[I, 2 I)`` the
+    gate ``x2``.  In f32 ``act = x2 * sigmoid(x2) * x1``; the fp8 call has no bias, alpha, beta or limit.  Per row and block
+    of 128 columns ``s = max(amax / 448, 2^-126)`` and ``q = e4m3(clamp(act / s, -448, 448))``, the rule and the device code
+    of ``fp8_quantize_1x128``.  Returns ``(q, scale)``: float8_e4m3fn ``[cum_m, I]`` and float32 ``[cum_m, I / 128]`` row-major.
+    Rows at or past ``m_indptr[-1]``: ``q`` is not written, ``scale`` is 1.0.
+    """
+    if gemm1_output.dtype != torch.bfloat16 or gemm1_output.dim() != 2:
+        raise ValueError("gemm1_output must be a 2D bfloat16 tensor (cum_m, 2 I)")
+    if m_indptr.dtype != torch.int32 or m_indptr.dim() != 1 or m_indptr.shape[0] < 2:
+        raise ValueError("m_indptr must be a 1D int32 tensor of G + 1 >= 2 entries")
+    cum_m, two_i = gemm1_output.shape
+    I, G = two_i // 2, m_indptr.shape[0] - 1
+    if two_i == 0 or two_i % 256 != 0:
+        raise NotImplementedError(f"intermediate_size {two_i / 2:g} must be a multiple of 128")
+    if G > _MAX_EXPERTS:
+        raise NotImplementedError(f"{G} groups: at most {_MAX_EXPERTS}")
+    _lib.require_gpu_tensor(gemm1_output, "gemm1_output")
+    _lib.require_gpu_tensor(m_indptr, "m_indptr")
+    dev = gemm1_output.device
+    q = torch.empty((cum_m, I), dtype=torch.float8_e4m3fn, device=dev)
+    scale = torch.empty((cum_m, I // _FP8_BLOCK), dtype=torch.float32, device=dev)
+    if cum_m:
+        _gated_act_fp8_block_into(gemm1_output, m_indptr, q, scale)
+    return q, scale

@@ -156,6 +156,31 @@ def group_gemm_fp8_nt_groupwise(
     return out
 
 
+def _group_gemm_fp8_into(a: torch.Tensor, b: torch.Tensor, a_scale: torch.Tensor, b_scale: torch.Tensor,
+                         out: torch.Tensor, m_indptr: torch.Tensor, scale_k_major: bool = True) -> None:
+    """fi_group_gemm_fp8_nt_groupwise with (1, 128, 128) scales on checked tensors, into ``out``: no allocation, no
+    dtype conversion, no copy -- every tensor is contiguous as it comes.  ``a`` ``(rows, k)`` and ``out`` ``(rows, n)`` may
+    have more rows than ``m_indptr[-1]`` (the fused MoE layer with a local expert window): the kernels take their row
+    tiles from the groups (csrc/gemm_common.h, group_of_tile), so those rows of ``a`` are never loaded and those of
+    ``out`` never stored; ``a_scale`` must hold finite values for all ``rows`` (the power-of-two check reads them all)."""
+    for t, name in ((a, "a"), (b, "b"), (a_scale, "a_scale"), (b_scale, "b_scale"), (out, "out"), (m_indptr, "m_indptr")):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if a_scale.dtype != torch.float32 or b_scale.dtype != torch.float32:
+        raise ValueError("a_scale and b_scale must be float32")
+    num_groups, n, k = b.shape
+    with torch.cuda.device(a.device):
+        _lib.check(
+            _lib.lib().fi_group_gemm_fp8_nt_groupwise(
+                a.data_ptr(), b.data_ptr(), a_scale.data_ptr(), b_scale.data_ptr(), out.data_ptr(),
+                m_indptr.data_ptr(), num_groups, a.shape[0], n, k, 1, 128, 128, int(bool(scale_k_major)),
+                _lib.fi_dtype(a.dtype), _lib.fi_dtype(b.dtype), _lib.fi_dtype(out.dtype),
+                _lib.current_stream(a.device),
+            ),
+            "group_gemm_fp8_nt_groupwise",
+        )
+
+
 def _group_gemm_mxfp4_into(a: torch.Tensor, b: torch.Tensor, a_scale: torch.Tensor, b_scale: torch.Tensor,
                            out: torch.Tensor, m_indptr: torch.Tensor, n: int, k: int) -> None:
     """fi_group_gemm_mxfp8_mxfp4_nt_groupwise on checked tensors; the scale buffers' sizes go along and are checked on

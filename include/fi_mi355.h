@@ -1168,6 +1168,76 @@ typedef struct fi_moe_finalize_params {
 
 FI_API int fi_moe_finalize(const fi_moe_finalize_params_t* params, fi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The same layer on DeepSeek's fp8 block-scale format, around two launches of fi_group_gemm_fp8_nt_groupwise in its
+ * (1, 128, 128) "K" scale mode.  ref: trtllm_fp8_block_scale_moe, flashinfer/fused_moe/core.py:1742-1816.
+ *   route -> permute (fp8 block) -> GEMM1 -> gated activation (fp8 block) -> GEMM2 -> finalize
+ * fi_moe_route, fi_moe_route_sigmoid and fi_moe_finalize are the ones above.  Activations carry one f32 scale per row
+ * and 128 columns; the block rule (csrc/fp8_block_quant.h) is
+ *   amax = max |x| over the block;  s = max(amax / 448, 2^-126);  q = e4m3(clamp(x / s, -448, 448)), nearest even,
+ * amax / 448 being the reference kernel's rule (csrc/trtllm_fused_moe_dev_kernel.cu:141-152); an all-zero block gets
+ * s = 2^-126 and q = 0, and the clamp keeps a quotient one ulp above 448 off the NaN byte 0x7F.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* fi_moe_permute_mxfp8 for fp8 block-scale activations: m_indptr and expanded_to_permuted are the same for the same
+ * ids (the same three sorting launches), and for p = expanded_to_permuted[i] >= 0, t = i / top_k:
+ *   x_permuted[p] = x[t];  scale_permuted[p, kb] = x_scale[kb * scale_stride_kb + t * scale_stride_t]
+ * scale_permuted is [num_tokens * top_k, hidden / 128] row-major, the a_scale of the grouped GEMM in "K" mode.  The
+ * scales of the input are read through both strides (in elements, >= 0): [hidden / 128, num_tokens] contiguous, the
+ * reference's layout, has strides (num_tokens, 1), the transposed view of a [num_tokens, hidden / 128] tensor
+ * (1, hidden / 128).  Rows of x_permuted at or past m_indptr[G] are not written; rows of scale_permuted there are
+ * written as 1.0f, so that EVERY word of scale_permuted is written (the GEMM's power-of-two check reads them all).
+ * Four launches.  workspace as fi_moe_permute_mxfp8.  hidden % 128 == 0; x, x_permuted 16-byte aligned. */
+typedef struct fi_moe_permute_fp8_block_params {
+  const int32_t* topk_ids;       /* [num_tokens, top_k] */
+  const void* x;                 /* [num_tokens, hidden] e4m3 */
+  const float* x_scale;          /* (hidden / 128) x num_tokens values by the two strides */
+  int32_t* m_indptr;             /* out [local_num_experts + 1] */
+  int32_t* expanded_to_permuted; /* out [num_tokens * top_k] */
+  void* x_permuted;              /* out [num_tokens * top_k, hidden] */
+  float* scale_permuted;         /* out [num_tokens * top_k, hidden / 128] */
+  uint16_t* unpacked_weights;    /* optional out [num_tokens, top_k] bf16, packed ids only */
+  int32_t* workspace;
+  int64_t scale_stride_kb, scale_stride_t;
+  int64_t workspace_bytes;
+  int32_t num_tokens, top_k, hidden;
+  int32_t local_expert_offset, local_num_experts;
+  int32_t packed;
+} fi_moe_permute_fp8_block_params_t;
+
+FI_API int fi_moe_permute_fp8_block(const fi_moe_permute_fp8_block_params_t* params, fi_stream_t stream);
+
+/* Plain SwiGLU between the two GEMMs, quantised by the block rule above.  For row r < m_indptr[num_groups] and column
+ * c < intermediate, with x1 = x[r, c] (the linear half) and x2 = x[r, intermediate + c] (the gate), in f32:
+ *   act = x2 * sigmoid(x2) * x1
+ * q[r] and scale[r, c / 128] follow from act by the block rule.  scale is [cum_m, intermediate / 128] row-major.  Rows
+ * at or past m_indptr[num_groups]: x is not read, q is not written, scale is 1.0f (EVERY word of scale is written).
+ * Only m_indptr[num_groups] is read.  intermediate % 128 == 0; x 16-byte, q 8-byte aligned. */
+typedef struct fi_moe_gated_act_fp8_block_params {
+  const void* x;           /* [cum_m, 2 * intermediate] bf16 */
+  const int32_t* m_indptr; /* [num_groups + 1] device */
+  void* q;                 /* out [cum_m, intermediate] e4m3 */
+  float* scale;            /* out [cum_m, intermediate / 128] */
+  int32_t cum_m, intermediate, num_groups;
+} fi_moe_gated_act_fp8_block_params_t;
+
+FI_API int fi_moe_gated_act_fp8_block(const fi_moe_gated_act_fp8_block_params_t* params, fi_stream_t stream);
+
+/* The block rule above on f16 / bf16 rows (csrc/fp8_block_quantize.hip): what feeds fi_moe_permute_fp8_block.
+ * input: [m, k], k % 128 == 0, row stride in elements (a multiple of 8, base 16-byte aligned).
+ * q: [m, k] e4m3 contiguous, 8-byte aligned.  scale: [k / 128, m] contiguous, the reference's layout of
+ * hidden_states_scale.  No host state, no synchronisation; an empty problem returns 0 without a launch. */
+typedef struct fi_fp8_quantize_1x128_params {
+  const void* input;
+  void* q;
+  float* scale;
+  int64_t input_stride;
+  int32_t m, k;
+  int32_t dtype; /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+} fi_fp8_quantize_1x128_params_t;
+
+FI_API int fi_fp8_quantize_1x128(const fi_fp8_quantize_1x128_params_t* params, fi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
