@@ -92,11 +92,17 @@ struct OffsetAllocator {
 };
 
 // The planners' chunk search: the smallest value in [lo, hi] for which too_many(value) is false (hi if it never is,
-// lo if the range is empty).  too_many must not turn true again as the value grows.
-template <class Pred>
-inline int64_t smallest_fitting(int64_t lo, int64_t hi, Pred too_many) {
+// lo if the range is empty).  too_many must not turn true again as the value grows.  The host planners search in
+// int64_t whatever their bounds' types; the planners on the device (plan_device.h) name a 32-bit T.
+template <typename T>
+struct search_bound {
+  using type = T;  // keeps lo and hi out of the deduction of T
+};
+template <typename T = int64_t, class Pred>
+__host__ __device__ inline T smallest_fitting(typename search_bound<T>::type lo, typename search_bound<T>::type hi,
+                                              Pred too_many) {
   while (lo < hi) {
-    const int64_t mid = (lo + hi) / 2;
+    const T mid = (lo + hi) / 2;
     if (too_many(mid)) lo = mid + 1; else hi = mid;
   }
   return lo;

@@ -17,44 +17,30 @@
 namespace fi {
 
 struct DevicePlanParams {
-  const int32_t* block_tables;
-  const int32_t* seq_lens;
-  int64_t block_tables_stride;
   // work list (fi_decode_plan_slot offsets of the int workspace)
   int32_t* request_indices;    // [padded]
   int32_t* kv_tile_indices;    // [padded]
   int32_t* o_indptr;           // [batch + 1]
   int32_t* chunk_slot;         // [2]: tokens per chunk, valid work items
   uint8_t* block_valid_mask;   // [padded], null for an unsplit plan
-  // CSR page table
-  int32_t* indptr;         // [batch + 1]
-  int32_t* indices;        // [batch * max_blocks]
-  int32_t* last_page_len;  // [batch]
-  int32_t batch, max_blocks, page_size;
+  PlanPageTable csr;
+  PlanRequests req;   // in front of the other scalars (plan_device.h)
   int32_t padded;     // capacity of the work list
   int32_t split;      // the host-known branch: batch * gdy < max_grid
   uint32_t gdy, max_grid;
   int32_t list_blocks;  // fill kernel: workgroups that write the work list; the rest compact page ids
-  int32_t row_blocks;   // fill kernel: workgroups per block-table row
 };
-
-// tokens and pages of request b that the plan covers (plan_device.h)
-__device__ __forceinline__ int32_t planned_len(const DevicePlanParams& p, int b) {
-  return planned_kv_len(p.seq_lens, b, p.max_blocks, p.page_size);
-}
-__device__ __forceinline__ uint32_t pages_of(const DevicePlanParams& p, int b) {
-  return pages_holding(planned_len(p, b), p.page_size);
-}
 
 __global__ __launch_bounds__(kPlanThreads) void decode_plan_scan_kernel(const DevicePlanParams p) {
   __shared__ uint32_t red[kPlanWaves];
-  __shared__ int32_t scan_pages[kPlanWaves], scan_chunks[kPlanWaves];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int B = p.batch;
+  __shared__ int32_t wave_tot[2][kPlanWaves];
+  const int tid = threadIdx.x;
+  const int B = p.req.batch;
 
-  uint32_t max_pages = 0, empty = 0;  // the longest request's pages, the requests without a page
+  // the longest request's pages and the requests without a page, in one pass over the lengths
+  uint32_t max_pages = 0, empty = 0;
   for (int b = tid; b < B; b += kPlanThreads) {
-    const uint32_t np = pages_of(p, b);
+    const uint32_t np = p.req.pages(b);
     max_pages = max(max_pages, np);
     empty += np == 0;
   }
@@ -62,8 +48,7 @@ __global__ __launch_bounds__(kPlanThreads) void decode_plan_scan_kernel(const De
   empty = block_reduce<kPlanWaves, RedSum>(empty, red);
 
   // estimate_decode_work (decode.hip): whole requests when they fill the grid, else smallest_fitting over
-  // [max(128 / page_size, 1), max_pages].  lo, hi and every reduced count are the same in all threads, so the loop
-  // is uniform; an empty range leaves its lower bound, as on the host.
+  // [max(128 / page_size, 1), max_pages].
   //
   // The list has a host-known capacity, padded = max(max_grid / gdy, batch), where the host planner grows its list
   // to the entries it counted.  Only empty requests can make the host rule's list outgrow it (they add one entry
@@ -72,59 +57,34 @@ __global__ __launch_bounds__(kPlanThreads) void decode_plan_scan_kernel(const De
   // its result is the host's whenever the host's list fits: always, when no request is empty.
   uint32_t pages_per_chunk = max(max_pages, 1u);
   if (p.split) {
-    uint32_t lo = max(128u / (uint32_t)p.page_size, 1u), hi = max_pages;
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) / 2;
-      uint32_t nb = 0;
-      for (int b = tid; b < B; b += kPlanThreads) nb += (pages_of(p, b) + mid - 1) / mid;
-      nb = block_reduce<kPlanWaves, RedSum>(nb, red);
-      if ((uint64_t)nb * p.gdy > p.max_grid || (uint64_t)nb + empty > (uint64_t)p.padded)
-        lo = mid + 1;
-      else
-        hi = mid;
-    }
-    pages_per_chunk = lo;
+    const uint32_t min_pages = max(128u / (uint32_t)p.req.page_size, 1u);
+    pages_per_chunk = smallest_fitting<uint32_t>(min_pages, max_pages, [&](uint32_t n) {
+      const uint32_t nb = request_sum(B, red, [&](int b) { return (p.req.pages(b) + n - 1) / n; });
+      return (uint64_t)nb * p.gdy > p.max_grid || (uint64_t)nb + empty > (uint64_t)p.padded;
+    });
   }
 
-  // exclusive scans of pages (indptr) and of chunks (o_indptr), kPlanThreads requests a round
-  int32_t carry_pages = 0, carry_chunks = 0;
+  // exclusive scans of pages (indptr) and of chunks (o_indptr)
+  FusedScan<2> scan;
   for (int base = 0; base < B; base += kPlanThreads) {
     const int b = base + tid;
     const bool valid = b < B;
-    const int32_t len = valid ? planned_len(p, b) : 0;
-    const int32_t np = valid ? (int32_t)pages_of(p, b) : 0;
+    const int32_t len = valid ? p.req.len(b) : 0;
+    const int32_t np = (int32_t)pages_holding(len, p.req.page_size);
     // the host rule counts an empty request as one chunk
     const int32_t nc = !valid ? 0 : p.split ? (int32_t)(((uint32_t)max(np, 1) + pages_per_chunk - 1) / pages_per_chunk) : 1;
-    // block_incl_scan (common.h) for two values at once, in its barrier convention: two barriers a round.  As two
-    // calls, four barriers, the planner's two launches measured 0.3-0.5 us of 9.5 slower.
-    const int32_t ip = wave_incl_scan(np), ic = wave_incl_scan(nc);
-    if (lane == 63) {
-      scan_pages[wave] = ip;
-      scan_chunks[wave] = ic;
-    }
-    __syncthreads();
-    int32_t before_pages = carry_pages, before_chunks = carry_chunks;
-#pragma unroll
-    for (int w = 0; w < kPlanWaves; ++w) {
-      if (w < wave) {
-        before_pages += scan_pages[w];
-        before_chunks += scan_chunks[w];
-      }
-      carry_pages += scan_pages[w];
-      carry_chunks += scan_chunks[w];
-    }
-    __syncthreads();
+    int32_t before[2];
+    scan.round({np, nc}, before, wave_tot);
     if (valid) {
-      p.indptr[b] = before_pages + ip - np;
-      p.o_indptr[b] = before_chunks + ic - nc;
-      p.last_page_len[b] = last_page_tokens(len, np, p.page_size);
+      store_page_range(p.csr, b, before[0], len, np, p.req.page_size);
+      p.o_indptr[b] = before[1];
     }
   }
   if (tid == 0) {
-    p.indptr[B] = carry_pages;
-    p.o_indptr[B] = carry_chunks;
-    p.chunk_slot[0] = (int32_t)(pages_per_chunk * (uint32_t)p.page_size);
-    p.chunk_slot[1] = carry_chunks;
+    p.csr.indptr[B] = scan.carry[0];
+    p.o_indptr[B] = scan.carry[1];
+    p.chunk_slot[0] = (int32_t)(pages_per_chunk * (uint32_t)p.req.page_size);
+    p.chunk_slot[1] = scan.carry[1];
   }
 }
 
@@ -141,30 +101,18 @@ __global__ __launch_bounds__(kPlanThreads) void decode_plan_fill_kernel(const De
   if ((int)blockIdx.x < p.list_blocks) {
     const int i = (int)blockIdx.x * kPlanThreads + tid;
     if (i >= p.padded) return;
-    const int32_t total = p.o_indptr[p.batch];
+    const int32_t total = p.o_indptr[p.req.batch];
     int32_t req = 0, tile = 0;
     if (i < total) {
-      // the request whose chunks hold entry i: the last b with o_indptr[b] <= i (every request has >= 1 chunk)
-      int lo = 0, hi = p.batch - 1;
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) / 2;
-        if (p.o_indptr[mid] <= i)
-          lo = mid;
-        else
-          hi = mid - 1;
-      }
-      req = lo;
-      tile = i - p.o_indptr[lo];
+      req = owner_of(p.o_indptr, p.req.batch, i);  // the request whose chunks hold entry i: every one has >= 1 chunk
+      tile = i - p.o_indptr[req];
     }
     p.request_indices[i] = req;
     p.kv_tile_indices[i] = tile;
     if (p.block_valid_mask) p.block_valid_mask[i] = i < total;
     return;
   }
-  const int blk = (int)blockIdx.x - p.list_blocks;
-  const int b = blk / p.row_blocks;
-  const int j = (blk - b * p.row_blocks) * kPlanThreads + tid;
-  compact_page_id(p.block_tables, p.block_tables_stride, p.indptr, p.indices, b, j);
+  compact_page_ids(p.req, p.csr, (int)blockIdx.x - p.list_blocks);
 }
 
 struct DevicePlanLayout {
@@ -225,51 +173,35 @@ using namespace fi;
 
 extern "C" FI_API int fi_batch_decode_plan_device_workspace(const fi_batch_decode_plan_device_params_t* a,
                                                             size_t* int_ws_bytes_out, size_t* float_ws_bytes_out) {
-  FI_REQUIRE(a && int_ws_bytes_out && float_ws_bytes_out, "batch_decode_plan_device_workspace: null argument");
-  DevicePlanLayout l;
-  if (device_plan_layout(*a, l)) return 1;
-  *int_ws_bytes_out = l.int_bytes;
-  *float_ws_bytes_out = l.float_bytes;
-  return 0;
+  return plan_workspace_sizes("batch_decode_plan_device_workspace", a, int_ws_bytes_out, float_ws_bytes_out,
+                              device_plan_layout);
 }
 
 extern "C" FI_API int fi_batch_decode_plan_device(const fi_batch_decode_plan_device_params_t* a,
                                                   int64_t* plan_info_out, int64_t* csr_offsets_out,
-                                                  fi_stream_t stream_) {
-  FI_REQUIRE(a && plan_info_out && csr_offsets_out, "batch_decode_plan_device: null argument");
-  FI_REQUIRE(a->block_tables && a->seq_lens && a->int_ws, "batch_decode_plan_device: null tensor");
-  FI_REQUIRE(a->block_tables_stride >= a->max_blocks, "batch_decode_plan_device: block table rows overlap");
+                                                  fi_stream_t stream) {
+  const char* name = "batch_decode_plan_device";
+  FI_REQUIRE(a && plan_info_out && csr_offsets_out, "%s: null argument", name);
+  if (check_plan_tensors(name, *a)) return 1;
   DevicePlanLayout l;
   if (device_plan_layout(*a, l)) return 1;
-  FI_REQUIRE(l.int_bytes <= a->int_ws_bytes, "batch_decode_plan_device: int workspace too small (%zu bytes, need %zu)",
-             a->int_ws_bytes, l.int_bytes);
-  FI_REQUIRE(l.float_bytes <= a->float_ws_bytes && (!l.split || a->float_ws),
-             "batch_decode_plan_device: float workspace too small (%zu bytes, need %zu)", a->float_ws_bytes,
-             l.float_bytes);
+  if (check_plan_workspaces(name, *a, l.int_bytes, l.float_bytes, l.split)) return 1;
 
   char* ib = (char*)a->int_ws;
   DevicePlanParams p;
-  p.block_tables = a->block_tables;
-  p.seq_lens = a->seq_lens;
-  p.block_tables_stride = a->block_tables_stride;
+  p.req = plan_requests(*a);
   p.request_indices = (int32_t*)(ib + l.req_off);
   p.kv_tile_indices = (int32_t*)(ib + l.tile_off);
   p.o_indptr = (int32_t*)(ib + l.oind_off);
   p.chunk_slot = (int32_t*)(ib + l.chunk_off);
   p.block_valid_mask = l.split ? (uint8_t*)(ib + l.mask_off) : nullptr;
-  p.indptr = (int32_t*)(ib + l.indptr_off);
-  p.indices = (int32_t*)(ib + l.indices_off);
-  p.last_page_len = (int32_t*)(ib + l.last_off);
-  p.batch = a->batch_size;
-  p.max_blocks = a->max_blocks;
-  p.page_size = a->page_size;
+  p.csr = plan_page_table(ib, l.indptr_off, l.indices_off, l.last_off, a->max_blocks);
   p.padded = (int32_t)l.padded;
   p.split = l.split;
   p.gdy = l.gdy;
   p.max_grid = l.max_grid;
   p.list_blocks = (int32_t)ceil_div<size_t>(l.padded, kPlanThreads);
-  p.row_blocks = ceil_div(a->max_blocks, kPlanThreads);
-  const int64_t fill_grid = (int64_t)p.list_blocks + (int64_t)a->batch_size * p.row_blocks;
+  const int64_t fill_grid = (int64_t)p.list_blocks + (int64_t)a->batch_size * p.csr.row_blocks;
   FI_REQUIRE(l.padded < (1ull << 31) && fill_grid < (1ll << 31), "batch_decode_plan_device: plan too large");
 
   for (int i = 0; i < FI_DECODE_PLAN_INFO_LEN; ++i) plan_info_out[i] = 0;
@@ -294,10 +226,5 @@ extern "C" FI_API int fi_batch_decode_plan_device(const fi_batch_decode_plan_dev
   csr_offsets_out[1] = l.indices_off;
   csr_offsets_out[2] = l.last_off;
 
-  hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(decode_plan_scan_kernel, dim3(1), dim3(kPlanThreads), 0, stream, p);
-  FI_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(decode_plan_fill_kernel, dim3((uint32_t)fill_grid), dim3(kPlanThreads), 0, stream, p);
-  FI_HIP_CALL(hipGetLastError());
-  return 0;
+  return launch_plan_kernels(decode_plan_scan_kernel, decode_plan_fill_kernel, fill_grid, p, stream);
 }

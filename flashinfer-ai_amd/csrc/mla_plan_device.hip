@@ -2,8 +2,8 @@
 //
 // It writes what fi_batch_mla_plan(enable_cuda_graph = 1) writes into the int workspace -- the header slots, the merge
 // indptr, the MlaItem list in the order request, chunk, row tile -- by the same chunk rule (mla.hip), for
-// qo_len = q_len_per_request in every request and kv_len = planned_kv_len(seq_lens, b), from a dense block table and
-// lengths that never leave the device.  There is no CSR page table: mla_paged_kernel addresses pages as
+// qo_len = q_len_per_request in every request and kv_len = PlanRequests::len(b), the clamped seq_lens[b], from a dense
+// block table and lengths that never leave the device.  There is no CSR page table: mla_paged_kernel addresses pages as
 // kv_indices[page_base + i], so run() is given kv_indices = block_tables and page_base = b * block_tables_stride, the
 // one field that differs from the host plan.
 // Two launches, both shaped by host-known values only:
@@ -30,7 +30,6 @@
 namespace fi {
 
 struct MlaDevicePlanParams {
-  const int32_t* seq_lens;
   int32_t* header;        // [4] of kMlaHeaderBytes
   int32_t* merge_indptr;  // [total_rows + 1]
   MlaItem* items;         // [capacity]
@@ -38,9 +37,9 @@ struct MlaDevicePlanParams {
   int32_t* chunk_indptr;  // [batch + 1] scan of chunks per request (>= 1 each)
   int32_t* split_indptr;  // [batch + 1] scan of the chunks of split requests (0 for a request in one chunk)
   int32_t* chunk_slot;    // [1] tokens per chunk
-  int64_t block_tables_stride;
   int64_t max_entries;    // partial states the float workspace holds
-  int32_t batch, max_blocks, page_size;
+  PlanRequests req;       // in front of the other scalars (plan_device.h); its block table goes to run(), only the
+                          // row stride is read here
   int32_t q_len, num_heads;
   int32_t tiles;          // row tiles per request
   int32_t capacity;       // of the item list
@@ -50,9 +49,6 @@ struct MlaDevicePlanParams {
   int32_t list_blocks;    // fill kernel: workgroups that write items; the rest write the merge indptr
 };
 
-__device__ __forceinline__ int32_t planned_len(const MlaDevicePlanParams& p, int b) {
-  return planned_kv_len(p.seq_lens, b, p.max_blocks, p.page_size);
-}
 // the host rule counts an empty request as one chunk
 __device__ __forceinline__ uint32_t chunks_of(int32_t len, uint32_t chunk) {
   return max(((uint32_t)len + chunk - 1) / chunk, 1u);
@@ -60,89 +56,60 @@ __device__ __forceinline__ uint32_t chunks_of(int32_t len, uint32_t chunk) {
 
 __global__ __launch_bounds__(kPlanThreads) void mla_plan_scan_kernel(const MlaDevicePlanParams p) {
   __shared__ uint32_t red[kPlanWaves];
-  __shared__ int32_t scan_chunks[kPlanWaves], scan_split[kPlanWaves];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int B = p.batch;
+  __shared__ int32_t wave_tot[2][kPlanWaves];
+  const int tid = threadIdx.x;
+  const int B = p.req.batch;
 
   uint32_t max_kv = 0;
-  for (int b = tid; b < B; b += kPlanThreads) max_kv = max(max_kv, (uint32_t)planned_len(p, b));
+  for (int b = tid; b < B; b += kPlanThreads) max_kv = max(max_kv, (uint32_t)p.req.len(b));
   max_kv = block_reduce<kPlanWaves, RedMax>(max_kv, red);
 
   // fi_batch_mla_plan's chunk rule (mla.hip), in kMlaTileKV tokens: whole requests when their tiles fill max_items,
   // else smallest_fitting over [kMlaMinChunk / 64, whole / 64].  items = tiles * chunks with the same tiles in every
-  // request, so "items > max_items" is "chunks > max_items / tiles" = chunk_limit.  lo, hi and every reduced count are
-  // the same in all threads, so the loops are uniform.  A thread's count saturates at chunk_limit + 1 (< 2^22, the
-  // host checked), so the sum of kPlanThreads of them fits 32 bits and still compares right.
+  // request, so "items > max_items" is "chunks > max_items / tiles" = chunk_limit.
   const uint32_t whole = max((max_kv + kMlaTileKV - 1) / kMlaTileKV, 1u) * kMlaTileKV;  // < 2^31: the host checked
   uint32_t chunk = whole;
   if (p.split) {
-    uint32_t lo = kMlaMinChunk / kMlaTileKV, hi = whole / kMlaTileKV;
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) / 2;
-      uint64_t n = 0;
-      for (int b = tid; b < B; b += kPlanThreads) n += chunks_of(planned_len(p, b), mid * kMlaTileKV);
-      uint32_t nc = (uint32_t)min(n, (uint64_t)p.chunk_limit + 1);
-      nc = block_reduce<kPlanWaves, RedSum>(nc, red);
-      if (nc > p.chunk_limit)
-        lo = mid + 1;
-      else
-        hi = mid;
-    }
-    chunk = min(whole, lo * kMlaTileKV);  // an empty range leaves its lower bound, as on the host
+    const uint32_t tiles = smallest_fitting<uint32_t>(kMlaMinChunk / kMlaTileKV, whole / kMlaTileKV, [&](uint32_t n) {
+      const auto chunks = [&](int b) { return (uint64_t)chunks_of(p.req.len(b), n * kMlaTileKV); };
+      return request_sum<true>(B, red, chunks, p.chunk_limit) > p.chunk_limit;
+    });
+    chunk = min(whole, tiles * kMlaTileKV);
   }
   // chunks grow until the partial states fit: rows x (chunks of split requests) entries.  chunk < whole only when the
   // search accepted it, so these chunks number <= chunk_limit and their sum needs no saturation.
   const uint64_t rows_per_request = (uint64_t)p.q_len * (uint64_t)p.num_heads;
   while (chunk < whole) {
-    uint32_t ns = 0;
-    for (int b = tid; b < B; b += kPlanThreads) {
-      const uint32_t c = chunks_of(planned_len(p, b), chunk);
-      ns += c > 1 ? c : 0;
-    }
-    ns = block_reduce<kPlanWaves, RedSum>(ns, red);
+    const uint32_t ns = request_sum(B, red, [&](int b) {
+      const uint32_t c = chunks_of(p.req.len(b), chunk);
+      return c > 1 ? c : 0;
+    });
     if ((uint64_t)ns * rows_per_request <= (uint64_t)p.max_entries) break;
     chunk *= 2;  // < 2 whole < 2^32
   }
   chunk = min(chunk, whole);
 
-  // exclusive scans of chunks and of split chunks, kPlanThreads requests a round
-  int32_t carry_chunks = 0, carry_split = 0;
+  // exclusive scans of chunks and of split chunks
+  FusedScan<2> scan;
   for (int base = 0; base < B; base += kPlanThreads) {
     const int b = base + tid;
     const bool valid = b < B;
-    const int32_t nc = valid ? (int32_t)chunks_of(planned_len(p, b), chunk) : 0;
-    const int32_t ns = nc > 1 ? nc : 0;
-    // block_incl_scan (common.h) for two values at once, in its barrier convention: two barriers a round
-    const int32_t ic = wave_incl_scan(nc), is = wave_incl_scan(ns);
-    if (lane == 63) {
-      scan_chunks[wave] = ic;
-      scan_split[wave] = is;
-    }
-    __syncthreads();
-    int32_t before_chunks = carry_chunks, before_split = carry_split;
-#pragma unroll
-    for (int w = 0; w < kPlanWaves; ++w) {
-      if (w < wave) {
-        before_chunks += scan_chunks[w];
-        before_split += scan_split[w];
-      }
-      carry_chunks += scan_chunks[w];
-      carry_split += scan_split[w];
-    }
-    __syncthreads();
+    const int32_t nc = valid ? (int32_t)chunks_of(p.req.len(b), chunk) : 0;
+    int32_t before[2];
+    scan.round({nc, nc > 1 ? nc : 0}, before, wave_tot);
     if (valid) {
-      p.chunk_indptr[b] = before_chunks + ic - nc;
-      p.split_indptr[b] = before_split + is - ns;
+      p.chunk_indptr[b] = before[0];
+      p.split_indptr[b] = before[1];
     }
   }
   if (tid == 0) {
-    p.chunk_indptr[B] = carry_chunks;
-    p.split_indptr[B] = carry_split;
+    p.chunk_indptr[B] = scan.carry[0];
+    p.split_indptr[B] = scan.carry[1];
     p.chunk_slot[0] = (int32_t)chunk;
     p.header[kMlaHdrMagic] = kMlaWsMagic;
-    p.header[kMlaHdrNumWork] = carry_chunks * p.tiles;  // <= capacity, see the file header
+    p.header[kMlaHdrNumWork] = scan.carry[0] * p.tiles;  // <= capacity, see the file header
     p.header[kMlaHdrItemsOff] = p.items_off;
-    p.header[kMlaHdrSplit] = carry_split > 0;
+    p.header[kMlaHdrSplit] = scan.carry[1] > 0;
   }
 }
 
@@ -154,20 +121,11 @@ __global__ __launch_bounds__(kPlanThreads) void mla_plan_fill_kernel(const MlaDe
   if (blk < p.list_blocks) {
     const int i = blk * kPlanThreads + tid;
     // items past the plan's count stay as they were, as the host planner leaves them: the kernel stops at the count
-    if (i >= p.capacity || i >= p.chunk_indptr[p.batch] * p.tiles) return;
+    if (i >= p.capacity || i >= p.chunk_indptr[p.req.batch] * p.tiles) return;
     const int32_t j = i / p.tiles, t = i - j * p.tiles;  // chunk among all requests' chunks, row tile
-    // the request that owns chunk j: the last b with chunk_indptr[b] <= j (every request has >= 1 chunk)
-    int lo = 0, hi = p.batch - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) / 2;
-      if (p.chunk_indptr[mid] <= j)
-        lo = mid;
-      else
-        hi = mid - 1;
-    }
-    const int b = lo;
+    const int b = owner_of(p.chunk_indptr, p.req.batch, j);  // every request has >= 1 chunk
     const int32_t first = p.chunk_indptr[b], nc = p.chunk_indptr[b + 1] - first, c = j - first;
-    const int32_t len = planned_len(p, b);
+    const int32_t len = p.req.len(b);
     const uint32_t chunk = (uint32_t)p.chunk_slot[0];
     MlaItem it;
     it.qo_start = b * p.q_len;
@@ -176,7 +134,7 @@ __global__ __launch_bounds__(kPlanThreads) void mla_plan_fill_kernel(const MlaDe
     it.kv_start = (int32_t)((uint32_t)c * chunk);  // < len when c > 0
     it.kv_end = (int32_t)min(((uint32_t)c + 1) * chunk, (uint32_t)len);  // the product < len + chunk < 2^32
     it.kv_len = len;
-    it.page_base = (int32_t)((int64_t)b * p.block_tables_stride);
+    it.page_base = (int32_t)((int64_t)b * p.req.block_tables_stride);
     it.chunk = nc > 1 ? c : -1;
     p.items[i] = it;
     return;
@@ -184,10 +142,10 @@ __global__ __launch_bounds__(kPlanThreads) void mla_plan_fill_kernel(const MlaDe
   blk -= p.list_blocks;
   const int64_t row = (int64_t)blk * kPlanThreads + tid;
   const int32_t rows_per_request = p.q_len * p.num_heads;
-  const int64_t total_rows = (int64_t)p.batch * rows_per_request;
+  const int64_t total_rows = (int64_t)p.req.batch * rows_per_request;
   if (row > total_rows) return;
   // packed row r of request b starts at the request's first entry + r x its chunks (none for a request in one chunk)
-  int32_t entry = p.split_indptr[p.batch] * rows_per_request;
+  int32_t entry = p.split_indptr[p.req.batch] * rows_per_request;
   if (row < total_rows) {
     const int b = (int)(row / rows_per_request), r = (int)(row - (int64_t)b * rows_per_request);
     const int32_t first = p.split_indptr[b];
@@ -201,6 +159,7 @@ struct MlaDevicePlanLayout {
   int64_t max_items, tiles, total_rows, capacity;
   int64_t items_off, scan_off;  // bytes; the scans: chunk_indptr [batch + 1], split_indptr [batch + 1], chunk size [1]
   size_t int_bytes;
+  size_t float_bytes = 0;  // the least: without room for partial states no request is split
 };
 
 // checks that need no pointer, and the layout of the int workspace: host-known values only
@@ -246,43 +205,34 @@ using namespace fi;
 
 extern "C" FI_API int fi_batch_mla_plan_device_workspace(const fi_batch_mla_plan_device_params_t* a,
                                                          size_t* int_ws_bytes_out, size_t* float_ws_bytes_out) {
-  FI_REQUIRE(a && int_ws_bytes_out && float_ws_bytes_out, "batch_mla_plan_device_workspace: null argument");
-  MlaDevicePlanLayout l;
-  if (mla_device_plan_layout(*a, l)) return 1;
-  *int_ws_bytes_out = l.int_bytes;
-  *float_ws_bytes_out = 0;  // without room for partial states no request is split
-  return 0;
+  return plan_workspace_sizes("batch_mla_plan_device_workspace", a, int_ws_bytes_out, float_ws_bytes_out,
+                              mla_device_plan_layout);
 }
 
 extern "C" FI_API int fi_batch_mla_plan_device(const fi_batch_mla_plan_device_params_t* a, int64_t* plan_info_out,
-                                               fi_stream_t stream_) {
-  FI_REQUIRE(a && plan_info_out, "batch_mla_plan_device: null argument");
+                                               fi_stream_t stream) {
+  const char* name = "batch_mla_plan_device";
+  FI_REQUIRE(a && plan_info_out, "%s: null argument", name);
   MlaDevicePlanLayout l;
   if (mla_device_plan_layout(*a, l)) return 1;
-  FI_REQUIRE(a->block_tables && a->seq_lens && a->int_ws, "batch_mla_plan_device: null tensor");
-  FI_REQUIRE(a->block_tables_stride >= a->max_blocks, "batch_mla_plan_device: block table rows overlap");
+  if (check_plan_tensors(name, *a)) return 1;
   // an item's page_base is an int32
   FI_REQUIRE((int64_t)a->batch_size * a->block_tables_stride < (1ll << 31),
              "batch_mla_plan_device: batch_size x block_tables_stride must fit 31 bits");
-  FI_REQUIRE(l.int_bytes <= a->int_ws_bytes, "batch_mla_plan_device: int workspace too small (%zu bytes, need %zu)",
-             a->int_ws_bytes, l.int_bytes);
+  if (check_plan_workspaces(name, *a, l.int_bytes, l.float_bytes, /*split=*/false)) return 1;
 
   char* ib = (char*)a->int_ws;
   int32_t* scans = (int32_t*)(ib + l.scan_off);
   MlaDevicePlanParams p;
-  p.seq_lens = a->seq_lens;
+  p.req = plan_requests(*a);
   p.header = (int32_t*)ib;
   p.merge_indptr = (int32_t*)(ib + kMlaHeaderBytes);
   p.items = (MlaItem*)(ib + l.items_off);
   p.chunk_indptr = scans;
   p.split_indptr = scans + a->batch_size + 1;
   p.chunk_slot = scans + 2 * (a->batch_size + 1);
-  p.block_tables_stride = a->block_tables_stride;
   // merge indptr entries are int32
   p.max_entries = std::min<int64_t>(mla_max_entries(a->float_ws ? a->float_ws_bytes : 0), (1ll << 31) - 1);
-  p.batch = a->batch_size;
-  p.max_blocks = a->max_blocks;
-  p.page_size = a->page_size;
   p.q_len = a->q_len_per_request;
   p.num_heads = a->num_heads;
   p.tiles = (int32_t)l.tiles;
@@ -311,10 +261,5 @@ extern "C" FI_API int fi_batch_mla_plan_device(const fi_batch_mla_plan_device_pa
   plan_info_out[FI_MLA_DTYPE] = a->q_dtype;
   plan_info_out[FI_MLA_MAGIC] = FI_MLA_PLAN_MAGIC;
 
-  hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(mla_plan_scan_kernel, dim3(1), dim3(kPlanThreads), 0, stream, p);
-  FI_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(mla_plan_fill_kernel, dim3((uint32_t)fill_grid), dim3(kPlanThreads), 0, stream, p);
-  FI_HIP_CALL(hipGetLastError());
-  return 0;
+  return launch_plan_kernels(mla_plan_scan_kernel, mla_plan_fill_kernel, fill_grid, p, stream);
 }

@@ -20,39 +20,30 @@
 namespace fi {
 
 struct PrefillDevicePlanParams {
-  const int32_t* block_tables;
-  const int32_t* seq_lens;
-  const int32_t* cum_seq_lens_q;
-  int64_t block_tables_stride;
   // work list (fi_prefill_plan_slot offsets of the int workspace)
   int32_t* request_indices;  // [capacity]
   int32_t* qo_tile_indices;  // [capacity]
   int32_t* kv_tile_indices;  // [capacity]
   int32_t* merge_indptr;     // [total_num_rows + 1]
   int32_t* chunk_slot;       // [2]: tokens per chunk, real work items
+  const int32_t* cum_seq_lens_q;  // [batch + 1] the caller's; beside the copy that is made from it
   // what the two kernels hand each other, and the kernels of run() read
   int32_t* qo_indptr;     // [batch + 1] first query row per request: cum_seq_lens_q clamped, non-decreasing
   int32_t* item_indptr;   // [batch + 1] scan of q tiles x chunks
   int32_t* entry_indptr;  // [batch + 1] scan of query rows x chunks
-  // CSR page table
-  int32_t* indptr;         // [batch + 1]
-  int32_t* indices;        // [batch * max_blocks]
-  int32_t* last_page_len;  // [batch]
-  int32_t batch, max_blocks, page_size;
+  PlanPageTable csr;
+  PlanRequests req;  // in front of the other scalars (plan_device.h)
   int32_t total_num_rows, group, window_left;
   int32_t capacity;    // of the work list
   int32_t split;       // the host-known branch: ceil(total_num_rows * group / 128) <= max_items
   uint32_t max_items;  // items a chunk size may make
-  // fill kernel: workgroups that write the work list, then merge_indptr; the rest compact page ids, row_blocks a row
-  int32_t list_blocks, merge_blocks, row_blocks;
+  // fill kernel: workgroups that write the work list, then merge_indptr; the rest compact page ids
+  int32_t list_blocks, merge_blocks;
 };
 
-__device__ __forceinline__ int32_t planned_len(const PrefillDevicePlanParams& p, int b) {
-  return planned_kv_len(p.seq_lens, b, p.max_blocks, p.page_size);
-}
 // keys the chunks of request b are cut from: kv_span of the host rule under the causal mask
 __device__ __forceinline__ uint32_t span_of(const PrefillDevicePlanParams& p, int b) {
-  return (uint32_t)kv_span(planned_len(p, b), 0, /*causal=*/true, p.window_left);
+  return (uint32_t)kv_span(p.req.len(b), 0, /*causal=*/true, p.window_left);
 }
 __device__ __forceinline__ int32_t rows_of(const PrefillDevicePlanParams& p, int b) {
   return p.qo_indptr[b + 1] - p.qo_indptr[b];
@@ -65,9 +56,9 @@ __device__ __forceinline__ uint32_t chunks_of(uint32_t span, uint32_t chunk) { r
 
 __global__ __launch_bounds__(kPlanThreads) void prefill_plan_scan_kernel(const PrefillDevicePlanParams p) {
   __shared__ uint32_t red[kPlanWaves];
-  __shared__ int32_t scan_pages[kPlanWaves], scan_items[kPlanWaves], scan_entries[kPlanWaves];
+  __shared__ int32_t wave_tot[3][kPlanWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int B = p.batch;
+  const int B = p.req.batch;
 
   // qo_indptr[b] = max over j <= b of clamp(cum_seq_lens_q[j], 0, total_num_rows): an inclusive scan with max in the
   // place of wave_incl_scan's sum, kPlanThreads entries a round.  Whatever the caller's tensor holds, the requests'
@@ -81,13 +72,13 @@ __global__ __launch_bounds__(kPlanThreads) void prefill_plan_scan_kernel(const P
       const int32_t o = __shfl_up(v, d, 64);
       if (lane >= d) v = max(v, o);
     }
-    if (lane == 63) scan_pages[wave] = v;
+    if (lane == 63) wave_tot[0][wave] = v;
     __syncthreads();
     int32_t before = row_carry;
 #pragma unroll
     for (int w = 0; w < kPlanWaves; ++w) {
-      if (w < wave) before = max(before, scan_pages[w]);
-      row_carry = max(row_carry, scan_pages[w]);
+      if (w < wave) before = max(before, wave_tot[0][w]);
+      row_carry = max(row_carry, wave_tot[0][w]);
     }
     __syncthreads();
     if (b <= B) p.qo_indptr[b] = max(before, v);
@@ -99,89 +90,43 @@ __global__ __launch_bounds__(kPlanThreads) void prefill_plan_scan_kernel(const P
   max_span = block_reduce<kPlanWaves, RedMax>(max_span, red);
 
   // choose_kv_chunk with graph_items != 0 (prefill.hip): smallest_fitting over [2, ceil(max_span / 64)] kv tiles, the
-  // items counted against max_items; no price model, no balance rule.  lo, hi and every reduced count are the same in
-  // all threads, so the loop is uniform.  A thread's count saturates at max_items + 1 (< 2^22, the host checked), so
-  // the sum of kPlanThreads of them fits 32 bits and still compares right.  In the unsplit branch the host knows that
+  // items counted against max_items; no price model, no balance rule.  In the unsplit branch the host knows that
   // nothing fits, and the result is the range's upper end, one chunk per request.
   const uint32_t hi_tiles = (max_span + kPlanTileKV - 1) / kPlanTileKV;
   uint32_t chunk_tiles = max(hi_tiles, 2u);
-  if (p.split) {
-    uint32_t lo = 2, hi = hi_tiles;
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) / 2;
-      uint64_t items = 0;
-      for (int b = tid; b < B; b += kPlanThreads)
-        items += (uint64_t)q_tiles_of(p, rows_of(p, b)) * chunks_of(span_of(p, b), mid * kPlanTileKV);
-      uint32_t n = (uint32_t)min(items, (uint64_t)p.max_items + 1);
-      n = block_reduce<kPlanWaves, RedSum>(n, red);
-      if (n > p.max_items)
-        lo = mid + 1;
-      else
-        hi = mid;
-    }
-    chunk_tiles = lo;  // an empty range leaves its lower bound, as on the host
-  }
+  if (p.split)
+    chunk_tiles = smallest_fitting<uint32_t>(2, hi_tiles, [&](uint32_t n) {
+      const auto items = [&](int b) {
+        return (uint64_t)q_tiles_of(p, rows_of(p, b)) * chunks_of(span_of(p, b), n * kPlanTileKV);
+      };
+      return request_sum<true>(B, red, items, p.max_items) > p.max_items;
+    });
   const uint32_t chunk = chunk_tiles * kPlanTileKV;
 
-  // exclusive scans of pages (indptr), of items and of partial-state entries, kPlanThreads requests a round
-  int32_t carry_pages = 0, carry_items = 0, carry_entries = 0;
+  // exclusive scans of pages (indptr), of items and of partial-state entries
+  FusedScan<3> scan;
   for (int base = 0; base < B; base += kPlanThreads) {
     const int b = base + tid;
     const bool valid = b < B;
-    const int32_t len = valid ? planned_len(p, b) : 0;
-    const int32_t np = (int32_t)pages_holding(len, p.page_size);
+    const int32_t len = valid ? p.req.len(b) : 0;
+    const int32_t np = (int32_t)pages_holding(len, p.req.page_size);
     const int32_t rows = valid ? rows_of(p, b) : 0;
     const int32_t nc = valid ? (int32_t)chunks_of(span_of(p, b), chunk) : 0;
-    const int32_t ni = (int32_t)q_tiles_of(p, rows) * nc, ne = rows * nc;
-    // block_incl_scan (common.h) for three values at once, in its barrier convention: two barriers a round
-    const int32_t ip = wave_incl_scan(np), ii = wave_incl_scan(ni), ie = wave_incl_scan(ne);
-    if (lane == 63) {
-      scan_pages[wave] = ip;
-      scan_items[wave] = ii;
-      scan_entries[wave] = ie;
-    }
-    __syncthreads();
-    int32_t before_pages = carry_pages, before_items = carry_items, before_entries = carry_entries;
-#pragma unroll
-    for (int w = 0; w < kPlanWaves; ++w) {
-      if (w < wave) {
-        before_pages += scan_pages[w];
-        before_items += scan_items[w];
-        before_entries += scan_entries[w];
-      }
-      carry_pages += scan_pages[w];
-      carry_items += scan_items[w];
-      carry_entries += scan_entries[w];
-    }
-    __syncthreads();
+    int32_t before[3];
+    scan.round({np, (int32_t)q_tiles_of(p, rows) * nc, rows * nc}, before, wave_tot);
     if (valid) {
-      p.indptr[b] = before_pages + ip - np;
-      p.item_indptr[b] = before_items + ii - ni;
-      p.entry_indptr[b] = before_entries + ie - ne;
-      p.last_page_len[b] = last_page_tokens(len, np, p.page_size);
+      store_page_range(p.csr, b, before[0], len, np, p.req.page_size);
+      p.item_indptr[b] = before[1];
+      p.entry_indptr[b] = before[2];
     }
   }
   if (tid == 0) {
-    p.indptr[B] = carry_pages;
-    p.item_indptr[B] = carry_items;
-    p.entry_indptr[B] = carry_entries;
+    p.csr.indptr[B] = scan.carry[0];
+    p.item_indptr[B] = scan.carry[1];
+    p.entry_indptr[B] = scan.carry[2];
     p.chunk_slot[0] = (int32_t)chunk;
-    p.chunk_slot[1] = carry_items;
+    p.chunk_slot[1] = scan.carry[1];
   }
-}
-
-// the last b in [0, batch) with indptr[b] <= x, for a non-decreasing indptr with indptr[0] <= x: the request that owns
-// item or row x when x < indptr[batch] (requests that own nothing repeat their neighbour's value and are passed over)
-__device__ __forceinline__ int owner_of(const int32_t* indptr, int batch, int32_t x) {
-  int lo = 0, hi = batch - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (indptr[mid] <= x)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
 }
 
 // Runs after prefill_plan_scan_kernel on the same stream and reads its scans and its chunk slot.
@@ -206,8 +151,8 @@ __global__ __launch_bounds__(kPlanThreads) void prefill_plan_fill_kernel(const P
     const int i = blk * kPlanThreads + tid;
     if (i >= p.capacity) return;
     int32_t req = -1, tile = 0, kvt = 0;  // -1: a padding item, as the host pads; the workgroup exits
-    if (i < p.item_indptr[p.batch]) {
-      req = owner_of(p.item_indptr, p.batch, i);
+    if (i < p.item_indptr[p.req.batch]) {
+      req = owner_of(p.item_indptr, p.req.batch, i);
       const int32_t nc = (int32_t)chunks_of(span_of(p, req), chunk);  // >= 1
       const int32_t first = p.item_indptr[req];
       const int32_t q_tiles = (p.item_indptr[req + 1] - first) / nc;
@@ -226,19 +171,16 @@ __global__ __launch_bounds__(kPlanThreads) void prefill_plan_fill_kernel(const P
     if (row > p.total_num_rows) return;
     // rows no request owns (before qo_indptr[0], from qo_indptr[batch] on) get empty ranges: the merge skips them
     int32_t entry = 0;
-    if (row >= p.qo_indptr[p.batch]) {
-      entry = p.entry_indptr[p.batch];
+    if (row >= p.qo_indptr[p.req.batch]) {
+      entry = p.entry_indptr[p.req.batch];
     } else if (row >= p.qo_indptr[0]) {
-      const int b = owner_of(p.qo_indptr, p.batch, row);
+      const int b = owner_of(p.qo_indptr, p.req.batch, row);
       entry = p.entry_indptr[b] + (row - p.qo_indptr[b]) * (int32_t)chunks_of(span_of(p, b), chunk);
     }
     p.merge_indptr[row] = entry;
     return;
   }
-  blk -= p.merge_blocks;
-  const int b = blk / p.row_blocks;
-  const int j = (blk - b * p.row_blocks) * kPlanThreads + tid;
-  compact_page_id(p.block_tables, p.block_tables_stride, p.indptr, p.indices, b, j);
+  compact_page_ids(p.req, p.csr, blk - p.merge_blocks);
 }
 
 struct PrefillDevicePlanLayout {
@@ -311,36 +253,25 @@ using namespace fi;
 
 extern "C" FI_API int fi_batch_prefill_plan_device_workspace(const fi_batch_prefill_plan_device_params_t* a,
                                                              size_t* int_ws_bytes_out, size_t* float_ws_bytes_out) {
-  FI_REQUIRE(a && int_ws_bytes_out && float_ws_bytes_out, "batch_prefill_plan_device_workspace: null argument");
-  PrefillDevicePlanLayout l;
-  if (prefill_device_plan_layout(*a, l)) return 1;
-  *int_ws_bytes_out = l.int_bytes;
-  *float_ws_bytes_out = l.float_bytes;
-  return 0;
+  return plan_workspace_sizes("batch_prefill_plan_device_workspace", a, int_ws_bytes_out, float_ws_bytes_out,
+                              prefill_device_plan_layout);
 }
 
 extern "C" FI_API int fi_batch_prefill_plan_device(const fi_batch_prefill_plan_device_params_t* a,
                                                    int64_t* plan_info_out, int64_t* csr_offsets_out,
-                                                   fi_stream_t stream_) {
-  FI_REQUIRE(a && plan_info_out && csr_offsets_out, "batch_prefill_plan_device: null argument");
-  FI_REQUIRE(a->block_tables && a->seq_lens && a->cum_seq_lens_q && a->int_ws,
-             "batch_prefill_plan_device: null tensor");
-  FI_REQUIRE(a->block_tables_stride >= a->max_blocks, "batch_prefill_plan_device: block table rows overlap");
+                                                   fi_stream_t stream) {
+  const char* name = "batch_prefill_plan_device";
+  FI_REQUIRE(a && plan_info_out && csr_offsets_out, "%s: null argument", name);
+  if (check_plan_tensors(name, *a, a->cum_seq_lens_q != nullptr)) return 1;
   PrefillDevicePlanLayout l;
   if (prefill_device_plan_layout(*a, l)) return 1;
-  FI_REQUIRE(l.int_bytes <= a->int_ws_bytes, "batch_prefill_plan_device: int workspace too small (%zu bytes, need %zu)",
-             a->int_ws_bytes, l.int_bytes);
-  FI_REQUIRE(l.float_bytes <= a->float_ws_bytes && (!l.split || a->float_ws),
-             "batch_prefill_plan_device: float workspace too small (%zu bytes, need %zu)", a->float_ws_bytes,
-             l.float_bytes);
+  if (check_plan_workspaces(name, *a, l.int_bytes, l.float_bytes, l.split)) return 1;
 
   char* ib = (char*)a->int_ws;
   auto at = [&](int64_t off) { return (int32_t*)(ib + off); };
   PrefillDevicePlanParams p;
-  p.block_tables = a->block_tables;
-  p.seq_lens = a->seq_lens;
+  p.req = plan_requests(*a);
   p.cum_seq_lens_q = a->cum_seq_lens_q;
-  p.block_tables_stride = a->block_tables_stride;
   p.request_indices = at(l.req_off);
   p.qo_tile_indices = at(l.tile_off);
   p.kv_tile_indices = at(l.kvt_off);
@@ -349,12 +280,7 @@ extern "C" FI_API int fi_batch_prefill_plan_device(const fi_batch_prefill_plan_d
   p.qo_indptr = at(l.qo_off);
   p.item_indptr = at(l.item_off);
   p.entry_indptr = at(l.entry_off);
-  p.indptr = at(l.indptr_off);
-  p.indices = at(l.indices_off);
-  p.last_page_len = at(l.last_off);
-  p.batch = a->batch_size;
-  p.max_blocks = a->max_blocks;
-  p.page_size = a->page_size;
+  p.csr = plan_page_table(ib, l.indptr_off, l.indices_off, l.last_off, a->max_blocks);
   p.total_num_rows = a->total_num_rows;
   p.group = a->num_qo_heads / a->num_kv_heads;
   p.window_left = a->window_left < 0 ? -1 : a->window_left;
@@ -363,8 +289,7 @@ extern "C" FI_API int fi_batch_prefill_plan_device(const fi_batch_prefill_plan_d
   p.max_items = (uint32_t)l.max_items;
   p.list_blocks = (int32_t)ceil_div<size_t>(l.capacity, kPlanThreads);
   p.merge_blocks = (int32_t)ceil_div<size_t>((size_t)a->total_num_rows + 1, kPlanThreads);
-  p.row_blocks = ceil_div(a->max_blocks, kPlanThreads);
-  const int64_t fill_grid = (int64_t)p.list_blocks + p.merge_blocks + (int64_t)a->batch_size * p.row_blocks;
+  const int64_t fill_grid = (int64_t)p.list_blocks + p.merge_blocks + (int64_t)a->batch_size * p.csr.row_blocks;
   FI_REQUIRE(l.capacity < (1ull << 31) && fill_grid < (1ll << 31), "batch_prefill_plan_device: plan too large");
 
   for (int i = 0; i < FI_PREFILL_PLAN_INFO_LEN; ++i) plan_info_out[i] = 0;
@@ -389,10 +314,5 @@ extern "C" FI_API int fi_batch_prefill_plan_device(const fi_batch_prefill_plan_d
   csr_offsets_out[2] = l.last_off;
   csr_offsets_out[3] = l.qo_off;
 
-  hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(prefill_plan_scan_kernel, dim3(1), dim3(kPlanThreads), 0, stream, p);
-  FI_HIP_CALL(hipGetLastError());
-  hipLaunchKernelGGL(prefill_plan_fill_kernel, dim3((uint32_t)fill_grid), dim3(kPlanThreads), 0, stream, p);
-  FI_HIP_CALL(hipGetLastError());
-  return 0;
+  return launch_plan_kernels(prefill_plan_scan_kernel, prefill_plan_fill_kernel, fill_grid, p, stream);
 }

@@ -15,14 +15,9 @@ from typing import Any, List, Optional, Tuple, Union
 import torch
 
 from . import _lib
+from ._plan_free import (_check_block_tables_and_lens, _check_len_fits_block_tables, _device_plan_regions,
+                         _hnd_cache_views, _one_sinks_tensor, _out_or_empty, _refuse_fp4_out_and_shared_kv)
 from ._wrapper import BatchAttentionWrapper
-from .decode import (
-    _check_block_tables_and_lens,
-    _device_plan_regions,
-    _hnd_cache_views,
-    _one_sinks_tensor,
-    _refuse_fp4_out_and_shared_kv,
-)
 from .page import get_seq_lens
 from .quantization import packbits, segment_packbits
 from .utils import (
@@ -925,12 +920,7 @@ def trtllm_batch_context_with_kv_cache(
         raise ValueError(f"the output dtype {o_dtype} differs from the query's {query.dtype}")
     if out_dtype is not None and canonicalize_torch_dtype(out_dtype) != o_dtype:
         raise ValueError(f"out_dtype {out_dtype} differs from out's {o_dtype}")
-    if out is None:
-        out = torch.empty(query.shape, dtype=o_dtype, device=query.device)
-    else:
-        check_shape_dtype_device(out, query.shape, o_dtype, query.device, "out")
-        if not out.is_contiguous():
-            raise ValueError("out must be contiguous")
+    out = _out_or_empty(out, query.shape, o_dtype, query.device)
     sinks = _one_sinks_tensor(sinks, num_qo_heads, query.device)
     if sinks is not None and fp8_query:
         raise ValueError("sinks need a float16 / bfloat16 query")
@@ -940,9 +930,7 @@ def trtllm_batch_context_with_kv_cache(
     kv, page_size, num_kv_heads, kv_head_dim = paged_kv(k_cache, v_cache, "HND", block_tables, None, None, batch_size)
     if kv_head_dim != head_dim:
         raise ValueError(f"head_dim of query ({head_dim}) and kv_cache ({kv_head_dim}) differ")
-    if max_kv_len > max_blocks * page_size:
-        raise ValueError(f"max_kv_len {max_kv_len} exceeds what block_tables can hold: {max_blocks} blocks of "
-                         f"{page_size} tokens")
+    _check_len_fits_block_tables("max_kv_len", max_kv_len, max_blocks, page_size)
     if batch_size == 0 or num_tokens == 0:
         return out
 

@@ -206,6 +206,6 @@ def test_c_entry_checks_before_any_launch(fi_lib):
 
 def test_new_sources_do_not_name_the_oracle():
     for rel in ("flashinfer-ai_amd/csrc/prefill_plan_device.hip", "flashinfer-ai_amd/csrc/prefill_plan.h",
-                "flashinfer-ai_amd/csrc/plan_device.h"):
+                "flashinfer-ai_amd/csrc/plan_device.h", "flashinfer-ai_amd/flashinfer/_plan_free.py"):
         with open(os.path.join(ROOT, rel)) as f:
             assert "oracle" not in f.read(), rel

@@ -45,6 +45,13 @@ PLAN_CASES = {
     "h_window_items_from_the_device": dict(qo=[10, 3, 0, 200, 5], kv=[4, 0, 50, 150, 3000], ps=16, mb=190, hint=0,
                                            window=100),
 }
+# the edges of a scan round of 256: qo_indptr has batch + 1 entries, so 255 requests fill one round of its max-scan
+# and 256 spill one entry into the next; the sum scans run over batch entries.  Once with a hint under which the
+# bisection chooses, once with one below the q tiles x 1 chunk that the requests with rows make anyway.
+for _b in (255, 256, 257, 513):
+    for _name, _hint in (("split", 512), ("nothing_fits", 64)):
+        PLAN_CASES[f"i_round_edge_{_b}_{_name}"] = dict(qo=_rand(_b, 0, 3, _b), kv=_rand(_b, 1, 600, _b + 1), ps=16,
+                                                        mb=38, hint=_hint)
 
 
 def _device_plan(fi_lib, cum_q, seq_lens, ps, mb, hint, rows, stride=None, window=-1, hq=HQ):

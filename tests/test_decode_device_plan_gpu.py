@@ -37,6 +37,11 @@ PLAN_CASES = {
     # beyond the issue's cases: empty requests (one chunk each on the host too) whose entries still fit the list
     "h_empty_requests_that_fit": ([54, 0, 700, 0], 16, 48, 128, None),
 }
+# the edges of the scan's round of 256 requests: one full round, one request into the second, one into the third;
+# 1..600 tokens in 38 blocks a row, once under a grid that splits (batch x 8 < 8192) and once under one that does not
+for _b in (256, 257, 513):
+    PLAN_CASES[f"i_round_edge_{_b}_split"] = (_mixed_lens(_b, 601, _b), 16, 38, 8192, None)
+    PLAN_CASES[f"i_round_edge_{_b}_unsplit"] = (_mixed_lens(_b, 601, _b), 16, 38, 64, None)
 
 
 def _device_plan(fi_lib, lens, ps, max_blocks, hint, stride):

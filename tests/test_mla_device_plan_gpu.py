@@ -44,6 +44,10 @@ PLAN_CASES = {
     "l_row_stride_wider_than_max_blocks": dict(lens=[54, 4000, 1, 700, 33], stride=300),
     "m_tile_spans_query_positions": dict(lens=[8736, 1, 33], H=8, q_len=3, ps=64),
     "n_no_float_workspace": dict(lens=[54, 4000, 1, 700, 33], float_bytes=0),
+    # the edges of the scan's round of 256 requests; split or not by the device's compute units, the host plan follows
+    "o_round_edge_256": dict(lens=_mixed_lens(256, 601, 256)),
+    "o_round_edge_257": dict(lens=_mixed_lens(257, 601, 257)),
+    "o_round_edge_513": dict(lens=_mixed_lens(513, 601, 513)),
 }
 
 
