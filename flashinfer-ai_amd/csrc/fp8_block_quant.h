@@ -24,18 +24,33 @@ __device__ __forceinline__ float fp8_block_scale(float lane_amax) {
   return fmaxf(group_reduce<kFp8BlockLanes, RedMax>(lane_amax) / 448.0f, 0x1p-126f);
 }
 
+// The clamped conversion: 4 f32 as 4 fp8 bytes of type DT (e4m3: largest finite 448, e5m2: 57344), round to nearest
+// even, saturating -- a value beyond the largest finite one would become NaN (e4m3fn) or infinity (e5m2).  Shared with
+// the MLA rope-and-quantise kernel (rope.hip).
+template <int DT = FI_DTYPE_FP8_E4M3>
+__device__ __forceinline__ uint32_t fp8_pack4_saturating(float y0, float y1, float y2, float y3) {
+  constexpr float kMax = DT == FI_DTYPE_FP8_E4M3 ? 448.f : 57344.f;
+  y0 = __builtin_amdgcn_fmed3f(y0, -kMax, kMax);
+  y1 = __builtin_amdgcn_fmed3f(y1, -kMax, kMax);
+  y2 = __builtin_amdgcn_fmed3f(y2, -kMax, kMax);
+  y3 = __builtin_amdgcn_fmed3f(y3, -kMax, kMax);
+  int packed;
+  if constexpr (DT == FI_DTYPE_FP8_E4M3) {
+    packed = __builtin_amdgcn_cvt_pk_fp8_f32(y0, y1, 0, false);
+    packed = __builtin_amdgcn_cvt_pk_fp8_f32(y2, y3, packed, true);
+  } else {
+    packed = __builtin_amdgcn_cvt_pk_bf8_f32(y0, y1, 0, false);
+    packed = __builtin_amdgcn_cvt_pk_bf8_f32(y2, y3, packed, true);
+  }
+  return (uint32_t)packed;
+}
+
 // 8 values divided by the block's scale as 8 e4m3 bytes
 __device__ __forceinline__ u32x2 fp8_block_pack8(const float* v, float s) {
   uint32_t w[2];
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    float y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = __builtin_amdgcn_fmed3f(v[4 * h + j] / s, -448.f, 448.f);
-    int packed = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-    packed = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], packed, true);
-    w[h] = (uint32_t)packed;
-  }
+  for (int h = 0; h < 2; ++h)
+    w[h] = fp8_pack4_saturating(v[4 * h] / s, v[4 * h + 1] / s, v[4 * h + 2] / s, v[4 * h + 3] / s);
   return u32x2{w[0], w[1]};
 }
 

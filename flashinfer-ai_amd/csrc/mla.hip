@@ -13,6 +13,8 @@
 // A request cut into several chunks writes f32 partial states to the float workspace; launch_merge_n merges
 // them (ragged, one entry range per packed row).  Every plan value the kernel uses is read from the int
 // workspace, so a captured run() stays correct after a re-plan.
+// An e4m3 cache (and query) is upcast exactly to the 16-bit compute type on the way into LDS (into the Q fragments);
+// from LDS onward there is one code.
 #include <algorithm>
 #include <vector>
 
@@ -24,9 +26,13 @@ namespace fi {
 
 constexpr int kMlaThreads = 256;
 constexpr int kMlaLdsRow = kMlaQK + 8;            // 16-bit elements per staged token (16 B pad against conflicts)
-constexpr int kMlaChunksPerToken = kMlaQK * 2 / 16;  // 72 16-byte chunks: 64 ckv + 8 kpe
-constexpr int kMlaLoadsPerThread = kMlaTileKV * kMlaChunksPerToken / kMlaThreads;  // 18
-static_assert(kMlaTileKV * kMlaChunksPerToken % kMlaThreads == 0, "loads must tile the threads");
+// 16-byte chunks of a cached token whose elements take `esz` bytes: 72 (64 ckv + 8 kpe) at 16 bit, 36 (32 + 4) as e4m3
+constexpr int mla_chunks_per_token(int esz) { return kMlaQK * esz / 16; }
+// 16-byte loads per thread and 64-token tile: 18 at 16 bit, 9 as e4m3
+constexpr int mla_loads_per_thread(int esz) { return kMlaTileKV * mla_chunks_per_token(esz) / kMlaThreads; }
+static_assert(kMlaTileKV * mla_chunks_per_token(2) % kMlaThreads == 0 &&
+                  kMlaTileKV * mla_chunks_per_token(1) % kMlaThreads == 0,
+              "loads must tile the threads");
 
 // the sizes a plan is cut for, the int workspace header and MlaItem: mla_plan.h
 
@@ -46,6 +52,7 @@ struct MlaParams {
   FastDiv page_div;
   int32_t page_size, num_heads, causal;
   float sm_scale_log2;  // sm_scale * log2(e)
+  const float* sm_scale_log2_dev;  // optional (an e4m3 cache only): read in place of sm_scale_log2, once per workgroup
 };
 
 template <int DT>
@@ -57,6 +64,10 @@ struct MlaType<FI_DTYPE_F16> {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
   }
   static __device__ __forceinline__ uint16_t from_f32(float x) { return f32_to_f16_bits(x); }
+  // two f32 that f16 holds exactly (every e4m3 value is one), as one word; a NaN stays a NaN
+  static __device__ __forceinline__ uint32_t pack_exact(float a, float b) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
+  }
 };
 template <>
 struct MlaType<FI_DTYPE_BF16> {
@@ -65,7 +76,26 @@ struct MlaType<FI_DTYPE_BF16> {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
   }
   static __device__ __forceinline__ uint16_t from_f32(float x) { return f32_to_bf16_bits(x); }
+  // two f32 that bf16 holds exactly (every e4m3 value has 3 mantissa bits): the high halves; the quiet NaN the
+  // fp8 convert gives (0x7fc00000) keeps its quiet bit
+  static __device__ __forceinline__ uint32_t pack_exact(float a, float b) {
+    return (__builtin_bit_cast(uint32_t, a) >> 16) | (__builtin_bit_cast(uint32_t, b) & 0xffff0000u);
+  }
 };
+
+// 8 e4m3 bytes -> 8 elements of the compute type, exactly: all 254 finite codes are f16 and bf16 values (largest 448,
+// smallest subnormal 2^-9), and the two NaN codes give NaN.  cvt_pk_f32_fp8 is the convert KVTraits<FP8_E4M3>::unpack uses.
+template <int DT>
+__device__ __forceinline__ void mla_upcast8(uint32_t lo, uint32_t hi, uint32_t* out) {
+  const uint32_t w[2] = {lo, hi};
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[h], false);
+    const f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[h], true);
+    out[2 * h] = MlaType<DT>::pack_exact(a[0], a[1]);
+    out[2 * h + 1] = MlaType<DT>::pack_exact(b[0], b[1]);
+  }
+}
 
 struct MlaSmem {
   uint16_t kv[kMlaTileKV][kMlaLdsRow];
@@ -74,10 +104,15 @@ struct MlaSmem {
   float red_sum[4][kMlaRows];
 };
 
-template <int DT>
+// DT: the compute and output type.  KV8 / Q8: the cache / the query holds e4m3 bytes, upcast to DT on the way into LDS /
+// into the Q fragments; from LDS onward all forms are one code.
+template <int DT, bool KV8 = false, bool Q8 = false>
 __global__ void __launch_bounds__(kMlaThreads) mla_paged_kernel(const MlaParams p) {
   using T = MlaType<DT>;
   using frag = typename T::frag;
+  constexpr int kQB = Q8 ? 1 : 2, kKB = KV8 ? 1 : 2;  // bytes per stored element
+  constexpr int kChunksPerToken = mla_chunks_per_token(kKB), kCkvChunks = kMlaCkv * kKB / 16;
+  constexpr int kLoadsPerThread = mla_loads_per_thread(kKB);
   __shared__ MlaSmem sm;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -88,6 +123,10 @@ __global__ void __launch_bounds__(kMlaThreads) mla_paged_kernel(const MlaParams 
   const int32_t* merge_indptr = p.int_ws + kMlaHeaderBytes / 4;
   const MlaItem* items = (const MlaItem*)((const char*)p.int_ws + p.int_ws[kMlaHdrItemsOff]);
   const int H = p.num_heads;
+  float sm_scale_log2 = p.sm_scale_log2;
+  if constexpr (KV8) {
+    if (p.sm_scale_log2_dev) sm_scale_log2 = *p.sm_scale_log2_dev;
+  }
 
   for (int w = blockIdx.x; w < num_work; w += gridDim.x) {
     const MlaItem it = items[w];
@@ -99,13 +138,21 @@ __global__ void __launch_bounds__(kMlaThreads) mla_paged_kernel(const MlaParams 
       const bool ok = r < rows;
       const int qi = ok ? r / H : 0, h = ok ? r % H : 0;
       const int64_t tok = it.qo_start + qi;
-      const char* qn = (const char*)p.q_nope + (tok * p.q_nope_stride_n + (int64_t)h * p.q_nope_stride_h) * 2;
-      const char* qp = (const char*)p.q_pe + (tok * p.q_pe_stride_n + (int64_t)h * p.q_pe_stride_h) * 2;
+      const char* qn = (const char*)p.q_nope + (tok * p.q_nope_stride_n + (int64_t)h * p.q_nope_stride_h) * kQB;
+      const char* qp = (const char*)p.q_pe + (tok * p.q_pe_stride_n + (int64_t)h * p.q_pe_stride_h) * kQB;
 #pragma unroll
       for (int s = 0; s < kMlaQK / 32; ++s) {
         const int k = 32 * s + 8 * lgrp;
         u32x4 v = {0, 0, 0, 0};
-        if (ok) v = k < kMlaCkv ? *(const u32x4*)(qn + k * 2) : *(const u32x4*)(qp + (k - kMlaCkv) * 2);
+        if constexpr (Q8) {  // 8 bytes per fragment, upcast once, before the kv walk (zero bytes are zeros)
+          u32x2 r = {0, 0};
+          if (ok) r = k < kMlaCkv ? *(const u32x2*)(qn + k) : *(const u32x2*)(qp + (k - kMlaCkv));
+          uint32_t u[4];
+          mla_upcast8<DT>(r[0], r[1], u);
+          v = u32x4{u[0], u[1], u[2], u[3]};
+        } else {
+          if (ok) v = k < kMlaCkv ? *(const u32x4*)(qn + k * 2) : *(const u32x4*)(qp + (k - kMlaCkv) * 2);
+        }
         qf[s] = __builtin_bit_cast(frag, v);
       }
     }
@@ -127,23 +174,24 @@ __global__ void __launch_bounds__(kMlaThreads) mla_paged_kernel(const MlaParams 
     for (int b = 0; b < 8; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // ---- global -> registers for the tile starting at t0 (tokens past kv_end are zeros, never read) ----
-    u32x4 pre[kMlaLoadsPerThread];
+    // (an e4m3 cache: the registers hold the raw bytes, 16 elements each, and half as many of them)
+    u32x4 pre[kLoadsPerThread];
     auto load_tile = [&](int t0) {
 #pragma unroll
-      for (int i = 0; i < kMlaLoadsPerThread; ++i) {
+      for (int i = 0; i < kLoadsPerThread; ++i) {
         const int c = tid + kMlaThreads * i;
-        const int tk = c / kMlaChunksPerToken, ch = c % kMlaChunksPerToken;
+        const int tk = c / kChunksPerToken, ch = c % kChunksPerToken;
         const int t = t0 + tk;
         u32x4 v = {0, 0, 0, 0};
         if (t < it.kv_end) {
           const int pi = (int)fast_div((uint32_t)t, p.page_div);
           const int entry = t - pi * p.page_size;
           const int64_t page = p.kv_indices[it.page_base + pi];
-          if (ch < kMlaCkv / 8)
-            v = *(const u32x4*)((const char*)p.ckv + (page * p.ckv_stride_page + entry * p.ckv_stride_n) * 2 + ch * 16);
+          if (ch < kCkvChunks)
+            v = *(const u32x4*)((const char*)p.ckv + (page * p.ckv_stride_page + entry * p.ckv_stride_n) * kKB + ch * 16);
           else
-            v = *(const u32x4*)((const char*)p.kpe + (page * p.kpe_stride_page + entry * p.kpe_stride_n) * 2 +
-                                (ch - kMlaCkv / 8) * 16);
+            v = *(const u32x4*)((const char*)p.kpe + (page * p.kpe_stride_page + entry * p.kpe_stride_n) * kKB +
+                                (ch - kCkvChunks) * 16);
         }
         pre[i] = v;
       }
@@ -152,9 +200,19 @@ __global__ void __launch_bounds__(kMlaThreads) mla_paged_kernel(const MlaParams 
     for (int t0 = it.kv_start; t0 < it.kv_end; t0 += kMlaTileKV) {
       __syncthreads();  // the previous tile's LDS reads are done
 #pragma unroll
-      for (int i = 0; i < kMlaLoadsPerThread; ++i) {
+      for (int i = 0; i < kLoadsPerThread; ++i) {
         const int c = tid + kMlaThreads * i;
-        *(u32x4*)&sm.kv[c / kMlaChunksPerToken][(c % kMlaChunksPerToken) * 8] = pre[i];
+        if constexpr (KV8) {
+          // chunk ch holds elements 16 ch .. 16 ch + 15 of the token: the columns of the 16-bit chunks 2 ch, 2 ch + 1
+          uint32_t u[8];
+          mla_upcast8<DT>(pre[i][0], pre[i][1], u);
+          mla_upcast8<DT>(pre[i][2], pre[i][3], u + 4);
+          uint16_t* dst = &sm.kv[c / kChunksPerToken][(c % kChunksPerToken) * 16];
+          *(u32x4*)dst = u32x4{u[0], u[1], u[2], u[3]};
+          *(u32x4*)(dst + 8) = u32x4{u[4], u[5], u[6], u[7]};
+        } else {
+          *(u32x4*)&sm.kv[c / kChunksPerToken][(c % kChunksPerToken) * 8] = pre[i];
+        }
       }
       __syncthreads();
       if (t0 + kMlaTileKV < it.kv_end) load_tile(t0 + kMlaTileKV);
@@ -172,7 +230,7 @@ __global__ void __launch_bounds__(kMlaThreads) mla_paged_kernel(const MlaParams 
       float sv[4], mx[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        sv[i] = (t < it.kv_end && t <= kv_last[i]) ? s4[i] * p.sm_scale_log2 : -INFINITY;
+        sv[i] = (t < it.kv_end && t <= kv_last[i]) ? s4[i] * sm_scale_log2 : -INFINITY;
         float x = sv[i];
         x = fmaxf(x, lane_xor<1>(x));
         x = fmaxf(x, lane_xor<2>(x));
@@ -402,10 +460,26 @@ extern "C" FI_API int fi_batch_mla_run(const int64_t* plan_info, int32_t plan_in
   const int64_t max_entries = mla_max_entries(a->float_ws_bytes);
   FI_REQUIRE(plan_info[FI_MLA_NUM_ENTRIES] <= max_entries && plan_info[FI_MLA_V_OFFSET] == mla_v_offset(a->float_ws_bytes),
              "batch_mla_run: float workspace differs from the plan's");
+  // storage types: 0 = the tensors hold `dtype`; an e4m3 cache with either query, an e4m3 query with an e4m3 cache
+  for (int32_t st : {a->q_fp8, a->kv_fp8}) {
+    FI_REQUIRE(st != FI_DTYPE_FP8_E5M2, "batch_mla_run: an e5m2 query or cache is not supported (fp8 is e4m3)");
+    FI_REQUIRE(st == 0 || st == FI_DTYPE_FP8_E4M3, "batch_mla_run: q_fp8 / kv_fp8 must be 0 or FI_DTYPE_FP8_E4M3, got %d", st);
+  }
+  const bool q8 = a->q_fp8 != 0, kv8 = a->kv_fp8 != 0;
+  FI_REQUIRE(!(q8 && !kv8), "batch_mla_run: an fp8 query with a 16-bit cache is not supported (an fp8 query needs an "
+                            "fp8 cache)");
+  FI_REQUIRE(!q8 || a->dtype == FI_DTYPE_BF16, "batch_mla_run: an fp8 query computes and writes bf16 (dtype %d given)",
+             a->dtype);
+  FI_REQUIRE(!a->sm_scale_log2_dev || kv8, "batch_mla_run: sm_scale_log2_dev is read with an fp8 cache only");
   // 16-byte vector loads: last dims contiguous (checked by the caller), rows 16-byte aligned
-  const int64_t strides[] = {a->q_nope_stride_n, a->q_nope_stride_h, a->q_pe_stride_n, a->q_pe_stride_h,
-                             a->ckv_stride_page, a->ckv_stride_n, a->kpe_stride_page, a->kpe_stride_n};
-  for (int64_t s : strides) FI_REQUIRE(s % 8 == 0, "batch_mla_run: strides must be multiples of 8 elements");
+  const int64_t q_strides[] = {a->q_nope_stride_n, a->q_nope_stride_h, a->q_pe_stride_n, a->q_pe_stride_h};
+  const int64_t kv_strides[] = {a->ckv_stride_page, a->ckv_stride_n, a->kpe_stride_page, a->kpe_stride_n};
+  for (int64_t s : q_strides)
+    FI_REQUIRE(s % (q8 ? 16 : 8) == 0, q8 ? "batch_mla_run: strides of an fp8 query must be multiples of 16 elements"
+                                          : "batch_mla_run: strides must be multiples of 8 elements");
+  for (int64_t s : kv_strides)
+    FI_REQUIRE(s % (kv8 ? 16 : 8) == 0, kv8 ? "batch_mla_run: strides of an fp8 cache must be multiples of 16 elements"
+                                            : "batch_mla_run: strides must be multiples of 8 elements");
   FI_REQUIRE(((uintptr_t)a->q_nope | (uintptr_t)a->q_pe | (uintptr_t)a->ckv | (uintptr_t)a->kpe) % 16 == 0,
              "batch_mla_run: tensors must be 16-byte aligned");
   if (a->num_rows == 0) return 0;
@@ -433,9 +507,16 @@ extern "C" FI_API int fi_batch_mla_run(const int64_t* plan_info, int32_t plan_in
   p.num_heads = a->num_heads;
   p.causal = a->causal ? 1 : 0;
   p.sm_scale_log2 = a->sm_scale * kLog2e;
+  p.sm_scale_log2_dev = a->sm_scale_log2_dev;
   const int grid = (int)plan_info[FI_MLA_GRID];
   hipStream_t st = (hipStream_t)stream;
-  if (a->dtype == FI_DTYPE_BF16)
+  if (q8)
+    mla_paged_kernel<FI_DTYPE_BF16, true, true><<<dim3(grid), dim3(kMlaThreads), 0, st>>>(p);
+  else if (kv8 && a->dtype == FI_DTYPE_BF16)
+    mla_paged_kernel<FI_DTYPE_BF16, true><<<dim3(grid), dim3(kMlaThreads), 0, st>>>(p);
+  else if (kv8)
+    mla_paged_kernel<FI_DTYPE_F16, true><<<dim3(grid), dim3(kMlaThreads), 0, st>>>(p);
+  else if (a->dtype == FI_DTYPE_BF16)
     mla_paged_kernel<FI_DTYPE_BF16><<<dim3(grid), dim3(kMlaThreads), 0, st>>>(p);
   else
     mla_paged_kernel<FI_DTYPE_F16><<<dim3(grid), dim3(kMlaThreads), 0, st>>>(p);

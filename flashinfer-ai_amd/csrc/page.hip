@@ -146,25 +146,27 @@ struct AppendMlaParams {
 };
 
 // MLA append (ref: AppendPagedKVMlaCacheKernel semantics, flashinfer/page.py:250-298): one 16-byte chunk per
-// thread, 72 chunks per token (64 of the 512-wide ckv row, 8 of the 64-wide kpe row), 16-bit elements.
-constexpr int kMlaAppendChunks = (512 + 64) * 2 / 16;
+// thread; a token is 72 chunks of 16-bit elements (64 of the 512-wide ckv row, 8 of the 64-wide kpe row) or 36 chunks
+// of fp8 bytes (32 + 4).  ESZ is the element size; strides are in elements.
+template <int ESZ>
 __global__ void __launch_bounds__(kPageThreads) append_paged_mla_kv_cache_kernel(const AppendMlaParams p) {
-  const int64_t total = (int64_t)p.nnz * kMlaAppendChunks;
+  constexpr int kCkvChunks = 512 * ESZ / 16, kChunks = (512 + 64) * ESZ / 16;
+  const int64_t total = (int64_t)p.nnz * kChunks;
   for (int64_t it = (int64_t)blockIdx.x * kPageThreads + threadIdx.x; it < total;
        it += (int64_t)gridDim.x * kPageThreads) {
-    const int c = (int)(it % kMlaAppendChunks);
-    const int i = (int)(it / kMlaAppendChunks);
+    const int c = (int)(it % kChunks);
+    const int i = (int)(it / kChunks);
     const int b = p.batch_indices[i];
     const int pos = p.positions[i];
     const int pi = (int)fast_div((uint32_t)pos, p.page_div);
     const int entry = pos - pi * p.page_size;
     const int64_t page = p.kv_indices[p.kv_indptr[b] + pi];
-    if (c < 64) {
-      *(u32x4*)(p.ckv_cache + (page * p.ckv_stride_page + entry * p.ckv_cache_stride_n) * 2 + c * 16) =
-          *(const u32x4*)(p.ckv + (int64_t)i * p.ckv_stride_n * 2 + c * 16);
+    if (c < kCkvChunks) {
+      *(u32x4*)(p.ckv_cache + (page * p.ckv_stride_page + entry * p.ckv_cache_stride_n) * ESZ + c * 16) =
+          *(const u32x4*)(p.ckv + (int64_t)i * p.ckv_stride_n * ESZ + c * 16);
     } else {
-      *(u32x4*)(p.kpe_cache + (page * p.kpe_stride_page + entry * p.kpe_cache_stride_n) * 2 + (c - 64) * 16) =
-          *(const u32x4*)(p.kpe + (int64_t)i * p.kpe_stride_n * 2 + (c - 64) * 16);
+      *(u32x4*)(p.kpe_cache + (page * p.kpe_stride_page + entry * p.kpe_cache_stride_n) * ESZ + (c - kCkvChunks) * 16) =
+          *(const u32x4*)(p.kpe + (int64_t)i * p.kpe_stride_n * ESZ + (c - kCkvChunks) * 16);
     }
   }
 }
@@ -177,15 +179,18 @@ extern "C" FI_API int fi_append_paged_mla_kv_cache(const fi_append_paged_mla_kv_
   FI_REQUIRE(a->head_dim_ckv == 512 && a->head_dim_kpe == 64,
              "append_paged_mla_kv_cache: unsupported head dims %d / %d (only 512 / 64)", a->head_dim_ckv,
              a->head_dim_kpe);
-  FI_REQUIRE(a->dtype == FI_DTYPE_F16 || a->dtype == FI_DTYPE_BF16,
-             "append_paged_mla_kv_cache: unsupported dtype %d (f16 / bf16)", a->dtype);
+  const int esz = (int)dtype_size(a->dtype);
+  FI_REQUIRE(esz == 1 || esz == 2, "append_paged_mla_kv_cache: unsupported dtype %d (f16 / bf16 / fp8 e4m3 / fp8 e5m2)",
+             a->dtype);
   FI_REQUIRE(a->append_ckv && a->append_kpe && a->batch_indices && a->positions && a->ckv_cache && a->kpe_cache &&
                  a->kv_indices && a->kv_indptr,
              "append_paged_mla_kv_cache: null tensor");
   FI_REQUIRE(a->nnz > 0 && a->page_size > 0, "append_paged_mla_kv_cache: bad nnz / page size");
   const int64_t strides[] = {a->append_ckv_stride_n, a->append_kpe_stride_n, a->ckv_stride_page, a->ckv_stride_n,
                              a->kpe_stride_page, a->kpe_stride_n};
-  for (int64_t s : strides) FI_REQUIRE(s % 8 == 0, "append_paged_mla_kv_cache: rows must be 16-byte aligned");
+  for (int64_t s : strides)
+    FI_REQUIRE(s * esz % 16 == 0, "append_paged_mla_kv_cache: rows must be 16-byte aligned (strides multiples of %d elements)",
+               16 / esz);
   FI_REQUIRE(((uintptr_t)a->append_ckv | (uintptr_t)a->append_kpe | (uintptr_t)a->ckv_cache |
               (uintptr_t)a->kpe_cache) % 16 == 0,
              "append_paged_mla_kv_cache: rows must be 16-byte aligned");
@@ -207,9 +212,12 @@ extern "C" FI_API int fi_append_paged_mla_kv_cache(const fi_append_paged_mla_kv_
   p.page_div = FastDiv((uint32_t)a->page_size);
   p.page_size = a->page_size;
   p.nnz = a->nnz;
-  const int64_t total = (int64_t)a->nnz * kMlaAppendChunks;
+  const int64_t total = (int64_t)a->nnz * ((512 + 64) * esz / 16);
   const int grid = (int)std::min<int64_t>((total + kPageThreads - 1) / kPageThreads, 256 * 8);
-  append_paged_mla_kv_cache_kernel<<<dim3(grid), dim3(kPageThreads), 0, (hipStream_t)stream>>>(p);
+  if (esz == 2)
+    append_paged_mla_kv_cache_kernel<2><<<dim3(grid), dim3(kPageThreads), 0, (hipStream_t)stream>>>(p);
+  else
+    append_paged_mla_kv_cache_kernel<1><<<dim3(grid), dim3(kPageThreads), 0, (hipStream_t)stream>>>(p);
   FI_HIP_CALL(hipGetLastError());
   return 0;
 }

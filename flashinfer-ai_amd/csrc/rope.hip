@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "fp8_block_quant.h"  // fp8_pack4_saturating
 
 namespace fi {
 
@@ -180,6 +181,85 @@ __global__ void __launch_bounds__(kRopeThreads) rope_kernel(const RopeParams p) 
   }
 }
 
+// ---- MLA: rotate the rope parts, quantise rope and nope parts to fp8 (ref: MLARopeQuantizeKernel semantics,
+// include/flashinfer/pos_enc.cuh:345-460) ----
+// A token has num_heads q rows and one k row, each 512 nope + 64 rope elements.  One thread takes one unit of a row:
+// unit u < 64 is nope chunk u (8 elements: one 16-byte load, scale, convert, one 8-byte store); unit 64 + t is rope
+// chunk pair t, the two chunks that hold each other's rotation partners, as in rope_kernel above with rotary_dim 64.
+struct MlaRopeQuantParams {
+  const uint16_t* in[4];   // q_rope, k_rope, q_nope, k_nope
+  uint8_t* out[4];
+  int64_t in_stride_n[4], in_stride_h[4], out_stride_n[4], out_stride_h[4];  // elements; the k rows' head strides are unused
+  const float* cos_sin_cache;  // [max_pos, 64]: cos | sin
+  const void* pos_ids;
+  int32_t nnz, num_heads, pos_ids_int64, interleave;
+  float scale_q, scale_kv;
+};
+constexpr int kMlaRopeDim = 64, kMlaNopeDim = 512;
+constexpr int kMlaQuantUnits = kMlaNopeDim / 8 + kMlaRopeDim / 16;  // 64 nope chunks + 4 rope chunk pairs per row
+
+template <int ODT>
+__device__ __forceinline__ u32x2 mla_quant8(const float* y, float scale) {
+  return u32x2{fp8_pack4_saturating<ODT>(y[0] * scale, y[1] * scale, y[2] * scale, y[3] * scale),
+               fp8_pack4_saturating<ODT>(y[4] * scale, y[5] * scale, y[6] * scale, y[7] * scale)};
+}
+
+template <int DT, int ODT>
+__global__ void __launch_bounds__(kRopeThreads) mla_rope_quantize_kernel(const MlaRopeQuantParams p) {
+  const int rows = p.num_heads + 1;  // q heads, then the k row
+  const int64_t total = (int64_t)p.nnz * rows * kMlaQuantUnits;
+  for (int64_t it = (int64_t)blockIdx.x * kRopeThreads + threadIdx.x; it < total;
+       it += (int64_t)gridDim.x * kRopeThreads) {
+    const int u = (int)(it % kMlaQuantUnits);
+    const int64_t r_ = it / kMlaQuantUnits;
+    const int row = (int)(r_ % rows);
+    const int64_t tok = r_ / rows;
+    const bool is_q = row < p.num_heads;
+    const float scale = is_q ? p.scale_q : p.scale_kv;
+    const int h = row;
+    if (u < kMlaNopeDim / 8) {
+      // (constant indices into the kernel arguments: a runtime index would copy them to scratch)
+      const uint16_t* src = (is_q ? p.in[2] + tok * p.in_stride_n[2] + h * p.in_stride_h[2]
+                                  : p.in[3] + tok * p.in_stride_n[3]) + 8 * u;
+      uint8_t* dst = (is_q ? p.out[2] + tok * p.out_stride_n[2] + h * p.out_stride_h[2]
+                           : p.out[3] + tok * p.out_stride_n[3]) + 8 * u;
+      float x[8];
+      KVTraits<DT>::unpack(*(const u32x4*)src, x);
+      *(u32x2*)dst = mla_quant8<ODT>(x, scale);
+      continue;
+    }
+    const int t = u - kMlaNopeDim / 8;
+    const int ca = p.interleave ? 2 * t : t;
+    const int cb = p.interleave ? 2 * t + 1 : t + kMlaRopeDim / 16;
+    const int64_t pos = p.pos_ids_int64 ? ((const int64_t*)p.pos_ids)[tok] : (int64_t)((const int32_t*)p.pos_ids)[tok];
+    const float* cs = p.cos_sin_cache + pos * kMlaRopeDim + 8 * t;  // pairs 8 t .. 8 t + 7
+    const float* sn = cs + kMlaRopeDim / 2;
+    const uint16_t* src = is_q ? p.in[0] + tok * p.in_stride_n[0] + h * p.in_stride_h[0] : p.in[1] + tok * p.in_stride_n[1];
+    uint8_t* dst = is_q ? p.out[0] + tok * p.out_stride_n[0] + h * p.out_stride_h[0] : p.out[1] + tok * p.out_stride_n[1];
+    float xa[8], xb[8], ya[8], yb[8];
+    KVTraits<DT>::unpack(*(const u32x4*)(src + 8 * ca), xa);
+    KVTraits<DT>::unpack(*(const u32x4*)(src + 8 * cb), xb);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      // interleaved: pair 8 t + j is elements 2 j, 2 j + 1 of the 16-element span (chunk a, then chunk b);
+      // otherwise element j of chunk a and element j of chunk b
+      const float x0 = p.interleave ? (j < 4 ? xa[2 * j] : xb[2 * j - 8]) : xa[j];
+      const float x1 = p.interleave ? (j < 4 ? xa[2 * j + 1] : xb[2 * j - 7]) : xb[j];
+      const float y0 = x0 * cs[j] - x1 * sn[j];  // ref: pos_enc.cuh:93-96, 143-145
+      const float y1 = x1 * cs[j] + x0 * sn[j];
+      if (p.interleave) {
+        if (j < 4) { ya[2 * j] = y0; ya[2 * j + 1] = y1; }
+        else { yb[2 * j - 8] = y0; yb[2 * j - 7] = y1; }
+      } else {
+        ya[j] = y0;
+        yb[j] = y1;
+      }
+    }
+    *(u32x2*)(dst + 8 * ca) = mla_quant8<ODT>(ya, scale);
+    *(u32x2*)(dst + 8 * cb) = mla_quant8<ODT>(yb, scale);
+  }
+}
+
 __global__ void rope_positions_kernel(const int32_t* __restrict__ indptr, const int32_t* __restrict__ offsets,
                                       int32_t* pos, int nnz) {
   const int b = blockIdx.x;
@@ -278,4 +358,63 @@ extern "C" FI_API int fi_apply_rope_append_paged_kv_cache(const fi_rope_params_t
   p.page_div = FastDiv((uint32_t)kv->page_size);
   p.page_size = kv->page_size;
   return rope_fill_and_launch(who, a, p, stream);
+}
+
+extern "C" FI_API int fi_mla_rope_quantize(const fi_mla_rope_quantize_params_t* a, fi_stream_t stream) {
+  const char* who = "mla_rope_quantize";
+  FI_REQUIRE(a, "%s: null params", who);
+  if (a->nnz == 0) return 0;
+  FI_REQUIRE(a->q_rope && a->k_rope && a->q_nope && a->k_nope && a->q_rope_out && a->k_rope_out && a->q_nope_out &&
+                 a->k_nope_out && a->cos_sin_cache && a->pos_ids,
+             "%s: null tensor", who);
+  FI_REQUIRE(a->nnz > 0 && a->num_heads > 0, "%s: bad nnz / num_heads", who);
+  FI_REQUIRE(a->rope_dim == kMlaRopeDim && a->nope_dim == kMlaNopeDim,
+             "%s: unsupported dims rope %d / nope %d (only 64 / 512)", who, a->rope_dim, a->nope_dim);
+  FI_REQUIRE(a->dtype == FI_DTYPE_F16 || a->dtype == FI_DTYPE_BF16, "%s: inputs must be f16 / bf16 (dtype %d)", who,
+             a->dtype);
+  FI_REQUIRE(a->out_dtype == FI_DTYPE_FP8_E4M3 || a->out_dtype == FI_DTYPE_FP8_E5M2,
+             "%s: outputs must be fp8 e4m3 / e5m2 (out_dtype %d)", who, a->out_dtype);
+  MlaRopeQuantParams p;
+  const void* in[4] = {a->q_rope, a->k_rope, a->q_nope, a->k_nope};
+  void* out[4] = {a->q_rope_out, a->k_rope_out, a->q_nope_out, a->k_nope_out};
+  const int64_t in_n[4] = {a->q_rope_stride_n, a->k_rope_stride_n, a->q_nope_stride_n, a->k_nope_stride_n};
+  const int64_t in_h[4] = {a->q_rope_stride_h, 0, a->q_nope_stride_h, 0};
+  const int64_t out_n[4] = {a->q_rope_out_stride_n, a->k_rope_out_stride_n, a->q_nope_out_stride_n,
+                            a->k_nope_out_stride_n};
+  const int64_t out_h[4] = {a->q_rope_out_stride_h, 0, a->q_nope_out_stride_h, 0};
+  for (int i = 0; i < 4; ++i) {
+    // 16-byte loads of 8 16-bit elements, 8-byte stores of 8 fp8 bytes
+    FI_REQUIRE(in_n[i] % 8 == 0 && in_h[i] % 8 == 0 && (uintptr_t)in[i] % 16 == 0,
+               "%s: input rows must be 16-byte aligned (strides multiples of 8 elements)", who);
+    FI_REQUIRE(out_n[i] % 8 == 0 && out_h[i] % 8 == 0 && (uintptr_t)out[i] % 8 == 0,
+               "%s: output rows must be 8-byte aligned (strides multiples of 8 elements)", who);
+    p.in[i] = (const uint16_t*)in[i];
+    p.out[i] = (uint8_t*)out[i];
+    p.in_stride_n[i] = in_n[i];
+    p.in_stride_h[i] = in_h[i];
+    p.out_stride_n[i] = out_n[i];
+    p.out_stride_h[i] = out_h[i];
+  }
+  p.cos_sin_cache = a->cos_sin_cache;
+  p.pos_ids = a->pos_ids;
+  p.nnz = a->nnz;
+  p.num_heads = a->num_heads;
+  p.pos_ids_int64 = a->pos_ids_int64 ? 1 : 0;
+  p.interleave = a->interleave ? 1 : 0;
+  p.scale_q = a->quant_scale_q;
+  p.scale_kv = a->quant_scale_kv;
+  const int64_t total = (int64_t)a->nnz * (a->num_heads + 1) * kMlaQuantUnits;
+  const dim3 grid((unsigned)std::min<int64_t>((total + kRopeThreads - 1) / kRopeThreads, 256 * 16)), block(kRopeThreads);
+  hipStream_t st = (hipStream_t)stream;
+  const bool bf = a->dtype == FI_DTYPE_BF16, e4 = a->out_dtype == FI_DTYPE_FP8_E4M3;
+  if (bf && e4)
+    mla_rope_quantize_kernel<FI_DTYPE_BF16, FI_DTYPE_FP8_E4M3><<<grid, block, 0, st>>>(p);
+  else if (bf)
+    mla_rope_quantize_kernel<FI_DTYPE_BF16, FI_DTYPE_FP8_E5M2><<<grid, block, 0, st>>>(p);
+  else if (e4)
+    mla_rope_quantize_kernel<FI_DTYPE_F16, FI_DTYPE_FP8_E4M3><<<grid, block, 0, st>>>(p);
+  else
+    mla_rope_quantize_kernel<FI_DTYPE_F16, FI_DTYPE_FP8_E5M2><<<grid, block, 0, st>>>(p);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
 }

@@ -1,6 +1,6 @@
 """flashinfer -- MI355X (gfx950) native implementation of FlashInfer's paged-KV attention hot path.
 
-Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / sparse / gemm / fused_moe / fused_moe_fp8 / fp8_quantization / fp4_quantization / sampling / norm / activation`` operator API
+Drop-in for the ``flashinfer.decode / prefill / attention (sinks) / cascade / page / sparse / gemm / fused_moe / fused_moe_fp8 / fp8_quantization / fp4_quantization / sampling / norm / activation / rope / mla`` operator API
 of FlashInfer v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-written HIP kernels behind the C ABI of
 ``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided; of the fp4 matmuls that is
 ``mm_fp4`` in its MXFP4 mode (``use_nvfp4=False, block_size=32``), not nvfp4.

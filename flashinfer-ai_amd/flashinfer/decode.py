@@ -629,8 +629,9 @@ def _mla_query_rows(query: torch.Tensor) -> int:
                          f"stride(0) = {query.stride(0)} is not q_len_per_request x stride(1) = "
                          f"{q_len} x {query.stride(1)}")
     stride_n = query.stride(1) if q_len > 1 else query.stride(0)
-    if stride_n % 8 or query.stride(2) % 8 or query.data_ptr() % 16:
-        raise ValueError("query: strides must be multiples of 8 elements and the base 16-byte aligned")
+    per16 = 16 // query.element_size()  # elements in 16 bytes: 8 at 16 bit, 16 for fp8
+    if stride_n % per16 or query.stride(2) % per16 or query.data_ptr() % 16:
+        raise ValueError(f"query: strides must be multiples of {per16} elements and the base 16-byte aligned")
     return stride_n
 
 
@@ -659,13 +660,16 @@ def trtllm_batch_decode_with_kv_cache_mla(
     allocation that depends on a length, so the whole call can be captured in a graph; a replay plans again from what
     ``block_tables`` and ``seq_lens`` hold then.
 
-    query : ``[batch_size, q_len_per_request, num_heads, 576]`` (``q_nope | q_pe``), float16 or bfloat16, contiguous in
-        the last dimension and flattenable to ``[batch_size * q_len_per_request, num_heads, 576]`` without a copy;
-        strides multiples of 8 elements, the base 16-byte aligned.  ``q_len_per_request > 1`` (MTP, speculative
+    query : ``[batch_size, q_len_per_request, num_heads, 576]`` (``q_nope | q_pe``), float16, bfloat16 or float8_e4m3fn,
+        contiguous in the last dimension and flattenable to ``[batch_size * q_len_per_request, num_heads, 576]`` without
+        a copy; strides multiples of 8 elements (16 for fp8), the base 16-byte aligned.  ``q_len_per_request > 1`` (MTP, speculative
         verify) is causal within the request: row ``i`` sees keys ``<= seq_len - q_len_per_request + i``, and a row
         that sees no key gives zeros.
     kv_cache : ``[num_pages, 1, page_size, 576]`` or ``[num_pages, page_size, 576]`` (``ckv | kpe``), of the query's
-        dtype.  Any page size is taken: the reference's 32 / 64 restriction and its ``block_num % (128 / block_size)``
+        dtype; strides multiples of 8 elements (16 for fp8).  Query and cache are both 16-bit or both float8_e4m3fn, as
+        :func:`flashinfer.rope.mla_rope_quantize_fp8` and an fp8 :func:`flashinfer.page.append_paged_mla_kv_cache`
+        leave them; the fp8 bytes are upcast exactly to bfloat16 while they are staged, and the kernel from there on is
+        the bfloat16 one.  Any page size is taken: the reference's 32 / 64 restriction and its ``block_num % (128 / block_size)``
         rule are tile constraints of its kernels and are not enforced here.
     workspace_buffer : one buffer on the query's device; the work list and the f32 partial states are carved out of
         it.  It need not be zeroed.  ValueError names the bytes needed when it is too small; whatever it holds beyond
@@ -677,20 +681,36 @@ def trtllm_batch_decode_with_kv_cache_mla(
         to it (the host never sees the value, so it cannot be refused); a length of 0 gives zero output rows.
     max_seq_len : checked against ``max_blocks * page_size``; otherwise unused.
     out : optional ``[batch_size, q_len_per_request, num_heads, 512]``, or ``[batch_size, num_heads, 512]`` when
-        ``q_len_per_request == 1``, contiguous, of the query's dtype; allocated in the first form when not given.
-    bmm1_scale : the full scale of the logits.  bmm2_scale : multiplies the output.
+        ``q_len_per_request == 1``, contiguous, of the query's dtype (bfloat16 for an fp8 query, as the reference
+        allocates); allocated in the first form when not given.
+    bmm1_scale : the full scale of the logits; with fp8 tensors the caller folds ``q_scale * k_scale`` into it (as the
+        reference: ``q_scale * k_scale * sm_scale``).  bmm2_scale : multiplies the output (``v_scale * o_scale``).
+    bmm1_scale_log2_tensor, bmm2_scale_tensor : with an fp8 query and cache only, and only both together: float32
+        tensors of one element on the query's device, which take precedence over the floats, as in the reference.  The
+        first is the logit scale times log2(e), read by the kernel; the second multiplies the output on the device.
+        Neither is read on the host, so a captured call follows them when they change in place.
     enable_pdl : accepted and ignored.
 
-    Not offered (NotImplementedError): an fp8 query or cache, ``bmm1_scale_log2_tensor`` / ``bmm2_scale_tensor``, and
-    ``sinks``.
+    Not offered (NotImplementedError): an fp8 query with a 16-bit cache or a 16-bit query with an fp8 cache, float8_e5m2,
+    ``bmm1_scale_log2_tensor`` / ``bmm2_scale_tensor`` with a 16-bit query or one without the other, and ``sinks``.
     """
     name = "trtllm_batch_decode_with_kv_cache_mla"
     fp8 = (torch.float8_e4m3fn, torch.float8_e5m2)
-    if query.dtype in fp8 or kv_cache.dtype in fp8:
-        raise NotImplementedError(f"{name}: an fp8 query or kv_cache is not supported (float16 / bfloat16)")
-    if bmm1_scale_log2_tensor is not None or bmm2_scale_tensor is not None:
-        raise NotImplementedError(f"{name}: bmm1_scale_log2_tensor / bmm2_scale_tensor are not supported "
-                                  "(pass bmm1_scale / bmm2_scale as floats)")
+    if torch.float8_e5m2 in (query.dtype, kv_cache.dtype):
+        raise NotImplementedError(f"{name}: a float8_e5m2 (e5m2) fp8 query or kv_cache is not supported (fp8 is "
+                                  "float8_e4m3fn)")
+    if (query.dtype in fp8) != (kv_cache.dtype in fp8):
+        raise NotImplementedError(f"{name}: an fp8 query or kv_cache needs the other to be fp8 too; a mixed pair "
+                                  f"({query.dtype} query, {kv_cache.dtype} kv_cache) is not supported")
+    is_fp8 = query.dtype in fp8
+    given = [n for n, t in (("bmm1_scale_log2_tensor", bmm1_scale_log2_tensor),
+                            ("bmm2_scale_tensor", bmm2_scale_tensor)) if t is not None]
+    if given and not is_fp8:
+        raise NotImplementedError(f"{name}: {' / '.join(given)} with a 16-bit query is not supported (pass bmm1_scale "
+                                  "/ bmm2_scale as floats)")
+    if len(given) == 1:
+        raise NotImplementedError(f"{name}: {given[0]} alone is not supported: give bmm1_scale_log2_tensor and "
+                                  "bmm2_scale_tensor together")
     if sinks is not None:
         raise NotImplementedError(f"{name}: sinks are not supported")
     if (qk_nope_head_dim, kv_lora_rank, qk_rope_head_dim) != (128, 512, 64):
@@ -700,9 +720,14 @@ def trtllm_batch_decode_with_kv_cache_mla(
                     ("block_tables", block_tables), ("seq_lens", seq_lens)):
         _lib.require_gpu_tensor(t, what)
     head_dim = kv_lora_rank + qk_rope_head_dim
-    if query.dtype not in (torch.float16, torch.bfloat16) or query.dim() != 4 or query.shape[-1] != head_dim:
-        raise ValueError(f"query must be a float16 / bfloat16 [batch_size, q_len_per_request, num_heads, {head_dim}] "
-                         "tensor")
+    if query.dtype not in (torch.float16, torch.bfloat16, torch.float8_e4m3fn) or query.dim() != 4 \
+            or query.shape[-1] != head_dim:
+        raise ValueError(f"query must be a float16 / bfloat16 / float8_e4m3fn [batch_size, q_len_per_request, "
+                         f"num_heads, {head_dim}] tensor")
+    for what, t in (("bmm1_scale_log2_tensor", bmm1_scale_log2_tensor), ("bmm2_scale_tensor", bmm2_scale_tensor)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != 1
+                              or t.device != query.device):
+            raise ValueError(f"{what} must be a float32 tensor of one element on the query's device")
     batch_size, q_len, num_heads, _ = query.shape
     if q_len == 0 or num_heads == 0:
         raise ValueError("query must hold at least one token per request and one head")
@@ -713,8 +738,9 @@ def trtllm_batch_decode_with_kv_cache_mla(
             or kv_cache.stride(-1) != 1:
         raise ValueError(f"kv_cache must be [num_pages, 1, page_size, {head_dim}] or [num_pages, page_size, {head_dim}]"
                          f", of the query's dtype {query.dtype} and contiguous in the last dimension")
-    if kv_cache.stride(0) % 8 or kv_cache.stride(1) % 8 or kv_cache.data_ptr() % 16:
-        raise ValueError("kv_cache: strides must be multiples of 8 elements and the base 16-byte aligned")
+    per16 = 16 // kv_cache.element_size()
+    if kv_cache.stride(0) % per16 or kv_cache.stride(1) % per16 or kv_cache.data_ptr() % 16:
+        raise ValueError(f"kv_cache: strides must be multiples of {per16} elements and the base 16-byte aligned")
     page_size = kv_cache.shape[1]
     seq_lens = _check_block_tables_and_lens(block_tables, seq_lens, workspace_buffer, batch_size)
     max_blocks = block_tables.shape[1]
@@ -724,11 +750,15 @@ def trtllm_batch_decode_with_kv_cache_mla(
     out_shape = (batch_size, q_len, num_heads, kv_lora_rank)
     if out is not None and q_len == 1 and out.dim() == 3:
         out_shape = (batch_size, num_heads, kv_lora_rank)
-    out = _out_or_empty(out, out_shape, query.dtype, query.device)
+    # an fp8 query computes in bf16 and writes bf16, as the reference allocates
+    compute_dtype = torch.bfloat16 if is_fp8 else query.dtype
+    out = _out_or_empty(out, out_shape, compute_dtype, query.device)
     if batch_size == 0:
         return out
 
-    dtype = _lib.fi_dtype(query.dtype)
+    # a plan is cut from lengths alone: the planner is given the compute dtype, run() the storage types
+    dtype = _lib.fi_dtype(compute_dtype)
+    storage = _lib.FI_DTYPE_FP8_E4M3 if is_fp8 else 0
     plan = _lib.fi_batch_mla_plan_device_params_t(
         block_tables=block_tables.data_ptr(), seq_lens=seq_lens.data_ptr(), block_tables_stride=block_tables.stride(0),
         batch_size=batch_size, max_blocks=max_blocks, page_size=page_size, num_heads=num_heads,
@@ -748,12 +778,16 @@ def trtllm_batch_decode_with_kv_cache_mla(
         kv_indices=block_tables.data_ptr(), o=out.data_ptr(), lse=None,
         float_ws=plan.float_ws, float_ws_bytes=plan.float_ws_bytes, int_ws=plan.int_ws, int_ws_bytes=plan.int_ws_bytes,
         num_rows=batch_size * q_len * num_heads, num_heads=num_heads, page_size=page_size, dtype=dtype, causal=1,
-        sm_scale=float(bmm1_scale))
+        sm_scale=1.0 if bmm1_scale is None else float(bmm1_scale), q_fp8=storage, kv_fp8=storage,
+        sm_scale_log2_dev=_lib.ptr(bmm1_scale_log2_tensor))
     lib = _lib.lib()
     with torch.cuda.device(query.device):
         stream = _lib.current_stream(query.device)
         _lib.check(lib.fi_batch_mla_plan_device(C.byref(plan), plan_info, stream), name)
         _lib.check(lib.fi_batch_mla_run(plan_info, _lib.FI_MLA_PLAN_INFO_LEN, C.byref(params), stream), name)
-    if bmm2_scale != 1.0:
+    if bmm2_scale_tensor is not None:
+        # on the device, no host read; in float32 and rounded once, as `out *= bmm2_scale` does with the float
+        out.copy_(out.float().mul_(bmm2_scale_tensor.reshape(())))
+    elif bmm2_scale is not None and bmm2_scale != 1.0:
         out *= bmm2_scale
     return out

@@ -26,7 +26,12 @@ class BatchMLAPagedAttentionWrapper(BatchAttentionWrapper):
     r"""Wrapper class for MLA PagedAttention on DeepSeek models, for decode, speculative verify and incremental
     prefill with the matrix-absorbed weights (ref: flashinfer/mla.py:85-420).
 
-    ``head_dim_ckv = 512`` and ``head_dim_kpe = 64`` only; q and the caches both float16 or both bfloat16.
+    ``head_dim_ckv = 512`` and ``head_dim_kpe = 64`` only; q float16 or bfloat16, the caches of q's dtype or
+    ``float8_e4m3fn``.  An fp8 cache is upcast exactly to q's dtype while it is staged, so the arithmetic is that of
+    the 16-bit kernel on ``cache.to(q.dtype)``.  There is no k_scale / v_scale argument: ``sm_scale`` is the full
+    scale of the logits, so the caller folds k_scale into it (``sm_scale * k_scale``) and multiplies the output by
+    v_scale.  An fp8 q is a ValueError here
+    (:func:`flashinfer.decode.trtllm_batch_decode_with_kv_cache_mla` takes one).
     ``ckv_cache``: ``[num_pages, page_size, 512]``, ``kpe_cache``: ``[num_pages, page_size, 64]`` (3-D, or 4-D
     with a middle head axis of 1).  Only the last dimension of each input must be contiguous, so views of one
     576-wide tensor (``q[..., :512]`` / ``q[..., 512:]``) are taken as they are.  ``lse`` is base 2.
@@ -84,6 +89,12 @@ class BatchMLAPagedAttentionWrapper(BatchAttentionWrapper):
         """
         if use_profiler:
             raise ValueError("BatchMLAPagedAttentionWrapper: the profiler is not available on MI355X")
+        if q_data_type not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"BatchMLAPagedAttentionWrapper: q_data_type must be float16 or bfloat16, got {q_data_type} "
+                             "(an fp8 query is taken by trtllm_batch_decode_with_kv_cache_mla only)")
+        if kv_data_type not in (q_data_type, torch.float8_e4m3fn):
+            raise ValueError(f"BatchMLAPagedAttentionWrapper: kv_data_type must be q_data_type ({q_data_type}) or "
+                             f"float8_e4m3fn, got {kv_data_type}")
         qo_indptr_host = qo_indptr.to("cpu").contiguous()
         kv_indptr_host = kv_indptr.to("cpu").contiguous()
         kv_len_arr_host = kv_len_arr.to("cpu").contiguous()
@@ -109,7 +120,8 @@ class BatchMLAPagedAttentionWrapper(BatchAttentionWrapper):
             qo_indptr_h=qo_indptr_host.data_ptr(), kv_indptr_h=kv_indptr_host.data_ptr(),
             kv_len_arr_h=kv_len_arr_host.data_ptr(), batch_size=batch_size, num_heads=num_heads,
             head_dim_ckv=head_dim_ckv, head_dim_kpe=head_dim_kpe, page_size=page_size, causal=int(bool(causal)),
-            q_dtype=_lib.fi_dtype(q_data_type), kv_dtype=_lib.fi_dtype(kv_data_type),
+            # a plan is cut from lengths alone: the planner is given the compute dtype for both, run() the storage type
+            q_dtype=_lib.fi_dtype(q_data_type), kv_dtype=_lib.fi_dtype(q_data_type),
             enable_cuda_graph=int(bool(self._use_cuda_graph)), fixed_split_size=0,
         )
         info = (C.c_int64 * _lib.FI_MLA_PLAN_INFO_LEN)()
@@ -145,7 +157,9 @@ class BatchMLAPagedAttentionWrapper(BatchAttentionWrapper):
         r"""Run the planned MLA attention (ref: flashinfer/mla.py:345-420).
 
         q_nope ``[nnz_qo, num_heads, 512]``, q_pe ``[nnz_qo, num_heads, 64]``; returns ``o`` of q_nope's shape
-        and dtype, and with ``return_lse`` also ``lse`` ``[nnz_qo, num_heads]`` float32 (base 2).
+        and dtype, and with ``return_lse`` also ``lse`` ``[nnz_qo, num_heads]`` float32 (base 2).  With an fp8
+        cache the strides of ckv_cache / kpe_cache are multiples of 16 elements and ``o`` is not yet multiplied by
+        v_scale (see the class docstring).
         """
         if profiler_buffer is not None:
             raise ValueError("BatchMLAPagedAttentionWrapper: profiler_buffer is not supported on MI355X")
@@ -193,6 +207,7 @@ class BatchMLAPagedAttentionWrapper(BatchAttentionWrapper):
             float_ws=float_ws, float_ws_bytes=float_ws_bytes, int_ws=int_ws, int_ws_bytes=int_ws_bytes,
             num_rows=nnz * H, num_heads=H, page_size=self._page_size, dtype=_lib.fi_dtype(q_nope.dtype),
             causal=int(self._causal), sm_scale=self._sm_scale,
+            kv_fp8=_lib.FI_DTYPE_FP8_E4M3 if ckv3.dtype == torch.float8_e4m3fn else 0,
         )
         with torch.cuda.device(q_nope.device):
             _lib.check(

@@ -258,7 +258,10 @@ def append_paged_mla_kv_cache(
     append_ckv ``[nnz, 512]``, append_kpe ``[nnz, 64]`` (last dim contiguous); ckv_cache
     ``[num_pages, page_size, 512]``, kpe_cache ``[num_pages, page_size, 64]``; batch_indices / positions
     ``[nnz]`` int32 (see :func:`get_batch_indices_positions`); the page table is the one AFTER the append.
-    Only ``ckv_dim = 512`` and ``kpe_dim = 64``, float16 or bfloat16.
+    Only ``ckv_dim = 512`` and ``kpe_dim = 64``; float16, bfloat16, float8_e4m3fn or float8_e5m2, one dtype for all
+    four tensors (the rows are copied as they are: an fp8 cache takes the fp8 rows
+    :func:`flashinfer.rope.mla_rope_quantize_fp8` returns).  Every row starts at a 16-byte boundary: strides are
+    multiples of 8 elements at 16 bit and of 16 elements for fp8.
     """
     if ckv_cache is None or kpe_cache is None:
         raise ValueError("append_paged_mla_kv_cache: ckv_cache and kpe_cache are required")

@@ -603,6 +603,8 @@ FI_API int fi_block_sparse_indices_to_vector_sparse_offsets(const int32_t* block
  *   causal: query qo_idx of a request sees keys kv_idx <= kv_len - qo_len + qo_idx
  * Packed row r of a request is (qo_idx = r / num_heads, head = r % num_heads); a work item is (request, tile of
  * 16 packed rows, kv chunk).  Only head_dim_ckv = 512, head_dim_kpe = 64 and q dtype == kv dtype (f16 / bf16).
+ * A plan is cut from lengths alone: the planners take the compute dtype for both of their dtype fields, and an e4m3
+ * cache or query is a matter of fi_batch_mla_run alone (q_fp8 / kv_fp8 of its params).
  * ---------------------------------------------------------------------------------------------- */
 #define FI_MLA_PLAN_INFO_LEN 16
 enum fi_mla_plan_slot {
@@ -660,6 +662,16 @@ typedef struct fi_batch_mla_params {
   int32_t num_rows; /* nnz_qo * num_heads of the q tensors */
   int32_t num_heads, page_size, dtype, causal;
   float sm_scale;
+  /* Storage types, 0 = the tensors hold `dtype` (f16 / bf16, the compute and output type, checked against the plan).
+   * FI_DTYPE_FP8_E4M3: the tensors hold e4m3 bytes, upcast exactly to `dtype` while they are staged; their strides are
+   * then multiples of 16 elements and their bases 16-byte aligned.  Offered: an fp8 cache with either query, and an
+   * fp8 query with an fp8 cache and dtype = bf16.  Refused by name: an fp8 query with a 16-bit cache, and e5m2.
+   * There is no scale in here: sm_scale is the full logit scale (the caller folds q_scale x k_scale into it) and the
+   * caller applies v_scale to o. */
+  int32_t q_fp8, kv_fp8;
+  /* optional, device, one f32: the logit scale already multiplied by log2(e) (the reference's bmm1_scale_log2_tensor),
+   * read by the kernel at run time in place of sm_scale x log2(e).  Only with an fp8 cache. */
+  const float* sm_scale_log2_dev;
 } fi_batch_mla_params_t;
 
 FI_API int fi_batch_mla_run(const int64_t* plan_info, int32_t plan_info_len, const fi_batch_mla_params_t* params,
@@ -715,7 +727,9 @@ FI_API int fi_batch_mla_plan_device_workspace(const fi_batch_mla_plan_device_par
                                               size_t* int_ws_bytes_out, size_t* float_ws_bytes_out);
 
 /* Append: row i of append_ckv [nnz, 512] / append_kpe [nnz, 64] goes to page
- * kv_indices[kv_indptr[batch_indices[i]] + positions[i] / page_size], entry positions[i] % page_size. */
+ * kv_indices[kv_indptr[batch_indices[i]] + positions[i] / page_size], entry positions[i] % page_size.
+ * dtype: f16 / bf16 (72 16-byte chunks per token) or FI_DTYPE_FP8_E4M3 / FI_DTYPE_FP8_E5M2 (36); the rows are copied as
+ * bytes.  Every row 16-byte aligned: strides multiples of 16 / sizeof(dtype) elements, bases 16-byte aligned. */
 typedef struct fi_append_paged_mla_kv_params {
   const void* append_ckv;
   int64_t append_ckv_stride_n;
@@ -770,6 +784,38 @@ FI_API int fi_apply_rope_append_paged_kv_cache(const fi_rope_params_t* params, c
 /* pos_ids[i] = offsets[b] + i - indptr[b] for indptr[b] <= i < indptr[b+1] (ref: pos_enc.cuh:540-575) */
 FI_API int fi_rope_positions_from_indptr(const int32_t* indptr, const int32_t* offsets, int32_t batch_size,
                                   int32_t nnz, int32_t* pos_ids, fi_stream_t stream);
+
+/* MLA: rotate the rope parts of q and k and quantise all four parts to fp8, in one launch.  ref: mla_rope_quantize_fp8,
+ * flashinfer/rope.py:1154-1220, kernel include/flashinfer/pos_enc.cuh:345-460.
+ *   q_rope [nnz, num_heads, 64], k_rope [nnz, 64], q_nope [nnz, num_heads, 512], k_nope [nnz, 512]: f16 / bf16 (dtype),
+ *   last dimension contiguous, the other strides in elements and free (slices of 576-wide tensors are taken as they are)
+ *   *_out: the same shapes in out_dtype (FI_DTYPE_FP8_E4M3 / FI_DTYPE_FP8_E5M2), with strides of their own
+ *   cos_sin_cache: f32 [max_pos, 64], cosines in columns 0..31 and sines in 32..63; row pos_ids[i] rotates token i
+ *   pos_ids: [nnz] int32, or int64 with pos_ids_int64 = 1
+ * The rotation is done in f32 (interleave = 1: pair (2i, 2i+1), else pair (i, i + 32), both with cos[i], sin[i]), the
+ * result times quant_scale_q / quant_scale_kv in f32, then converted round-to-nearest-even, saturating at +-448 (e4m3)
+ * or +-57344 (e5m2).  The nope parts are scaled and converted only.  Input rows 16-byte aligned (strides multiples of 8
+ * elements), output rows 8-byte aligned (strides multiples of 8 elements). */
+typedef struct fi_mla_rope_quantize_params {
+  const void* q_rope;
+  const void* k_rope;
+  const void* q_nope;
+  const void* k_nope;
+  void* q_rope_out;
+  void* k_rope_out;
+  void* q_nope_out;
+  void* k_nope_out;
+  const float* cos_sin_cache;
+  const void* pos_ids;
+  int64_t q_rope_stride_n, q_rope_stride_h, k_rope_stride_n, q_nope_stride_n, q_nope_stride_h, k_nope_stride_n;
+  int64_t q_rope_out_stride_n, q_rope_out_stride_h, k_rope_out_stride_n;
+  int64_t q_nope_out_stride_n, q_nope_out_stride_h, k_nope_out_stride_n;
+  int32_t nnz, num_heads, rope_dim, nope_dim; /* rope_dim 64, nope_dim 512 */
+  int32_t dtype, out_dtype, pos_ids_int64, interleave;
+  float quant_scale_q, quant_scale_kv;
+} fi_mla_rope_quantize_params_t;
+
+FI_API int fi_mla_rope_quantize(const fi_mla_rope_quantize_params_t* params, fi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Sampling: logits -> probabilities -> token.  ref: csrc/flashinfer_sampling_binding.cu:20-82 (exports),
