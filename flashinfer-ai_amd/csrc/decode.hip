@@ -93,6 +93,8 @@ struct DecodeChoice {
 };
 
 // The one decode kernel rule, for plan (which knows neither the logits transform nor the strides) and run.
+// tests/variant_cases.py (decode_kernel) restates it, to give the oracle the rotation rounding of the kernel that runs
+// and to count which kernels its cases reach: change the two together.
 static DecodeChoice choose_decode(int group, int q_dt, int kv_dt, int head_dim, int page_size, bool rope,
                                   bool plain_logits, bool strides_fit_31_bits) {
   DecodeChoice c;

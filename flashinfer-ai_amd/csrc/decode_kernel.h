@@ -103,7 +103,7 @@ struct DecodeWave {
   float q[GT][VEC];
   float o[GT][VEC];
   float m[GT], d[GT];
-  float slope_l2[GT];
+  float slope_l2[GT];  // ALiBi slope in the units of the pre-scaled dot product (x log2e; x 1 / cap with a soft cap)
   float s_scale;  // multiplies the (pre-scaled) dot product; != 1 only with soft cap
   // rope state
   float freq[ROPE ? VEC : 1];
@@ -330,7 +330,7 @@ struct DecodeWave {
     // ---- q: load, (rope), pre-scale ----
     const bool soft_cap = p.logits_soft_cap > 0.f;
     // without soft cap: s = (q.k) * sm_scale*log2e; alibi: s = (q.k*sm_scale + slope*pos)*log2e
-    // with soft cap:    s = tanh(q.k * sm_scale/cap) * cap*log2e      (ref: variants.cuh:47-53)
+    // with soft cap:    s = tanh((q.k*sm_scale + slope*pos) / cap) * cap*log2e      (ref: variants.cuh:47-53)
     const float q_scale = soft_cap ? p.sm_scale / p.logits_soft_cap : p.sm_scale * kLog2e;
     s_scale = soft_cap ? p.logits_soft_cap * kLog2e : 1.0f;
     if constexpr (ROPE) {
@@ -385,7 +385,9 @@ struct DecodeWave {
       }
       m[g] = kMInit;
       d[g] = 0.f;
-      slope_l2[g] = p.use_alibi ? p.alibi_slopes[head] * kLog2e : 0.f;
+      // the bias joins the pre-scaled dot product, so it carries q's pre-scale without sm_scale: log2e, or 1 / cap
+      // under a soft cap (the bias goes through the tanh: ref variants.cuh:67-73)
+      slope_l2[g] = p.use_alibi ? p.alibi_slopes[head] * (soft_cap ? 1.f / p.logits_soft_cap : kLog2e) : 0.f;
     }
 
     // ---- stream the chunk ----

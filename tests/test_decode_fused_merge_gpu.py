@@ -106,6 +106,20 @@ def test_alibi():
     run_checked(c, 8, 2, 128, torch.float16, expect_slot=2, fused=True, pos_encoding_mode="ALIBI")
 
 
+def test_alibi_and_soft_cap_together():
+    # both logit transforms in one fused launch, q x 3 and a cap of 8 so that the cap bites; the lse at the 2e-3 of
+    # tests/test_attention_variants_gpu.py
+    kw = dict(pos_encoding_mode="ALIBI", logits_soft_cap=8.0)
+    c = case((256,) * 3, 8, 2, 128, torch.float16, seed=13, q_gain=3.0, **kw)
+    run_checked(c, 8, 2, 128, torch.float16, expect_slot=2, fused=True, lse_tol=2e-3, **kw)
+
+
+def test_sm_scale_on_four_chunks():
+    # a softmax scale away from 1 / sqrt(head_dim): the chunks' partial states meet in LDS in units of that scale
+    c = case((512,) * 2, 8, 2, 128, torch.bfloat16, seed=14, sm_scale=0.05)
+    run_checked(c, 8, 2, 128, torch.bfloat16, expect_slot=4, fused=True, lse_tol=2e-3, sm_scale=0.05)
+
+
 def test_fp8_e4m3_cache():
     # the oracle sees the same (already quantised) cache values, so the 16-bit tolerance applies
     c = case((256,) * 3, 8, 2, 128, torch.float16, kv_dtype=torch.float8_e4m3fn, seed=7)
