@@ -594,6 +594,59 @@ __global__ void __launch_bounds__(kMoeThreads) moe_finalize_kernel(const MoeFina
   }
 }
 
+// The finalize of the 16-bit layer (cutlass_fused_moe): f32 weights, y and out of either 16-bit dtype, no bias.  The
+// same walk as above; the products stay single f32 operations (no packed v_pk_fma_f32), in the order of the slots.
+struct MoeFinalize16Args {
+  const uint16_t* y;
+  const float* weights;
+  const int32_t* map;
+  uint16_t* out;
+  int32_t num_tokens, top_k, hidden, rows, tpr_log2;
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FI_SINGLE_F32_OPS __attribute__((target("no-packed-fp32-ops")))
+#else
+#define FI_SINGLE_F32_OPS
+#endif
+
+template <int DT>
+__global__ void __launch_bounds__(kMoeThreads) FI_SINGLE_F32_OPS moe_finalize_16bit_kernel(const MoeFinalize16Args A) {
+  const RowTeam team = row_team<kMoeThreads>(A.tpr_log2, A.num_tokens);
+  if (team.past_end) return;
+  const int64_t token = team.row;
+  int rows[FI_MOE_MAX_TOP_K];
+  float w[FI_MOE_MAX_TOP_K];
+#pragma unroll
+  for (int j = 0; j < FI_MOE_MAX_TOP_K; ++j) {
+    rows[j] = -1;
+    w[j] = 0.f;
+    if (j < A.top_k) {
+      const int p = A.map[token * A.top_k + j];
+      if (p >= 0 && p < A.rows) {
+        rows[j] = p;
+        w[j] = A.weights[token * A.top_k + j];
+      }
+    }
+  }
+  for (int c = team.lane; c < A.hidden / 8; c += team.size) {
+    const int col = c * 8;
+    float acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < FI_MOE_MAX_TOP_K; ++j) {
+      if (rows[j] >= 0) {
+        float yv[8];
+        load_16bit<DT, 8>(A.y + (int64_t)rows[j] * A.hidden + col, yv);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = __builtin_fmaf(w[j], yv[i], acc[i]);
+      }
+    }
+    store_16bit<DT, 8>(A.out + token * A.hidden + col, acc);
+  }
+}
+
 static bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p % a) == 0; }
 
 // the limits of both route entry points on num_experts and top_k
@@ -908,6 +961,61 @@ extern "C" FI_API int fi_moe_finalize(const fi_moe_finalize_params_t* p, fi_stre
   a.tpr_log2 = row_team_log2(p->hidden / 8, kMoeThreads);
   const uint32_t grid = (uint32_t)ceil_div<int64_t>(p->num_tokens, kMoeThreads >> a.tpr_log2);
   moe_finalize_kernel<<<dim3(grid), dim3(kMoeThreads), 0, (hipStream_t)stream>>>(a);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}
+
+extern "C" FI_API int fi_moe_sort(const fi_moe_sort_params_t* p, fi_stream_t stream) {
+  FI_REQUIRE(p, "moe_sort: null params");
+  FI_REQUIRE(p->num_tokens >= 0 && p->top_k >= 0 && p->local_num_experts >= 0 && p->local_expert_offset >= 0,
+             "moe_sort: negative size (num_tokens %d, top_k %d, local_expert_offset %d, local_num_experts %d)", p->num_tokens,
+             p->top_k, p->local_expert_offset, p->local_num_experts);
+  FI_REQUIRE(p->local_num_experts >= 1 && p->local_num_experts <= FI_MOE_MAX_EXPERTS,
+             "moe_sort: local_num_experts %d is not in [1, %d]", p->local_num_experts, FI_MOE_MAX_EXPERTS);
+  FI_REQUIRE(p->top_k >= 1 && p->top_k <= FI_MOE_MAX_TOP_K, "moe_sort: top_k %d is not in [1, %d]", p->top_k,
+             FI_MOE_MAX_TOP_K);
+  if (p->num_tokens == 0) return 0;
+  const int64_t n = (int64_t)p->num_tokens * p->top_k;
+  FI_REQUIRE(n < (1ll << 31), "moe_sort: too many rows");
+  FI_REQUIRE(p->topk_ids && p->m_indptr && p->expanded_to_permuted && p->permuted_to_expanded && p->workspace,
+             "moe_sort: null tensor");
+  MoePermuteArgs a{};
+  if (const int rc = moe_sort_args("moe_sort", a, p->topk_ids, p->m_indptr, p->expanded_to_permuted, nullptr, p->workspace,
+                                   p->workspace_bytes, n, p->top_k, p->local_expert_offset, p->local_num_experts, false))
+    return rc;
+  a.p2e = p->permuted_to_expanded;  // the caller's list instead of the workspace's
+  moe_sort_launch(a, (hipStream_t)stream);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}
+
+extern "C" FI_API int fi_moe_finalize_16bit(const fi_moe_finalize_16bit_params_t* p, fi_stream_t stream) {
+  FI_REQUIRE(p, "moe_finalize_16bit: null params");
+  FI_REQUIRE(p->num_tokens >= 0 && p->top_k >= 0 && p->hidden >= 0 && p->rows >= 0,
+             "moe_finalize_16bit: negative size (num_tokens %d, top_k %d, hidden %d, rows %d)", p->num_tokens, p->top_k,
+             p->hidden, p->rows);
+  FI_REQUIRE(p->top_k >= 1 && p->top_k <= FI_MOE_MAX_TOP_K, "moe_finalize_16bit: top_k %d is not in [1, %d]", p->top_k,
+             FI_MOE_MAX_TOP_K);
+  FI_REQUIRE(p->hidden > 0 && p->hidden % 8 == 0, "moe_finalize_16bit: hidden %d must be a positive multiple of 8", p->hidden);
+  FI_REQUIRE(p->dtype == FI_DTYPE_F16 || p->dtype == FI_DTYPE_BF16, "moe_finalize_16bit: dtype %d is not f16 or bf16",
+             p->dtype);
+  if (p->num_tokens == 0) return 0;
+  FI_REQUIRE(p->weights && p->expanded_to_permuted && p->out && (p->rows == 0 || p->y), "moe_finalize_16bit: null tensor");
+  FI_REQUIRE(aligned(p->y, 16) && aligned(p->out, 16) && aligned(p->weights, 4) && aligned(p->expanded_to_permuted, 4),
+             "moe_finalize_16bit: y and out must be 16-byte aligned, weights and expanded_to_permuted 4-byte aligned");
+  MoeFinalize16Args a{};
+  a.y = (const uint16_t*)p->y;
+  a.weights = p->weights;
+  a.map = p->expanded_to_permuted;
+  a.out = (uint16_t*)p->out;
+  a.num_tokens = p->num_tokens;
+  a.top_k = p->top_k;
+  a.hidden = p->hidden;
+  a.rows = p->rows;
+  a.tpr_log2 = row_team_log2(p->hidden / 8, kMoeThreads);
+  const dim3 grid((uint32_t)ceil_div<int64_t>(p->num_tokens, kMoeThreads >> a.tpr_log2)), block(kMoeThreads);
+  if (p->dtype == FI_DTYPE_BF16) moe_finalize_16bit_kernel<FI_DTYPE_BF16><<<grid, block, 0, (hipStream_t)stream>>>(a);
+  else moe_finalize_16bit_kernel<FI_DTYPE_F16><<<grid, block, 0, (hipStream_t)stream>>>(a);
   FI_HIP_CALL(hipGetLastError());
   return 0;
 }

@@ -28,6 +28,10 @@ where the reference's kernel and the routine its tests compare it with would let
 format, f32 scales per token and 128 columns instead of E8M0 bytes: with ``moe_route`` and ``moe_finalize`` they are the
 steps of ``flashinfer.fused_moe_fp8.trtllm_fp8_block_scale_moe``, which lives in a module of its own.
 
+``moe_sort``, ``moe_group_gemm_16bit`` (csrc/gemm_16bit.hip; it gathers its rows itself and applies SwiGLU in its epilogue)
+and ``moe_finalize_16bit`` are the stages of the layer on unquantised f16 / bf16 weights,
+``flashinfer.fused_moe_16bit.cutlass_fused_moe``, which lives in a module of its own as the fp8 layer does.
+
 Nothing here reads a device value on the host or synchronises, and every buffer's size depends on shapes alone, so a
 call can be captured into a graph.
 """
@@ -767,3 +771,167 @@ def moe_gated_act_fp8_block(gemm1_output: torch.Tensor, m_indptr: torch.Tensor) 
     if cum_m:
         _gated_act_fp8_block_into(gemm1_output, m_indptr, q, scale)
     return q, scale
+
+
+# ---- the unquantised layer: f16 / bf16 activations and weights (Mixtral, Qwen-MoE served as they ship) -------------------
+_16BIT = (torch.float16, torch.bfloat16)
+
+
+def moe_sort(topk_ids: torch.Tensor, local_expert_offset: int,
+             local_num_experts: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Sort the slots by local expert without moving any data: the three sorting launches of ``moe_permute_mxfp8`` on
+    their own.  Not part of the reference.
+
+    ``topk_ids`` is int32 ``[T, top_k]`` of global expert ids.  Returns ``(m_indptr, expanded_idx_to_permuted_idx,
+    permuted_idx_to_expanded_idx)``: the first two are what ``moe_permute_mxfp8`` returns for the same ids; the third is
+    int32 ``[T * top_k]`` with the expanded index ``t * top_k + j`` of every permuted row (entries at or past
+    ``m_indptr[-1]`` are unwritten), which ``moe_group_gemm_16bit`` takes as ``a_row_ids`` with ``a_row_ids_div=top_k``.
+    """
+    if topk_ids.dtype != torch.int32 or topk_ids.dim() != 2:
+        raise ValueError("topk_ids must be a 2D int32 tensor (T, top_k)")
+    T, top_k = topk_ids.shape
+    if not 1 <= top_k <= _MAX_TOP_K:
+        raise NotImplementedError(f"top_k {top_k} is not in [1, {_MAX_TOP_K}]")
+    if not 1 <= local_num_experts <= _MAX_EXPERTS or local_expert_offset < 0:
+        raise NotImplementedError(
+            f"local_num_experts {local_num_experts} is not in [1, {_MAX_EXPERTS}] or local_expert_offset {local_expert_offset} < 0")
+    _lib.require_gpu_tensor(topk_ids, "topk_ids")
+    dev, n, G = topk_ids.device, T * top_k, local_num_experts
+    m_indptr = torch.empty((G + 1,), dtype=torch.int32, device=dev)
+    emap = torch.empty((n,), dtype=torch.int32, device=dev)
+    p2e = torch.empty((n,), dtype=torch.int32, device=dev)
+    if T == 0:
+        m_indptr.zero_()
+        return m_indptr, emap, p2e
+    blocks = -(-n // _lib.FI_MOE_SORT_BLOCK)
+    workspace = torch.empty((blocks * G + n,), dtype=torch.int32, device=dev)
+    p = _lib.fi_moe_sort_params_t(
+        topk_ids=topk_ids.contiguous().data_ptr(), m_indptr=m_indptr.data_ptr(), expanded_to_permuted=emap.data_ptr(),
+        permuted_to_expanded=p2e.data_ptr(), workspace=workspace.data_ptr(), workspace_bytes=_lib.nbytes(workspace),
+        num_tokens=T, top_k=top_k, local_expert_offset=local_expert_offset, local_num_experts=G)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fi_moe_sort(C.byref(p), _lib.current_stream(dev)), "moe_sort")
+    return m_indptr, emap, p2e
+
+
+def moe_group_gemm_16bit(
+    a: torch.Tensor,
+    b: torch.Tensor,
+    m_indptr: torch.Tensor,
+    a_row_ids: Optional[torch.Tensor] = None,
+    swiglu: bool = False,
+    alpha: Optional[torch.Tensor] = None,
+    beta: Optional[torch.Tensor] = None,
+    limit: Optional[torch.Tensor] = None,
+    out: Optional[torch.Tensor] = None,
+    a_row_ids_div: int = 1,
+) -> torch.Tensor:
+    """Grouped f16 / bf16 GEMM (csrc/gemm_16bit.hip): ``d[r] = a[row(r)] @ b[g].T`` for ``m_indptr[g] <= r < m_indptr[g + 1]``,
+    f32 accumulation, one rounding.  Not part of the reference.
+
+    ``a`` ``[rows, k]`` and ``b`` ``[G, n, k]`` of one dtype, ``k % 64 == 0``, ``n % 64 == 0``; ``m_indptr`` int32 ``[G + 1]`` on
+    the device.  ``a_row_ids`` (int32, one entry per row of the output) makes ``row(r) = a_row_ids[r] // a_row_ids_div``, so
+    that the rows are gathered by the GEMM's own loads; without it ``row(r) = r`` and the output has ``a``'s rows.
+
+    ``swiglu``: ``b[g]`` is ``[2 I, k]`` with rows ``[0, I)`` the linear half and ``[I, 2 I)`` the gate (``I % 64 == 0``); with
+    ``x2`` and ``x1`` the two products of an element, the output ``[rows, I]`` is ``silu(x1) * x2``, or with ``alpha``, ``beta``,
+    ``limit`` (f32 ``[G]``, all three or none) ``x1 = min(x1, limit); x1 * sigmoid(alpha * x1) * (clamp(x2, -limit, limit) +
+    beta)``, in f32 from the f32 accumulators.  Rows at or past ``m_indptr[-1]`` are not written.  ``out`` is returned.
+    """
+    if a.dtype not in _16BIT or a.dim() != 2:
+        raise ValueError(f"a must be a 2D float16 or bfloat16 tensor, got {a.dtype} {tuple(a.shape)}")
+    if b.dtype != a.dtype or b.dim() != 3 or b.shape[2] != a.shape[1]:
+        raise ValueError(f"b must be {a.dtype} of shape (G, n, {a.shape[1]}), got {b.dtype} {tuple(b.shape)}")
+    G, n, k = b.shape
+    if m_indptr.dtype != torch.int32 or tuple(m_indptr.shape) != (G + 1,):
+        raise ValueError(f"m_indptr must be int32 of shape ({G + 1},), got {m_indptr.dtype} {tuple(m_indptr.shape)}")
+    rows = a.shape[0]
+    if a_row_ids is not None:
+        if a_row_ids.dtype != torch.int32 or a_row_ids.dim() != 1:
+            raise ValueError("a_row_ids must be a 1D int32 tensor")
+        rows = a_row_ids.shape[0]
+        if a_row_ids_div < 1 or (rows and not a.shape[0]):
+            raise ValueError(f"a_row_ids_div {a_row_ids_div} must be >= 1 and a must have rows")
+    if k == 0 or k % 64 != 0 or n % (128 if swiglu else 64) != 0:
+        raise ValueError(f"k {k} must be a positive multiple of 64 and n {n} a multiple of {128 if swiglu else 64}")
+    if G > _MAX_EXPERTS:
+        raise ValueError(f"{G} groups: at most {_MAX_EXPERTS}")
+    gates = [t for t in (alpha, beta, limit) if t is not None]
+    if gates and (len(gates) != 3 or not swiglu):
+        raise ValueError("alpha, beta and limit come all three or not at all, and with swiglu only")
+    alpha, beta, limit = (None if t is None else _per_expert(t, name, (G,)).contiguous()
+                          for t, name in ((alpha, "alpha"), (beta, "beta"), (limit, "limit")))
+    width = n // 2 if swiglu else n
+    if out is None:
+        out = torch.empty((rows, width), dtype=a.dtype, device=a.device)
+    elif out.dtype != a.dtype or tuple(out.shape) != (rows, width) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {a.dtype} tensor of shape ({rows}, {width})")
+    for t, name in ((a, "a"), (b, "b"), (m_indptr, "m_indptr"), (a_row_ids, "a_row_ids"), (out, "out")):
+        if t is not None:
+            _lib.require_gpu_tensor(t, name)
+    if not b.is_contiguous():
+        raise ValueError("b must be contiguous: there is no silent copy of a weight tensor")
+    if rows == 0 or n == 0 or G == 0:
+        return out
+    a_c = contiguous_aligned(a, 16)
+    p = _lib.fi_group_gemm_16bit_params_t(
+        a=a_c.data_ptr(), a_row_ids=_lib.ptr(None if a_row_ids is None else a_row_ids.contiguous()), b=b.data_ptr(),
+        d=out.data_ptr(), m_indptr=m_indptr.contiguous().data_ptr(), alpha=_lib.ptr(alpha), beta=_lib.ptr(beta),
+        limit=_lib.ptr(limit), num_groups=G, cum_m=rows, a_rows=a.shape[0], n=n, k=k, a_row_ids_div=a_row_ids_div,
+        dtype=_lib.fi_dtype(a.dtype),
+        epilogue=_lib.FI_GEMM16_EPILOGUE_SWIGLU if swiglu else _lib.FI_GEMM16_EPILOGUE_NONE)
+    with torch.cuda.device(a.device):
+        if _lib.lib().fi_group_gemm_16bit_nt(C.byref(p), _lib.current_stream(a.device)) != 0:
+            raise ValueError("group_gemm_16bit_nt: " + _lib.lib().fi_last_error().decode("utf-8", "replace"))
+    return out
+
+
+def moe_finalize_16bit(
+    gemm2_output: torch.Tensor,
+    token_final_scales: torch.Tensor,
+    expanded_idx_to_permuted_idx: torch.Tensor,
+    output: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """``out[t] = dtype(sum_j w[t, j] * y[p(t, j)])`` over the slots with ``p >= 0``, accumulated in f32 in the order of ``j``;
+    a token without a local slot gets zeros.  ``moe_finalize`` with float32 weights and either 16-bit dtype, without a bias.
+
+    ``gemm2_output`` f16 / bf16 ``[T * top_k, H]``, ``token_final_scales`` float32 ``[T, top_k]``,
+    ``expanded_idx_to_permuted_idx`` int32 ``[T * top_k]``.  ``output``, if given, is contiguous ``[T, H]`` of ``gemm2_output``'s
+    dtype and is returned.
+    """
+    if gemm2_output.dtype not in _16BIT or gemm2_output.dim() != 2:
+        raise ValueError("gemm2_output must be a 2D float16 or bfloat16 tensor (T * top_k, H)")
+    if token_final_scales.dtype != torch.float32 or token_final_scales.dim() != 2:
+        raise ValueError("token_final_scales must be a 2D float32 tensor (T, top_k)")
+    T, top_k = token_final_scales.shape
+    rows, H = gemm2_output.shape
+    if expanded_idx_to_permuted_idx.dtype != torch.int32 or expanded_idx_to_permuted_idx.numel() != T * top_k:
+        raise ValueError(f"expanded_idx_to_permuted_idx must be int32 with {T * top_k} entries")
+    if not 1 <= top_k <= _MAX_TOP_K:
+        raise NotImplementedError(f"top_k {top_k} is not in [1, {_MAX_TOP_K}]")
+    if H == 0 or H % 8 != 0:
+        raise NotImplementedError(f"hidden size {H} must be a multiple of 8")
+    if output is not None:
+        _check_output_16bit(output, T, H, gemm2_output.dtype)
+    for t, name in ((gemm2_output, "gemm2_output"), (token_final_scales, "token_final_scales"),
+                    (expanded_idx_to_permuted_idx, "expanded_idx_to_permuted_idx"), (output, "output")):
+        if t is not None:
+            _lib.require_gpu_tensor(t, name)
+    dev = gemm2_output.device
+    if output is None:
+        output = torch.empty((T, H), dtype=gemm2_output.dtype, device=dev)
+    if T == 0:
+        return output
+    y = contiguous_aligned(gemm2_output, 16)
+    p = _lib.fi_moe_finalize_16bit_params_t(
+        y=y.data_ptr(), weights=token_final_scales.contiguous().data_ptr(),
+        expanded_to_permuted=expanded_idx_to_permuted_idx.contiguous().data_ptr(), out=output.data_ptr(), num_tokens=T,
+        top_k=top_k, hidden=H, rows=rows, dtype=_lib.fi_dtype(gemm2_output.dtype))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fi_moe_finalize_16bit(C.byref(p), _lib.current_stream(dev)), "moe_finalize_16bit")
+    return output
+
+
+def _check_output_16bit(output: torch.Tensor, T: int, H: int, dtype: torch.dtype) -> None:
+    if output.dtype != dtype or tuple(output.shape) != (T, H) or not output.is_contiguous() or output.data_ptr() % 16 != 0:
+        raise ValueError(f"output must be a contiguous, 16-byte aligned {dtype} tensor of shape ({T}, {H})")

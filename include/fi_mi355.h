@@ -1284,6 +1284,80 @@ typedef struct fi_fp8_quantize_1x128_params {
 
 FI_API int fi_fp8_quantize_1x128(const fi_fp8_quantize_1x128_params_t* params, fi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The unquantised layer: f16 / bf16 activations and weights, around two launches of fi_group_gemm_16bit_nt.
+ * ref: cutlass_fused_moe, flashinfer/fused_moe/core.py:758-786; compute_with_experts,
+ * tests/moe/test_trtllm_cutlass_fused_moe.py:171-210.
+ *   sort -> GEMM1 (gathers its rows, SwiGLU in its epilogue) -> GEMM2 -> finalize (16 bit)
+ * The caller routes (token_selected_experts / token_final_scales); no permuted copy of the activations and no
+ * [rows, 2 * intermediate] tensor is written.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The three sorting launches of fi_moe_permute_mxfp8 on their own: m_indptr and expanded_to_permuted as there for the
+ * same ids, and permuted_to_expanded[p] = i for p = expanded_to_permuted[i] >= 0 (entries at or past m_indptr[G] are
+ * not written).  No data is moved.  workspace as fi_moe_permute_mxfp8. */
+typedef struct fi_moe_sort_params {
+  const int32_t* topk_ids;       /* [num_tokens, top_k] expert ids */
+  int32_t* m_indptr;             /* out [local_num_experts + 1] */
+  int32_t* expanded_to_permuted; /* out [num_tokens * top_k] */
+  int32_t* permuted_to_expanded; /* out [num_tokens * top_k] */
+  int32_t* workspace;
+  int64_t workspace_bytes;
+  int32_t num_tokens, top_k;
+  int32_t local_expert_offset, local_num_experts;
+} fi_moe_sort_params_t;
+
+FI_API int fi_moe_sort(const fi_moe_sort_params_t* params, fi_stream_t stream);
+
+enum fi_gemm16_epilogue {
+  FI_GEMM16_EPILOGUE_NONE = 0,  /* d is [cum_m, n] */
+  FI_GEMM16_EPILOGUE_SWIGLU = 1 /* b[g] is [2 I, k], rows [0, I) the linear half, [I, 2 I) the gate; d is [cum_m, I] */
+};
+
+/* Grouped 16-bit NT GEMM (csrc/gemm_16bit.hip).  For the rows r of group g (m_indptr[g] <= r < m_indptr[g+1]):
+ *   x[r, j] = sum_k a[row(r), k] * b[g, j, k],  row(r) = r, or with a_row_ids the row a_row_ids[r] / a_row_ids_div of a
+ *   (clamped into [0, a_rows)); f32 accumulation.
+ *   FI_GEMM16_EPILOGUE_NONE:   d[r, j] = dtype(x[r, j]), d is [cum_m, n].
+ *   FI_GEMM16_EPILOGUE_SWIGLU: with I = n / 2, x2 = x[r, c] and x1 = x[r, I + c], in f32 and rounded once:
+ *     x1 = min(x1, limit[g]);  d[r, c] = dtype(x1 * sigmoid(alpha[g] * x1) * (clamp(x2, -limit[g], limit[g]) + beta[g]))
+ *     alpha / beta / limit all three or all NULL (1 / 0 / +inf: silu(x1) * x2); d is [cum_m, I].
+ *   a: [a_rows, k], b: [G, n, k], d: one dtype, f16 or bf16, contiguous, 16-byte aligned.  m_indptr: int32 [G+1] on the
+ *   DEVICE, ascending, m_indptr[G] <= cum_m; a_row_ids: optional int32 [cum_m] on the device, only its entries below
+ *   m_indptr[G] are read.  k % 64 == 0, k > 0; n % 64 == 0 (SWIGLU: n % 128 == 0); G <= FI_MOE_MAX_EXPERTS.
+ * Empty groups are legal; rows of d at or past m_indptr[G] are not written.  One launch, no workspace, no host state, no
+ * synchronisation; the result does not depend on scheduling. */
+typedef struct fi_group_gemm_16bit_params {
+  const void* a;
+  const int32_t* a_row_ids; /* optional */
+  const void* b;
+  void* d;
+  const int32_t* m_indptr;
+  const float* alpha; /* optional [num_groups], SWIGLU only */
+  const float* beta;
+  const float* limit;
+  int32_t num_groups, cum_m, a_rows, n, k;
+  int32_t a_row_ids_div; /* >= 1, read with a_row_ids: the layer passes top_k and permuted_to_expanded */
+  int32_t dtype;         /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+  int32_t epilogue;      /* enum fi_gemm16_epilogue */
+} fi_group_gemm_16bit_params_t;
+
+FI_API int fi_group_gemm_16bit_nt(const fi_group_gemm_16bit_params_t* params, fi_stream_t stream);
+
+/* out[t] = dtype(sum_j w[t, j] * y[p(t, j)]) over the slots with 0 <= p(t, j) = expanded_to_permuted[t * top_k + j] <
+ * rows, accumulated in f32 in the order of j and rounded once; a token without such a slot gets zeros.  fi_moe_finalize
+ * with f32 weights (token_final_scales of cutlass_fused_moe) and either 16-bit dtype, without a bias.
+ * hidden % 8 == 0; y and out 16-byte aligned. */
+typedef struct fi_moe_finalize_16bit_params {
+  const void* y;                       /* [rows, hidden] f16 / bf16 */
+  const float* weights;                /* [num_tokens, top_k] */
+  const int32_t* expanded_to_permuted; /* [num_tokens * top_k] */
+  void* out;                           /* [num_tokens, hidden], the dtype of y */
+  int32_t num_tokens, top_k, hidden, rows;
+  int32_t dtype; /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+} fi_moe_finalize_16bit_params_t;
+
+FI_API int fi_moe_finalize_16bit(const fi_moe_finalize_16bit_params_t* params, fi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
