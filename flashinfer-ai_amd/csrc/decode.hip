@@ -361,21 +361,63 @@ static int check_and_fill_decode(const char* who, const A& a, int kv_dt, int hea
   return 0;
 }
 
-}  // namespace fi
+// decode_mfma16_multi_inst.hip
+hipError_t decode_mfma16_multi_launch(const DecodeMultiParams& p, int q_dtype, int kv_dtype, int head_dim, int grid,
+                                      hipStream_t stream);
 
-extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes, void* int_ws,
-                                   size_t int_ws_bytes, const int64_t* plan_info,
-                                   int32_t plan_info_len, const fi_batch_decode_params_t* a,
-                                   fi_stream_t stream_) {
-  return fi_batch_decode_run_sinks(float_ws, float_ws_bytes, int_ws, int_ws_bytes, plan_info, plan_info_len, a,
-                                   /*sinks=*/nullptr, stream_);
+// q_len = T > 1 query tokens per request on the plan of a one-token run: kp is filled as for that run (work list,
+// chunk size, window, graph mask).  The 16x16x32 kernel's MULTI form takes col_tiles = ceil(T G / 16) waves per
+// (chunk, kv head); a split plan leaves partial states [o_indptr[req] + chunk][T Hq][D] (+ lse) that the n-way merge
+// folds as T Hq "heads" per request, which is the [batch * T, Hq, D] output.  The plan sized its partial-state
+// region for Hq heads, so this one is laid over the float workspace from its start.
+static int launch_decode_multi(const DecodeKernelParams& kp, const fi_batch_decode_params_t& a, int q_len,
+                               int64_t padded, void* float_ws, size_t float_ws_bytes, bool strides_fit_31_bits,
+                               hipStream_t stream) {
+  const fi_paged_kv_t& kv = a.kv;
+  const bool fp8 = kv.dtype == FI_DTYPE_FP8_E4M3 || kv.dtype == FI_DTYPE_FP8_E5M2;
+  FI_REQUIRE(a.pos_encoding_mode == FI_POS_NONE,
+             "batch_decode_run: q_len_per_req = %d takes pos_encoding_mode NONE only (rotate before the cache)", q_len);
+  FI_REQUIRE(q_len <= 16 && q_len * kp.group_size <= 64,
+             "batch_decode_run: q_len_per_req = %d x group size %d: at most 16 tokens and 64 (token, head) columns per "
+             "kv head; use the prefill entry points beyond that", q_len, kp.group_size);
+  FI_REQUIRE((kv.dtype == a.q_dtype || fp8) && (kv.head_dim == 64 || kv.head_dim == 128) && kv.indices &&
+                 strides_fit_31_bits,
+             "batch_decode_run: q_len_per_req > 1 needs a cache of the q dtype or fp8, head_dim 64 / 128 (got %d) and "
+             "page / token strides below 2^31 elements", kv.head_dim);
+  DecodeMultiParams mp;
+  static_cast<DecodeKernelParams&>(mp) = kp;
+  mp.q_len = q_len;
+  mp.col_tiles = ceil_div(q_len * kp.group_size, 16);
+  mp.head_tiles = mp.col_tiles;
+  mp.num_items = (int32_t)(padded * kv.num_kv_heads * mp.col_tiles);
+  const int64_t heads = (int64_t)q_len * a.num_qo_heads;
+  if (kp.split_kv) {
+    const size_t need = (size_t)padded * heads * (kv.head_dim + 1) * sizeof(float);
+    FI_REQUIRE(float_ws && ((uintptr_t)float_ws % 16) == 0 && need <= float_ws_bytes,
+               "batch_decode_run: float workspace too small for q_len_per_req = %d: %zu bytes, need %zu (16-byte "
+               "aligned)", q_len, float_ws_bytes, need);
+    mp.tmp_o = (float*)float_ws;
+    mp.tmp_lse = mp.tmp_o + (size_t)padded * heads * kv.head_dim;
+  }
+  FI_HIP_CALL(decode_mfma16_multi_launch(mp, a.q_dtype, kv.dtype, kv.head_dim, ceil_div(mp.num_items, kDecodeWaves),
+                                         stream));
+  if (kp.split_kv) {
+    MergeNParams m{mp.tmp_o, mp.tmp_lse, kp.o_indptr, kp.o, kp.lse, 0, kv.batch_size,
+                   (int32_t)heads, kv.head_dim, FI_DTYPE_F32, a.q_dtype};
+    m.sinks = kp.sinks;
+    m.sink_heads = a.num_qo_heads;  // sinks are per query head: "head" t Hq + h reads sinks[h]
+    FI_HIP_CALL(launch_merge_n(m, stream));
+  }
+  return 0;
 }
 
-extern "C" FI_API int fi_batch_decode_run_sinks(void* float_ws, size_t float_ws_bytes, void* int_ws,
-                                         size_t int_ws_bytes, const int64_t* plan_info,
-                                         int32_t plan_info_len, const fi_batch_decode_params_t* a,
-                                         const float* sinks, fi_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+}  // namespace fi
+
+// fi_batch_decode_run[_sinks] (q_len 1) and fi_batch_decode_run_multi (q_len > 1: the MULTI form of the 16x16x32
+// kernel on the same plan)
+static int batch_decode_run(void* float_ws, size_t float_ws_bytes, void* int_ws, size_t int_ws_bytes,
+                            const int64_t* plan_info, int32_t plan_info_len, const fi_batch_decode_params_t* a,
+                            const float* sinks, int q_len, hipStream_t stream) {
   // decode takes 16-bit queries only; with sinks that is said first, so before any launch
   FI_REQUIRE(!sinks || !a || a->q_dtype == FI_DTYPE_F16 || a->q_dtype == FI_DTYPE_BF16,
              "batch_decode_run: attention sinks need f16 / bf16 queries (q dtype %d)", a->q_dtype);
@@ -436,6 +478,9 @@ extern "C" FI_API int fi_batch_decode_run_sinks(void* float_ws, size_t float_ws_
   kp.plan_window_left = (int32_t)plan_info[FI_DP_WINDOW_LEFT];
   FI_REQUIRE(kp.plan_window_left < 0 || kp.plan_window_left == a->window_left,
              "batch_decode_run: window_left %d differs from the planned %d", a->window_left, kp.plan_window_left);
+  if (q_len > 1)
+    return launch_decode_multi(kp, *a, q_len, padded, float_ws, float_ws_bytes,
+                               kv.stride_page < (1ll << 31) && kv.stride_n < (1ll << 31), stream);
   if (split) {
     FI_REQUIRE(float_ws, "batch_decode_run: split-kv plan needs the float workspace");
     const size_t need = (size_t)plan_info[FI_DP_S_OFFSET] +
@@ -469,6 +514,31 @@ extern "C" FI_API int fi_batch_decode_run_sinks(void* float_ws, size_t float_ws_
   }
   return launch_decode(kp, choice, a->q_dtype, kv.dtype, kv.head_dim, a->pos_encoding_mode == FI_POS_ROPE_LLAMA,
                        /*merge_n=*/0, kv.batch_size, stream);
+}
+
+extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes, void* int_ws,
+                                   size_t int_ws_bytes, const int64_t* plan_info,
+                                   int32_t plan_info_len, const fi_batch_decode_params_t* a,
+                                   fi_stream_t stream_) {
+  return fi_batch_decode_run_sinks(float_ws, float_ws_bytes, int_ws, int_ws_bytes, plan_info, plan_info_len, a,
+                                   /*sinks=*/nullptr, stream_);
+}
+
+extern "C" FI_API int fi_batch_decode_run_sinks(void* float_ws, size_t float_ws_bytes, void* int_ws,
+                                         size_t int_ws_bytes, const int64_t* plan_info,
+                                         int32_t plan_info_len, const fi_batch_decode_params_t* a,
+                                         const float* sinks, fi_stream_t stream_) {
+  return batch_decode_run(float_ws, float_ws_bytes, int_ws, int_ws_bytes, plan_info, plan_info_len, a, sinks,
+                          /*q_len=*/1, (hipStream_t)stream_);
+}
+
+extern "C" FI_API int fi_batch_decode_run_multi(void* float_ws, size_t float_ws_bytes, void* int_ws,
+                                         size_t int_ws_bytes, const int64_t* plan_info,
+                                         int32_t plan_info_len, const fi_batch_decode_params_t* a,
+                                         const float* sinks, int32_t q_len_per_req, fi_stream_t stream_) {
+  FI_REQUIRE(q_len_per_req >= 1, "batch_decode_run: q_len_per_req must be >= 1, got %d", q_len_per_req);
+  return batch_decode_run(float_ws, float_ws_bytes, int_ws, int_ws_bytes, plan_info, plan_info_len, a, sinks,
+                          q_len_per_req, (hipStream_t)stream_);
 }
 
 extern "C" FI_API int fi_single_decode_run(const fi_single_decode_params_t* a, void* tmp, size_t tmp_bytes,

@@ -70,6 +70,13 @@ struct DecodeKernelParams {
   const float* sinks;
 };
 
+// decode_mfma16_kernel's MULTI form (q_len query tokens per request, fi_batch_decode_run_multi): the fields above,
+// and behind them what only that form reads, so the argument block of every other kernel is the one it was.
+struct DecodeMultiParams : DecodeKernelParams {
+  int32_t q_len;      // T: rows req * T .. req * T + T - 1 of q / o belong to request req
+  int32_t col_tiles;  // ceil(T * group_size / 16): waves per (chunk, kv head)
+};
+
 // K/V rows are read once per wave: non-temporal.  When a GQA group is processed as several head tiles the
 // neighbouring waves stream the SAME rows, so those loads stay temporal and the partner hits in L2.
 template <bool NT>

@@ -22,6 +22,8 @@
 // prefill kernel, prefill.cuh:465-612): q rotated once, every K row while it is staged into LDS; both rounded to
 // T16 for the MFMA as that path rounds them in shared memory.
 #pragma once
+#include <type_traits>
+
 #include "decode_kernel.h"
 #include "prefill_kernel.h"
 
@@ -59,11 +61,22 @@ __device__ __forceinline__ float reduce_rows(float x) {
   return MAX ? fmaxf(c, d) : c + d;
 }
 
+// MULTI: q_len = T query tokens per request (speculative verify; the cache already holds them, token t of a request
+// of L keys at position L - T + t).  The 16 columns of the MFMAs are (token, head) pairs instead of heads alone:
+// column r of a (request, kv head) is token r / G, head r % G, r < T G; a wave owns 16 of them, and the col_tiles =
+// ceil(T G / 16) waves of neighbouring items stream the same K/V rows.  Column c sees keys [lo_c, hi_c):
+//   hi_c = L - T + t + 1,   lo_c = max(0, L - T + t - window_left)   (0 without a window)
+// The main loop is the one-token loop; the per-column bounds cost a compare only on tiles that cross one (the last
+// T - 1 keys, the window's lower edge).  No fused RoPE, no ALiBi, no FUSE.
+template <bool MULTI>
+using DecodeParamsOf = std::conditional_t<MULTI, DecodeMultiParams, DecodeKernelParams>;
+
 // (an fp8 cache with ROPE at head_dim 128 stages 16 dims per lane -- twice the rotation state -- and does not fit
 // 256 registers: that instantiation runs one workgroup per CU)
-template <int T16, int KVS, int D, bool PAGED, bool ROPE, bool FUSE = false>
+template <int T16, int KVS, int D, bool PAGED, bool ROPE, bool FUSE = false, bool MULTI = false>
 __global__ void __launch_bounds__(kDecodeThreads, (ROPE && D == 128 && KVS != T16) ? 1 : 2)
-    decode_mfma16_kernel(const DecodeKernelParams p) {
+    decode_mfma16_kernel(const DecodeParamsOf<MULTI> p) {
+  static_assert(!MULTI || (PAGED && !ROPE && !FUSE), "MULTI: paged, no fused RoPE, no FUSE");
   using M = MfmaType<T16>;
   using frag_t = typename M::frag;
   constexpr int kTile = 32;
@@ -101,8 +114,15 @@ __global__ void __launch_bounds__(kDecodeThreads, (ROPE && D == 128 && KVS != T1
   const int lc = lane & 15, lg = lane >> 4;
 
   // ---- item -> (work, kv head); one head tile: the whole group (<= 16 heads) is this wave's 16 columns ----
-  int kv_head = item % p.num_kv_heads;
-  const int work = item / p.num_kv_heads;
+  // MULTI: item -> (work, kv head, column tile), the column tiles of a (work, kv head) on neighbouring waves
+  int kv_item = item;
+  [[maybe_unused]] int col_tile = 0;
+  if constexpr (MULTI) {
+    col_tile = item % p.col_tiles;
+    kv_item = item / p.col_tiles;
+  }
+  int kv_head = kv_item % p.num_kv_heads;
+  const int work = kv_item / p.num_kv_heads;
   int req = 0, kv_tile = work;
   [[maybe_unused]] bool active = true;
   if constexpr (FUSE) {
@@ -140,21 +160,53 @@ __global__ void __launch_bounds__(kDecodeThreads, (ROPE && D == 128 && KVS != T1
     const int np = p.indptr[req + 1] - page_begin;
     chunk_base = np > 0 ? max((np - 1) * p.page_size - p.plan_window_left, 0) / p.page_size * p.page_size : 0;
   }
-  const int win_start = p.window_left >= 0 ? max(0, kv_len - 1 - p.window_left) : 0;
+  int win_start = p.window_left >= 0 ? max(0, kv_len - 1 - p.window_left) : 0;
+  const int G = p.group_size;  // <= 16 (checked on the host); MULTI: T G <= 64
+  // MULTI: this lane's column -> (token, head) and its keys [col_lo, col_hi); the wave's tiles at or above
+  // mask_hi or below mask_lo cross some column's bound.  Columns past T G alias the last one and are not stored.
+  [[maybe_unused]] int col_tok = 0, col_head = 0, col_lo = 0, col_hi = 0, mask_lo = 0, mask_hi = 0;
+  [[maybe_unused]] bool col_valid = true;
+  if constexpr (MULTI) {
+    const int T = p.q_len, ncol = T * G, r = col_tile * 16 + lc;
+    col_valid = r < ncol;
+    col_tok = min(r, ncol - 1) / G;
+    col_head = min(r, ncol - 1) - col_tok * G;
+    const int tok_first = col_tile * 16 / G, tok_last = min(col_tile * 16 + 15, ncol - 1) / G;
+    const int first_key = kv_len - T - max(p.window_left, 0);  // of token 0, before the clamp to 0
+    col_hi = kv_len - T + col_tok + 1;
+    mask_hi = kv_len - T + tok_first + 1;
+    if (p.window_left >= 0) {
+      col_lo = max(0, first_key + col_tok);
+      win_start = max(0, first_key + tok_first);  // tiles below the lowest bound of the wave's columns are skipped
+      mask_lo = max(0, first_key + tok_last);
+    } else {
+      win_start = 0;
+    }
+    // plan() cut the chunks from the page of the LAST token's first key: the T - 1 tokens before it see up to T - 1
+    // keys more, so the chunks start that much earlier and the request's last chunk runs to the end
+    chunk_base = max(chunk_base - (T - 1), 0);
+  }
   const int kv_chunk_size = p.kv_chunk_size_ptr ? *p.kv_chunk_size_ptr : p.kv_chunk_size;
   int chunk_start = chunk_base + (p.split_kv ? kv_tile * kv_chunk_size : 0);
   int chunk_end = p.split_kv ? min(chunk_start + kv_chunk_size, kv_len) : kv_len;
   if constexpr (FUSE)
     if (!active) chunk_end = chunk_start;
+  if constexpr (MULTI) {
+    if (p.split_kv && p.plan_window_left >= 0 && kv_tile == p.o_indptr[req + 1] - p.o_indptr[req] - 1)
+      chunk_end = kv_len;
+    col_hi = min(col_hi, chunk_end);
+    mask_hi = min(mask_hi, chunk_end);
+  }
   if (win_start > chunk_start) chunk_start += (win_start - chunk_start) / kTile * kTile;
-  const int G = p.group_size;  // <= 16 (checked on the host)
   const int head0 = kv_head * G;
-  const int head = head0 + min(lc, G - 1);
+  const int head = head0 + (MULTI ? col_head : min(lc, G - 1));
 
   // ---- Q fragments ----
   frag_t qf[KSTEPS];
   {
-    const uint16_t* qrow = (const uint16_t*)p.q + (int64_t)req * p.q_stride_n + (int64_t)head * p.q_stride_h;
+    int64_t q_row = req;
+    if constexpr (MULTI) q_row = (int64_t)req * p.q_len + col_tok;
+    const uint16_t* qrow = (const uint16_t*)p.q + q_row * p.q_stride_n + (int64_t)head * p.q_stride_h;
 #pragma unroll
     for (int ks = 0; ks < KSTEPS; ++ks)
       qf[ks] = __builtin_bit_cast(frag_t, *(const u32x4*)(qrow + 32 * ks + 8 * lg));
@@ -218,8 +270,14 @@ __global__ void __launch_bounds__(kDecodeThreads, (ROPE && D == 128 && KVS != T1
     for (int ps = 0; ps < NPASS; ++ps) {
       const int64_t off = (int64_t)((uint64_t)(uint32_t)pg[ps] * stride_page32 +
                                     (uint64_t)(uint32_t)en[ps] * stride_n32) + thread_off;
-      st.k[ps] = __builtin_nontemporal_load((const u32x4*)((const char*)p.k + off * KV_BYTES));
-      st.v[ps] = __builtin_nontemporal_load((const u32x4*)((const char*)p.v + off * KV_BYTES));
+      if constexpr (MULTI) {
+        // several column tiles stream the same rows: those loads stay temporal, the partner waves hit in L2
+        st.k[ps] = p.col_tiles > 1 ? load16<false>(p.k, off * KV_BYTES) : load16<true>(p.k, off * KV_BYTES);
+        st.v[ps] = p.col_tiles > 1 ? load16<false>(p.v, off * KV_BYTES) : load16<true>(p.v, off * KV_BYTES);
+      } else {
+        st.k[ps] = __builtin_nontemporal_load((const u32x4*)((const char*)p.k + off * KV_BYTES));
+        st.v[ps] = __builtin_nontemporal_load((const u32x4*)((const char*)p.v + off * KV_BYTES));
+      }
     }
   };
   // K image: 16-byte chunks XOR-swizzled so that the 16 rows one ds_read_b128 lane group touches spread over
@@ -384,9 +442,11 @@ __global__ void __launch_bounds__(kDecodeThreads, (ROPE && D == 128 && KVS != T1
             s_acc[h][j] = t * kLog2e;
           }
       }
-      if (tile0 + kTile > chunk_end || tile0 < win_start) {
-        // register j of half h is kv row 16 h + 4 g + j; visible rows are [win_start, chunk_end)
-        const int lo = win_start - tile0 - 4 * lg, hi = chunk_end - tile0 - 4 * lg;
+      if (MULTI ? (tile0 + kTile > mask_hi || tile0 < mask_lo) : (tile0 + kTile > chunk_end || tile0 < win_start)) {
+        // register j of half h is kv row 16 h + 4 g + j; visible rows are [win_start, chunk_end), with MULTI the
+        // column's own [col_lo, col_hi).  A column with no visible row in the tile gets mx = -inf below: m_run keeps
+        // its finite value, alpha = 1 and every p = 0.
+        const int lo = (MULTI ? col_lo : win_start) - tile0 - 4 * lg, hi = (MULTI ? col_hi : chunk_end) - tile0 - 4 * lg;
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -486,10 +546,13 @@ __global__ void __launch_bounds__(kDecodeThreads, (ROPE && D == 128 && KVS != T1
   float lse_v = empty ? FI_NEG_INF : m_run + fast_log2(l_run);
   // attention sink of this lane's head (lanes past the group: a valid head, unused), on a final output only: once
   // per row, for FUSE after the fold of the chunks
-  if (p.sinks && !split_out) fold_sink(m_run, l_run, p.sinks[min(head0 + lc, p.num_qo_heads - 1)] * kLog2e, inv, lse_v);
-  if (lc < G) {
-    const int qo_head = head0 + lc;
-    const int64_t out_row = split_out ? (int64_t)(p.o_indptr ? p.o_indptr[req] : 0) + kv_tile : req;
+  if (p.sinks && !split_out)
+    fold_sink(m_run, l_run, p.sinks[MULTI ? head : min(head0 + lc, p.num_qo_heads - 1)] * kLog2e, inv, lse_v);
+  if (MULTI ? col_valid : lc < G) {
+    const int qo_head = MULTI ? head : head0 + lc;
+    int64_t out_row = split_out ? (int64_t)(p.o_indptr ? p.o_indptr[req] : 0) + kv_tile : req;
+    // MULTI: T rows per request, and per partial state [T Hq][D]: the merge runs over T Hq "heads"
+    if constexpr (MULTI) out_row = out_row * p.q_len + col_tok;
     const int64_t ob = (out_row * p.num_qo_heads + qo_head) * D;
 #pragma unroll
     for (int db = 0; db < DBLK; ++db) {

@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(kMergeThreads) merge_n_kernel(const MergeNPara
   const bool empty = !(dsum > 0.f) || mx <= FI_NEG_INF;
   float inv = empty ? 0.f : 1.0f / dsum;
   float lse = empty ? FI_NEG_INF : mx + fast_log2(dsum);
-  if (p.sinks) fold_sink(mx, empty ? 0.f : dsum, p.sinks[head] * kLog2e, inv, lse);
+  if (p.sinks) fold_sink(mx, empty ? 0.f : dsum, p.sinks[p.sink_heads > 0 ? head % p.sink_heads : head] * kLog2e, inv, lse);
 #pragma unroll
   for (int k = 0; k < kMergeMaxPerLane; ++k) {
     const int i = lane + 64 * k;
@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(kMergeThreads) merge_n_f32_kernel(const MergeN
   const bool empty = !(dsum > 0.f) || mx <= FI_NEG_INF;
   float inv = empty ? 0.f : 1.0f / dsum;
   float lse = empty ? FI_NEG_INF : mx + fast_log2(dsum);
-  if (p.sinks) fold_sink(mx, empty ? 0.f : dsum, p.sinks[head] * kLog2e, inv, lse);
+  if (p.sinks) fold_sink(mx, empty ? 0.f : dsum, p.sinks[p.sink_heads > 0 ? head % p.sink_heads : head] * kLog2e, inv, lse);
 #pragma unroll
   for (int i = 0; i < VEC; ++i) store_any_float(p.v_out, ob + i, acc[i] * inv, p.out_dtype);
   if (lane == 0 && p.s_out) p.s_out[(int64_t)row * p.num_heads + head] = lse;

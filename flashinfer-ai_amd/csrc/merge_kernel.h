@@ -38,6 +38,9 @@ struct MergeNParams {
   // run with sinks folds them (fold_sink, common.h), once per output row; a row of empty partials becomes
   // (0, sink_log2).  NULL everywhere else.
   const float* sinks;
+  // > 0: the sinks tensor holds sink_heads entries and head h reads sinks[h % sink_heads] (multi-token decode merges
+  // q_len x Hq "heads" per request, token-major); 0: one entry per head
+  int32_t sink_heads;
 };
 
 struct Merge2Params {

@@ -366,11 +366,26 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
             returned logsumexp includes the sink, so a state with a folded sink must not be merged again
             (``merge_state`` and the cascade wrappers would count it twice).  The tensor is read when the kernels
             run: a captured ``run`` sees the values it holds at replay.
+        q_len_per_req : query tokens per request, ``T`` (speculative verify: EAGLE, MTP, a draft model's tokens; ref:
+            flashinfer/decode.py:1277-1278).  ``q`` is then ``[batch_size * T, num_qo_heads, head_dim]``, rows
+            ``b * T .. b * T + T - 1`` being request ``b``'s tokens in order, and ``out`` / ``lse`` have ``batch_size *
+            T`` rows too.  The cache already holds the ``T`` tokens: token ``t`` of a request of ``L`` keys sits at
+            position ``L - T + t`` and sees keys ``j <= L - T + t`` (with ``window_left = w``, ``j >= L - T + t - w``);
+            a token that sees no key gives a zero row and the "no key" logsumexp ``-5e4``.  ``T > 1`` runs on the plan
+            of a one-token run, on the 16x16x32 matrix-core kernel with (token, head) pairs as its columns: float16 /
+            bfloat16 ``q``, a cache of that dtype or fp8, ``head_dim`` 64 / 128, ``T <= 16`` and ``T * num_qo_heads /
+            num_kv_heads <= 64`` (ValueError beyond: use :class:`BatchPrefillWithPagedKVCacheWrapper`).
+            ``pos_encoding_mode`` ``ROPE_LLAMA`` / ``ALIBI`` with ``T > 1`` is a NotImplementedError (rotate before
+            the cache).  A split plan keeps ``T`` times the partial states of a one-token run in the float workspace;
+            ValueError names the bytes when it is too small.  ``None`` and 1 are the one-token run.
         Returns the output ``[batch_size, num_qo_heads, head_dim]`` (and the base-2 logsumexp
         ``[batch_size, num_qo_heads]`` when ``return_lse``).  (ref: flashinfer/decode.py:1163-1374)
         """
         if self._plan_info is None:
             raise RuntimeError("plan() must be called before run()")
+        q_len = 1 if q_len_per_req is None else int(q_len_per_req)
+        if q_len != 1:
+            self._check_multi_token(q_len)
         sinks_ptr = 0 if sinks is None else self._sinks_ptr(sinks, q)
         if args:
             raise ValueError("additional kernel arguments require jit_args, which is not supported")
@@ -386,15 +401,22 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
         cache_t = paged_kv_cache if torch.is_tensor(paged_kv_cache) else paged_kv_cache[0]
         key = (q.data_ptr(), q.stride(), q.shape, cache_t.data_ptr(), cache_t.stride(), cache_t.shape,
                None if torch.is_tensor(paged_kv_cache) else paged_kv_cache[1].data_ptr(),
-               out.data_ptr(), lse.data_ptr() if return_lse else 0, q_scale, k_scale, self._plan_serial, sinks_ptr)
+               out.data_ptr(), lse.data_ptr() if return_lse else 0, q_scale, k_scale, self._plan_serial, sinks_ptr,
+               q_len)
         cached = self._run_cache
         if cached is not None and cached[0] == key:
             params = cached[1]
         else:
-            params = self._build_run_params(q, paged_kv_cache, q_scale, k_scale, out, lse if return_lse else None)
+            params = self._build_run_params(q, paged_kv_cache, q_scale, k_scale, out, lse if return_lse else None,
+                                            q_len)
             self._run_cache = (key, params, q, paged_kv_cache)  # keep the tensors alive with the pointers
         dev_index = q.device.index
-        if sinks_ptr:
+        if q_len != 1:
+            with torch.cuda.device(q.device):
+                status = self._lib_run_multi(self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes,
+                                             self._plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, params, sinks_ptr or None,
+                                             q_len, torch.cuda.current_stream().cuda_stream)
+        elif sinks_ptr:
             if torch.cuda.current_device() == dev_index:
                 status = self._lib_run_sinks(self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes,
                                              self._plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, params, sinks_ptr,
@@ -419,7 +441,31 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
             out = _apply_v_scale(out, v_scale)
         return (out, lse) if return_lse else out
 
-    def _build_run_params(self, q, paged_kv_cache, q_scale, k_scale, out, lse):
+    def _check_multi_token(self, q_len: int) -> None:
+        """What run(q_len_per_req = T > 1) refuses from the plan alone, before any tensor is looked at."""
+        group = self._num_qo_heads // self._num_kv_heads
+        if q_len < 1:
+            raise ValueError(f"q_len_per_req must be at least 1, got {q_len}")
+        if self._pos_encoding_mode != "NONE":
+            raise NotImplementedError(
+                f"q_len_per_req={q_len} with pos_encoding_mode={self._pos_encoding_mode!r} is not supported: the "
+                "multi-token kernel has no fused RoPE / ALiBi (apply the rotation before the cache)")
+        if q_len > 16 or q_len * group > 64:
+            raise ValueError(
+                f"q_len_per_req={q_len} with {group} query heads per kv head: batch decode takes at most 16 tokens "
+                "and 64 (token, head) pairs per kv head; use BatchPrefillWithPagedKVCacheWrapper (causal, qo_len = "
+                "q_len_per_req) beyond that")
+        if self._head_dim not in (64, 128):
+            raise ValueError(f"q_len_per_req={q_len} needs head_dim 64 or 128, got {self._head_dim}")
+        if self._plan_info[_lib.FI_DP_SPLIT_KV]:
+            need = (self._plan_info[_lib.FI_DP_PADDED_BATCH_SIZE] * q_len * self._num_qo_heads
+                    * (self._head_dim + 1) * 4)
+            if need > _lib.nbytes(self._float_workspace_buffer):
+                raise ValueError(
+                    f"float workspace too small for q_len_per_req={q_len}: {need} bytes needed for the split-KV "
+                    f"partial states, {_lib.nbytes(self._float_workspace_buffer)} given")
+
+    def _build_run_params(self, q, paged_kv_cache, q_scale, k_scale, out, lse, q_len=1):
         """Validate the run() arguments against the plan and build the C argument block."""
         _lib.require_gpu_tensor(q, "q")
         k_cache, v_cache = _unpack_paged_kv_cache(paged_kv_cache, self._kv_layout)
@@ -429,9 +475,11 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
             self._paged_kv_last_page_len_buf, self._batch_size)
         pos_encoding_mode = self._pos_encoding_mode
         _check_pos_encoding_mode(pos_encoding_mode)
-        if q.dim() != 3 or q.shape[0] != self._batch_size or q.shape[1] != self._num_qo_heads:
+        if q.dim() != 3 or q.shape[0] != self._batch_size * q_len or q.shape[1] != self._num_qo_heads:
             raise ValueError(
-                f"q must have shape [{self._batch_size}, {self._num_qo_heads}, head_dim], got {tuple(q.shape)}"
+                f"q must have shape [{self._batch_size * q_len}, {self._num_qo_heads}, head_dim]"
+                + (f" (batch_size x q_len_per_req = {self._batch_size} x {q_len} rows)" if q_len != 1 else "")
+                + f", got {tuple(q.shape)}"
             )
         if q.shape[2] != head_dim or head_dim != self._head_dim:
             raise ValueError("head_dim of q / kv cache does not match the planned head_dim")
@@ -460,6 +508,7 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
         self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes = self._workspace_args
         self._lib_run = _lib.lib().fi_batch_decode_run
         self._lib_run_sinks = _lib.lib().fi_batch_decode_run_sinks
+        self._lib_run_multi = _lib.lib().fi_batch_decode_run_multi
         return C.byref(params)
 
     def forward_return_lse(

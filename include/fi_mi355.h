@@ -176,6 +176,21 @@ FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes, void* int_
 FI_API int fi_batch_decode_run_sinks(void* float_ws, size_t float_ws_bytes, void* int_ws, size_t int_ws_bytes,
                               const int64_t* plan_info, int32_t plan_info_len,
                               const fi_batch_decode_params_t* params, const float* sinks, fi_stream_t stream);
+/* fi_batch_decode_run_sinks with q_len_per_req = T query tokens per request (speculative verify; ref: the
+ * q_len_per_req argument, flashinfer/decode.py:1277-1278, :2076).  q, o are [batch * T, num_qo_heads, head_dim] and
+ * lse [batch * T, num_qo_heads]; rows b T .. b T + T - 1 are request b's tokens in order.  The cache already holds
+ * them: token t of a request of L keys sits at position L - T + t and sees keys j <= L - T + t (j >= L - T + t -
+ * window_left with a window); a token that sees no key gives o = 0, lse = FI_NEG_INF.  T = 1 is
+ * fi_batch_decode_run_sinks.  T > 1 runs the 16x16x32 matrix-core kernel with (token, head) pairs as its columns:
+ * 16-bit q, a cache of the q dtype or fp8, head_dim 64 / 128, T <= 16 and T * (num_qo_heads / num_kv_heads) <= 64;
+ * pos_encoding_mode must be FI_POS_NONE.  The call works on the plan of a one-token run (work list, chunk size, window,
+ * graph mask) and lays its own partial states over the float workspace: a split plan needs
+ * padded * T * num_qo_heads * (head_dim + 1) floats, and the error names the bytes when there are fewer.  No
+ * allocation, no host read: capturable like fi_batch_decode_run. */
+FI_API int fi_batch_decode_run_multi(void* float_ws, size_t float_ws_bytes, void* int_ws, size_t int_ws_bytes,
+                              const int64_t* plan_info, int32_t plan_info_len,
+                              const fi_batch_decode_params_t* params, const float* sinks, int32_t q_len_per_req,
+                              fi_stream_t stream);
 
 /* Device-side planning: the plan of fi_batch_decode_plan(enable_cuda_graph = 1, window_left = -1), written by kernels
  * on `stream` from lengths that stay on the device.  No host read-back, no copy, no synchronisation: the call may be
