@@ -84,7 +84,10 @@ hipError_t decode_mfma16_launch(const DecodeKernelParams& p, int q_dtype, int kv
 constexpr int kMfmaMinGroup = 5;
 constexpr int kMfmaMinGroupFp8 = 3;
 
-enum class DecodeKernel { VALU, MFMA32, MFMA16 };
+// fp8-query decode (decode_fp8_kernel.h, decode_fp8_inst.hip): q, K, V e4m3, a 16-bit output
+hipError_t decode_fp8_launch(const DecodeKernelParams& p, int o_dtype, int head_dim, int grid, hipStream_t stream);
+
+enum class DecodeKernel { VALU, MFMA32, MFMA16, FP8Q };
 
 struct DecodeChoice {
   DecodeKernel kind;
@@ -98,6 +101,9 @@ struct DecodeChoice {
 static DecodeChoice choose_decode(int group, int q_dt, int kv_dt, int head_dim, int page_size, bool rope,
                                   bool plain_logits, bool strides_fit_31_bits) {
   DecodeChoice c;
+  // an e4m3 query (with an e4m3 cache, head_dim 64 / 128, a group of <= 16: decode_q_dtype_refusal) has one kernel,
+  // whose wave covers the whole group
+  if (q_dt == FI_DTYPE_FP8_E4M3) return {DecodeKernel::FP8Q, 1, 1};
   // groups larger than 4 are processed as several 4-head tiles by neighbouring waves of one workgroup
   // (they stream the same K/V rows, so HBM sees them once): measured 1.7-1.9x faster than an 8-head tile,
   // which is VALU-bound and spills (profiles/r01 notes in DESIGN.md).
@@ -133,11 +139,14 @@ static DecodeChoice choose_decode(int group, int q_dt, int kv_dt, int head_dim, 
 
 // The chosen kernel, then for a split kv axis the n-way merge of the partial states of merge_rows output rows:
 // ragged over kp.o_indptr (batch), or merge_n per row (single).
+// o_dt: the output dtype, the q dtype for every kernel but the fp8-query one.
 static int launch_decode(const DecodeKernelParams& kp, const DecodeChoice& c, int q_dt, int kv_dt, int head_dim,
-                         bool rope, int merge_n, int merge_rows, hipStream_t stream) {
+                         bool rope, int merge_n, int merge_rows, hipStream_t stream, int o_dt) {
   if (kp.num_items > 0) {
     const int grid = ceil_div(kp.num_items, kDecodeWaves);
-    if (c.kind == DecodeKernel::MFMA16)
+    if (c.kind == DecodeKernel::FP8Q)
+      FI_HIP_CALL(decode_fp8_launch(kp, o_dt, head_dim, grid, stream));
+    else if (c.kind == DecodeKernel::MFMA16)
       FI_HIP_CALL(decode_mfma16_launch(kp, q_dt, kv_dt, head_dim, rope, grid, stream));
     else if (c.kind == DecodeKernel::MFMA32)
       FI_HIP_CALL(decode_mfma_launch(kp, q_dt, kv_dt, head_dim, rope, grid, stream));
@@ -147,7 +156,7 @@ static int launch_decode(const DecodeKernelParams& kp, const DecodeChoice& c, in
   if (kp.split_kv) {
     // ref: VariableLengthMergeStates after the partition-kv kernel, decode.cuh:798-821
     MergeNParams mp{kp.tmp_o, kp.tmp_lse, kp.o_indptr, kp.o, kp.lse, merge_n, merge_rows,
-                    kp.num_qo_heads, head_dim, FI_DTYPE_F32, q_dt};
+                    kp.num_qo_heads, head_dim, FI_DTYPE_F32, o_dt};
     mp.sinks = kp.sinks;  // the decode kernels left the partial states without them
     FI_HIP_CALL(launch_merge_n(mp, stream));
   }
@@ -212,6 +221,16 @@ DecodeGridShape decode_grid_shape(int num_qo_heads, int num_kv_heads, int head_d
 
 bool decode_kernel_exists(int kv_dtype, int head_dim) { return find_launcher(kv_dtype, head_dim) != nullptr; }
 
+const char* decode_q_dtype_refusal(int q_dtype, int kv_dtype, int head_dim, int num_qo_heads, int num_kv_heads) {
+  if (q_dtype == FI_DTYPE_F16 || q_dtype == FI_DTYPE_BF16) return nullptr;
+  if (q_dtype != FI_DTYPE_FP8_E4M3) return "q dtype must be f16 / bf16, or fp8 e4m3 with an e4m3 cache";
+  if (kv_dtype != FI_DTYPE_FP8_E4M3) return "an fp8 e4m3 q dtype needs an e4m3 kv dtype";
+  if (head_dim != 64 && head_dim != 128) return "an fp8 e4m3 q dtype needs head_dim 64 or 128";
+  if (num_kv_heads > 0 && num_qo_heads / num_kv_heads > 16)
+    return "an fp8 e4m3 q dtype takes at most 16 query heads per kv head";
+  return nullptr;
+}
+
 }  // namespace fi
 
 using namespace fi;
@@ -229,8 +248,9 @@ extern "C" FI_API int fi_batch_decode_plan(void* float_ws, size_t float_ws_bytes
   FI_REQUIRE(num_kv_heads > 0 && num_qo_heads % num_kv_heads == 0,
              "batch_decode_plan: num_qo_heads (%d) must be a multiple of num_kv_heads (%d)",
              num_qo_heads, num_kv_heads);
-  FI_REQUIRE(q_dtype == FI_DTYPE_F16 || q_dtype == FI_DTYPE_BF16,
-             "batch_decode_plan: q dtype must be f16/bf16");
+  const char* const q_refusal = decode_q_dtype_refusal(q_dtype, kv_dtype, head_dim, num_qo_heads, num_kv_heads);
+  FI_REQUIRE(!q_refusal, "batch_decode_plan: %s (q dtype %d, kv dtype %d, head_dim %d)", q_refusal, q_dtype, kv_dtype,
+             head_dim);
   FI_REQUIRE(find_launcher(kv_dtype, head_dim) != nullptr,
              "batch_decode_plan: unsupported kv dtype %d / head_dim %d", kv_dtype, head_dim);
   for (int i = 0; i < batch_size; ++i)
@@ -325,8 +345,9 @@ namespace fi {
 template <class A>
 static int check_and_fill_decode(const char* who, const A& a, int kv_dt, int head_dim, int num_kv_heads,
                                  int page_size, int64_t kv_stride_page, int64_t kv_stride_n, int64_t kv_stride_h,
-                                 DecodeKernelParams& kp, DecodeChoice& choice) {
-  FI_REQUIRE(a.q_dtype == FI_DTYPE_F16 || a.q_dtype == FI_DTYPE_BF16, "%s: q dtype must be f16/bf16", who);
+                                 DecodeKernelParams& kp, DecodeChoice& choice, bool fp8_q) {
+  // fp8_q: the caller (fi_batch_decode_run_fp8) has checked the e4m3 q / e4m3 cache pair
+  FI_REQUIRE(fp8_q || a.q_dtype == FI_DTYPE_F16 || a.q_dtype == FI_DTYPE_BF16, "%s: q dtype must be f16/bf16", who);
   FI_REQUIRE(num_kv_heads > 0 && a.num_qo_heads % num_kv_heads == 0,
              "%s: num_qo_heads must be a multiple of num_kv_heads", who);
   FI_REQUIRE(find_launcher(kv_dt, head_dim), "%s: unsupported kv dtype %d / head_dim %d", who, kv_dt, head_dim);
@@ -415,9 +436,29 @@ static int launch_decode_multi(const DecodeKernelParams& kp, const fi_batch_deco
 
 // fi_batch_decode_run[_sinks] (q_len 1) and fi_batch_decode_run_multi (q_len > 1: the MULTI form of the 16x16x32
 // kernel on the same plan)
+// o_dtype: kOutputHasQDtype for those three, whose output has the (16-bit) q dtype; an FI_DTYPE (>= 0) for
+// fi_batch_decode_run_fp8, an e4m3 query over an e4m3 cache with an f16 / bf16 output on decode_fp8_kernel.h -- the same
+// plan, work list, partial states and merge.
+constexpr int kOutputHasQDtype = -1;
 static int batch_decode_run(void* float_ws, size_t float_ws_bytes, void* int_ws, size_t int_ws_bytes,
                             const int64_t* plan_info, int32_t plan_info_len, const fi_batch_decode_params_t* a,
-                            const float* sinks, int q_len, hipStream_t stream) {
+                            const float* sinks, int q_len, hipStream_t stream, int o_dtype) {
+  const bool fp8_q = o_dtype != kOutputHasQDtype;
+  if (fp8_q) {
+    FI_REQUIRE(a, "batch_decode_run_fp8: null params");
+    FI_REQUIRE(a->q_dtype == FI_DTYPE_FP8_E4M3 && a->kv.dtype == FI_DTYPE_FP8_E4M3,
+               "batch_decode_run_fp8: q dtype %d with kv dtype %d: takes an fp8 e4m3 query with an e4m3 cache only",
+               a->q_dtype, a->kv.dtype);
+    FI_REQUIRE(o_dtype == FI_DTYPE_F16 || o_dtype == FI_DTYPE_BF16,
+               "batch_decode_run_fp8: the output dtype must be f16 / bf16, got %d", o_dtype);
+    const char* const refusal =
+        decode_q_dtype_refusal(a->q_dtype, a->kv.dtype, a->kv.head_dim, a->num_qo_heads, a->kv.num_kv_heads);
+    FI_REQUIRE(!refusal, "batch_decode_run_fp8: %s", refusal);
+    FI_REQUIRE(a->pos_encoding_mode == FI_POS_NONE && !(a->logits_soft_cap > 0.f),
+               "batch_decode_run_fp8: fused RoPE, ALiBi and a logits soft cap are not supported with an fp8 query");
+    FI_REQUIRE(a->kv.indices && a->kv.stride_page < (1ll << 31) && a->kv.stride_n < (1ll << 31),
+               "batch_decode_run_fp8: needs a page table and page / token strides below 2^31 elements");
+  }
   // decode takes 16-bit queries only; with sinks that is said first, so before any launch
   FI_REQUIRE(!sinks || !a || a->q_dtype == FI_DTYPE_F16 || a->q_dtype == FI_DTYPE_BF16,
              "batch_decode_run: attention sinks need f16 / bf16 queries (q dtype %d)", a->q_dtype);
@@ -437,10 +478,11 @@ static int batch_decode_run(void* float_ws, size_t float_ws_bytes, void* int_ws,
   DecodeKernelParams kp;
   DecodeChoice choice;
   if (check_and_fill_decode("batch_decode_run", *a, kv.dtype, kv.head_dim, kv.num_kv_heads, kv.page_size,
-                            kv.stride_page, kv.stride_n, kv.stride_h, kp, choice))
+                            kv.stride_page, kv.stride_n, kv.stride_h, kp, choice, fp8_q))
     return 1;
   const size_t esz = dtype_size(kv.dtype);
-  FI_REQUIRE(((uintptr_t)a->q % 16) == 0 && (a->q_stride_n * 2) % 16 == 0 && (a->q_stride_h * 2) % 16 == 0,
+  const int q_esz = fp8_q ? 1 : 2;
+  FI_REQUIRE(((uintptr_t)a->q % 16) == 0 && (a->q_stride_n * q_esz) % 16 == 0 && (a->q_stride_h * q_esz) % 16 == 0,
              "batch_decode_run: q rows must be 16-byte aligned");
   FI_REQUIRE((kv.stride_n * esz) % 16 == 0 && (kv.stride_h * esz) % 16 == 0 &&
                  (kv.stride_page * esz) % 16 == 0 && ((uintptr_t)kv.k_data % 16) == 0 &&
@@ -513,7 +555,7 @@ static int batch_decode_run(void* float_ws, size_t float_ws_bytes, void* int_ws,
     return 0;
   }
   return launch_decode(kp, choice, a->q_dtype, kv.dtype, kv.head_dim, a->pos_encoding_mode == FI_POS_ROPE_LLAMA,
-                       /*merge_n=*/0, kv.batch_size, stream);
+                       /*merge_n=*/0, kv.batch_size, stream, fp8_q ? o_dtype : a->q_dtype);
 }
 
 extern "C" FI_API int fi_batch_decode_run(void* float_ws, size_t float_ws_bytes, void* int_ws,
@@ -529,7 +571,7 @@ extern "C" FI_API int fi_batch_decode_run_sinks(void* float_ws, size_t float_ws_
                                          int32_t plan_info_len, const fi_batch_decode_params_t* a,
                                          const float* sinks, fi_stream_t stream_) {
   return batch_decode_run(float_ws, float_ws_bytes, int_ws, int_ws_bytes, plan_info, plan_info_len, a, sinks,
-                          /*q_len=*/1, (hipStream_t)stream_);
+                          /*q_len=*/1, (hipStream_t)stream_, kOutputHasQDtype);
 }
 
 extern "C" FI_API int fi_batch_decode_run_multi(void* float_ws, size_t float_ws_bytes, void* int_ws,
@@ -538,7 +580,15 @@ extern "C" FI_API int fi_batch_decode_run_multi(void* float_ws, size_t float_ws_
                                          const float* sinks, int32_t q_len_per_req, fi_stream_t stream_) {
   FI_REQUIRE(q_len_per_req >= 1, "batch_decode_run: q_len_per_req must be >= 1, got %d", q_len_per_req);
   return batch_decode_run(float_ws, float_ws_bytes, int_ws, int_ws_bytes, plan_info, plan_info_len, a, sinks,
-                          q_len_per_req, (hipStream_t)stream_);
+                          q_len_per_req, (hipStream_t)stream_, kOutputHasQDtype);
+}
+
+extern "C" FI_API int fi_batch_decode_run_fp8(void* float_ws, size_t float_ws_bytes, void* int_ws,
+                                       size_t int_ws_bytes, const int64_t* plan_info, int32_t plan_info_len,
+                                       const fi_batch_decode_params_t* a, int32_t o_dtype, fi_stream_t stream_) {
+  FI_REQUIRE(o_dtype >= 0, "batch_decode_run_fp8: the output dtype must be f16 / bf16, got %d", o_dtype);
+  return batch_decode_run(float_ws, float_ws_bytes, int_ws, int_ws_bytes, plan_info, plan_info_len, a,
+                          /*sinks=*/nullptr, /*q_len=*/1, (hipStream_t)stream_, o_dtype);
 }
 
 extern "C" FI_API int fi_single_decode_run(const fi_single_decode_params_t* a, void* tmp, size_t tmp_bytes,
@@ -551,7 +601,8 @@ extern "C" FI_API int fi_single_decode_run(const fi_single_decode_params_t* a, v
   DecodeKernelParams kp;
   DecodeChoice choice;
   if (check_and_fill_decode("single_decode_run", *a, a->kv_dtype, a->head_dim, a->num_kv_heads, vpage,
-                            (int64_t)vpage * a->kv_stride_n, a->kv_stride_n, a->kv_stride_h, kp, choice))
+                            (int64_t)vpage * a->kv_stride_n, a->kv_stride_n, a->kv_stride_h, kp, choice,
+                            /*fp8_q=*/false))
     return 1;
   const size_t esz = dtype_size(a->kv_dtype);
   FI_REQUIRE(((uintptr_t)a->q % 16) == 0 && (a->q_stride_h * 2) % 16 == 0,
@@ -592,5 +643,5 @@ extern "C" FI_API int fi_single_decode_run(const fi_single_decode_params_t* a, v
   }
   // partial states are [nchunks, Hq, D] == dense [row=1, n=nchunks, Hq, D]
   return launch_decode(kp, choice, a->q_dtype, a->kv_dtype, a->head_dim, a->pos_encoding_mode == FI_POS_ROPE_LLAMA,
-                       nchunks, /*merge_rows=*/1, stream);
+                       nchunks, /*merge_rows=*/1, stream, a->q_dtype);
 }

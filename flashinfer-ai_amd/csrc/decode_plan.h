@@ -17,4 +17,9 @@ DecodeGridShape decode_grid_shape(int num_qo_heads, int num_kv_heads, int head_d
 // a batch-decode kernel exists for the cache dtype and head_dim
 bool decode_kernel_exists(int kv_dtype, int head_dim);
 
+// The q dtypes a plan is cut for: f16 / bf16 with any cache the kernels take, or e4m3 together with an e4m3 cache,
+// head_dim 64 / 128 and a GQA group of <= 16 heads (decode_fp8_kernel.h).  nullptr when the pair is served, else the
+// refusal (it names the "q dtype") for the planner's error.
+const char* decode_q_dtype_refusal(int q_dtype, int kv_dtype, int head_dim, int num_qo_heads, int num_kv_heads);
+
 }  // namespace fi

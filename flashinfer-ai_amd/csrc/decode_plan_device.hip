@@ -131,8 +131,10 @@ static int device_plan_layout(const fi_batch_decode_plan_device_params_t& a, Dev
   FI_REQUIRE(a.num_kv_heads > 0 && a.num_qo_heads % a.num_kv_heads == 0,
              "batch_decode_plan_device: num_qo_heads (%d) must be a multiple of num_kv_heads (%d)", a.num_qo_heads,
              a.num_kv_heads);
-  FI_REQUIRE(a.q_dtype == FI_DTYPE_F16 || a.q_dtype == FI_DTYPE_BF16,
-             "batch_decode_plan_device: q dtype must be f16/bf16");
+  const char* const q_refusal =
+      decode_q_dtype_refusal(a.q_dtype, a.kv_dtype, a.head_dim, a.num_qo_heads, a.num_kv_heads);
+  FI_REQUIRE(!q_refusal, "batch_decode_plan_device: %s (q dtype %d, kv dtype %d, head_dim %d)", q_refusal, a.q_dtype,
+             a.kv_dtype, a.head_dim);
   FI_REQUIRE(decode_kernel_exists(a.kv_dtype, a.head_dim),
              "batch_decode_plan_device: unsupported kv dtype %d / head_dim %d", a.kv_dtype, a.head_dim);
   // 32-bit token and page counts, as the decode kernels hold them

@@ -5,6 +5,8 @@ of FlashInfer v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-writte
 ``libfi_mi355.so`` (include/fi_mi355.h).  Only the path named in DESIGN.md is provided; of the fp4 matmuls that is
 ``mm_fp4`` in its MXFP4 mode (``use_nvfp4=False, block_size=32``), not nvfp4.  ``fused_moe_16bit`` holds
 ``cutlass_fused_moe`` in its unquantised f16 / bf16 mode, on the grouped 16-bit GEMM of csrc/gemm_16bit.hip.
+Batch decode (the wrappers and ``decode.trtllm_batch_decode_with_kv_cache``) also takes a float8_e4m3fn query over a
+float8_e4m3fn cache, on the fp8 matrix instructions (csrc/decode_fp8_kernel.h), with a float16 / bfloat16 output.
 """
 from . import _lib as _lib
 from . import activation as activation

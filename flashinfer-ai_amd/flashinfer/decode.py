@@ -5,8 +5,8 @@ device).
 
 Same names, arguments, defaults and error behaviour as the reference's ``flashinfer/decode.py``
 (single :389-578; wrapper :581-1410; CUDA-graph wrapper :1413-1480; plan-free :2054-2071, MLA :2298-2315), with the JIT
-module layer replaced by the ahead-of-time C ABI of libfi_mi355.so.  The kernels are csrc/decode_kernel.h and, for MLA,
-csrc/mla.hip.
+module layer replaced by the ahead-of-time C ABI of libfi_mi355.so.  The kernels are csrc/decode_kernel.h, for an fp8
+query over an fp8 cache csrc/decode_fp8_kernel.h and, for MLA, csrc/mla.hip.
 """
 from __future__ import annotations
 
@@ -37,6 +37,37 @@ from .utils import (
     dense_kv_dims,
     paged_kv,
 )
+
+
+_FP8 = (torch.float8_e4m3fn, torch.float8_e5m2)
+
+
+def _refuse_fp8_query_extras(name: str, q_dtype, kv_dtype, sinks=None, q_len: int = 1, pos_encoding_mode: str = "NONE",
+                             logits_soft_cap: Optional[float] = None) -> None:
+    """NotImplementedError, by name, for what the fp8-query decode kernel (csrc/decode_fp8_kernel.h) does not take: it
+    serves a float8_e4m3fn query over a float8_e4m3fn cache, one token per request, plain logits, no sinks."""
+    if torch.float8_e5m2 in (q_dtype, kv_dtype):
+        raise NotImplementedError(f"{name}: an fp8 query in float8_e5m2 (e5m2), or over an e5m2 cache, is not supported "
+                                  "(float8_e4m3fn query and cache)")
+    if kv_dtype != torch.float8_e4m3fn:
+        raise NotImplementedError(f"{name}: an fp8 query over a {kv_dtype} cache is not supported (an fp8 query needs "
+                                  "a float8_e4m3fn cache)")
+    if sinks is not None:
+        raise NotImplementedError(f"{name}: sinks with an fp8 query are not supported")
+    if q_len != 1:
+        raise NotImplementedError(f"{name}: q_len_per_req={q_len} with an fp8 query is not supported")
+    if pos_encoding_mode != "NONE":
+        raise NotImplementedError(f"{name}: pos_encoding_mode={pos_encoding_mode!r} with an fp8 query is not supported "
+                                  "(rotate before the cache)")
+    if logits_soft_cap is not None and logits_soft_cap > 0:
+        raise NotImplementedError(f"{name}: logits_soft_cap with an fp8 query is not supported")
+
+
+def _check_fp8_query_out(out: torch.Tensor, q: torch.Tensor) -> None:
+    """The output of an fp8-query run: the query's shape, float16 or bfloat16, contiguous."""
+    if out.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"out of an fp8 query must be float16 or bfloat16, got {out.dtype}")
+    check_shape_dtype_device(out, q.shape, out.dtype, q.device, "out")
 
 
 def fast_decode_plan(
@@ -289,6 +320,9 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
             if kv_data_type is None:
                 kv_data_type = data_type
         q_data_type, kv_data_type = canonicalize_qkv_dtypes(q_data_type, kv_data_type)
+        if q_data_type in _FP8:
+            _refuse_fp8_query_extras("BatchDecodeWithPagedKVCacheWrapper.plan", q_data_type, kv_data_type,
+                                     pos_encoding_mode=pos_encoding_mode, logits_soft_cap=logits_soft_cap)
         if fixed_split_size is not None and not self.use_tensor_cores:
             raise ValueError("fixed_split_size is only supported by tensor core decode for now.")
 
@@ -356,7 +390,11 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
     ) -> Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
         r"""Compute batch decode attention between ``q`` and the paged KV cache.
 
-        q : ``[batch_size, num_qo_heads, head_dim]``.
+        q : ``[batch_size, num_qo_heads, head_dim]``.  A float8_e4m3fn ``q`` (``plan(q_data_type=e4m3,
+            kv_data_type=e4m3)``, ``head_dim`` 64 / 128, at most 16 query heads per kv head) runs both products on the
+            fp8 matrix instructions (csrc/decode_fp8_kernel.h); ``q_scale * k_scale`` scale the logits, ``v_scale`` the
+            output, which is bfloat16 unless ``out`` is a float16 tensor.  With an fp8 query ``pos_encoding_mode !=
+            "NONE"``, ``logits_soft_cap``, ``sinks`` and ``q_len_per_req > 1`` are NotImplementedError at plan or run.
         paged_kv_cache : a 5-D tensor ``[max_num_pages, 2, page_size, num_kv_heads, head_dim]`` (NHD) /
             ``[max_num_pages, 2, num_kv_heads, page_size, head_dim]`` (HND), or a ``(k_cache, v_cache)``
             tuple of 4-D tensors.
@@ -384,6 +422,11 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
         if self._plan_info is None:
             raise RuntimeError("plan() must be called before run()")
         q_len = 1 if q_len_per_req is None else int(q_len_per_req)
+        fp8_q = self._cached_q_data_type in _FP8
+        if fp8_q:
+            _refuse_fp8_query_extras("BatchDecodeWithPagedKVCacheWrapper.run", self._cached_q_data_type,
+                                     self._cached_kv_data_type, sinks, q_len, self._pos_encoding_mode,
+                                     self._logits_soft_cap)
         if q_len != 1:
             self._check_multi_token(q_len)
         sinks_ptr = 0 if sinks is None else self._sinks_ptr(sinks, q)
@@ -395,14 +438,15 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
         if return_lse and lse is None:
             lse = torch.empty((q.size(0), q.size(1)), dtype=torch.float32, device=q.device)
         if out is None:
-            out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+            # an fp8 query writes bfloat16 unless `out` says float16 (the convention of the MLA call)
+            out = torch.empty(q.shape, dtype=torch.bfloat16 if fp8_q else q.dtype, device=q.device)
 
         # Steady-state calls (same tensors every layer / step) reuse the validated argument block.
         cache_t = paged_kv_cache if torch.is_tensor(paged_kv_cache) else paged_kv_cache[0]
         key = (q.data_ptr(), q.stride(), q.shape, cache_t.data_ptr(), cache_t.stride(), cache_t.shape,
                None if torch.is_tensor(paged_kv_cache) else paged_kv_cache[1].data_ptr(),
                out.data_ptr(), lse.data_ptr() if return_lse else 0, q_scale, k_scale, self._plan_serial, sinks_ptr,
-               q_len)
+               q_len, out.dtype)
         cached = self._run_cache
         if cached is not None and cached[0] == key:
             params = cached[1]
@@ -411,7 +455,12 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
                                             q_len)
             self._run_cache = (key, params, q, paged_kv_cache)  # keep the tensors alive with the pointers
         dev_index = q.device.index
-        if q_len != 1:
+        if fp8_q:
+            with torch.cuda.device(q.device):
+                status = self._lib_run_fp8(self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes,
+                                           self._plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, params,
+                                           _lib.fi_dtype(out.dtype), torch.cuda.current_stream().cuda_stream)
+        elif q_len != 1:
             with torch.cuda.device(q.device):
                 status = self._lib_run_multi(self._fws_ptr, self._fws_bytes, self._iws_ptr, self._iws_bytes,
                                              self._plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, params, sinks_ptr or None,
@@ -489,7 +538,10 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
             raise ValueError("q must be contiguous in head_dim")
         if lse is not None:
             check_shape_dtype_device(lse, (q.size(0), q.size(1)), torch.float32, q.device, "lse")
-        check_shape_dtype_device(out, q.shape, q.dtype, q.device, "out")
+        if q.dtype in _FP8:
+            _check_fp8_query_out(out, q)
+        else:
+            check_shape_dtype_device(out, q.shape, q.dtype, q.device, "out")
         if not out.is_contiguous():
             raise ValueError("out must be contiguous")
         alibi = None
@@ -509,6 +561,7 @@ class BatchDecodeWithPagedKVCacheWrapper(BatchAttentionWrapper):
         self._lib_run = _lib.lib().fi_batch_decode_run
         self._lib_run_sinks = _lib.lib().fi_batch_decode_run_sinks
         self._lib_run_multi = _lib.lib().fi_batch_decode_run_multi
+        self._lib_run_fp8 = _lib.lib().fi_batch_decode_run_fp8
         return C.byref(params)
 
     def forward_return_lse(
@@ -587,7 +640,10 @@ def trtllm_batch_decode_with_kv_cache(
     is no host synchronisation and no allocation that depends on a length, so the whole call can be captured in a
     graph; a replay plans again from what ``block_tables`` and ``seq_lens`` hold then.
 
-    query : ``[batch_size, num_qo_heads, head_dim]``, float16 or bfloat16.
+    query : ``[batch_size, num_qo_heads, head_dim]``, float16 or bfloat16; or float8_e4m3fn over a float8_e4m3fn
+        cache (``head_dim`` 64 / 128, at most 16 query heads per kv head; strides multiples of 16 elements): both
+        products then run on the fp8 matrix instructions from the cache bytes as they lie (csrc/decode_fp8_kernel.h),
+        with the reference's fp8 rounding of the probabilities, e4m3(448 * 2^(x - max)).
     kv_cache : one tensor ``[num_pages, 2, num_kv_heads, page_size, head_dim]`` (the HND layout), or a ``(k, v)`` tuple
         of ``[num_pages, num_kv_heads, page_size, head_dim]`` tensors.
     workspace_buffer : one buffer on the query's device; the work list, the page table and the f32 partial states are
@@ -597,35 +653,52 @@ def trtllm_batch_decode_with_kv_cache(
     seq_lens : int32 (or uint32) ``[batch_size]`` on the device.  A length beyond ``max_blocks * page_size`` is CLAMPED
         to it (the host never sees the value, so it cannot be refused); a length of 0 gives a zero output row.
     max_seq_len : checked against ``max_blocks * page_size``; otherwise unused.
-    bmm1_scale : the full scale of the logits (``sm_scale``).  bmm2_scale : multiplies the output.
+    bmm1_scale : the full scale of the logits (``sm_scale``; with an fp8 query the caller folds ``q_scale * k_scale``
+        into it).  bmm2_scale : multiplies the output (``v_scale``).
     window_left : sliding window, ``-1`` for none.  Chunks are cut over all pages; the kernel masks.
-    out : optional output tensor of the query's shape and dtype.  out_dtype : the query's dtype, if given.
+    out : optional output tensor of the query's shape and dtype.  out_dtype : the query's dtype, if given.  With an
+        fp8 query ``out`` or ``out_dtype`` must name float16 or bfloat16.
     sinks : optional float32 ``[num_qo_heads]`` attention-sink logits (or a one-element list holding them).
     enable_pdl : accepted and ignored.
 
-    Not offered (NotImplementedError): ``q_len_per_req != 1``, an fp8 query, ``out_dtype="nvfp4"`` / an FP4Tensor
-    ``out`` / ``o_sf_scale`` / ``o_sf_vec_size``, and the ``[num_pages, 1, ...]`` cache with K and V shared.
+    Not offered (NotImplementedError): ``q_len_per_req != 1``, an fp8 query over a cache that is not float8_e4m3fn,
+    a float8_e5m2 query, ``sinks`` with an fp8 query, an fp8 query with neither ``out`` nor ``out_dtype`` (the reference
+    would allocate an fp8 output: pass ``out_dtype``), ``out_dtype="nvfp4"`` / an FP4Tensor ``out`` / ``o_sf_scale`` /
+    ``o_sf_vec_size``, and the ``[num_pages, 1, ...]`` cache with K and V shared.
     """
     if q_len_per_req is not None and q_len_per_req != 1:
         raise NotImplementedError(f"trtllm_batch_decode_with_kv_cache: q_len_per_req={q_len_per_req} is not "
                                   "supported (one query token per request)")
-    if query.dtype in (torch.float8_e4m3fn, torch.float8_e5m2):
-        raise NotImplementedError("trtllm_batch_decode_with_kv_cache: an fp8 query is not supported "
-                                  "(float16 / bfloat16)")
-    _refuse_fp4_out_and_shared_kv("trtllm_batch_decode_with_kv_cache", kv_cache, out, out_dtype, o_sf_scale,
-                                  o_sf_vec_size)
+    who = "trtllm_batch_decode_with_kv_cache"
+    fp8_q = query.dtype in _FP8
+    if fp8_q:
+        cache0 = kv_cache if torch.is_tensor(kv_cache) else kv_cache[0]
+        _refuse_fp8_query_extras(who, query.dtype, cache0.dtype, sinks)
+        if out is None and out_dtype is None:
+            raise NotImplementedError(f"{who}: an fp8 query with neither out nor out_dtype would get an fp8 output, "
+                                      "which is not supported: pass out_dtype=torch.bfloat16 (or float16)")
+    _refuse_fp4_out_and_shared_kv(who, kv_cache, out, out_dtype, o_sf_scale, o_sf_vec_size)
     for name, t in (("query", query), ("workspace_buffer", workspace_buffer), ("block_tables", block_tables),
                     ("seq_lens", seq_lens)):
         _lib.require_gpu_tensor(t, name)
     k_cache, v_cache = _hnd_cache_views(kv_cache)
-    if query.dtype not in (torch.float16, torch.bfloat16) or query.dim() != 3 or query.stride(-1) != 1:
-        raise ValueError("query must be a float16 / bfloat16 [batch_size, num_qo_heads, head_dim] tensor, contiguous "
-                         "in head_dim")
+    if query.dtype not in (torch.float16, torch.bfloat16, torch.float8_e4m3fn) or query.dim() != 3 \
+            or query.stride(-1) != 1:
+        raise ValueError("query must be a float16 / bfloat16 / float8_e4m3fn [batch_size, num_qo_heads, head_dim] "
+                         "tensor, contiguous in head_dim")
     batch_size, num_qo_heads, head_dim = query.shape
     seq_lens = _check_block_tables_and_lens(block_tables, seq_lens, workspace_buffer, batch_size)
-    if out_dtype is not None and canonicalize_torch_dtype(out_dtype) != query.dtype:
-        raise ValueError(f"out_dtype {out_dtype} differs from the query's {query.dtype}")
-    out = _out_or_empty(out, query.shape, query.dtype, query.device)
+    if fp8_q:
+        o_dtype = out.dtype if out_dtype is None else canonicalize_torch_dtype(out_dtype)
+        if o_dtype in _FP8:
+            raise NotImplementedError(f"{who}: an fp8 output ({o_dtype}) of an fp8 query is not supported")
+        if o_dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"an fp8 query needs out or out_dtype to name float16 or bfloat16, got {o_dtype}")
+    else:
+        o_dtype = query.dtype
+        if out_dtype is not None and canonicalize_torch_dtype(out_dtype) != query.dtype:
+            raise ValueError(f"out_dtype {out_dtype} differs from the query's {query.dtype}")
+    out = _out_or_empty(out, query.shape, o_dtype, query.device)
     sinks = _one_sinks_tensor(sinks, num_qo_heads, query.device)
 
     max_blocks = block_tables.shape[1]
@@ -642,8 +715,7 @@ def trtllm_batch_decode_with_kv_cache(
         batch_size=batch_size, max_blocks=max_blocks, page_size=page_size, num_qo_heads=num_qo_heads,
         num_kv_heads=num_kv_heads, head_dim=head_dim, q_dtype=_lib.fi_dtype(query.dtype),
         kv_dtype=_lib.fi_dtype(k_cache.dtype), max_grid_hint=0)
-    _device_plan_regions(workspace_buffer, plan, "fi_batch_decode_plan_device_workspace",
-                         "trtllm_batch_decode_with_kv_cache")
+    _device_plan_regions(workspace_buffer, plan, "fi_batch_decode_plan_device_workspace", who)
     plan_info = (C.c_int64 * _lib.FI_DECODE_PLAN_INFO_LEN)()
     csr = (C.c_int64 * 3)()
     params = _lib.fi_batch_decode_params_t(
@@ -654,14 +726,18 @@ def trtllm_batch_decode_with_kv_cache(
     lib = _lib.lib()
     with torch.cuda.device(query.device):
         stream = _lib.current_stream(query.device)
-        _lib.check(lib.fi_batch_decode_plan_device(C.byref(plan), plan_info, csr, stream),
-                   "trtllm_batch_decode_with_kv_cache")
+        _lib.check(lib.fi_batch_decode_plan_device(C.byref(plan), plan_info, csr, stream), who)
         # the page table the planner's kernels write, in place of the one plan() would have been given
         params.kv.indptr, params.kv.indices, params.kv.last_page_len = (plan.int_ws + off for off in csr)
-        _lib.check(lib.fi_batch_decode_run_sinks(plan.float_ws, plan.float_ws_bytes, plan.int_ws, plan.int_ws_bytes,
+        if fp8_q:
+            status = lib.fi_batch_decode_run_fp8(plan.float_ws, plan.float_ws_bytes, plan.int_ws, plan.int_ws_bytes,
                                                  plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, C.byref(params),
-                                                 _lib.ptr(sinks), stream),
-                   "trtllm_batch_decode_with_kv_cache")
+                                                 _lib.fi_dtype(o_dtype), stream)
+        else:
+            status = lib.fi_batch_decode_run_sinks(plan.float_ws, plan.float_ws_bytes, plan.int_ws, plan.int_ws_bytes,
+                                                   plan_info, _lib.FI_DECODE_PLAN_INFO_LEN, C.byref(params),
+                                                   _lib.ptr(sinks), stream)
+        _lib.check(status, who)
     if bmm2_scale != 1.0:
         out *= bmm2_scale
     return out

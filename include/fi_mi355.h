@@ -152,12 +152,12 @@ typedef struct fi_batch_decode_params {
   const void* q; /* [batch, num_qo_heads, head_dim], strides below */
   int64_t q_stride_n, q_stride_h;
   fi_paged_kv_t kv;
-  void* o;    /* [batch, num_qo_heads, head_dim] contiguous, dtype = q dtype */
+  void* o;    /* [batch, num_qo_heads, head_dim] contiguous, dtype = q dtype (fi_batch_decode_run_fp8: its o_dtype) */
   float* lse; /* optional [batch, num_qo_heads] */
   const float* alibi_slopes;    /* [num_qo_heads], used when pos_encoding_mode == FI_POS_ALIBI */
   const int32_t* q_rope_offset; /* optional [batch]; NULL = kv_len-1 (ref: decode.cuh:445-450) */
   int32_t num_qo_heads;
-  int32_t q_dtype;           /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+  int32_t q_dtype;           /* FI_DTYPE_F16 / FI_DTYPE_BF16; FI_DTYPE_FP8_E4M3 for fi_batch_decode_run_fp8 */
   int32_t pos_encoding_mode; /* fi_pos_encoding_mode */
   int32_t window_left;       /* -1 = full */
   float logits_soft_cap;     /* 0 = off */
@@ -192,9 +192,24 @@ FI_API int fi_batch_decode_run_multi(void* float_ws, size_t float_ws_bytes, void
                               const fi_batch_decode_params_t* params, const float* sinks, int32_t q_len_per_req,
                               fi_stream_t stream);
 
+/* fi_batch_decode_run with an fp8 QUERY: params->q_dtype == FI_DTYPE_FP8_E4M3 over an e4m3 cache (params->kv.dtype),
+ * head_dim 64 / 128, num_qo_heads / num_kv_heads <= 16, pos_encoding_mode FI_POS_NONE, no logits soft cap; o (and the
+ * merge of a split plan) is written in `o_dtype`, FI_DTYPE_F16 or FI_DTYPE_BF16.  Any other combination is an error
+ * before any launch.  The caller folds q_scale * k_scale into sm_scale and applies v_scale to the output.  Both
+ * products run on the fp8 matrix instructions from the cache bytes as they lie (csrc/decode_fp8_kernel.h); P is
+ * rounded as the reference's fp8 attention rounds it, e4m3(448 * 2^(x - m)) with the row sum from the unrounded P.
+ * The plan is fi_batch_decode_plan / fi_batch_decode_plan_device with the same dtype pair (both accept an e4m3
+ * q_dtype only together with an e4m3 kv_dtype); the work list, the f32 partial states and the merge launch are those of
+ * fi_batch_decode_run, FI_DP_UNIFORM_CHUNKS is ignored (always two launches for a split plan).  The query's strides are
+ * in elements (= bytes) and its rows 16-byte aligned.  Capturable like fi_batch_decode_run. */
+FI_API int fi_batch_decode_run_fp8(void* float_ws, size_t float_ws_bytes, void* int_ws, size_t int_ws_bytes,
+                            const int64_t* plan_info, int32_t plan_info_len,
+                            const fi_batch_decode_params_t* params, int32_t o_dtype, fi_stream_t stream);
+
 /* Device-side planning: the plan of fi_batch_decode_plan(enable_cuda_graph = 1, window_left = -1), written by kernels
  * on `stream` from lengths that stay on the device.  No host read-back, no copy, no synchronisation: the call may be
- * captured in a graph together with the fi_batch_decode_run[_sinks] that follows it, and a replay plans again from
+ * captured in a graph together with the fi_batch_decode_run[_sinks] (or, for an e4m3 q_dtype over an e4m3 kv_dtype,
+ * the fi_batch_decode_run_fp8) that follows it, and a replay plans again from
  * whatever `block_tables` and `seq_lens` hold then.  (The reference's plan-free decode entry,
  * trtllm_batch_decode_with_kv_cache, flashinfer/decode.py:2054-2071, takes the same two tensors.)
  *
@@ -215,7 +230,8 @@ FI_API int fi_batch_decode_run_multi(void* float_ws, size_t float_ws_bytes, void
  * FI_DP_KV_CHUNK_SIZE_PTR_OFFSET (tokens per chunk, which the decode kernels read through kv_chunk_size_ptr, then the
  * number of valid work items).
  * Errors (fi_last_error) before any launch: null tensors, batch_size <= 0, a workspace too small (the message states
- * the bytes needed), an unsupported head_dim / dtype. */
+ * the bytes needed), an unsupported head_dim / dtype (an e4m3 q_dtype is planned only together with an e4m3 kv_dtype,
+ * head_dim 64 / 128 and at most 16 query heads per kv head; the message names the "q dtype"). */
 typedef struct fi_batch_decode_plan_device_params {
   const int32_t* block_tables; /* [batch_size, max_blocks] device, rows block_tables_stride elements apart */
   const int32_t* seq_lens;     /* [batch_size] device: kv tokens per request */
