@@ -1,10 +1,12 @@
 """fp8 groupwise-scaled GEMM operators (``gemm_fp8_nt_groupwise``, ``group_gemm_fp8_nt_groupwise``), the grouped
 GEMM with MXFP8 activations and MXFP4 weights (``group_gemm_mxfp8_mxfp4_nt_groupwise``) and the dense MXFP4 x MXFP4
-matmul (``mm_fp4`` in its ``use_nvfp4=False`` mode).
+matmul (``mm_fp4`` in its ``use_nvfp4=False`` mode), and the masked batched fp8 GEMM of expert-parallel decode
+(``batch_deepgemm_fp8_nt_groupwise``).
 
-API of the reference's ``flashinfer/gemm.py`` (:2321-2484, :2657-2811, :2814-2949, :2012-2160); the kernels are
+API of the reference's ``flashinfer/gemm.py`` (:2321-2484, :2657-2811, :2814-2949, :2012-2160, :3121-3256); the kernels are
 csrc/gemm.hip (MFMA fp8, two-level accumulation per 128-wide K block), csrc/gemm_mxfp4.hip and csrc/mm_fp4.hip
-(block-scaled MFMA, the E8M0 scale bytes ride the instruction's scale operands).  NVIDIA-only knobs (``mma_sm``, ``backend``, tile shapes, ``swap_ab``)
+(block-scaled MFMA, the E8M0 scale bytes ride the instruction's scale operands) and csrc/gemm_masked.hip (weight
+streaming, tile list built on the device).  NVIDIA-only knobs (``mma_sm``, ``backend``, tile shapes, ``swap_ab``)
 are accepted and ignored.
 """
 from __future__ import annotations
@@ -379,4 +381,87 @@ def mm_fp4(
     fi_mm_mxfp4 = _lib.lib().fi_mm_mxfp4
     with torch.cuda.device(a.device):
         _lib.check(fi_mm_mxfp4(C.byref(p), _lib.current_stream(a.device)), "mm_fp4")
+    return out
+
+
+def batch_deepgemm_fp8_nt_groupwise(
+    a: torch.Tensor,  # (batch_size, m, k)
+    b: torch.Tensor,  # (batch_size, n, k)
+    a_scale: torch.Tensor,  # (batch_size, m, k // block_size)
+    b_scale: torch.Tensor,  # (batch_size, n // block_size, k // block_size)
+    masked_m: torch.Tensor,  # (batch_size, )
+    expected_m: int,
+    scale_granularity_mnk: Tuple[int, int, int] = (1, 128, 128),
+    out: Optional[torch.Tensor] = None,  # (batch_size, m, n)
+    out_dtype: Optional[torch.dtype] = None,
+) -> torch.Tensor:
+    r"""Masked batched fp8 GEMM with groupwise scales, the layout of a low-latency expert-parallel dispatch (ref:
+    flashinfer/gemm.py:3121-3256): every expert ``e`` owns ``m`` rows of ``a`` and ``out`` and ``masked_m[e]`` says how
+    many leading rows are real.  With ``r = min(masked_m[e], m)``::
+
+        out[e, :r] = (a[e, :r] * a_scale[e, :r] per 128-block) @ (b[e] * b_scale[e] per block).T
+
+    f32 accumulation, every 128-wide k block's product scaled before it is added, one rounding.  The kernel is
+    csrc/gemm_masked.hip (weight streaming, row tiles of 16 to 128 tokens, its tile list built from ``masked_m`` on the
+    device).
+
+    a : ``(E, m, k)`` float8_e4m3fn; rows ``r .. m - 1`` of ``a[e]`` and ``a_scale[e]`` are not read.
+    b : ``(E, n, k)`` float8_e4m3fn.
+    a_scale : ``(E, m, k // 128)`` float32; b_scale : ``(E, n // 128, k // 128)`` float32.
+    masked_m : ``(E,)`` int32 on the device; the host never reads it, so the call can be captured into a graph and a
+        replay follows what ``masked_m`` holds then.
+    expected_m : a host-side hint (>= 1) for the rows per expert; it picks the row-tile height and never the result.
+    scale_granularity_mnk : only ``(1, 128, 128)``.
+    out / out_dtype : ``(E, m, n)`` bf16 (default) or fp16; rows ``r .. m - 1`` of ``out[e]`` keep what they held.
+    ``n % 128 == 0``, ``k % 128 == 0``, ``E <= 1024``; every tensor contiguous.
+    """
+    tensors = ((a, "a"), (b, "b"), (a_scale, "a_scale"), (b_scale, "b_scale"), (masked_m, "masked_m"))
+    if tuple(scale_granularity_mnk) != (1, 128, 128):
+        raise NotImplementedError(f"scale_granularity_mnk = {tuple(scale_granularity_mnk)}: only (1, 128, 128) is provided")
+    if a.dtype == torch.float8_e5m2 or b.dtype == torch.float8_e5m2:
+        raise NotImplementedError("a / b in float8_e5m2 are not provided: only float8_e4m3fn")
+    if a.dtype != torch.float8_e4m3fn or b.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"a and b must be float8_e4m3fn, got {a.dtype} and {b.dtype}")
+    if a.ndim != 3 or b.ndim != 3:
+        raise ValueError(f"a must be (E, m, k) and b (E, n, k), got a.shape = {tuple(a.shape)}, b.shape = {tuple(b.shape)}")
+    num_experts, m, k = a.shape
+    n = b.shape[1]
+    if b.shape[0] != num_experts or b.shape[2] != k:
+        raise ValueError(f"Shape mismatch. a.shape = {tuple(a.shape)}, b.shape = {tuple(b.shape)}")
+    if n % 128 != 0 or k % 128 != 0:
+        raise ValueError(f"n = {n} and k = {k} must be multiples of 128")
+    if a_scale.dtype != torch.float32 or b_scale.dtype != torch.float32:
+        raise ValueError(f"a_scale and b_scale must be float32, got {a_scale.dtype} and {b_scale.dtype}")
+    if tuple(a_scale.shape) != (num_experts, m, k // 128):
+        raise ValueError(f"a_scale must be {(num_experts, m, k // 128)}, got {tuple(a_scale.shape)}")
+    if tuple(b_scale.shape) != (num_experts, n // 128, k // 128):
+        raise ValueError(f"b_scale must be {(num_experts, n // 128, k // 128)}, got {tuple(b_scale.shape)}")
+    if masked_m.dtype != torch.int32 or tuple(masked_m.shape) != (num_experts,):
+        raise ValueError(f"masked_m must be int32 of shape {(num_experts,)}, got {masked_m.dtype} {tuple(masked_m.shape)}")
+    if int(expected_m) < 1:
+        raise ValueError(f"expected_m = {expected_m} must be at least 1")
+    if out is None:
+        out_dtype = out_dtype or torch.bfloat16
+    else:
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise ValueError(f"Output dtype mismatch. Expected {out_dtype}, got {out.dtype}.")
+        out_dtype = out.dtype
+        tensors += ((out, "out"),)
+        if tuple(out.shape) != (num_experts, m, n):
+            raise ValueError(f"out must be {(num_experts, m, n)}, got {tuple(out.shape)}")
+    _validate_fp8_output_dtype(out_dtype)
+    for t, name in tensors:
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous, got strides {t.stride()}")
+    for t, name in tensors:
+        _lib.require_gpu_tensor(t, name)
+    if out is None:
+        out = torch.empty((num_experts, m, n), device=a.device, dtype=out_dtype)
+    p = _lib.fi_batch_gemm_fp8_nt_masked_params_t(
+        a=a.data_ptr(), b=b.data_ptr(), a_scale=a_scale.data_ptr(), b_scale=b_scale.data_ptr(), d=out.data_ptr(),
+        masked_m=masked_m.data_ptr(), a_stride_e=m * k, b_stride_e=n * k, d_stride_e=m * n, num_experts=num_experts,
+        m=m, n=n, k=k, expected_m=int(expected_m), d_dtype=_lib.fi_dtype(out_dtype))
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.lib().fi_batch_gemm_fp8_nt_masked(C.byref(p), _lib.current_stream(a.device)),
+                   "batch_deepgemm_fp8_nt_groupwise")
     return out

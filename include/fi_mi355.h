@@ -1389,6 +1389,36 @@ typedef struct fi_moe_finalize_16bit_params {
 
 FI_API int fi_moe_finalize_16bit(const fi_moe_finalize_16bit_params_t* params, fi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Masked batched fp8 GEMM for expert-parallel MoE decode (csrc/gemm_masked.hip; ref: batch_deepgemm_fp8_nt_groupwise,
+ * flashinfer/gemm.py:3121-3256, over deep_gemm.py m_grouped_fp8_gemm_nt_masked).  Every expert owns m rows of a and d
+ * whether they are used or not; masked_m[e], on the DEVICE, says how many leading rows are real.  With
+ * r = min(masked_m[e], m), for i < r:
+ *   d[e, i, j] = sum_kb a_scale[e, i, kb] * b_scale[e, j / 128, kb] * sum_{k in 128-block kb} a[e, i, k] * b[e, j, k]
+ * f32 accumulation, one round-to-nearest to the output dtype.  Rows r .. m - 1 of a and a_scale are NOT read (they may
+ * be uninitialised) and those of d are NOT written; masked_m[e] <= 0 leaves expert e alone.
+ *   a: (E, m, k) e4m3, b: (E, n, k) e4m3, a_scale: (E, m, k / 128) f32, b_scale: (E, n / 128, k / 128) f32,
+ *   d: (E, m, n) f16 / bf16, all contiguous: the expert strides (in elements) are carried and must be m k, n k, m n.
+ *   n % 128 == 0, k % 128 == 0, k > 0, E <= 1024; a / b 16-byte, d 8-byte, scales and masked_m 4-byte aligned.
+ * expected_m >= 1 is a hint that picks the row-tile height (16 / 32 / 64 / 128: the smallest that holds it); the result
+ * does not depend on it, bit for bit.  One launch of a fixed grid that builds its tile list from masked_m on the device:
+ * no workspace, no host state, no host read of masked_m, no synchronisation -- the call may be captured into a graph
+ * and a replay follows what masked_m holds then.  E == 0, m == 0 or n == 0 returns 0 without a launch. */
+typedef struct fi_batch_gemm_fp8_nt_masked_params {
+  const void* a;
+  const void* b;
+  const float* a_scale;
+  const float* b_scale;
+  void* d;
+  const int32_t* masked_m; /* [num_experts] device */
+  int64_t a_stride_e, b_stride_e, d_stride_e;
+  int32_t num_experts, m, n, k;
+  int32_t expected_m;
+  int32_t d_dtype; /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+} fi_batch_gemm_fp8_nt_masked_params_t;
+
+FI_API int fi_batch_gemm_fp8_nt_masked(const fi_batch_gemm_fp8_nt_masked_params_t* params, fi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
