@@ -7,6 +7,7 @@ of FlashInfer v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-writte
 ``cutlass_fused_moe`` in its unquantised f16 / bf16 mode, on the grouped 16-bit GEMM of csrc/gemm_16bit.hip.
 Batch decode (the wrappers and ``decode.trtllm_batch_decode_with_kv_cache``) also takes a float8_e4m3fn query over a
 float8_e4m3fn cache, on the fp8 matrix instructions (csrc/decode_fp8_kernel.h), with a float16 / bfloat16 output.
+``SegmentGEMMWrapper`` is the float16 / bfloat16 segment GEMM of multi-LoRA serving, on csrc/segment_gemm.hip.
 """
 from . import _lib as _lib
 from . import activation as activation
@@ -61,6 +62,7 @@ from .fused_moe import trtllm_fp4_block_scale_moe as trtllm_fp4_block_scale_moe
 from .fused_moe import (
     trtllm_fp4_block_scale_routed_moe as trtllm_fp4_block_scale_routed_moe,
 )
+from .gemm import SegmentGEMMWrapper as SegmentGEMMWrapper
 from .gemm import gemm_fp8_nt_groupwise as gemm_fp8_nt_groupwise
 from .gemm import group_gemm_fp8_nt_groupwise as group_gemm_fp8_nt_groupwise
 from .gemm import mm_fp4 as mm_fp4

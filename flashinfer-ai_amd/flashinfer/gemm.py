@@ -1,12 +1,14 @@
 """fp8 groupwise-scaled GEMM operators (``gemm_fp8_nt_groupwise``, ``group_gemm_fp8_nt_groupwise``), the grouped
 GEMM with MXFP8 activations and MXFP4 weights (``group_gemm_mxfp8_mxfp4_nt_groupwise``) and the dense MXFP4 x MXFP4
-matmul (``mm_fp4`` in its ``use_nvfp4=False`` mode), and the masked batched fp8 GEMM of expert-parallel decode
-(``batch_deepgemm_fp8_nt_groupwise``).
+matmul (``mm_fp4`` in its ``use_nvfp4=False`` mode), the masked batched fp8 GEMM of expert-parallel decode
+(``batch_deepgemm_fp8_nt_groupwise``), and the f16 / bf16 segment GEMM of multi-LoRA serving (``SegmentGEMMWrapper``).
 
-API of the reference's ``flashinfer/gemm.py`` (:2321-2484, :2657-2811, :2814-2949, :2012-2160, :3121-3256); the kernels are
+API of the reference's ``flashinfer/gemm.py`` (:2321-2484, :2657-2811, :2814-2949, :2012-2160, :3121-3256, :1300-1553); the
+kernels are
 csrc/gemm.hip (MFMA fp8, two-level accumulation per 128-wide K block), csrc/gemm_mxfp4.hip and csrc/mm_fp4.hip
 (block-scaled MFMA, the E8M0 scale bytes ride the instruction's scale operands) and csrc/gemm_masked.hip (weight
-streaming, tile list built on the device).  NVIDIA-only knobs (``mma_sm``, ``backend``, tile shapes, ``swap_ab``)
+streaming, tile list built on the device) and csrc/segment_gemm.hip (skinny grouped GEMM in two forms, segment records
+built on the device).  NVIDIA-only knobs (``mma_sm``, ``backend``, tile shapes, ``swap_ab``)
 are accepted and ignored.
 """
 from __future__ import annotations
@@ -465,3 +467,124 @@ def batch_deepgemm_fp8_nt_groupwise(
         _lib.check(_lib.lib().fi_batch_gemm_fp8_nt_masked(C.byref(p), _lib.current_stream(a.device)),
                    "batch_deepgemm_fp8_nt_groupwise")
     return out
+
+
+class SegmentGEMMWrapper:
+    r"""Segment GEMM for multi-LoRA batches (ref: flashinfer/gemm.py:1300-1553): the rows of ``x`` are cut into
+    ``batch_size`` consecutive segments and segment ``i`` is multiplied by its own weight::
+
+        y[seg i] = x[seg i] @ W[weight_indices[i]]        (W[i] without weight_indices)
+
+    in float16 or bfloat16 with f32 accumulation and one rounding.  The kernel is csrc/segment_gemm.hip: a long-k form
+    for the shrink step (``d_in -> r``) and a wide-n form for the expand step (``r -> d_out``) and every other shape,
+    chosen from ``(d_in, d_out)`` alone.
+
+    >>> workspace_buffer = torch.empty(128 * 1024 * 1024, dtype=torch.int8, device="cuda")
+    >>> segment_gemm = SegmentGEMMWrapper(workspace_buffer)
+    >>> seg_lens = torch.tensor([1, 2, 3, 4], dtype=torch.int64)
+    >>> x = torch.randn(10, 128, device="cuda", dtype=torch.float16)
+    >>> weights = torch.randn(4, 256, 128, device="cuda", dtype=torch.float16)  # column major
+    >>> y = segment_gemm.run(x, weights, 4, True, seg_lens=seg_lens)             # y[1:3] == x[1:3] @ weights[1].T
+    """
+
+    def __init__(self, float_workspace_buffer: torch.Tensor, backend: str = "auto") -> None:
+        r"""``float_workspace_buffer`` is kept for the reference's signature; the kernels need only the 1 MiB int
+        workspace allocated here on the same device (the segment records).  ``backend`` is accepted and ignored."""
+        self._int_workspace_buffer = torch.empty((1024 * 1024,), dtype=torch.int8, device=float_workspace_buffer.device)
+        self._float_workspace_buffer = float_workspace_buffer
+        self.backend = backend
+
+    def reset_workspace_buffer(self, float_workspace_buffer: torch.Tensor, int_workspace_buffer: torch.Tensor) -> None:
+        self._float_workspace_buffer = float_workspace_buffer
+        self._int_workspace_buffer = int_workspace_buffer
+
+    def run(
+        self,
+        x: torch.Tensor,
+        weights: torch.Tensor,
+        batch_size: int,
+        weight_column_major: bool,
+        out: Optional[torch.Tensor] = None,
+        seg_lens: Optional[torch.Tensor] = None,
+        seg_indptr: Optional[torch.Tensor] = None,
+        weight_indices: Optional[torch.Tensor] = None,
+    ) -> torch.Tensor:
+        r"""x : ``(rows, d_in)`` float16 / bfloat16, contiguous.
+        weights : ``(num_weights, d_out, d_in)`` if ``weight_column_major`` else ``(num_weights, d_in, d_out)``, the dtype
+            of ``x``, contiguous (no silent copy of a weight tensor).  Both layouts are read as they lie.
+        batch_size : the number of segments.
+        out : ``(rows, d_out)``, the dtype of ``x``; allocated with ``torch.empty`` when not given.
+        seg_lens / seg_indptr : int64 ``(batch_size,)`` resp. ``(batch_size + 1,)``; one of them, ``seg_indptr`` wins.
+        weight_indices : optional int64 ``(batch_size,)``.
+        The three index tensors may live on the CPU: they are moved to ``x.device``, and that is the only copy -- nothing
+        is read back, so a call with device tensors can be captured into a graph.
+
+        ``d_in`` and ``d_out`` must be multiples of 8 (16-byte rows, as in the reference).  Rows of ``out`` that no
+        segment covers (at or past ``seg_indptr[-1]``) are NOT written; the reference zero-fills them.  Segment bounds are
+        clamped into ``[0, rows]``, a segment of negative length is empty, and a segment whose weight id is outside
+        ``[0, num_weights)`` is skipped, its rows not written; none of this is reported."""
+        if seg_lens is None and seg_indptr is None:
+            raise ValueError("Either seg_lens or seg_indptr should be provided.")
+        if x.dtype in _FP8:
+            raise NotImplementedError("float8 x (the reference's sm90-only mode) is not provided: float16 / bfloat16 only")
+        if x.dtype == torch.float32:
+            raise NotImplementedError("float32 x is not provided: float16 / bfloat16 only")
+        if x.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"x must be float16 or bfloat16, got {x.dtype}")
+        if weights.dtype != x.dtype or (out is not None and out.dtype != x.dtype):
+            raise ValueError(f"x, weights and out must share one dtype, got {x.dtype}, {weights.dtype}"
+                             + (f" and {out.dtype}" if out is not None else ""))
+        if x.ndim != 2 or weights.ndim != 3:
+            raise ValueError(f"x must be (rows, d_in) and weights 3-D, got {tuple(x.shape)} and {tuple(weights.shape)}")
+        rows, d_in = x.shape
+        num_weights = weights.shape[0]
+        w_in, d_out = (weights.shape[2], weights.shape[1]) if weight_column_major else (weights.shape[1], weights.shape[2])
+        if w_in != d_in:
+            raise ValueError(f"Shape mismatch. x.shape = {tuple(x.shape)}, weights.shape = {tuple(weights.shape)}, "
+                             f"weight_column_major = {bool(weight_column_major)}")
+        if d_in % 8 != 0 or d_out % 8 != 0:
+            raise ValueError(f"d_in = {d_in} and d_out = {d_out} must be multiples of 8")
+        if out is not None and tuple(out.shape) != (rows, d_out):
+            raise ValueError(f"Output tensor shape mismatch, expected {(rows, d_out)}, got {tuple(out.shape)}")
+        if not weights.is_contiguous():
+            raise ValueError(f"weights must be contiguous (no silent copy of a weight tensor), got strides {weights.stride()}")
+        if not x.is_contiguous() or (out is not None and not out.is_contiguous()):
+            raise ValueError("x and out must be contiguous")
+        batch_size = int(batch_size)
+        for t, name, length in ((seg_indptr, "seg_indptr", batch_size + 1),
+                                (seg_lens if seg_indptr is None else None, "seg_lens", batch_size),
+                                (weight_indices, "weight_indices", batch_size)):
+            if t is not None and tuple(t.shape) != (length,):
+                raise ValueError(f"{name} must have shape ({length},) for batch_size = {batch_size}, got {tuple(t.shape)}")
+        ws = self._int_workspace_buffer
+        if _lib.nbytes(ws) < 16 + 16 * batch_size:
+            raise ValueError(f"the int workspace ({_lib.nbytes(ws)} bytes) cannot hold {batch_size} segment records "
+                             f"({16 + 16 * batch_size} bytes)")
+        tensors = ((x, "x"), (weights, "weights"), (ws, "int_workspace_buffer")) + (((out, "out"),) if out is not None else ())
+        for t, name in tensors:
+            if t.device != x.device:
+                raise ValueError(f"{name} is on {t.device}, x on {x.device}: they must share one device")
+        for t, name in tensors:
+            _lib.require_gpu_tensor(t, name)
+        if out is None:
+            out = torch.empty((rows, d_out), dtype=x.dtype, device=x.device)
+        seg, widx = (seg_indptr if seg_indptr is not None else seg_lens), weight_indices
+        seg = seg.to(device=x.device, dtype=torch.int64).contiguous()
+        if widx is not None:
+            widx = widx.to(device=x.device, dtype=torch.int64).contiguous()
+
+        def i64(t):  # the header types these three as const int64_t*
+            return None if t is None else C.cast(t.data_ptr(), C.POINTER(C.c_int64))
+
+        p = _lib.fi_segment_gemm_params_t(
+            x=x.data_ptr(), weights=weights.data_ptr(), y=out.data_ptr(),
+            seg_lens=i64(seg if seg_indptr is None else None),
+            seg_indptr=i64(seg if seg_indptr is not None else None), weight_indices=i64(widx),
+            int_workspace=ws.data_ptr(), int_workspace_bytes=_lib.nbytes(ws), rows=rows, d_in=d_in, d_out=d_out,
+            batch_size=batch_size, num_weights=num_weights, weight_column_major=int(bool(weight_column_major)),
+            dtype=_lib.fi_dtype(x.dtype))
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().fi_segment_gemm(C.byref(p), _lib.current_stream(x.device)), "SegmentGEMMWrapper.run")
+        return out
+
+    forward = run

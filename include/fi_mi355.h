@@ -1419,6 +1419,46 @@ typedef struct fi_batch_gemm_fp8_nt_masked_params {
 
 FI_API int fi_batch_gemm_fp8_nt_masked(const fi_batch_gemm_fp8_nt_masked_params_t* params, fi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Segment GEMM for multi-LoRA batches (csrc/segment_gemm.hip; ref: SegmentGEMMWrapper, flashinfer/gemm.py:1300-1553).
+ * The rows of x and y are cut into batch_size consecutive segments; for the rows r of segment s
+ *   y[r, j] = dtype(sum_k x[r, k] * W[w(s)][k, j]),  w(s) = weight_indices ? weight_indices[s] : s
+ * f32 accumulation, one round-to-nearest to the dtype.
+ *   x: [rows, d_in], y: [rows, d_out], weights: [num_weights, d_out, d_in] (weight_column_major != 0: W[w][k, j] is
+ *   weights[w, j, k]) or [num_weights, d_in, d_out] (weight_column_major == 0), all of one dtype, f16 or bf16, contiguous
+ *   and 16-byte aligned.  d_in % 8 == 0, d_in > 0, d_out % 8 == 0; nothing else is a multiple of anything.
+ *   Segments: seg_indptr, int64 [batch_size + 1] on the DEVICE, segment s = rows [seg_indptr[s], seg_indptr[s + 1]); or,
+ *   when it is NULL, seg_lens, int64 [batch_size] on the device, segment s = the seg_lens[s] rows behind those of the
+ *   segments in front of it.  weight_indices: optional int64 [batch_size] on the device.
+ * Bad metadata does not become a bad address, and is not reported: every segment bound is clamped into [0, rows]; a
+ * segment of negative length (or whose end lies in front of its begin) is empty; a segment whose weight id is outside
+ * [0, num_weights) is skipped and its rows of y are NOT written.  Rows of y that no segment covers are not written.
+ * One kind of bad metadata is neither skipped nor empty: a seg_indptr that is not ascending makes segments overlap.
+ * Every segment is then taken on its own clamped bounds, so a row that two segments cover is written by both (which
+ * result stays is not defined), and the segments may hold more row tiles than the grid, which is sized for
+ * ceil(rows / tile) + batch_size of them: the tiles past that count are not computed and their rows keep what they held.
+ * int_workspace: 16 + 16 * batch_size bytes on the device, 16-byte aligned, written by every call (the segment
+ * records); two calls in flight at once need two workspaces.  Two launches (records, then the product on a grid sized
+ * from rows and batch_size), no host read of the metadata, no synchronisation: the call may be captured into a graph.
+ * Which of the kernel's two forms runs depends on (d_in, d_out) alone; the result does not depend on scheduling.
+ * rows == 0, batch_size == 0, d_out == 0 or num_weights == 0 returns 0 without a launch. */
+typedef struct fi_segment_gemm_params {
+  const void* x;
+  const void* weights;
+  void* y;
+  const int64_t* seg_lens;       /* [batch_size], read when seg_indptr is NULL */
+  const int64_t* seg_indptr;     /* [batch_size + 1], or NULL */
+  const int64_t* weight_indices; /* optional [batch_size] */
+  void* int_workspace;
+  int64_t int_workspace_bytes;
+  int32_t rows, d_in, d_out;
+  int32_t batch_size, num_weights;
+  int32_t weight_column_major;
+  int32_t dtype; /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+} fi_segment_gemm_params_t;
+
+FI_API int fi_segment_gemm(const fi_segment_gemm_params_t* params, fi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
