@@ -184,6 +184,27 @@ __device__ __forceinline__ f32x16g mfma_fp8_zero(const i32x8g& b, const i32x8g& 
   return mfma_fp8<MA_E5M2, MB_E5M2>(b, a, z);
 }
 
+// ---- weight streaming on the 16x16x128 MFMA (gemm_masked.hip, bmm_fp8.hip) ----
+// barrier that waits for this wave's LDS accesses only: __syncthreads() would also drain the loads in flight, which
+// are the stream.  One asm statement, as wait_vmcnt_barrier (common.h).
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+__device__ __forceinline__ u32x4 quad_xor1(const u32x4& v) {
+  u32x4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v[i], DPP_QUAD_XOR1, 0xf, 0xf, true);
+  return r;
+}
+
+// The two loads of a 16-row weight block (lo: the even row of the lane's pair, hi: the odd row; both chunk 2 g + (c & 1))
+// as the lane's operand: chunks 2 g and 2 g + 1 of row c.  An even lane keeps lo and takes its neighbour's lo, an odd
+// lane takes its neighbour's hi and keeps hi.
+__device__ __forceinline__ i32x8g weight_frag(const u32x4& lo, const u32x4& hi, bool odd) {
+  const u32x4 got = quad_xor1(odd ? lo : hi);
+  const u32x4 p0 = odd ? got : lo, p1 = odd ? hi : got;
+  return i32x8g{(int)p0[0], (int)p0[1], (int)p0[2], (int)p0[3], (int)p1[0], (int)p1[1], (int)p1[2], (int)p1[3]};
+}
+
 // ---- output ----
 // two floats rounded to dt (f16 / bf16) in one dword, `lo` in the low half
 __device__ __forceinline__ uint32_t pack_16bit(float lo, float hi, int dt) {

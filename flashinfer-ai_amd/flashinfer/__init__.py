@@ -8,6 +8,8 @@ of FlashInfer v0.3.1 (ref: flashinfer/__init__.py:23-145), backed by hand-writte
 Batch decode (the wrappers and ``decode.trtllm_batch_decode_with_kv_cache``) also takes a float8_e4m3fn query over a
 float8_e4m3fn cache, on the fp8 matrix instructions (csrc/decode_fp8_kernel.h), with a float16 / bfloat16 output.
 ``SegmentGEMMWrapper`` is the float16 / bfloat16 segment GEMM of multi-LoRA serving, on csrc/segment_gemm.hip.
+``bmm_fp8`` is the batched fp8 matmul with one scale per tensor (fp8 linear layers, the absorbed MLA projections), on
+csrc/bmm_fp8.hip.
 """
 from . import _lib as _lib
 from . import activation as activation
@@ -63,6 +65,7 @@ from .fused_moe import (
     trtllm_fp4_block_scale_routed_moe as trtllm_fp4_block_scale_routed_moe,
 )
 from .gemm import SegmentGEMMWrapper as SegmentGEMMWrapper
+from .gemm import bmm_fp8 as bmm_fp8
 from .gemm import gemm_fp8_nt_groupwise as gemm_fp8_nt_groupwise
 from .gemm import group_gemm_fp8_nt_groupwise as group_gemm_fp8_nt_groupwise
 from .gemm import mm_fp4 as mm_fp4

@@ -1,10 +1,12 @@
 """fp8 groupwise-scaled GEMM operators (``gemm_fp8_nt_groupwise``, ``group_gemm_fp8_nt_groupwise``), the grouped
 GEMM with MXFP8 activations and MXFP4 weights (``group_gemm_mxfp8_mxfp4_nt_groupwise``) and the dense MXFP4 x MXFP4
 matmul (``mm_fp4`` in its ``use_nvfp4=False`` mode), the masked batched fp8 GEMM of expert-parallel decode
-(``batch_deepgemm_fp8_nt_groupwise``), and the f16 / bf16 segment GEMM of multi-LoRA serving (``SegmentGEMMWrapper``).
+(``batch_deepgemm_fp8_nt_groupwise``), the f16 / bf16 segment GEMM of multi-LoRA serving (``SegmentGEMMWrapper``), and
+the batched fp8 matmul with one scale per tensor (``bmm_fp8``, on csrc/bmm_fp8.hip: the weight stream of
+csrc/gemm_masked.hip with one accumulator chain, k / n / m tails and a form whose waves split k).
 
-API of the reference's ``flashinfer/gemm.py`` (:2321-2484, :2657-2811, :2814-2949, :2012-2160, :3121-3256, :1300-1553); the
-kernels are
+API of the reference's ``flashinfer/gemm.py`` (:2321-2484, :2657-2811, :2814-2949, :2012-2160, :3121-3256, :1300-1553,
+:2227-2318); the kernels are
 csrc/gemm.hip (MFMA fp8, two-level accumulation per 128-wide K block), csrc/gemm_mxfp4.hip and csrc/mm_fp4.hip
 (block-scaled MFMA, the E8M0 scale bytes ride the instruction's scale operands) and csrc/gemm_masked.hip (weight
 streaming, tile list built on the device) and csrc/segment_gemm.hip (skinny grouped GEMM in two forms, segment records
@@ -26,6 +28,113 @@ _FP8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 def _validate_fp8_output_dtype(dtype: torch.dtype) -> None:
     if dtype not in (torch.bfloat16, torch.float16):
         raise ValueError(f"Unsupported output dtype: {dtype}. Only torch.bfloat16 and torch.float16 are supported.")
+
+
+def bmm_fp8(
+    A: torch.Tensor,
+    B: torch.Tensor,
+    A_scale: torch.Tensor,
+    B_scale: torch.Tensor,
+    dtype: torch.dtype,
+    out: Optional[torch.Tensor] = None,
+    backend: Literal["cudnn", "cublas", "cutlass", "auto"] = "cublas",
+) -> torch.Tensor:
+    r"""Batched fp8 matmul with one scale per tensor (ref: flashinfer/gemm.py:2227-2318)::
+
+        out[b, i, j] = dtype(A_scale * B_scale * sum_k A[b, i, k] * B[b, k, j])
+
+    f32 accumulation over the whole of ``k``, one multiply by ``A_scale * B_scale`` in f32, one rounding to nearest.  The
+    kernel is csrc/bmm_fp8.hip: the weights stream from global memory into the fp8 MFMA, in row tiles of 16 to 128 tokens;
+    for few tokens and few tiles (a decode-time linear layer) the four waves of a workgroup split ``k`` between them.  It
+    serves a dense prefill-size GEMM (``m`` in the thousands) correctly but is not tuned for it: a 256-wide MFMA-bound
+    tile for that regime is not provided.
+
+    A : ``(b, m, k)`` float8_e4m3fn or float8_e5m2, contiguous.
+    B : ``(b, k, n)`` float8_e4m3fn or float8_e5m2, COLUMN-major: ``B.transpose(-2, -1)`` must be contiguous, the storage
+        is ``(b, n, k)``.  There is no silent copy of a weight tensor: anything else raises ValueError.  ``A`` and ``B`` both
+        float8_e5m2 raises ValueError (the reference's cuBLAS path has no such product).
+    A_scale, B_scale : float32 tensors of exactly one element, of any shape, on the device.  The kernel reads them, the
+        host never does: no synchronisation, so the call can be captured into a graph, and a replay uses what the scale
+        tensors hold then.
+    dtype : torch.bfloat16 or torch.float16.
+    out : optional contiguous ``(b, m, n)`` tensor of ``dtype``; it is returned.
+    backend : one of the reference's names, checked and then ignored.
+    ``k % 16 == 0``, ``k > 0`` and ``n % 8 == 0``; any ``m >= 0`` and ``b >= 0``.  Nothing needs to be a multiple of 128.
+
+    Examples
+    --------
+    >>> import torch
+    >>> import torch.nn.functional as F
+    >>> import flashinfer
+    >>> def to_float8(x, dtype=torch.float8_e4m3fn):
+    ...     finfo = torch.finfo(dtype)
+    ...     min_val, max_val = x.aminmax()
+    ...     amax = torch.maximum(min_val.abs(), max_val.abs()).clamp(min=1e-12)
+    ...     scale = finfo.max / amax
+    ...     x_scl_sat = (x * scale).clamp(min=finfo.min, max=finfo.max)
+    ...     return x_scl_sat.to(dtype), scale.float().reciprocal()
+    >>>
+    >>> input = torch.randn([16, 48, 64], device="cuda", dtype=torch.bfloat16)
+    >>> input_fp8, input_inv_s = to_float8(input, dtype=torch.float8_e4m3fn)
+    >>> # column major weight
+    >>> weight = torch.randn([16, 80, 64], device="cuda", dtype=torch.bfloat16).transpose(-2, -1)
+    >>> weight_fp8, weight_inv_s = to_float8(weight, dtype=torch.float8_e4m3fn)
+    >>> out = flashinfer.bmm_fp8(input_fp8, weight_fp8, input_inv_s, weight_inv_s, torch.bfloat16)
+    >>> out.shape
+    torch.Size([16, 48, 80])
+    >>> out.dtype
+    torch.bfloat16
+    """
+    _validate_fp8_output_dtype(dtype)
+    if backend not in ("cudnn", "cublas", "cutlass", "auto"):
+        raise ValueError(f"Unsupported backend: {backend}")
+    if A.dtype not in _FP8 or B.dtype not in _FP8:
+        raise ValueError(f"A and B must be float8_e4m3fn or float8_e5m2, got {A.dtype} and {B.dtype}")
+    if A.dtype == torch.float8_e5m2 and B.dtype == torch.float8_e5m2:
+        raise ValueError("A and B are both float8_e5m2: at least one operand must be float8_e4m3fn")
+    if A.ndim != 3 or B.ndim != 3:
+        raise ValueError(f"A must be (b, m, k) and B (b, k, n), got A.shape = {tuple(A.shape)}, B.shape = {tuple(B.shape)}")
+    batch, m, k = A.shape
+    n = B.shape[2]
+    if B.shape[0] != batch or B.shape[1] != k:
+        raise ValueError(f"Shape mismatch. A.shape = {tuple(A.shape)}, B.shape = {tuple(B.shape)}")
+    if k == 0 or k % 16 != 0:
+        raise ValueError(f"k = {k} must be a positive multiple of 16")
+    if n % 8 != 0:
+        raise ValueError(f"n = {n} must be a multiple of 8")
+    if not A.is_contiguous():
+        raise ValueError(f"A must be contiguous, got strides {A.stride()}")
+    if not B.transpose(-2, -1).is_contiguous():
+        raise ValueError(f"B must be column-major (b, k, n): pass w.transpose(-2, -1) of the (b, n, k) weight; got strides "
+                         f"{B.stride()} and there is no silent copy of a weight tensor")
+    for t, name in ((A_scale, "A_scale"), (B_scale, "B_scale")):
+        if t.dtype != torch.float32 or t.numel() != 1:
+            raise ValueError(f"{name} must be a float32 tensor of one element, got {t.dtype} with {t.numel()} elements")
+    tensors = ((A, "A"), (B, "B"), (A_scale, "A_scale"), (B_scale, "B_scale"))
+    if out is not None:
+        tensors += ((out, "out"),)
+        if tuple(out.shape) != (batch, m, n):
+            raise ValueError(f"Output shape mismatch. Expected {(batch, m, n)}, got {tuple(out.shape)}.")
+        if out.dtype != dtype:
+            raise ValueError(f"Output dtype mismatch. Expected {dtype}, got {out.dtype}.")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+    for t, name in tensors:
+        _lib.require_gpu_tensor(t, name)
+    for t, name in tensors:
+        if t.device != A.device:
+            raise ValueError(f"{name} is on {t.device}, A on {A.device}: they must share one device")
+    if out is None:
+        out = torch.empty((batch, m, n), device=A.device, dtype=dtype)
+    if batch == 0 or m == 0 or n == 0:
+        return out
+    p = _lib.fi_bmm_fp8_params_t(
+        a=A.data_ptr(), b=B.data_ptr(), a_scale=A_scale.data_ptr(), b_scale=B_scale.data_ptr(), d=out.data_ptr(),
+        a_stride_b=m * k, b_stride_b=n * k, d_stride_b=m * n, batch=batch, m=m, n=n, k=k,
+        a_dtype=_lib.fi_dtype(A.dtype), b_dtype=_lib.fi_dtype(B.dtype), d_dtype=_lib.fi_dtype(dtype))
+    with torch.cuda.device(A.device):
+        _lib.check(_lib.lib().fi_bmm_fp8(C.byref(p), _lib.current_stream(A.device)), "bmm_fp8")
+    return out
 
 
 def gemm_fp8_nt_groupwise(

@@ -1459,6 +1459,40 @@ typedef struct fi_segment_gemm_params {
 
 FI_API int fi_segment_gemm(const fi_segment_gemm_params_t* params, fi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Batched fp8 matmul with one scale per tensor (csrc/bmm_fp8.hip; ref: bmm_fp8, flashinfer/gemm.py:2227-2318):
+ *   d[b, i, j] = dtype(a_scale[0] * b_scale[0] * sum_k a[b, i, k] * w[b, j, k])
+ * accumulated in f32 over the whole of k, multiplied once by a_scale[0] * b_scale[0] in f32, rounded once to nearest.
+ *   a: (batch, m, k) rows of k; b: (batch, n, k) rows of k -- the storage of the reference's column-major (batch, k, n)
+ *   operand; d: (batch, m, n) rows of n, f16 / bf16.  The batch strides are in elements, at least a batch entry, those
+ *   of a / b multiples of 16 and that of d of 4.  a_dtype / b_dtype: FI_DTYPE_FP8_E4M3 or FI_DTYPE_FP8_E5M2, not both
+ *   e5m2 (the reference has no such product).
+ *   a_scale, b_scale: one f32 each on the DEVICE.  The kernel reads them, the host never does: no synchronisation, the
+ *   call may be captured into a graph and a replay uses what they hold then.
+ *   k % 16 == 0, k > 0, n % 8 == 0, any m and batch; nothing needs to be a multiple of 128.  a / b 16-byte, d 8-byte,
+ *   the scales 4-byte aligned.
+ * Bytes of a row at or past k are never loaded (the last 128-wide k block is completed with zero codes), rows at or past
+ * n or m are never stored, and a workgroup stays inside the batch entry it works on.
+ * One launch, no workspace; the tile list is known on the host and is the grid.  Row tiles of 16 / 32 / 64 / 128 tokens
+ * (the smallest that holds m) by 128 weight rows, the 4 waves of a workgroup side by side along n; or, with a row tile
+ * of at most 32 tokens, at least 4 k blocks and fewer such tiles than fi_num_compute_units(), by 32 weight rows with the
+ * 4 waves along k and their partial sums added in a fixed order.  Within either form the result does not depend on the
+ * row tile or on scheduling.  Not tuned for m in the thousands.
+ * batch == 0, m == 0 or n == 0 returns 0 without a launch. */
+typedef struct fi_bmm_fp8_params {
+  const void* a;
+  const void* b;
+  const float* a_scale; /* [1] device */
+  const float* b_scale; /* [1] device */
+  void* d;
+  int64_t a_stride_b, b_stride_b, d_stride_b;
+  int32_t batch, m, n, k;
+  int32_t a_dtype, b_dtype; /* FI_DTYPE_FP8_E4M3 / FI_DTYPE_FP8_E5M2 */
+  int32_t d_dtype;          /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+} fi_bmm_fp8_params_t;
+
+FI_API int fi_bmm_fp8(const fi_bmm_fp8_params_t* params, fi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
