@@ -610,3 +610,37 @@ extern "C" FI_API int fi_group_gemm_fp8_nt_groupwise(const void* a, const void* 
   FI_HIP_CALL(launch_gemm(p, (hipStream_t)stream));
   return 0;
 }
+
+extern "C" FI_API int fi_group_gemm_fp8_nt_contiguous(const fi_group_gemm_fp8_nt_contiguous_params_t* p, fi_stream_t stream) {
+  const char* who = "group_gemm_fp8_nt_contiguous";
+  FI_REQUIRE(p, "%s: null params", who);
+  FI_REQUIRE(p->num_groups >= 0 && p->m >= 0 && p->n >= 0 && p->k >= 0, "%s: negative size (G %d, m %d, n %d, k %d)", who,
+             p->num_groups, p->m, p->n, p->k);
+  FI_REQUIRE(p->n % 128 == 0, "%s: n %d must be a multiple of 128", who, p->n);
+  FI_REQUIRE(p->k > 0 && p->k % 128 == 0, "%s: k %d must be a positive multiple of 128", who, p->k);
+  FI_REQUIRE(p->d_dtype == FI_DTYPE_F16 || p->d_dtype == FI_DTYPE_BF16, "%s: output dtype %d is not f16 / bf16", who, p->d_dtype);
+  if (p->num_groups == 0 || p->m == 0 || p->n == 0) return 0;
+  FI_REQUIRE(p->a && p->b && p->a_scale && p->b_scale && p->d && p->m_indices, "%s: null tensor", who);
+  FI_REQUIRE(((uintptr_t)p->a % 16) == 0 && ((uintptr_t)p->b % 16) == 0 && ((uintptr_t)p->d % 8) == 0 &&
+                 ((uintptr_t)p->a_scale % 4) == 0 && ((uintptr_t)p->b_scale % 4) == 0 && ((uintptr_t)p->m_indices % 4) == 0,
+             "%s: a / b must be 16-byte, d 8-byte, the scales and m_indices 4-byte aligned", who);
+  // 32-bit offsets inside a tile's 128 rows of a and 256 rows of b
+  FI_REQUIRE((int64_t)256 * p->k < (1ll << 31), "%s: k %d too large for 32-bit tile offsets", who, p->k);
+  FI_REQUIRE((int64_t)ceil_div(p->m, 128) * ceil_div(p->n, 256) < (1ll << 31), "%s: too many tiles", who);
+  ContigGemmParams g{};
+  g.a = (const uint8_t*)p->a;
+  g.b = (const uint8_t*)p->b;
+  g.a_scale = p->a_scale;
+  g.b_scale = p->b_scale;
+  g.d = p->d;
+  g.m_indices = p->m_indices;
+  g.num_groups = p->num_groups;
+  g.m = p->m;
+  g.n = p->n;
+  g.k = p->k;
+  g.out_dtype = p->d_dtype;
+  // one workgroup per compute unit, a multiple of 8 so that every XCD has the same number
+  launch_gemm_contig(g, std::max(8, fi_num_compute_units() / 8 * 8), (hipStream_t)stream);
+  FI_HIP_CALL(hipGetLastError());
+  return 0;
+}

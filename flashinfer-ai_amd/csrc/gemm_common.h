@@ -257,4 +257,18 @@ void launch_pow2_check(const GemmParams& p, hipStream_t stream);
 // otherwise the fold variant (the reverse).
 void launch_gemm_big(const GemmParams& p, bool hws, int grid, hipStream_t stream);
 
+// Contiguous layout (gemm_contig.hip): row r of a belongs to group m_indices[r], every 128-row block to one group or
+// to none.  e4m3 operands, "K" major scales per (1, 128, 128); a persistent grid of `grid` workgroups.
+struct ContigGemmParams {
+  const uint8_t* a;
+  const uint8_t* b;
+  const float* a_scale;
+  const float* b_scale;
+  void* d;
+  const int32_t* m_indices;  // [m] device
+  int32_t num_groups, m, n, k;
+  int32_t out_dtype;
+};
+void launch_gemm_contig(const ContigGemmParams& p, int grid, hipStream_t stream);
+
 }  // namespace fi

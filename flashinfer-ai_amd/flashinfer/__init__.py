@@ -10,6 +10,9 @@ float8_e4m3fn cache, on the fp8 matrix instructions (csrc/decode_fp8_kernel.h), 
 ``SegmentGEMMWrapper`` is the float16 / bfloat16 segment GEMM of multi-LoRA serving, on csrc/segment_gemm.hip.
 ``bmm_fp8`` is the batched fp8 matmul with one scale per tensor (fp8 linear layers, the absorbed MLA projections), on
 csrc/bmm_fp8.hip.
+``flashinfer.gemm.group_deepgemm_fp8_nt_groupwise`` / ``flashinfer.deep_gemm.m_grouped_fp8_gemm_nt_contiguous`` (neither
+re-exported here, as in the reference) is the grouped fp8 GEMM in the contiguous layout of expert-parallel prefill, on
+csrc/gemm_contig.hip.
 """
 from . import _lib as _lib
 from . import activation as activation

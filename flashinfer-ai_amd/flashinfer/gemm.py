@@ -1,7 +1,9 @@
 """fp8 groupwise-scaled GEMM operators (``gemm_fp8_nt_groupwise``, ``group_gemm_fp8_nt_groupwise``), the grouped
 GEMM with MXFP8 activations and MXFP4 weights (``group_gemm_mxfp8_mxfp4_nt_groupwise``) and the dense MXFP4 x MXFP4
 matmul (``mm_fp4`` in its ``use_nvfp4=False`` mode), the masked batched fp8 GEMM of expert-parallel decode
-(``batch_deepgemm_fp8_nt_groupwise``), the f16 / bf16 segment GEMM of multi-LoRA serving (``SegmentGEMMWrapper``), and
+(``batch_deepgemm_fp8_nt_groupwise``), the contiguous-layout grouped fp8 GEMM of expert-parallel prefill
+(``group_deepgemm_fp8_nt_groupwise``, on csrc/gemm_contig.hip: one group per 128-row block, named by a per-row index
+on the device), the f16 / bf16 segment GEMM of multi-LoRA serving (``SegmentGEMMWrapper``), and
 the batched fp8 matmul with one scale per tensor (``bmm_fp8``, on csrc/bmm_fp8.hip: the weight stream of
 csrc/gemm_masked.hip with one accumulator chain, k / n / m tails and a form whose waves split k).
 
@@ -575,6 +577,89 @@ def batch_deepgemm_fp8_nt_groupwise(
     with torch.cuda.device(a.device):
         _lib.check(_lib.lib().fi_batch_gemm_fp8_nt_masked(C.byref(p), _lib.current_stream(a.device)),
                    "batch_deepgemm_fp8_nt_groupwise")
+    return out
+
+
+def group_deepgemm_fp8_nt_groupwise(
+    a: torch.Tensor,  # (m, k)
+    b: torch.Tensor,  # (batch_size, n, k)
+    a_scale: torch.Tensor,  # (m, k // block_size)
+    b_scale: torch.Tensor,  # (batch_size, n // block_size, k // block_size)
+    m_indices: torch.Tensor,  # (m, )
+    scale_granularity_mnk: Tuple[int, int, int] = (1, 128, 128),
+    out: Optional[torch.Tensor] = None,  # (m, n)
+    out_dtype: Optional[torch.dtype] = None,
+) -> torch.Tensor:
+    r"""Grouped fp8 GEMM with groupwise scales in the contiguous layout of a normal-mode expert-parallel dispatch (ref:
+    flashinfer/gemm.py:2991-3118): row ``r`` of ``a`` belongs to group ``m_indices[r]`` and every group's segment is
+    padded to a multiple of 128 rows, so block ``i`` (rows ``128 i .. 128 i + 127``, the last one possibly short) has one
+    group ``g = m_indices[128 i]``.  Segments may come in any order and a group may own several of them.  For the rows
+    ``r`` of a block with ``0 <= g < G`` whose own index is not negative::
+
+        out[r] = (a[r] * a_scale[r] per 128-block) @ (b[g] * b_scale[g] per block).T
+
+    f32 accumulation, every 128-wide k block's product scaled before it is added, one rounding.  A block whose ``g`` is
+    negative or ``>= G`` is dead: nothing is loaded for it and nothing stored.  Rows of a live block with a negative index
+    are tail padding: their ``a`` / ``a_scale`` are not read and their ``out`` rows keep what they held.  A non-negative
+    index that differs from its block's first one is a caller error; the block's ``g`` is used.  The kernel is
+    csrc/gemm_contig.hip (128 x 256 tiles on a persistent grid, the group of a tile one scalar load).
+
+    a : ``(m, k)`` float8_e4m3fn; b : ``(G, n, k)`` float8_e4m3fn.
+    a_scale : ``(m, k // 128)`` float32; b_scale : ``(G, n // 128, k // 128)`` float32.
+    m_indices : ``(m,)`` int32 on the device; the host never reads it, so the call can be captured into a graph and a
+        replay follows what ``m_indices`` holds then.
+    scale_granularity_mnk : only ``(1, 128, 128)``.
+    out / out_dtype : ``(m, n)`` bf16 (default) or fp16.
+    ``n % 128 == 0``, ``k % 128 == 0``, any ``m >= 0``; every tensor contiguous.
+    """
+    tensors = ((a, "a"), (b, "b"), (a_scale, "a_scale"), (b_scale, "b_scale"), (m_indices, "m_indices"))
+    if tuple(scale_granularity_mnk) != (1, 128, 128):
+        raise NotImplementedError(f"scale_granularity_mnk = {tuple(scale_granularity_mnk)}: only (1, 128, 128) is provided")
+    if a.dtype == torch.float8_e5m2 or b.dtype == torch.float8_e5m2:
+        raise NotImplementedError("a / b in float8_e5m2 are not provided: only float8_e4m3fn")
+    if a.dtype != torch.float8_e4m3fn or b.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"a and b must be float8_e4m3fn, got {a.dtype} and {b.dtype}")
+    if a.ndim != 2 or b.ndim != 3:
+        raise ValueError(f"a must be (m, k) and b (G, n, k), got a.shape = {tuple(a.shape)}, b.shape = {tuple(b.shape)}")
+    m, k = a.shape
+    num_groups, n = b.shape[0], b.shape[1]
+    if b.shape[2] != k:
+        raise ValueError(f"Shape mismatch. a.shape = {tuple(a.shape)}, b.shape = {tuple(b.shape)}")
+    if n % 128 != 0 or k % 128 != 0 or k == 0:
+        raise ValueError(f"n = {n} and k = {k} must be multiples of 128 (k a positive one)")
+    if a_scale.dtype != torch.float32 or b_scale.dtype != torch.float32:
+        raise ValueError(f"a_scale and b_scale must be float32, got {a_scale.dtype} and {b_scale.dtype}")
+    if tuple(a_scale.shape) != (m, k // 128):
+        raise ValueError(f"a_scale must be {(m, k // 128)}, got {tuple(a_scale.shape)}")
+    if tuple(b_scale.shape) != (num_groups, n // 128, k // 128):
+        raise ValueError(f"b_scale must be {(num_groups, n // 128, k // 128)}, got {tuple(b_scale.shape)}")
+    if m_indices.dtype != torch.int32 or tuple(m_indices.shape) != (m,):
+        raise ValueError(f"m_indices must be int32 of shape {(m,)}, got {m_indices.dtype} {tuple(m_indices.shape)}")
+    if out is None:
+        out_dtype = out_dtype or torch.bfloat16
+    else:
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise ValueError(f"Output dtype mismatch. Expected {out_dtype}, got {out.dtype}.")
+        out_dtype = out.dtype
+        tensors += ((out, "out"),)
+        if tuple(out.shape) != (m, n):
+            raise ValueError(f"out must be {(m, n)}, got {tuple(out.shape)}")
+    _validate_fp8_output_dtype(out_dtype)
+    for t, name in tensors:
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous, got strides {t.stride()}")
+    if m == 0:  # nothing to launch, wherever the tensors live
+        return out if out is not None else torch.empty((0, n), device=a.device, dtype=out_dtype)
+    for t, name in tensors:
+        _lib.require_gpu_tensor(t, name)
+    if out is None:
+        out = torch.empty((m, n), device=a.device, dtype=out_dtype)
+    p = _lib.fi_group_gemm_fp8_nt_contiguous_params_t(
+        a=a.data_ptr(), b=b.data_ptr(), a_scale=a_scale.data_ptr(), b_scale=b_scale.data_ptr(), d=out.data_ptr(),
+        m_indices=m_indices.data_ptr(), num_groups=num_groups, m=m, n=n, k=k, d_dtype=_lib.fi_dtype(out_dtype))
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.lib().fi_group_gemm_fp8_nt_contiguous(C.byref(p), _lib.current_stream(a.device)),
+                   "group_deepgemm_fp8_nt_groupwise")
     return out
 
 

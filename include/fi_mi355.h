@@ -1420,6 +1420,36 @@ typedef struct fi_batch_gemm_fp8_nt_masked_params {
 FI_API int fi_batch_gemm_fp8_nt_masked(const fi_batch_gemm_fp8_nt_masked_params_t* params, fi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Contiguous-layout grouped fp8 GEMM for expert-parallel MoE prefill (csrc/gemm_contig.hip; ref:
+ * group_deepgemm_fp8_nt_groupwise, flashinfer/gemm.py:2991-3118, over deep_gemm.py m_grouped_fp8_gemm_nt_contiguous).
+ * Every row of a carries its group in m_indices[row], on the DEVICE, and every group's segment is padded to a multiple
+ * of 128 rows: block i is rows 128 i .. min(128 i + 127, m - 1) and g = m_indices[128 i] is its group.  Segments may
+ * come in any order and a group may own several of them.
+ *   g < 0 or g >= num_groups: the block is dead -- nothing of a, a_scale or b is loaded and nothing of d stored.
+ *   otherwise, for every row r of the block with m_indices[r] >= 0:
+ *     d[r, j] = sum_kb a_scale[r, kb] * b_scale[g, j / 128, kb] * sum_{k in 128-block kb} a[r, k] * b[g, j, k]
+ *   f32 accumulation, the k blocks in ascending order, one round-to-nearest to the output dtype.  Rows of a live block
+ *   with a negative index are tail padding: a and a_scale there are NOT read and d is NOT written.  A non-negative
+ *   index that differs from the block's first one is a caller error: the block's g is used.
+ *   a: (m, k) e4m3, b: (G, n, k) e4m3, a_scale: (m, k / 128) f32, b_scale: (G, n / 128, k / 128) f32,
+ *   d: (m, n) f16 / bf16, m_indices: (m) int32, all contiguous.  n % 128 == 0, k % 128 == 0, k > 0, any m >= 0 (the
+ *   last block may be short); a / b 16-byte, d 8-byte, scales and m_indices 4-byte aligned.
+ * One launch of a fixed grid, no workspace, no host read of m_indices, no synchronisation: the call may be captured
+ * into a graph and a replay follows what m_indices holds then.  m == 0, n == 0 or G == 0 returns 0 without a launch. */
+typedef struct fi_group_gemm_fp8_nt_contiguous_params {
+  const void* a;
+  const void* b;
+  const float* a_scale;
+  const float* b_scale;
+  void* d;
+  const int32_t* m_indices; /* [m] device */
+  int32_t num_groups, m, n, k;
+  int32_t d_dtype; /* FI_DTYPE_F16 / FI_DTYPE_BF16 */
+} fi_group_gemm_fp8_nt_contiguous_params_t;
+
+FI_API int fi_group_gemm_fp8_nt_contiguous(const fi_group_gemm_fp8_nt_contiguous_params_t* params, fi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Segment GEMM for multi-LoRA batches (csrc/segment_gemm.hip; ref: SegmentGEMMWrapper, flashinfer/gemm.py:1300-1553).
  * The rows of x and y are cut into batch_size consecutive segments; for the rows r of segment s
  *   y[r, j] = dtype(sum_k x[r, k] * W[w(s)][k, j]),  w(s) = weight_indices ? weight_indices[s] : s

@@ -34,6 +34,7 @@ UNITS = {
     "prefill_fp8_inst": (["-fno-slp-vectorize"], {"batch_prefill_fp8_kernel": {0, 2, 3, 4, 6, 8, 12}}),
     "gemm": ([], {"group_gemm_fp8_dma_kernel": {0, 8}}),
     "gemm_big": ([], {"group_gemm_fp8_big_kernel": {0}}),
+    "gemm_contig": ([], {"group_gemm_fp8_contig_kernel": {0, 8}}),
     # 16-bit prefill at head_dim 256: asm MFMAs with O / Q in accumulator registers (no hand-written barriers)
     "prefill_inst:bf16_256": (["-DFI_PF_T16=1", "-DFI_PF_KVS=1", "-DFI_PF_QS=1", "-DFI_PF_D=256"], {"batch_prefill_kernel": None}),
     "prefill_inst:f16_256": (["-DFI_PF_T16=0", "-DFI_PF_KVS=0", "-DFI_PF_QS=0", "-DFI_PF_D=256"], {"batch_prefill_kernel": None}),
